@@ -10,6 +10,7 @@ already resident in HBM:
   replacement + KDE, N=M=20000) -> device RANSAC/DLT/LM homography solve -> (N>1) RCCL all-gather of H.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 448b32|672b16|pyr-fp16] [--conv-stack off|fp32|fp16|amp]
+                    [--dump-outputs DIR]
 
 `--gpus N` with N > 1 works both ways: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (the ranks
 are already there: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) and as the bare command `python bench.py
@@ -163,7 +164,36 @@ def parse_args():
     ap.add_argument("--dry-run", action="store_true",
                     help="no kernels: every rank contributes made-up 3x3 matrices, so that rank start-up, the H all-gather and the JSON relay "
                          "can be exercised without a GPU (tests/test_parallel_cpu.py, with --backend gloo)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0: the gathered homographies and its own "
+                         "sampled matches per image size) as DIR/<name>.npy, at most 64 MB in all, for output-by-output comparison of two builds")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+SAMPLER_SEED = 0        # torch's CPU generator, reset before every timed loop: the sampler draws its seeds from it (ops.sample_without_replacement)
+DUMP_BYTES = 64 << 20   # --dump-outputs budget
+
+
+def dump_outputs(path, arrays):
+    """{name: array} -> path/<name>.npy in float32 (float64 stays float64), at most DUMP_BYTES in all: smallest first, every array
+    gets an equal share of what is left; one larger than its share keeps a fixed, seeded sample of its rows (first axis), the same
+    rows from run to run, in their original order."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    items = sorted(((k, np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)) for k, a in arrays.items()),
+                   key=lambda kv: kv[1].nbytes)
+    budget = DUMP_BYTES
+    for i, (name, a) in enumerate(items):
+        share = budget // (len(items) - i)
+        if a.nbytes > share and a.shape[0] > 1:
+            keep = max(1, share * a.shape[0] // a.nbytes)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        budget -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def self_launch(args):
@@ -564,7 +594,9 @@ def main():
                 (gm, _), t_sample = timed(lambda: sample_batched(m, warp, cert, 5000))
                 _, t_solve = timed(lambda: estimate_homographies(gm, sc.sizes, iters=m.ransac_iters, seed=0))
                 print(f"[breakdown] {sc.size}: match({sc.size}+{sc.up}) {t_match:.2f} ms | sample {t_sample:.2f} ms | solve {t_solve:.2f} ms", file=sys.stderr)
+        torch.manual_seed(SAMPLER_SEED)
         dt, (Hall, outs) = timed_loop(lambda i: step(0), args.steps, sync)
+        last = (Hall, outs)  # what the timed path returned in its last step (--dump-outputs)
         # The roofline op is timed in steps of its own, on ONE stream per scene with nothing beside it (in the pipelined timed region
         # the previous step's sampling + solve share the chip with it: 96 -> 107 us in round 3), HIP events around the C-ABI call.
         plain = runner if not args.pipeline else SceneRunner(scenes, pipeline=False)
@@ -591,7 +623,8 @@ def main():
             for i in range(args.warmup):
                 step(i)
             sync()
-            dt2, _ = timed_loop(lambda i: step(0), args.steps, sync)
+            torch.manual_seed(SAMPLER_SEED)
+            dt2, last = timed_loop(lambda i: step(0), args.steps, sync)
             retimed = {"first_pool_pairs_per_s": first_try, "second_pool_pairs_per_s": round(world * pairs_per_step * args.steps / dt2, 2),
                        "why": "the first stream pool ran the three-stage steps slower than one stream runs them: streams sharing a hardware queue"}
             dt = dt2  # `value` = the measurement on the rebuilt pool (one protocol, not the better of two: ADVICE r5); the first is on the line
@@ -833,6 +866,12 @@ def main():
         out["other_workloads"] = others
     if graph_leg is not None:
         out["graph_replay"] = graph_leg
+    if rank == 0 and args.dump_outputs:
+        Hall, outs = last
+        arrays = {"homographies": Hall.cpu().numpy()}
+        for sc, (_, good) in zip(scenes, outs):
+            arrays[f"matches_{sc.size}"] = good.cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if in_group:
