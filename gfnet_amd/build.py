@@ -56,32 +56,6 @@ def _compile(src, verbose, extra):
     return obj, False
 
 
-def build_ablate(verbose=False):
-    """Timing-experiment build (tools/ only): same sources with -DGFN_ABLATE -> libgfnet_hip_ablate.so."""
-    out = os.path.join(CSRC, "libgfnet_hip_ablate.so")
-    cmd = [HIPCC] + FLAGS + ["-DGFN_ABLATE", "-shared", "-o", out] + sources()
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    return out
-
-
-def build_variant(name, flags, src_name="local_corr.hip", verbose=False):
-    """A/B builds (tools/ab_lean.py): csrc/libgfnet_hip_<name>.so = the product objects with ONE source recompiled with extra flags.
-    Not the product path."""
-    build(verbose=verbose)
-    src = os.path.join(CSRC, src_name)
-    obj = os.path.join(CSRC, f"{src_name[:-4]}_{name}.o")
-    out = os.path.join(CSRC, f"libgfnet_hip_{name}.so")
-    cmd = [HIPCC] + FLAGS + FILE_FLAGS.get(src_name, []) + list(flags) + ["-c", src, "-o", obj]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    others = [s[:-4] + ".o" for s in sources() if not s.endswith(src_name)]
-    subprocess.run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out, obj] + others, check=True)
-    return out
-
-
 def build(force=False, verbose=False, extra=()):
     srcs = sources()
     if force:
@@ -101,18 +75,5 @@ def build(force=False, verbose=False, extra=()):
 
 
 if __name__ == "__main__":
-    if "--ablate" in sys.argv:
-        print(build_ablate(verbose=True))
-        sys.exit(0)
-    if "--variant" in sys.argv:  # python -m gfnet_amd.build --variant NAME [--src file.hip] <compiler flags, passed through verbatim>
-        i = sys.argv.index("--variant")
-        rest = sys.argv[i + 2:]
-        src_name = "local_corr.hip"
-        if "--src" in rest:
-            j = rest.index("--src")
-            src_name = rest[j + 1]
-            rest = rest[:j] + rest[j + 2:]
-        print(build_variant(sys.argv[i + 1], rest, src_name, verbose=True))  # (`-mllvm <opt>` keeps its value token: ADVICE r5)
-        sys.exit(0)
     extra = [a for a in sys.argv[1:] if a.startswith("-") and a != "--force"]
     print(build(force="--force" in sys.argv, verbose=True, extra=extra))

@@ -2,7 +2,6 @@
 // and csrc/conv_stack_half.hip (the same kernel on fp16 maps).  Opens its own anonymous namespace.
 #pragma once
 #include "common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -108,22 +107,11 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
                                                                                const float *__restrict__ packed,
                                                                                float *__restrict__ y, int M, int K, int G,
                                                                                int tiles_x, int tiles_y, int ngrp, unsigned nwork,
-                                                                               int tpb, int dbg_arg) {
+                                                                               int tpb) {
     static_assert(F16 || !(HIN || HOUT), "fp16 maps go with fp16 1x1 operands");
     static_assert(!MM || F16, "the matrix-core depthwise takes fp16 operands");
     static_assert(KW == 1 || (KW == 2 && MM && F16), "two K tiles per iteration: matrix-core depthwise only");
     constexpr int NPT = kNP * KW, KTT = kKT * KW;  // channel pairs / channels per iteration
-#ifdef GFN_ABLATE  // timing experiments only (tools/ablate_convblock.py): skip parts of the kernel; results are wrong
-    const int dbg = dbg_arg;
-    // bit 64: s_memtime stamps at the phase boundaries of a few workgroups (device printf at the end)
-    const bool stamping = (dbg & 64) && (blockIdx.x % 997) == 500 && (threadIdx.x & 63) == 0 && ((threadIdx.x >> 6) & 1) == 0;
-    long long stamp[40];
-    for (int i = 0; i < 40; ++i) stamp[i] = 0;
-#define CSTAMP(i) do { if (stamping && (i) < 40) stamp[i] = __builtin_readcyclecounter(); } while (0)
-#else
-    constexpr int dbg = 0;
-#define CSTAMP(i) do { } while (0)
-#endif
     static_assert(NB == 1 || (NB == 2 && NS == 1 && MT <= 3), "256-cell tiles: one slab of at most 96 output channels");
     constexpr int NT = 256 * NS;
     constexpr int BN = kBN * NB;            // cells per workgroup tile
@@ -231,8 +219,7 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
             l_valid |= ok ? 1 << i : 0;
         }
     };
-    if (!(dbg & 32))
-        for (int e = tid; e < (MM ? NPT * HR * PH : kNP * PP) / 4; e += NT) reinterpret_cast<float4 *>(Xs)[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int e = tid; e < (MM ? NPT * HR * PH : kNP * PP) / 4; e += NT) reinterpret_cast<float4 *>(Xs)[e] = make_float4(0.f, 0.f, 0.f, 0.f);
 
     static_assert(APT <= 4, "weight tile slots");
     static_assert(BMS <= NT, "one bias value per thread");
@@ -250,7 +237,6 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
         if (e < AV4) As4[buf][e] = v;
     };
     auto issue = [&]() {  // fetch (l_item, l_kt) into registers, advance the load stage
-        if (dbg & 1) return;
         const unsigned kx = (unsigned)l_kt * (unsigned)((HIN ? NPT : KTT) * plane) * 4u;  // the iteration's first pair / channel
 #pragma unroll
         for (int i = 0; i < XPP; ++i) {
@@ -275,7 +261,6 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
         }
     };
     auto commit = [&](int buf) {
-        if (dbg & 16) return;
 #pragma unroll
         for (int i = 0; i < XPP; ++i) {
             if constexpr (MM) {
@@ -345,66 +330,57 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
     float *dw_dst = &Bs[(F16 ? dp : 2 * dp) * BN + dr * TW + dc];  // fp32: channel 2dp here, 2dp+1 one plane (BN) further
 
     if (total <= 0) return;
-    CSTAMP(0);
     load_stage_enter_item();
     issue();
-    CSTAMP(1);
     __syncthreads();  // Xs zeroed
-    CSTAMP(2);
     unsigned c_item = w_begin;  // the item being accumulated
     int c_kt = 0;
     for (int t = 0; t < total; ++t) {
         const int buf = t & 1;
         commit(buf);
-        CSTAMP(3 + 6 * t);
         __syncthreads();
-        CSTAMP(4 + 6 * t);
         if (t + 1 < total) issue();
-        CSTAMP(5 + 6 * t);
         if constexpr (MM) {
-            if (!(dbg & 2)) {
-                typedef float f32x4v __attribute__((ext_vector_type(4)));
-                const int n = lane & 15, xo = n >> 1, ch = n & 1, kg = lane >> 4, mrow = lane & 15;
-                const int ar = mrow % RS, ac = mrow / RS;  // A operand: this lane's row segment
-                const float *xbase = &Xs[ar * PH + 8 * ac + 4 * kg];
-                _Float16 *bs16 = reinterpret_cast<_Float16 *>(Bs);
-                int tix[4];  // table entry of this lane's k pair i (cell 4kg + i of the window) for its output cell xo; 5 = zero
+            typedef float f32x4v __attribute__((ext_vector_type(4)));
+            const int n = lane & 15, xo = n >> 1, ch = n & 1, kg = lane >> 4, mrow = lane & 15;
+            const int ar = mrow % RS, ac = mrow / RS;  // A operand: this lane's row segment
+            const float *xbase = &Xs[ar * PH + 8 * ac + 4 * kg];
+            _Float16 *bs16 = reinterpret_cast<_Float16 *>(Bs);
+            int tix[4];  // table entry of this lane's k pair i (cell 4kg + i of the window) for its output cell xo; 5 = zero
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int dx = 4 * kg + i - xo - 2;
-                    tix[i] = ch * 40 + ((unsigned)dx <= 4u ? dx : 5);
+            for (int i = 0; i < 4; ++i) {
+                const int dx = 4 * kg + i - xo - 2;
+                tix[i] = ch * 40 + ((unsigned)dx <= 4u ? dx : 5);
+            }
+#pragma unroll
+            for (int pi = 0; pi < NPT / (4 * NS); ++pi) {
+                const int pr_ = wave + 4 * NS * pi;  // channel pair of the K tile
+                const float *tw = &Ps[pr_ * kMM2];
+                f16x8 T[5];
+#pragma unroll
+                for (int dy = 0; dy < 5; ++dy) {
+                    const f32x4v t = {tw[tix[0] + 8 * dy], tw[tix[1] + 8 * dy], tw[tix[2] + 8 * dy], tw[tix[3] + 8 * dy]};
+                    T[dy] = __builtin_bit_cast(f16x8, t);
                 }
+                const float cb = tw[80 + ch], al = tw[82 + ch], be = tw[84 + ch];
 #pragma unroll
-                for (int pi = 0; pi < NPT / (4 * NS); ++pi) {
-                    const int pr_ = wave + 4 * NS * pi;  // channel pair of the K tile
-                    const float *tw = &Ps[pr_ * kMM2];
-                    f16x8 T[5];
+                for (int sub = 0; sub < NB; ++sub) {
+                    f32x4v d = {0.f, 0.f, 0.f, 0.f};
+                    const float *xs = xbase + pr_ * (HR * PH) + sub * RS * PH;
 #pragma unroll
                     for (int dy = 0; dy < 5; ++dy) {
-                        const f32x4v t = {tw[tix[0] + 8 * dy], tw[tix[1] + 8 * dy], tw[tix[2] + 8 * dy], tw[tix[3] + 8 * dy]};
-                        T[dy] = __builtin_bit_cast(f16x8, t);
+                        const f16x8 a = __builtin_bit_cast(f16x8, *reinterpret_cast<const f32x4v *>(xs + dy * PH));
+                        d = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, T[dy], d, 0, 0, 0);
                     }
-                    const float cb = tw[80 + ch], al = tw[82 + ch], be = tw[84 + ch];
 #pragma unroll
-                    for (int sub = 0; sub < NB; ++sub) {
-                        f32x4v d = {0.f, 0.f, 0.f, 0.f};
-                        const float *xs = xbase + pr_ * (HR * PH) + sub * RS * PH;
-#pragma unroll
-                        for (int dy = 0; dy < 5; ++dy) {
-                            const f16x8 a = __builtin_bit_cast(f16x8, *reinterpret_cast<const f32x4v *>(xs + dy * PH));
-                            d = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, T[dy], d, 0, 0, 0);
-                        }
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {  // D row 4kg + j = row segment (r, c); column n = (cell xo, channel ch)
-                            const int m = 4 * kg + j, r = m % RS, c = m / RS;
-                            const int cell = (sub * RS + r) * TW + 8 * c + xo;
-                            bs16[(pr_ * BN + cell) * 2 + ch] = (_Float16)dw_finish(d[j], cb, al, be);
-                        }
+                    for (int j = 0; j < 4; ++j) {  // D row 4kg + j = row segment (r, c); column n = (cell xo, channel ch)
+                        const int m = 4 * kg + j, r = m % RS, c = m / RS;
+                        const int cell = (sub * RS + r) * TW + 8 * c + xo;
+                        bs16[(pr_ * BN + cell) * 2 + ch] = (_Float16)dw_finish(d[j], cb, al, be);
                     }
                 }
             }
-        } else
-        if (!(dbg & 2)) {  // depthwise: RB output rows x CPT cells x one channel pair; every halo row and every tap row is read once
+        } else {  // depthwise: RB output rows x CPT cells x one channel pair; every halo row and every tap row is read once
             f32x2 a[RB][CPT];
 #pragma unroll
             for (int ro = 0; ro < RB; ++ro)
@@ -459,12 +435,9 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
                 }
             }
         }
-        CSTAMP(6 + 6 * t);
         __syncthreads();
-        CSTAMP(7 + 6 * t);
 #pragma unroll
         for (int g = 0; g < NB; ++g) {
-            if (dbg & 4) break;
             const int cell = (g * 4 + cw) * 32 + col;  // this lane's B column
             if constexpr (F16) {  // one v_mfma_f32_32x32x16_f16 per row tile: lane (n or m = lane&31, kg = lane>>5) holds 8 halfs
                 // channel pairs 4kh .. 4kh+3 of this cell = halfs k = 8kh .. 8kh+7 (of k-step ks)
@@ -512,7 +485,6 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
                 }
             }
         }
-        CSTAMP(8 + 6 * t);
         if (++c_kt < nk) continue;
         // item finished: D[row][col], col = lane&31 -> cell (g*4+cw)*32+col of the tile, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
         int b, row0, col0, m0;
@@ -524,7 +496,7 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
     for (int g = 0; g < NB; ++g) {
         const int p = (g * 4 + cw) * 32 + col;
         const int gy = row0 + p / TW, gx = col0 + p % TW;
-        if (gy >= G || gx >= G || ((dbg & 8) && acc[0][0] != 12345.f)) continue;
+        if (gy >= G || gx >= G) continue;
         float *yb = y + (size_t)b * (HOUT ? (M + 1) / 2 : M) * plane + (size_t)gy * G + gx;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
@@ -577,39 +549,21 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
         for (int i = 0; i < NB * MT; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-        CSTAMP(33 + (int)(c_item - w_begin));  // item stored
     }
-#ifdef GFN_ABLATE
-    if (stamping) {
-        for (int i = 1; i < 40; ++i)
-            if (stamp[i]) printf("CS %u %d %d %lld\n", blockIdx.x, (int)(threadIdx.x >> 6), i, stamp[i] - stamp[0]);
-    }
-#endif
-#undef CSTAMP
 }
 
-// GFN_CONV_TPB (environment, experiments): work items per workgroup of the fused kernel, 0 = heuristic
-static int g_conv_tpb = [] {
-    const char *e = gfn::exp_env("GFN_CONV_TPB");
-    return e ? atoi(e) : 0;
-}();
-
 template <int MT, int TW, int NS, bool F16, int NB, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1>
-int launch_fused_mt(const float *x, const float *packed, float *y, int B, int M, int K, int G, int dbg, hipStream_t s) {
+int launch_fused_mt(const float *x, const float *packed, float *y, int B, int M, int K, int G, hipStream_t s) {
     constexpr int TH = kBN * NB / TW;
     const int tiles_x = (G + TW - 1) / TW, tiles_y = (G + TH - 1) / TH;
     const int ngrp = (M + 32 * MT * NS - 1) / (32 * MT * NS);
     const long nwork = (long)B * tiles_x * tiles_y * ngrp;
     if (nwork > 0x7fffffffL) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: too many tiles");
     // work items per workgroup (pipelined back to back)
-    int tpb = nwork >= 16384 ? 2 : 1;  // measured: pays only on the largest grids
-#ifdef GFN_CONV_TPB_FORCE  // A/B builds (python -m gfnet_amd.build --variant NAME --src conv_stack_half.hip -DGFN_CONV_TPB_FORCE=4)
-    if (nwork >= 16384) tpb = GFN_CONV_TPB_FORCE;
-#endif
-    if (g_conv_tpb > 0) tpb = g_conv_tpb;
+    const int tpb = nwork >= 16384 ? 2 : 1;  // measured: pays only on the largest grids
     const unsigned grid = (unsigned)((nwork + tpb - 1) / tpb);
     hipLaunchKernelGGL((dwpw_fused_kernel<MT, TW, NS, F16, NB, HIN, HOUT, MM, KW>), dim3(grid), dim3(256 * NS), 0, s, x, packed, y, M, K, G, tiles_x,
-                       tiles_y, ngrp, (unsigned)nwork, tpb, dbg);
+                       tiles_y, ngrp, (unsigned)nwork, tpb);
     return gfn::check_launch("dwpw_fused_kernel");
 }
 
@@ -618,37 +572,35 @@ int launch_fused_mt(const float *x, const float *packed, float *y, int B, int M,
 // (M <= 96: the fine scales, bound by LDS and HBM traffic rather than the matrix core) take 256-cell
 // tiles with two output rows per depthwise thread when the map divides into them.
 template <int TW, bool F16, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1>
-int launch_fused(const float *x, const float *packed, float *y, int B, int M, int K, int G, int dbg, hipStream_t s) {
+int launch_fused(const float *x, const float *packed, float *y, int B, int M, int K, int G, hipStream_t s) {
     const int tiles = (M + 31) / 32;
-    static const bool nb1 = gfn::exp_env("GFN_CONV_NB1") != nullptr;  // experiments: 128-cell tiles for the narrow blocks too
-    if (F16 && tiles <= 3 && TW >= 16 && G % (2 * kBN / TW) == 0 && !nb1) {  // fp32: the larger tiles cost a resident workgroup (LDS)
+    if (F16 && tiles <= 3 && TW >= 16 && G % (2 * kBN / TW) == 0) {  // fp32: the larger tiles cost a resident workgroup (LDS)
         if constexpr (F16 && TW >= 16) {
             switch (tiles) {
-                case 1: return launch_fused_mt<1, TW, 1, F16, 2, HIN, HOUT, MM>(x, packed, y, B, M, K, G, dbg, s);
-                case 2: return launch_fused_mt<2, TW, 1, F16, 2, HIN, HOUT, MM>(x, packed, y, B, M, K, G, dbg, s);
-                default: return launch_fused_mt<3, TW, 1, F16, 2, HIN, HOUT, MM>(x, packed, y, B, M, K, G, dbg, s);
+                case 1: return launch_fused_mt<1, TW, 1, F16, 2, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
+                case 2: return launch_fused_mt<2, TW, 1, F16, 2, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
+                default: return launch_fused_mt<3, TW, 1, F16, 2, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
             }
         }
     }
-    static const bool ns1 = gfn::exp_env("GFN_CONV_NS1") != nullptr;  // experiments: one slab per workgroup, two workgroups per cell tile
-    if (tiles <= 7 || ns1) {
+    if (tiles <= 7) {
         switch (tiles) {
-            case 1: return launch_fused_mt<1, TW, 1, F16, 1, HIN, HOUT, MM>(x, packed, y, B, M, K, G, dbg, s);
-            case 2: return launch_fused_mt<2, TW, 1, F16, 1, HIN, HOUT, MM>(x, packed, y, B, M, K, G, dbg, s);
-            case 3: return launch_fused_mt<3, TW, 1, F16, 1, HIN, HOUT, MM>(x, packed, y, B, M, K, G, dbg, s);
-            case 4: return launch_fused_mt<4, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, dbg, s);
-            case 5: return launch_fused_mt<5, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, dbg, s);
-            case 6: return launch_fused_mt<6, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, dbg, s);
-            default: return launch_fused_mt<7, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, dbg, s);
+            case 1: return launch_fused_mt<1, TW, 1, F16, 1, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
+            case 2: return launch_fused_mt<2, TW, 1, F16, 1, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
+            case 3: return launch_fused_mt<3, TW, 1, F16, 1, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
+            case 4: return launch_fused_mt<4, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
+            case 5: return launch_fused_mt<5, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
+            case 6: return launch_fused_mt<6, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
+            default: return launch_fused_mt<7, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
         }
     }
     const int ngrp = (tiles + 13) / 14;
     const int mt = ((tiles + ngrp - 1) / ngrp + 1) / 2;  // row tiles per slab
     switch (mt) {
-        case 4: return launch_fused_mt<4, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, dbg, s);
-        case 5: return launch_fused_mt<5, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, dbg, s);
-        case 6: return launch_fused_mt<6, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, dbg, s);
-        default: return launch_fused_mt<7, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, dbg, s);
+        case 4: return launch_fused_mt<4, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
+        case 5: return launch_fused_mt<5, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
+        case 6: return launch_fused_mt<6, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
+        default: return launch_fused_mt<7, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
     }
 }
 

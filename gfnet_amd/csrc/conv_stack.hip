@@ -263,20 +263,16 @@ GFN_EXPORT int gfn_conv_block_fwd(const float *x, const float *packed, float *y,
     if (B == 0) return GFN_OK;
     hipStream_t s = (hipStream_t)stream;
     if ((long)C * G * G > 0x1fffffffL) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: a map (C*G*G floats) must stay below 2 GB");
-    const int dbg = variant >> 8;  // ablation mask, honoured by -DGFN_ABLATE builds only
-#ifdef GFN_ABLATE
-    variant &= 0xff;
-#endif
     if (variant < 0 || variant > 3) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: variant must be 0..3 (got %d)", variant);
     const bool f16 = (variant & 2) != 0;
     const bool fused = !(variant & 1) && (G & 3) == 0;
     if (fused) {
         // tile width: full 128-byte rows where the map allows, narrower tiles for the 5*2^k grids
         if (G % 32 == 0 || G > 160)
-            return f16 ? launch_fused<32, true>(x, packed, y, B, M, C, G, dbg, s) : launch_fused<32, false>(x, packed, y, B, M, C, G, dbg, s);
+            return f16 ? launch_fused<32, true>(x, packed, y, B, M, C, G, s) : launch_fused<32, false>(x, packed, y, B, M, C, G, s);
         if (G % 16 == 0 || G > 64)
-            return f16 ? launch_fused<16, true>(x, packed, y, B, M, C, G, dbg, s) : launch_fused<16, false>(x, packed, y, B, M, C, G, dbg, s);
-        return f16 ? launch_fused<8, true>(x, packed, y, B, M, C, G, dbg, s) : launch_fused<8, false>(x, packed, y, B, M, C, G, dbg, s);
+            return f16 ? launch_fused<16, true>(x, packed, y, B, M, C, G, s) : launch_fused<16, false>(x, packed, y, B, M, C, G, s);
+        return f16 ? launch_fused<8, true>(x, packed, y, B, M, C, G, s) : launch_fused<8, false>(x, packed, y, B, M, C, G, s);
     }
     int nblk, mt;
     slab_shape(M, &nblk, &mt);

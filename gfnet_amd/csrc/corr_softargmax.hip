@@ -21,10 +21,6 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef GFN_CORR_BF16X3
-#define GFN_CORR_BF16X3 1   // 0: the row-tile path stays on the exact-fp32 matrix core instruction at every channel count
-#endif
-
 // x = h + m + l exactly (three round-to-nearest bf16 pieces of 8 significant bits each cover the 24 of an fp32 value)
 __device__ __forceinline__ void split3(float v, __bf16 &h, __bf16 &m, __bf16 &l) {
     h = (__bf16)v;
@@ -39,8 +35,7 @@ __device__ __forceinline__ void split3(float v, __bf16 &h, __bf16 &m, __bf16 &l)
 template <int KS, bool WRITE_VOL, bool WRITE_FLOW, typename FT>
 __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restrict__ f0, const FT *__restrict__ f1,
                                                               float *__restrict__ vol, float *__restrict__ flow, int B,
-                                                              int Bh, int C, int H0, int W0, int H1, int W1, float sqrt_c,
-                                                              const bf16x8 *__restrict__ aimg) {
+                                                              int Bh, int C, int H0, int W0, int H1, int W1, float sqrt_c) {
     const int N0 = H0 * W0, N1 = H1 * W1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int itiles = (N0 + 31) >> 5;
@@ -114,7 +109,7 @@ __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restri
             m = mn;
         };
         const int ntiles = H1 * parts;
-        if constexpr (KS == 32 && GFN_CORR_BF16X3 != 0) {
+        if constexpr (KS == 32) {
             // Round 6, 64-channel maps (GFNet's stride-16 features): the products on the bf16 matrix core instruction with both operands
             // split three ways (x = h + m + l, exact).  Six of the nine piece products are kept -- h.h, h.m, m.h, m.m, h.l, l.h; the dropped
             // m.l, l.m, l.l are <= 2^-23 of |a||b|, the size of an fp32 product's own rounding -- in 24 v_mfma_f32_32x32x16_bf16 per tile
@@ -140,49 +135,6 @@ __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restri
 #pragma unroll
                     for (int e = 0; e < 8; ++e) a[8 * c4 + e] = (float)f1b[(size_t)min(16 * c4 + 8 * h + e, C - 1) * N1 + jl];  // channels >= C meet zeros in b*
             };
-            if (aimg) {  // (kernel argument: uniform)
-                // the B-positions' operand comes pre-split from the workspace (split_rows_kernel below): every one of the 32 waves that
-                // walk a direction's tiles used to split the same values again -- ~300 of a tile's ~420 vector instructions, on one
-                // wave per SIMD.  Twelve 16-byte loads per tile and lane instead of 32 4-byte ones, nothing but the softmax on the VALU.
-                const bf16x8 *img = aimg + (size_t)b * ntiles * 12 * 64 + lane;
-                bf16x8 a_cur[12], a_nxt[12];
-#pragma unroll
-                for (int k = 0; k < 12; ++k) a_cur[k] = img[k * 64];
-#pragma unroll
-                for (int k = 0; k < 12; ++k) asm volatile("" : "+v"(a_cur[k]));
-                for (int t = 0; t < ntiles; ++t) {
-                    if (t + 1 < ntiles) {
-#pragma unroll
-                        for (int k = 0; k < 12; ++k) a_nxt[k] = img[((size_t)(t + 1) * 12 + k) * 64];
-                    }
-                    f32x16 accs = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc = accs;
-#pragma unroll
-                    for (int c4 = 0; c4 < 4; ++c4) {
-                        accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[4 + c4], bm[c4], accs, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[c4], bm[c4], acc, 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int c4 = 0; c4 < 4; ++c4) {
-                        accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[c4], bl[c4], accs, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[4 + c4], bh[c4], acc, 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int c4 = 0; c4 < 4; ++c4) {
-                        accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[8 + c4], bh[c4], accs, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[c4], bh[c4], acc, 0, 0, 0);
-                    }
-                    acc += accs;
-#pragma unroll
-                    for (int k = 0; k < 12; ++k) a_cur[k] = a_nxt[k];
-                    if (parts == 1 || !(t & 1)) {
-                        softmax_tile(acc, gxA, parts == 1 ? t : t >> 1);
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[r] = ((maskB >> r) & 1u) ? acc[r] : -INFINITY;
-                        softmax_tile(acc, gxB, t >> 1);
-                    }
-                }
-            } else {
             float r_cur[32], r_nxt[32];
             load_raw(r_cur, 0);
 #pragma unroll
@@ -225,7 +177,6 @@ __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restri
                     for (int r = 0; r < 16; ++r) acc[r] = ((maskB >> r) & 1u) ? acc[r] : -INFINITY;
                     softmax_tile(acc, gxB, t >> 1);
                 }
-            }
             }
         } else {
         float a_cur[KS], a_nxt[KS];
@@ -341,9 +292,11 @@ __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restri
     }
 }
 
-// The row-tile path on pre-split operand images as a kernel of its own (round 6): nothing of the general kernel's other paths lives in
-// its register allocation, so two waves fit a SIMD (<= 256 registers; the general kernel sits at 292 = one wave) and the image loads of
-// one wave hide behind the other's matrix work.  PARTS = row tiles per grid row (1: W1 == 32, 2: 33..64).
+// The row-tile path on pre-split operand images as a kernel of its own (round 6).  Every wave that walks a direction's tiles would
+// split the same values again (~300 of a tile's ~420 vector instructions); here a tile is twelve 16-byte loads per lane.  Nothing
+// of the general kernel's other paths lives in its register allocation, so two waves fit a SIMD (<= 256 registers; the general
+// kernel sits at 284 = one wave) and the image loads of one wave hide behind the other's matrix work.  PARTS = row tiles per grid
+// row (1: W1 == 32, 2: 33..64).
 template <int PARTS, typename FT>
 __global__ __launch_bounds__(256, 2) void corr_softargmax_img_kernel(const FT *__restrict__ f0, const FT *__restrict__ f1, float *__restrict__ flow,
                                                                      int B, int Bh, int C, int H0, int W0, int H1, int W1, float sqrt_c,
@@ -490,10 +443,7 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const FT *__restrict__ 
 
 // bytes of workspace the split-bf16 path wants for this shape (0: the shape does not take it)
 int64_t split_ws_bytes(int B, int C, int H1, int W1) {
-#ifndef GFN_CORR_PRESPLIT
-#define GFN_CORR_PRESPLIT 1   // 0: A/B builds in which every wave splits the operand itself
-#endif
-    if (GFN_CORR_BF16X3 == 0 || GFN_CORR_PRESPLIT == 0 || C <= 32 || C > 64 || W1 < 32 || W1 > 64) return 0;
+    if (C <= 32 || C > 64 || W1 < 32 || W1 > 64) return 0;
     const int64_t ntiles = (int64_t)H1 * (W1 > 32 ? 2 : 1);
     return (int64_t)B * ntiles * 12 * 64 * 16;
 }
@@ -565,13 +515,13 @@ int launch_corr(const FT *f0, const FT *f1, float *vol, float *flow, int B, int 
         }
     }
     if (C <= 16)
-        hipLaunchKernelGGL((corr_softargmax_kernel<8, WV, WF, FT>), grid, block, 0, stream, f0, f1, vol, flow, B, Bh, C, H0, W0, H1, W1, sc, aimg);
+        hipLaunchKernelGGL((corr_softargmax_kernel<8, WV, WF, FT>), grid, block, 0, stream, f0, f1, vol, flow, B, Bh, C, H0, W0, H1, W1, sc);
     else if (C <= 32)
-        hipLaunchKernelGGL((corr_softargmax_kernel<16, WV, WF, FT>), grid, block, 0, stream, f0, f1, vol, flow, B, Bh, C, H0, W0, H1, W1, sc, aimg);
+        hipLaunchKernelGGL((corr_softargmax_kernel<16, WV, WF, FT>), grid, block, 0, stream, f0, f1, vol, flow, B, Bh, C, H0, W0, H1, W1, sc);
     else if (C <= 64)
-        hipLaunchKernelGGL((corr_softargmax_kernel<32, WV, WF, FT>), grid, block, 0, stream, f0, f1, vol, flow, B, Bh, C, H0, W0, H1, W1, sc, aimg);
+        hipLaunchKernelGGL((corr_softargmax_kernel<32, WV, WF, FT>), grid, block, 0, stream, f0, f1, vol, flow, B, Bh, C, H0, W0, H1, W1, sc);
     else
-        hipLaunchKernelGGL((corr_softargmax_kernel<64, WV, WF, FT>), grid, block, 0, stream, f0, f1, vol, flow, B, Bh, C, H0, W0, H1, W1, sc, aimg);
+        hipLaunchKernelGGL((corr_softargmax_kernel<64, WV, WF, FT>), grid, block, 0, stream, f0, f1, vol, flow, B, Bh, C, H0, W0, H1, W1, sc);
     return gfn::check_launch("corr_softargmax_kernel");
 }
 

@@ -596,13 +596,6 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinParams P) {
     __shared__ FinShared sh;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int N = P.N;
-#ifdef GFN_ABLATE
-    long long fin_t[5] = {(long long)__builtin_readcyclecounter(), 0, 0, 0, 0};
-    int fin_lm = 0;
-#define FIN_STAMP(i) fin_t[i] = (long long)__builtin_readcyclecounter()
-#else
-#define FIN_STAMP(i) do { } while (0)
-#endif
     const float4 *pts = reinterpret_cast<const float4 *>(P.pts) + (size_t)b * N;
     const float *wgt = P.weight ? P.weight + (size_t)b * N : nullptr;
     unsigned char *mask = P.mask ? P.mask + (size_t)b * N : nullptr;
@@ -707,7 +700,6 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinParams P) {
     double Hb[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) Hb[k] = (P.mode == 0) ? sh.H[k] : 0.0;
-    FIN_STAMP(1);
 
     // ---- normalised DLT: centroid and mean absolute deviation (OpenCV runKernel) -----------------
     {
@@ -801,13 +793,9 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinParams P) {
     };
     if (tid < 9) sh.h[tid] = sh.H[tid] / sh.H[8];
     __syncthreads();
-    FIN_STAMP(2);
     lm_gram(sh.h, sh.G);
     double S = sh.G[80], lambda = 1e-3;
     for (int it = 0; it < P.lm_iters; ++it) {
-#ifdef GFN_ABLATE
-        ++fin_lm;
-#endif
         // solve (G8 + lambda diag) delta = -g on wave 0, one row per lane
         if (wave == 0) {
             double M[9];
@@ -843,12 +831,6 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinParams P) {
         __syncthreads();
         if (stop) break;
     }
-    FIN_STAMP(3);
-#ifdef GFN_ABLATE
-    if (tid == 0 && b < 3)
-        printf("finish b%d: select+mask %lld | DLT %lld | LM %lld cycles, %d LM iterations, %d inliers\n", b, fin_t[1] - fin_t[0], fin_t[2] - fin_t[1],
-               fin_t[3] - fin_t[2], fin_lm, cnt);
-#endif
     if (tid < 9) P.H[(size_t)b * 9 + tid] = sh.h[tid];
 }
 

@@ -82,9 +82,8 @@ __global__ __launch_bounds__(kKdeThreads) void kde4_kernel(const float *__restri
 // nothing.  The caller sorts queries and reference points along a Morton curve of the A-image
 // coordinates (gfn_kde_morton_keys + a sort); every 64 consecutive points then form a compact block.
 // Each wave owns one block of 64 queries, keeps its bounding box, and skips every reference block
-// whose box is farther than the cut-off (wave-uniform test on 8 scalars); the surviving blocks run
-// the same packed inner loop as kde4_kernel.  Truncation error < M * 2^-32 absolute (densities
-// are >= 1 from the self term).
+// whose box is farther than the cut-off (kde4_mfma_kernel below).  Truncation error < M * 2^-32
+// absolute (densities are >= 1 from the self term).
 constexpr float kKdeCutoffLog2 = 32.f;
 
 // 16-bit position of a point along a Hilbert curve over the A-image coordinates (8 bits per axis; the B-image position follows
@@ -271,70 +270,13 @@ __global__ __launch_bounds__(256) void kde4_bbox_kernel(const float *__restrict_
     else if (lane < 8) box[wid * 8 + lane] = hi[lane - 4];
 }
 
-__global__ __launch_bounds__(kKdeThreads) void kde4_culled_kernel(const float *__restrict__ xs, const float *__restrict__ ys,
-                                                                  const float *__restrict__ box, float *__restrict__ part,
-                                                                  int N, int Mp) {
-    const int bt = blockIdx.z;
-    const int n = blockIdx.x * kKdeThreads + threadIdx.x;
-    const int MS = gridDim.y, ms = blockIdx.y;
-    const int nblk = (Mp + 63) >> 6;
-    const int per = (nblk + MS - 1) / MS;
-    const int b0 = ms * per, b1 = min(nblk, b0 + per);
-    const float4 xv = (n < N) ? reinterpret_cast<const float4 *>(xs)[(size_t)bt * N + n] : make_float4(0, 0, 0, 0);
-    // bounding box of this wave's 64 queries (idle lanes repeat lane 0's neighbourhood via +-inf)
-    float qlo[4] = {xv.x, xv.y, xv.z, xv.w}, qhi[4] = {xv.x, xv.y, xv.z, xv.w};
-    if (n >= N) {
-#pragma unroll
-        for (int d = 0; d < 4; ++d) { qlo[d] = 3e38f; qhi[d] = -3e38f; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            qlo[d] = fminf(qlo[d], __shfl_xor(qlo[d], o));
-            qhi[d] = fmaxf(qhi[d], __shfl_xor(qhi[d], o));
-        }
-    }
-    const f32x2 x0 = {xv.x, xv.x}, x1 = {xv.y, xv.y}, x2 = {xv.z, xv.z}, x3 = {xv.w, xv.w};
-    const f32x2 *yp = reinterpret_cast<const f32x2 *>(ys) + (size_t)bt * (Mp >> 1) * 4;
-    const float *bx = box + (size_t)bt * nblk * 8;
-    f32x2 acc = {0.f, 0.f};
-    for (int blk = b0; blk < b1; ++blk) {
-        // squared distance between the two boxes (pre-scaled units: the exponent itself)
-        float d2 = 0.f;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            const float g = fmaxf(fmaxf(qlo[d] - bx[blk * 8 + 4 + d], bx[blk * 8 + d] - qhi[d]), 0.f);
-            d2 = fmaf(g, g, d2);
-        }
-        if (d2 > kKdeCutoffLog2) continue;  // the same for every lane of the wave
-        const int p0 = blk * 32, p1 = min(Mp >> 1, p0 + 32);
-#pragma unroll 4
-        for (int p = p0; p < p1; ++p) {
-            const f32x2 e0 = x0 - yp[(size_t)p * 4 + 0];
-            const f32x2 e1 = x1 - yp[(size_t)p * 4 + 1];
-            const f32x2 e2 = x2 - yp[(size_t)p * 4 + 2];
-            const f32x2 e3 = x3 - yp[(size_t)p * 4 + 3];
-            f32x2 sq = e0 * e0;
-            sq = __builtin_elementwise_fma(e1, e1, sq);
-            sq = __builtin_elementwise_fma(e2, e2, sq);
-            sq = __builtin_elementwise_fma(e3, e3, sq);
-            f32x2 e;
-            e.x = __builtin_amdgcn_exp2f(-sq.x);
-            e.y = __builtin_amdgcn_exp2f(-sq.y);
-            acc += e;
-        }
-    }
-    if (n < N) part[((size_t)bt * MS + ms) * N + n] = acc.x + acc.y;
-}
-
-// ---- matrix-core variant of the culled kernel --------------------------------------------------------
+// ---- matrix-core culled kernel -------------------------------------------------------------------
 // The exponent |x-y|^2 = |x|^2 + |y|^2 - 2 x.y of a 32 x 32 tile of (query, point) pairs is one pair of
 // v_mfma_f32_32x32x16_bf16: every fp32 coordinate is split into three bf16 pieces (8+8+8 mantissa bits,
 // exact), the products that matter (h.h, h.l, l.h, h.ll, ll.h, l.l per axis: 24 slots) and the squared
 // norms (3 + 3 slots against ones) fill K = 32, so D comes out as the exponent itself (error ~1e-5 from the
 // fp32 accumulation of +-300 magnitudes, i.e. 1e-5 relative on a term).  What is left on the VALU per pair
-// is v_exp_f32 and half a packed add -- 2.4x fewer vector cycles than the difference form above.
+// is v_exp_f32 and half a packed add -- 2.4x fewer vector cycles than the difference form (kde4_kernel).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -395,7 +337,7 @@ __global__ __launch_bounds__(256) void kde4_operands_kernel(const float *__restr
 }
 
 // One wave = 64 queries (two 32-row tiles); reference blocks of 64 points (two 32-column tiles) culled by their
-// bounding boxes as in kde4_culled_kernel.  Lane (col = lane&31, kh = lane>>5) accumulates its column of every tile;
+// bounding boxes.  Lane (col = lane&31, kh = lane>>5) accumulates its column of every tile;
 // the 32 columns are summed across lanes once at the end.
 //   * the cull runs 64 blocks at a time: lane L tests block base+L against the wave's query box, one ballot gives the
 //     survivor mask, and the wave then walks the set bits (the per-block test cost 20 vector instructions and one exposed
@@ -417,7 +359,7 @@ template <bool SYM>
 __global__ __launch_bounds__(kKdeThreads, 4) void kde4_mfma_kernel(const float *__restrict__ xs, const bf16x8 *__restrict__ aop,
                                                                 const bf16x8 *__restrict__ bop, const float *__restrict__ box,
                                                                 float *__restrict__ part, unsigned long long *__restrict__ colacc,
-                                                                int N, int Mp, int NT, int MT, int tile_cull) {
+                                                                int N, int Mp, int NT, int MT) {
     const int bt = blockIdx.z;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q0 = blockIdx.x * kKdeThreads + wave * 64;
@@ -473,7 +415,6 @@ __global__ __launch_bounds__(kKdeThreads, 4) void kde4_mfma_kernel(const float *
             const float4 lo0 = t[0], hi0 = t[1], lo1 = t[2], hi1 = t[3];
             k00 = near(ql0, qh0, lo0, hi0); k01 = near(ql0, qh0, lo1, hi1);
             k10 = near(ql1, qh1, lo0, hi0); k11 = near(ql1, qh1, lo1, hi1);
-            if (!tile_cull) k00 = k01 = k10 = k11 = (k00 | k01 | k10 | k11);  // experiments: cull per 64 x 64 block only
         }
         const unsigned long long m00 = __ballot(k00), m01 = __ballot(k01), m10 = __ballot(k10), m11 = __ballot(k11);
         unsigned long long mask = m00 | m01 | m10 | m11;
@@ -679,7 +620,7 @@ GFN_EXPORT int64_t gfn_kde_sorted_scratch_floats(int Bt, int N, int M) {
            (int64_t)Bt * N * 2 + 4;                        // + the fixed-point column sums of the symmetric kernel
 }
 
-// Density of spatially sorted 4-D points (see kde4_culled_kernel): x (Bt,N,4), y (Bt,M,4), both in
+// Density of spatially sorted 4-D points (see kde4_mfma_kernel): x (Bt,N,4), y (Bt,M,4), both in
 // the order of their gfn_kde_morton_keys; out (Bt,N) in the order of x.
 GFN_EXPORT int gfn_kde_density_sorted(const float *x, const float *y, float *out, const int *perm, int Bt, int N, int M, double std,
                                       int round_fp16, float *scratch, int64_t scratch_floats, gfn_stream_t stream) {
@@ -704,36 +645,27 @@ GFN_EXPORT int gfn_kde_density_sorted(const float *x, const float *y, float *out
         while (blocks * MS < 2048 && nblk / (MS * 2) >= 8 && MS < 32) MS *= 2;
     }
     float *dst = (MS > 1 || perm) ? part : out;  // perm: results leave through the combine kernel, in the caller's order
-    static const bool valu_only = gfn::exp_env("GFN_KDE_VALU") != nullptr;  // experiments: the difference-form kernel
-    static const bool no_sym = gfn::exp_env("GFN_KDE_NOSYM") != nullptr;    // experiments: full N x N evaluation
-    const bool sym = x == y && N == M && !no_sym;
-    static const int tile_cull = gfn::exp_env("GFN_KDE_NOTILE") == nullptr;  // experiments: 0 = cull per block only
-    if (valu_only) {
-        hipLaunchKernelGGL(kde4_culled_kernel, dim3((N + kKdeThreads - 1) / kKdeThreads, MS, Bt), dim3(kKdeThreads), 0, s, xs, ys,
-                           box, dst, N, Mp);
-        if (int e = gfn::check_launch("kde4_culled_kernel")) return e;
-    } else {
-        const int NT = (N + 63) / 64 * 2, MT = nblk * 2;
-        float *opbase = part + (((int64_t)Bt * 32 * N + 3) & ~(int64_t)3);
-        bf16x8 *aop = reinterpret_cast<bf16x8 *>(opbase), *bop = aop + (int64_t)Bt * NT * 128;
-        const long npts = (long)Bt * 32 * (NT > MT ? NT : MT);
-        hipLaunchKernelGGL(kde4_operands_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, s, xs, ys, aop, bop, N, M, Mp, NT,
-                           MT, Bt);
-        if (sym) {
-            unsigned long long *colacc = reinterpret_cast<unsigned long long *>(bop + (int64_t)Bt * MT * 128);
-            if (hipMemsetAsync(colacc, 0, sizeof(unsigned long long) * (size_t)Bt * N, s) != hipSuccess)
-                return gfn::fail(GFN_ERR_LAUNCH, "kde_sorted: memset failed");
-            hipLaunchKernelGGL(kde4_mfma_kernel<true>, dim3((N + kKdeThreads - 1) / kKdeThreads, MS, Bt), dim3(kKdeThreads), 0, s, xs, aop,
-                               bop, box32, part, colacc, N, Mp, NT, MT, tile_cull);
-            if (int e = gfn::check_launch("kde4_mfma_kernel")) return e;
-            const long total = (long)Bt * N;
-            hipLaunchKernelGGL(kde_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, colacc, perm, out, N, MS, Bt);
-            return gfn::check_launch("kde_combine_kernel");
-        }
-        hipLaunchKernelGGL(kde4_mfma_kernel<false>, dim3((N + kKdeThreads - 1) / kKdeThreads, MS, Bt), dim3(kKdeThreads), 0, s, xs, aop, bop,
-                           box32, dst, nullptr, N, Mp, NT, MT, tile_cull);
+    const bool sym = x == y && N == M;
+    const int NT = (N + 63) / 64 * 2, MT = nblk * 2;
+    float *opbase = part + (((int64_t)Bt * 32 * N + 3) & ~(int64_t)3);
+    bf16x8 *aop = reinterpret_cast<bf16x8 *>(opbase), *bop = aop + (int64_t)Bt * NT * 128;
+    const long npts = (long)Bt * 32 * (NT > MT ? NT : MT);
+    hipLaunchKernelGGL(kde4_operands_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, s, xs, ys, aop, bop, N, M, Mp, NT,
+                       MT, Bt);
+    if (sym) {
+        unsigned long long *colacc = reinterpret_cast<unsigned long long *>(bop + (int64_t)Bt * MT * 128);
+        if (hipMemsetAsync(colacc, 0, sizeof(unsigned long long) * (size_t)Bt * N, s) != hipSuccess)
+            return gfn::fail(GFN_ERR_LAUNCH, "kde_sorted: memset failed");
+        hipLaunchKernelGGL(kde4_mfma_kernel<true>, dim3((N + kKdeThreads - 1) / kKdeThreads, MS, Bt), dim3(kKdeThreads), 0, s, xs, aop,
+                           bop, box32, part, colacc, N, Mp, NT, MT);
         if (int e = gfn::check_launch("kde4_mfma_kernel")) return e;
+        const long total = (long)Bt * N;
+        hipLaunchKernelGGL(kde_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, colacc, perm, out, N, MS, Bt);
+        return gfn::check_launch("kde_combine_kernel");
     }
+    hipLaunchKernelGGL(kde4_mfma_kernel<false>, dim3((N + kKdeThreads - 1) / kKdeThreads, MS, Bt), dim3(kKdeThreads), 0, s, xs, aop, bop,
+                       box32, dst, nullptr, N, Mp, NT, MT);
+    if (int e = gfn::check_launch("kde4_mfma_kernel")) return e;
     if (MS > 1 || perm) {
         const long total = (long)Bt * N;
         hipLaunchKernelGGL(kde_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, nullptr, perm, out, N, MS, Bt);

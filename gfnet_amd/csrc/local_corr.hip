@@ -72,19 +72,7 @@ struct LcParams {
     int planned;                      // lean path: the plan is already in scratch (gfn_refiner_input_plan_fwd_dt wrote it)
     int mq;                           // r >= 5: the first launch is the matrix-core tile kernel (local_corr_mq.h)
     int *plan;                        // lean path: [4 * B*tiles] per-tile staging regions written by the plan launch (16-byte aligned)
-#ifdef GFN_ABLATE
-    int dbg;  // timing experiments only (tools/probe_local_corr.py): bit mask of stages to skip
-#endif
 };
-
-#ifdef GFN_ABLATE
-#define ABL(p, bit) (((p).dbg & (bit)) != 0)
-// phase time stamps of one workgroup (tools/ablate_local_corr.py --stamps): s_memtime at the phase boundaries
-#define STAMP(i) do { if (stamping) stamp[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define ABL(p, bit) false
-#define STAMP(i) do { } while (0)
-#endif
 
 // f1 map of direction b.  Symmetric batches are virtual: the second half of the directions reads
 // the other image's features (f1_second) instead of a concatenated copy (model/network.py:213-222).
@@ -388,11 +376,6 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int G = p.G, H = p.H, W = p.W;
-#ifdef GFN_ABLATE
-    const bool stamping = ABL(p, 512) && blockIdx.x == 2000 && tid == 0 && !SECOND;
-    long long stamp[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    STAMP(0);
     auto cell_gi = [&](int cell) { return row0 + cell / TW; };
     auto cell_gj = [&](int cell) { return col0 + cell % TW; };
     auto cell_ok = [&](int cell) { return (cell / TW < rows) & (row0 + cell / TW < G) & (col0 + cell % TW < G); };
@@ -418,7 +401,7 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
                 const int e = e0 + q * kThreads;
                 const int c = e / NC, cell = e - c * NC;
                 const int gi = cell_gi(cell), gj = cell_gj(cell);
-                const bool ok = (e < total) & cell_ok(cell) & !ABL(p, 4);
+                const bool ok = (e < total) & cell_ok(cell);
                 v[q] = f0b[ok ? (size_t)c * G * G + (size_t)gi * G + gj : 0];  // clamped address, select below
                 v[q] = ok ? v[q] : 0.f;
             }
@@ -430,7 +413,6 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
             }
         }
     }
-    STAMP(11);
     int bx0 = kFar, by0 = kFar, bx1 = -kFar, by1 = -kFar;  // this cell's window clipped to the image
     bool inside = true;                                      // ... and whether clipping changed nothing
     if (tid < NC) {
@@ -462,7 +444,6 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
         cellNy[tid] = ny;
         cellSlow[tid] = slow;
     }
-    STAMP(12);
     if (STAGED && wave < (NC + 63) / 64) {  // bounding box: reduce inside the wave (all 64 lanes take
         // part, idle ones with the identity) with DPP row shifts / broadcasts -- the ds_bpermute butterfly took 1500+ cycles
         // of every tile's critical path -- then one LDS update per wave and bound
@@ -484,9 +465,7 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
     }
     // the zero slot (index kCapSlots) is what every out-of-image tap reads
     if (STAGED && tid < kSlotV4) s4[kCapSlots * kSlotV4 + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-    STAMP(1);
     __syncthreads();
-    STAMP(2);
 
     // ---- the staging region (block-uniform) -----------------------------------------------------
     Region u;
@@ -511,7 +490,6 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
             if (tid == 0) p.todo[kTodoHdr + atomicAdd(p.todo, 1)] = (int)wid;
         } else {
             __syncthreads();
-            if (ABL(p, 1024)) return;
             process_tile<R, ROUNDS, false, TW, true, FT, STAGE, QOK>(p, b, row0, col0, rows, wid, smem);  // gather from L2
         }
         return;
@@ -536,14 +514,14 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
 #pragma unroll
         for (int n = 0; n < kQuadPre; ++n) qlq.it[n] = quad_item<false, FT, kSlotV4, true>(up, H, W, wave, lane, n);
         quad_issue<kQuadPre, false, FT, kSlotV4, true>(preq, f1r, 0u, H, W, up, wave, lane, qlq, 0);
-    } else if (STAGED && !ABL(p, 1)) {
+    } else if (STAGED) {
         stage_issue(pre0, f1b, H, W, u, wave, lane, 0);
     }
 
     // fraction table: the reference's fp32 coordinate of every tap column / row of every cell
     // (local_correlation.py:55 adds window offsets in normalised units, grid_sample un-normalises)
     auto fill_table = [&]() {
-        for (int e = tid; e < NC * 2 * D && !ABL(p, 32); e += kThreads) {
+        for (int e = tid; e < NC * 2 * D; e += kThreads) {
             const int cell = e / (2 * D), a = e - cell * (2 * D);
             const bool isy = a >= D;
             const int k = isy ? a - D : a;
@@ -598,18 +576,16 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
         }
     }
 
-    STAMP(3);
     // ---- main loop: 16 channels at a time ----------------------------------------------------
     const size_t cs = (size_t)G * G;
     if (quads) {
         quad_commit<kQuadPre, false, FT>(s4, preq, H, W, up, wave, lane, qlq, 0);
         quad_rest<false, FT>(s4, f1r, 0u, H, W, up, wave, lane, qlq, kQuadPre);
-    } else if (STAGED && !ABL(p, 1)) {
+    } else if (STAGED) {
         stage_commit(s4, pre0);
         stage_rest<2>(s4, f1b, H, W, u, wave, lane, PRE0);
     }
     if (STAGED) __syncthreads();
-    STAMP(4);
     for (int c0 = 0; c0 < p.C; c0 += kChunk) {
         const FT *f1c = f1b + (size_t)c0 * H * W;
         const bool more = c0 + kChunk < p.C;
@@ -623,7 +599,7 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
             // next chunk's loads: in flight across this chunk's D-stage
             const unsigned next_off = (unsigned)(c0 + kChunk) * (unsigned)(H * W) * (unsigned)sizeof(FT);
             if (more && quads) quad_issue<kQuadPre, false, FT, kSlotV4, true>(preq, f1r, next_off, H, W, up, wave, lane, qlq, 0);
-            else if (more && !ABL(p, 1)) stage_issue(pre, f1c + (size_t)kChunk * H * W, H, W, u, wave, lane, 0);
+            else if (more) stage_issue(pre, f1c + (size_t)kChunk * H * W, H, W, u, wave, lane, 0);
         }
 #pragma unroll
         for (int rd = 0; rd < ROUNDS; ++rd) {
@@ -634,7 +610,6 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
                 f[0] = a0.x; f[1] = a0.y; f[2] = a0.z; f[3] = a0.w; f[4] = a1.x; f[5] = a1.y; f[6] = a1.z; f[7] = a1.w;
                 f[8] = a2.x; f[9] = a2.y; f[10] = a2.z; f[11] = a2.w; f[12] = a3.x; f[13] = a3.y; f[14] = a3.z; f[15] = a3.w;
             }
-            if (ABL(p, 2)) continue;
             if (STAGED) {
 #pragma unroll
                 for (int t = 0; t < NP; ++t) {
@@ -664,7 +639,7 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
                             const int pp = s16 + 16 * (t0 + tt);
                             const int yy = pp / PW, xx = pp - yy * PW;
                             const int X = cX0 + xx, Y = cY0 + yy;
-                            in[tt] = (pp < P) & ((unsigned)X < (unsigned)W) & ((unsigned)Y < (unsigned)H) & !ABL(p, 2048);
+                            in[tt] = (pp < P) & ((unsigned)X < (unsigned)W) & ((unsigned)Y < (unsigned)H);
                             const unsigned off = in[tt] ? (unsigned)(Y * W + X) : 0u;  // offset 0 when outside: valid memory, masked below
 #pragma unroll
                             for (int k = 0; k < kChunk; ++k) v[tt][k] = f1c[k * plane + off];  // scalar plane base + 32-bit lane offset
@@ -690,25 +665,22 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
         for (int rd = 0; rd < ROUNDS; ++rd)
 #pragma unroll
             for (int t = 0; t < NP; ++t) asm volatile("" : "+v"(acc[rd][t]));  // pins the FMAs above this point
-        STAMP(5 + (c0 != 0 ? 2 : 0));
         if (STAGED && more) {
             __syncthreads();  // everyone is done reading this chunk
             if (quads) {
                 const unsigned next_off = (unsigned)(c0 + kChunk) * (unsigned)(H * W) * (unsigned)sizeof(FT);
                 quad_commit<kQuadPre, false, FT>(s4, preq, H, W, up, wave, lane, qlq, 0);
                 quad_rest<false, FT>(s4, f1r, next_off, H, W, up, wave, lane, qlq, kQuadPre);
-            } else if (!ABL(p, 1)) {
+            } else {
                 stage_commit(s4, pre);
                 stage_rest<2>(s4, f1c + (size_t)kChunk * H * W, H, W, u, wave, lane, PRE);
             }
             __syncthreads();
-            STAMP(6);
         }
     }
 
     // ---- epilogue: D -> LDS, per-tap fractions, bilinear combination, coalesced stores -------
     __syncthreads();
-    STAMP(8);
 #pragma unroll
     for (int rd = 0; rd < ROUNDS; ++rd) {
         const int cell = rd * 32 + cr;
@@ -720,7 +692,6 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
     }
     if (!kEarlyTab) fill_table();
     __syncthreads();
-    STAMP(9);
     {
         // each wave combines CW cells x a strided subset of the K taps: lane -> cell (so that stores run
         // along the grid row), taps strided over the waves (and over lane halves when NC == 32)
@@ -730,7 +701,7 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
         const int cell = (wave / (kWaves / NCB)) * CW + (lane & (CW - 1));
         const int kphase = (wave % (kWaves / NCB)) * (64 / CW) + (lane / CW);
         const int gi = cell_gi(cell), gj = cell_gj(cell);
-        if (cell_ok(cell) && !cellSlow[cell] && !ABL(p, 8)) {
+        if (cell_ok(cell) && !cellSlow[cell]) {
             // one tap ROW (ky) at a time: the two D rows it needs are read once (2*PW LDS reads for D
             // outputs), the column fractions of the cell stay in registers
             const float *dc = dbuf + cell * DS;
@@ -763,16 +734,8 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
         }
     }
 
-    STAMP(10);
-#ifdef GFN_ABLATE
-    if (stamping)
-        printf("stamps(cycles from entry): flow-issued+f0 staged %lld | cells done %lld | setup-done %lld | barrier %lld | addressing %lld | chunk0 staged %lld | D chunk0 %lld | chunk1 staged %lld | "
-               "D chunk1 %lld | barrier %lld | dbuf+table %lld | combine+stores issued %lld\n",
-               stamp[11] - stamp[0], stamp[12] - stamp[0], stamp[1] - stamp[0], stamp[2] - stamp[0], stamp[3] - stamp[0], stamp[4] - stamp[0], stamp[5] - stamp[0], stamp[6] - stamp[0],
-               stamp[7] - stamp[0], stamp[8] - stamp[0], stamp[9] - stamp[0], stamp[10] - stamp[0]);
-#endif
     // ---- flagged cells: general per-tap routine (about one cell in 10^4) ------------------------
-    if (*nSlow != 0 && !ABL(p, 16)) {  // block-uniform, rare
+    if (*nSlow != 0) {  // block-uniform, rare
         // compact the flagged cells (cellX0 is free now), then spread (cell, tap) pairs over the whole workgroup
         __syncthreads();
         if (tid == 0) {
@@ -795,16 +758,6 @@ __device__ __forceinline__ void process_tile(const LcParams &p, int b, int row0,
 template <int R, int ROUNDS, typename FT, bool QOK = true>
 __global__ __launch_bounds__(kThreads, 4) void local_corr_tile_kernel(LcParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-#ifdef GFN_ABLATE
-    {   // experiment: de-synchronise the two workgroups of a CU (first dispatch wave only)
-        const unsigned bid = blockIdx.x;
-        const bool late = (ABL(p, 64) && ((bid >> 8) & 1)) || (ABL(p, 128) && (bid & 1)) || (ABL(p, 256) && ((bid >> 3) & 1));
-        if (late && bid < 512) {
-            const int n = p.dbg >> 12;  // sleep units of ~64*127 cycles
-            for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);
-        }
-    }
-#endif
     const unsigned wid = gfn::xcd_remap(blockIdx.x, gridDim.x);
     const int tiles = p.tiles_x * p.tiles_y;
     const int b = wid / tiles, tile = wid - b * tiles;
@@ -872,27 +825,18 @@ bool lean_shape(int C, int H, int W, int G, int r, int f16) {
     if (!(r >= 1 && r <= 7 && (C == 16 || C == 32 || C == 64) && !(f16 && (W & 1)) && (long)C * H * W < (1L << 30) && K * G * G < (1L << 30) &&
           (long)C * G * G < (1L << 30)))
         return false;
-    // Large windows (r >= 5): the lean tile kernel handles them (f0 block staged chunk by chunk, 65 792-byte stage at r = 7) and is on
-    // par with the round-1 kernel on smooth flows where the 4 x 16-cell tile's region fits the stage (r = 7 on 32 x 32 maps: 80.7 vs
-    // 79.5 us), slower where every tile would be staged in halves (r = 6 at spacing 1.75: 113 vs 79 us) and under the raw
-    // soft-argmax flows scale 16 sees in the bench (160 vs 110 + 44 us: its in-launch second-launch workers) -- the round-1 kernel
-    // with quad staging keeps them.  -DGFN_LEAN_R7=1 builds send r = 7 here.
-    if (r >= 5) {
-#if defined(GFN_LEAN_R7) && GFN_LEAN_R7
-        const double sx = (double)W / G, sy = (double)H / G, pw = 2 * r + 2;
-        return (3 * sy + pw + 1) * (15 * sx + pw + 4) <= 0.95 * 819;
-#else
-        return false;
-#endif
-    }
-    return true;
+    // Large windows (r >= 5) stay on the round-1 kernel with quad staging: a lean tile kernel for them (f0 block staged chunk by chunk)
+    // measured on par where the 4 x 16-cell tile's region fits the stage (r = 7 on 32 x 32 maps: 80.7 vs 79.5 us), slower where every
+    // tile would be staged in halves (r = 6 at spacing 1.75: 113 vs 79 us) and under the raw soft-argmax flows scale 16 sees in the
+    // bench (160 vs 110 + 44 us).
+    return r <= 4;
 }
 
 // large windows on 64-channel maps: the matrix-core tile kernel of local_corr_mq.h is the first launch (byte offsets into the maps and
 // the kOffRange marker share 31 bits)
 bool mq_shape(int C, int H, int W, int G, int r, int f16) {
     const long K = (long)(2 * r + 1) * (2 * r + 1);
-    return GFN_MQ != 0 && r >= 5 && r <= 7 && C == 64 && !(f16 && (W & 1)) && (long)C * H * W * (f16 ? 2 : 4) < 0x7FFFFFF0L &&
+    return r >= 5 && r <= 7 && C == 64 && !(f16 && (W & 1)) && (long)C * H * W * (f16 ? 2 : 4) < 0x7FFFFFF0L &&
            K * G * G * 4 < 0x7FFFFFF0L && (long)C * G * G * 4 < 0x7FFFFFF0L;
 }
 
@@ -944,7 +888,7 @@ int launch_tiles_staged(const LcParams &p, unsigned total, size_t lds, hipStream
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(local_corr_irregular_kernel<R, ROUNDS, FT, QOK>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
     bool mq = false;
-    if constexpr (R >= 5 && GFN_MQ != 0) {
+    if constexpr (R >= 5) {
         static_assert(ROUNDS == 1, "the matrix-core kernel's tiles are the round-1 kernel's 2 x 16 cells: they share the second launch");
         mq = p.mq != 0;
         if (mq) {
@@ -973,7 +917,7 @@ int launch_lean_path(const LcParams &p0, hipStream_t stream) {
     const unsigned total = (unsigned)p.B * p.tiles_x * p.tiles_y;
     if ((size_t)p.todo_ints < (size_t)total + kTodoHdr) return gfn::fail(GFN_ERR_SCRATCH, "local_corr: scratch too small");
     const size_t lds2 = Lean<R>::kStageLds + ((NC * 20 + 32 + 15) & ~15) + (Lean<R>::kTabInStage ? 0 : Lean<R>::kTabBytes) +  // (the table: inside the stage at r = 3, 4)
-                        (size_t)NC * ((Lean<R>::kF0Chunk ? kChunk : p.C) + 4) * 4;
+                        (size_t)NC * (p.C + 4) * 4;
     if (lds2 > kMaxLds) return -1000;
     if (!p.planned) {
         hipLaunchKernelGGL((local_corr_plan_kernel<R>), dim3((total + 4 * kPlanPerWave - 1) / (4 * kPlanPerWave)), dim3(256), 0, stream, p);
@@ -1006,12 +950,7 @@ int launch_lean_path(const LcParams &p0, hipStream_t stream) {
 
 template <int R, int ROUNDS, typename FT>
 int launch_tile(const LcParams &p0, hipStream_t stream, bool lean) {
-#if defined(GFN_LEAN_R7) && GFN_LEAN_R7
-    constexpr bool kLeanBuilt = true;
-#else
-    constexpr bool kLeanBuilt = R <= 4;  // lean_shape() never takes r >= 5 in this build: do not instantiate those kernels
-#endif
-    if constexpr (kLeanBuilt) {
+    if constexpr (R <= 4) {  // lean_shape() never takes r >= 5: do not instantiate those kernels
         if (lean) {
             const int rc = launch_lean_path<R, FT>(p0, stream);
             if (rc != -1000) return rc;  // -1000: the lean kernel's LDS does not take this shape -> round-1 kernel below
@@ -1098,10 +1037,6 @@ GFN_EXPORT int gfn_local_corr_fwd_dt(const float *f0, int64_t f0_bs, const void 
     p.todo = reinterpret_cast<int *>(scratch);
     p.todo_ints = scratch ? scratch_bytes / 4 : 0;
     p.plan = nullptr;
-#ifdef GFN_ABLATE
-    p.dbg = variant >> 8;
-    variant &= 0xff;
-#endif
 
     // the tiled path needs the tile list in scratch; without it the general kernel still gives the right answer
     // variant 0: the tiled path (lean fp32 tile kernel for r <= 4, the matrix-core kernel for r >= 5 on 64-channel maps); 1: general
@@ -1211,10 +1146,7 @@ GFN_EXPORT int gfn_refiner_input_plan_fwd_dt(const void *f0, const void *f1, int
         case 1: return h ? launch_ri_plan<1, _Float16>(q, p, s, keep) : launch_ri_plan<1, float>(q, p, s, keep);
         case 2: return h ? launch_ri_plan<2, _Float16>(q, p, s, keep) : launch_ri_plan<2, float>(q, p, s, keep);
         case 3: return h ? launch_ri_plan<3, _Float16>(q, p, s, keep) : launch_ri_plan<3, float>(q, p, s, keep);
-        case 4: return h ? launch_ri_plan<4, _Float16>(q, p, s, keep) : launch_ri_plan<4, float>(q, p, s, keep);
-        case 5: return h ? launch_ri_plan<5, _Float16>(q, p, s, keep) : launch_ri_plan<5, float>(q, p, s, keep);
-        case 6: return h ? launch_ri_plan<6, _Float16>(q, p, s, keep) : launch_ri_plan<6, float>(q, p, s, keep);
-        default: return h ? launch_ri_plan<7, _Float16>(q, p, s, keep) : launch_ri_plan<7, float>(q, p, s, keep);
+        default: return h ? launch_ri_plan<4, _Float16>(q, p, s, keep) : launch_ri_plan<4, float>(q, p, s, keep);  // lean_shape: r <= 4
     }
 }
 

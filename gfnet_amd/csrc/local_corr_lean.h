@@ -25,15 +25,6 @@
 
 constexpr int kMmNBW = 10;  // local_corr_mq.h: accumulator blocks per wave of the matrix-core kernel (a group's box: <= 2 kMmNBW rows)
 
-#ifndef GFN_LEAN_STAGE2_KB
-#define GFN_LEAN_STAGE2_KB 40
-#endif
-#ifndef GFN_LEAN_TAB_IN_STAGE
-#define GFN_LEAN_TAB_IN_STAGE 1
-#endif
-#ifndef GFN_LEAN_STAGE4_KB
-#define GFN_LEAN_STAGE4_KB 64
-#endif
 constexpr int kPlanInts = 16;  // per tile: region A x0, y0, (h << 16) | w, flags; region B x0, y0, (h << 16) | w, geometry of A;
                                // geometry of B, direction b, row0 | col0 << 16, spare ...  (geometry = pitch | quads per row << 8 | items << 16:
                                // round 4 -- the tile kernel no longer derives the regions' pitch and item count (region_fits) and the tile's
@@ -53,27 +44,23 @@ __device__ __forceinline__ int cell_col(int c) { return (c & 7) + ((c >> 5) << 3
 // 40 KB three workgroups fit a CU
 template <int R>
 struct Lean {
-    // + cells, fraction table, f0 block <= 80 KB: two workgroups per CU.  r = 7: the D buffer that aliases the stage (64 cells x 257
-    // floats) needs 65 792 bytes; with the f0 block staged chunk by chunk (kF0Chunk) the total stays at 80 160
+    // + cells, fraction table, f0 block <= 80 KB: two workgroups per CU
+    static_assert(R <= 4, "r >= 5 takes the round-1 kernel (lean_shape)");
     static constexpr int kDbuf = ((64 * ((2 * R + 2) * (2 * R + 2) + 1) + 16) * 4 + 15) & ~15;  // + 16: the skew of cells 32-63 (lean_tile)
-    // Round 5 experiment (-DGFN_LEAN_STAGE4_KB=68): r = 3 / 4 stage the f0 block chunk by chunk too (5 KB instead of 9 KB on 32-channel
-    // maps) and give the 4 KB to the stage, 870 positions instead of 819, so that the 7.4 % of the bench's scale-4 tiles whose regions
-    // are 44 x 19 = 836 pixels are staged whole instead of as two halves.  Measured SLOWER (bench flows 105.8 vs 102.7 us, homography
-    // flows 98.4 vs 95.7): the per-chunk f0 loads and filing cost every tile more than the halves cost the few.
-    static constexpr int kStage34 = GFN_LEAN_STAGE4_KB * 1024;
-    static constexpr int kStage = R <= 2 ? GFN_LEAN_STAGE2_KB * 1024 : (kDbuf > kStage34 ? kDbuf : kStage34);
-    static constexpr bool kF0Chunk = R >= 5 || (R >= 3 && GFN_LEAN_STAGE4_KB > 64);  // 16 channels of the f0 block in LDS at a time
+    // (r = 3 / 4 with the f0 block staged chunk by chunk and 4 KB more stage measured slower: the per-chunk f0 loads cost every tile
+    // more than staging the few large regions in halves)
+    static constexpr int kStage = R <= 2 ? 40 * 1024 : 64 * 1024;
     // Round 5: r >= 3 keep the fraction table (64 cells x 19 floats) INSIDE the stage, behind the D buffer: it is filled after the main
-    // loop (measured level with filling it up front, GFN_LEAN_TABLE_LATE above), when the stage holds nothing else, and its 5 KB go to
-    // the stage instead -- 880 positions instead of 819 at r = 4: the 44 x 19-pixel regions of the bench's flows (7.4 % of the
-    // scale-4 tiles) are staged whole instead of as two halves.  The workgroup's LDS total is unchanged.
-    static constexpr bool kTabInStage = GFN_LEAN_TAB_IN_STAGE != 0 && R >= 3 && R <= 4;
+    // loop (measured level with filling it up front), when the stage holds nothing else, and its 5 KB go to the stage instead -- 880
+    // positions instead of 819 at r = 4: the 44 x 19-pixel regions of the bench's flows (7.4 % of the scale-4 tiles) are staged
+    // whole instead of as two halves.  The workgroup's LDS total is unchanged.
+    static constexpr bool kTabInStage = R >= 3;
     static constexpr int kTabBytes = ((64 * (2 * (2 * R + 1) + 1) + 16) * 4 + 15) & ~15;
     static constexpr int kStageLds = kStage + (kTabInStage ? kTabBytes : 0);   // bytes of LDS the stage spans
     static constexpr int kTabOff = (kDbuf + 15) & ~15;                         // table offset inside the stage (kTabInStage)
     static_assert(!kTabInStage || kTabOff + kTabBytes <= kStageLds, "the late table lies behind the D buffer");
     static constexpr int kCap = kStageLds / (kSlotV4 * 16);
-    static constexpr int kMinWaves = (R <= 2 && GFN_LEAN_STAGE2_KB <= 44) ? 6 : 4;  // waves per SIMD the register allocation must allow
+    static constexpr int kMinWaves = R <= 2 ? 6 : 4;  // waves per SIMD the register allocation must allow
     static constexpr int PW = 2 * R + 2;
 };
 
@@ -292,8 +279,7 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
     // and table rows start 32 DS / 32 TS dwords apart = on the same bank: every epilogue read was a 2-way conflict.  Rows of cells
     // 32-63 are skewed by 16 dwords.
     constexpr int kSkew = 16;
-    constexpr bool F0CH = Lean<R>::kF0Chunk;       // the f0 block goes through LDS one 16-channel chunk at a time
-    constexpr int CS = (F0CH ? kChunk : C) + 4;
+    constexpr int CS = C + 4;
     static_assert((NC * DS + kSkew) * 4 <= kStageBytes, "D buffer must fit in the stage it aliases");
 
     float4 *s4 = reinterpret_cast<float4 *>(smem);
@@ -313,24 +299,17 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
     const int G = p.G, H = p.H, W = p.W;
     const float xhi = p.win_xhi, xlo = -xhi, yhi = p.win_yhi, ylo = -yhi;
     const unsigned GG4 = (unsigned)(G * G) * 4u;  // bytes of a (G,G) plane
-#ifdef GFN_ABLATE
-    const bool stamping = ABL(p, 512) && (blockIdx.x % 1999) == 1000 && (tid & 63) == 0 && (tid >> 6) < 2;
-    long long stamp[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    STAMP(0);
 
     // ---- flow (wave 0), the f0 block and the first chunk's stage loads all go out at once ---------------------------------------
     // The tile kernels queue for the vector-memory pipe (a wave-load costs 30-40 cycles of the CU's texture-address path, and a
     // tile issued ~180 of them): every load that is not needed is gone.  lane = cell id (cells 0-31 left half, 32-63 right half);
     // only wave 0 reads the 64 flows and files the per-cell arrays; the fraction table is derived from those behind the barrier.
-#ifndef GFN_LEAN_FLOW_ALL
-#define GFN_LEAN_FLOW_ALL 0  // 1: every wave reads the flows (14 more loads per tile) and does its table share and patch addressing under the stage loads; 0: wave 0 only, both behind the barrier.  Measured level (r = 4: 98.1 / 148.1 vs 99.0 / 150.1 us): with two workgroups per CU the tile kernels are bound by the total of their vector instructions, not by where in the tile they sit
-#endif
-    constexpr bool kFlowAll = GFN_LEAN_FLOW_ALL != 0;
+    // (every wave reading the flows and doing its table share and patch addressing under the stage loads measured level: with two
+    // workgroups per CU the tile kernels are bound by the total of their vector instructions, not by where in the tile they sit)
     const int my_gi = row0 + cell_row(lane), my_gj = col0 + cell_col(lane);
     const bool my_ok = (my_gi < G) & (my_gj < G);
     float my_nx = 0.f, my_ny = 0.f;
-    if (kFlowAll || wave == 0) {  // scalar
+    if (wave == 0) {  // scalar
         const rsrc_t flr = make_rsrc(p.flow + (size_t)b * 2 * G * G, 2u * GG4);
         const unsigned fo = my_ok ? (unsigned)(my_gi * G + my_gj) * 4u : 0u;
         my_nx = buf_ld(flr, fo, 0u);
@@ -338,7 +317,7 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
     }
     // the tile's f0 block: wave w takes channels w, w + 8, ...; one 16-byte load per lane = four consecutive cells of a grid row of
     // one of them (lane >> 4 = which channel, lane & 15 = tile row and column quad): C / 32 loads per wave instead of C / 8
-    constexpr int NF0 = (F0CH ? kChunk : C) / kWaves;   // channels per wave (of the chunk, when staged chunk by chunk)
+    constexpr int NF0 = C / kWaves;                     // channels per wave
     constexpr int NF0L = (NF0 + 3) / 4;                 // loads per wave
     f32x4 f0q[NF0L];
     const int fk = lane >> 4, fr = (lane & 15) >> 2, fqd = lane & 3;
@@ -350,11 +329,12 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
     // instead of 2).  Now a wave takes NF0 CONSECUTIVE channels and the row of cell c is c ^ (tile row of c) -- the tile row XORed into
     // the column's low bits: 16 banks per pass (2-way: free for 4-byte stores).  The D-stage reads row f0_row(cell).
     auto f0_row = [](int cell) { return cell ^ ((cell >> 3) & 3); };
-    auto f0_issue = [&](int c0) {   // c0: first channel of the chunk (0 when the whole block is staged at once)
+    // (f0_issue / f0_commit stay lambdas: written out in place, the same code gets a different register allocation in every tile kernel)
+    auto f0_issue = [&]() {
         const bool in = f0_lane & (row0 + fr < G) & (col0 + 4 * fqd < G);
 #pragma unroll
         for (int l = 0; l < NF0L; ++l) {
-            const int ch = c0 + wave * NF0 + 4 * l + fk;
+            const int ch = wave * NF0 + 4 * l + fk;
             const unsigned fgoff = in ? (unsigned)((row0 + fr) * G + col0 + 4 * fqd) * 4u + (unsigned)ch * GG4 : 0u;
             f0q[l] = buf_ld4(f0r, fgoff, 0u);
         }
@@ -363,7 +343,7 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
         if (f0_lane) {
 #pragma unroll
             for (int l = 0; l < NF0L; ++l) {
-                const int ch = wave * NF0 + 4 * l + fk;   // channel inside what f0s holds
+                const int ch = wave * NF0 + 4 * l + fk;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int fc = 4 * fqd + e;
@@ -374,7 +354,7 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
             }
         }
     };
-    if (!ABL(p, 4)) f0_issue(0);
+    f0_issue();
     // items of a chunk in flight per wave.  r <= 2: the 40 KB stage holds 512 positions = 512 lane items of a 16-channel chunk = one
     // item per lane, so a second register set only ever repeated the first item's loads -- half of the kernel's vector-memory
     // instructions, each a full trip through the texture-address path
@@ -388,8 +368,7 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
     const QuadLane qlA = quad_lane(uA);
     const rsrc_t f1r = make_rsrc(f1_of<FT>(p, b), (unsigned)C * (unsigned)(H * W) * (unsigned)sizeof(FT));
     QuadRegs<PRE, FT> pre;
-    if (!ABL(p, 1)) quad_issue<PRE, CHECK, FT, kSlotV4, (R >= 3)>(pre, f1r, 0u, H, W, uA, wave, lane, qlA, 0);
-    STAMP(1);
+    quad_issue<PRE, CHECK, FT, kSlotV4, (R >= 3)>(pre, f1r, 0u, H, W, uA, wave, lane, qlA, 0);
     const QuadLane qlB = HALVES ? quad_lane(uB) : qlA;
 
     // ---- per-cell set-up (wave 0), f0 block and first chunk -> LDS ------------------------------------------------------------
@@ -403,7 +382,7 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
         const unsigned long long slow_mask = __ballot(c.flag == kCellSlow);
         if (lane == 0) hdr[4] = __popcll(slow_mask);
     }
-    if (!ABL(p, 4)) f0_commit();
+    f0_commit();
     auto fill_table = [&](float cnx, float cny, int cX0, int cY0) {
         // fraction table: the reference's fp32 coordinate of every tap column / row of every cell (local_correlation.py:55 adds
         // window offsets in normalised units, grid_sample un-normalises).  lane = cell, wave = tap index: no division.  Read by the
@@ -427,7 +406,6 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
         }
         return tab_bad;
     };
-    bool tab_bad = false;
     // ---- per-lane D-stage addressing: the float4 index of every (round, pass) patch position of the lane's cell ----------------------
     int g, s16;
     lane_group(lane, g, s16);
@@ -435,12 +413,8 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
     // Round 5: one register per (round, pass) holding the BYTE address of the position's slot (ds_read_b128 takes it as it is, the
     // four float4s of a slot through the instruction's offset field).  Rounds 2-4 packed two float4 indices per register because the
     // kernel sat at 128 VGPRs with the second-launch worker inlined; unpacking cost a v_and / v_bfe + v_lshl_add per position and
-    // chunk (~65 of a wave's ~1 030 vector instructions at r = 4).  -DGFN_LEAN_APK=1: the packed form.
-#ifndef GFN_LEAN_APK
-#define GFN_LEAN_APK 0
-#endif
-    constexpr bool kApk = GFN_LEAN_APK != 0;
-    unsigned apk[ROUNDS][kApk ? (NP + 1) / 2 : NP];
+    // chunk (~65 of a wave's ~1 030 vector instructions at r = 4).
+    unsigned apk[ROUNDS][NP];
     auto addressing = [&](int rd, int X0, int Y0) {
         const RowPlan &u = (HALVES && rd == 1) ? uB : uA;
         // cells without a patch (off the grid, flagged, empty) read slot 0 onwards: valid memory, result unused
@@ -451,54 +425,24 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
             const int yy = DivPW<PW>::div(pp), xx = pp - yy * PW;
             int slot = base + yy * u.pitch + xx;
             if (16 * t + 15 >= P) slot = pp < P ? slot : 0;  // positions past the patch (last pass only)
-            const unsigned a = (unsigned)(slot * kSlotV4);
-            if (!kApk)
-                apk[rd][t] = a * 16u;
-            else if (t & 1)
-                apk[rd][t >> 1] |= a << 16;
-            else
-                apk[rd][t >> 1] = a;
+            apk[rd][t] = (unsigned)(slot * kSlotV4) * 16u;
         }
     };
-    if (kFlowAll) {
-        // every wave has the 64 flows (lane = cell id): its share of the fraction table AND its lanes' patch addresses (the origins
-        // of the lane's two cells come from the lanes that hold them) are worked out under the stage loads' latency instead of
-        // behind the barrier, where they were ~3 k of a tile's 22 k cycles at r = 4 with nothing in flight
-        const CellBox c = cell_box<PW>(my_ok, my_ok ? my_nx : 0.f, my_ok ? my_ny : 0.f, xlo, ylo, W, H);
-        tab_bad = fill_table(my_ok ? my_nx : 0.f, my_ok ? my_ny : 0.f, c.X0, c.Y0);
-#pragma unroll
-        for (int rd = 0; rd < ROUNDS; ++rd) addressing(rd, __shfl(c.X0, rd * 32 + cr), __shfl(c.Y0, rd * 32 + cr));
-    }
-    STAMP(2);
-    if (!ABL(p, 1)) {
-        quad_commit<PRE, CHECK, FT>(s4, pre, H, W, uA, wave, lane, qlA, 0);
-        quad_rest<CHECK, FT>(s4, f1r, 0u, H, W, uA, wave, lane, qlA, PRE);
-    }
-    STAMP(3);
+    quad_commit<PRE, CHECK, FT>(s4, pre, H, W, uA, wave, lane, qlA, 0);
+    quad_rest<CHECK, FT>(s4, f1r, 0u, H, W, uA, wave, lane, qlA, PRE);
     __syncthreads();
-    STAMP(4);
-    // Round 5 experiment: the fraction table is only read by the epilogue; filled behind the main loop (-DGFN_LEAN_TABLE_LATE=1) it is
-    // out of the chain barrier -> addressing -> first product and runs beside the other waves' D-stages
-#ifndef GFN_LEAN_TABLE_LATE
-#define GFN_LEAN_TABLE_LATE 0  // measured level (r = 4: 96.5 vs 96.3 us, r = 2: 150.3 vs 153.9): the tile kernels are bound by what they issue, not by where in the tile it sits
-#endif
-    constexpr bool kTableLate = (GFN_LEAN_TABLE_LATE != 0 || kTabIn) && !kFlowAll;
-    static_assert(!kTabIn || !kFlowAll, "the table in the stage is filled behind the main loop");
-    if (!kTableLate) {
-        if (!kFlowAll && !ABL(p, 32)) tab_bad = fill_table(cellNx[lane], cellNy[lane], cellX0[lane], cellY0[lane]);
+    if (!kTabIn) {
+        const bool tab_bad = fill_table(cellNx[lane], cellNy[lane], cellX0[lane], cellY0[lane]);
         if (tab_bad && atomicOr(&cellFlag[lane], kCellSlow) == 0) atomicAdd(&hdr[4], 1);  // rare
     }
 
-    if (!kFlowAll) {
 #pragma unroll
-        for (int rd = 0; rd < ROUNDS; ++rd) addressing(rd, cellX0[rd * 32 + cr], cellY0[rd * 32 + cr]);
-    }
+    for (int rd = 0; rd < ROUNDS; ++rd) addressing(rd, cellX0[rd * 32 + cr], cellY0[rd * 32 + cr]);
     float acc[ROUNDS][NP];
 #pragma unroll
     for (int rd = 0; rd < ROUNDS; ++rd)
 #pragma unroll
         for (int t = 0; t < NP; ++t) acc[rd][t] = 0.f;
-    STAMP(5);
 
     // ---- main loop: 16 channels at a time (per half when the tile is staged in halves) ------------------------------------
     constexpr int NS = HALVES ? 2 * NCH : NCH;  // steps: (half, chunk)
@@ -515,26 +459,22 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
 #pragma unroll
         for (int rd = 0; rd < ROUNDS; ++rd)
 #pragma unroll
-            for (int h = 0; h < (kApk ? (NP + 1) / 2 : NP); ++h) asm volatile("" : "+v"(apk[rd][h]));  // keep the (packed) addresses as they are: no recomputation per chunk
-        if (more && !ABL(p, 1)) {  // next step's loads: in flight across this D-stage
+            for (int h = 0; h < NP; ++h) asm volatile("" : "+v"(apk[rd][h]));  // keep the addresses as they are: no recomputation per chunk
+        if (more)  // next step's loads: in flight across this D-stage
             quad_issue<PRE, CHECK, FT, kSlotV4, (R >= 3)>(pre, f1r, next_off, H, W, un, wave, lane, qn, 0);
-            if (F0CH) f0_issue(nch * kChunk);
-        }
 #pragma unroll
         for (int rd = 0; rd < ROUNDS; ++rd) {
             if (HALVES && rd != half) continue;
-            if (ABL(p, 2)) continue;
             float f[kChunk];
             {
-                const float4 *fq = reinterpret_cast<const float4 *>(f0s + f0_row(rd * 32 + cr) * CS + (F0CH ? 0 : c0));
+                const float4 *fq = reinterpret_cast<const float4 *>(f0s + f0_row(rd * 32 + cr) * CS + c0);
                 const float4 a0 = fq[0], a1 = fq[1], a2 = fq[2], a3 = fq[3];
                 f[0] = a0.x; f[1] = a0.y; f[2] = a0.z; f[3] = a0.w; f[4] = a1.x; f[5] = a1.y; f[6] = a1.z; f[7] = a1.w;
                 f[8] = a2.x; f[9] = a2.y; f[10] = a2.z; f[11] = a2.w; f[12] = a3.x; f[13] = a3.y; f[14] = a3.z; f[15] = a3.w;
             }
 #pragma unroll
             for (int t = 0; t < NP; ++t) {
-                const float4 *q = kApk ? s4 + ((t & 1) ? (apk[rd][t >> 1] >> 16) : (apk[rd][t >> 1] & 0xFFFFu))
-                                       : reinterpret_cast<const float4 *>(smem + apk[rd][t]);
+                const float4 *q = reinterpret_cast<const float4 *>(smem + apk[rd][t]);
                 const float4 v0 = q[0], v1 = q[1], v2 = q[2], v3 = q[3];
                 float a = acc[rd][t];
                 a = fmaf(f[0], v0.x, a);  a = fmaf(f[1], v0.y, a);  a = fmaf(f[2], v0.z, a);  a = fmaf(f[3], v0.w, a);
@@ -549,29 +489,18 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
         for (int rd = 0; rd < ROUNDS; ++rd)
 #pragma unroll
             for (int t = 0; t < NP; ++t) asm volatile("" : "+v"(acc[rd][t]));  // pins the FMAs above this point
-        STAMP(st == 0 ? 6 : 9);
         if (more) {
             __syncthreads();  // everyone is done reading this step's pixels
-            STAMP(7);
-            if (!ABL(p, 1)) {
-                quad_commit<PRE, CHECK, FT>(s4, pre, H, W, un, wave, lane, qn, 0);
-                quad_rest<CHECK, FT>(s4, f1r, next_off, H, W, un, wave, lane, qn, PRE);
-            }
-            if (F0CH) f0_commit();
+            quad_commit<PRE, CHECK, FT>(s4, pre, H, W, un, wave, lane, qn, 0);
+            quad_rest<CHECK, FT>(s4, f1r, next_off, H, W, un, wave, lane, qn, PRE);
             __syncthreads();
-            STAMP(8);
         }
     }
 
     // ---- epilogue: D -> LDS, bilinear combination, coalesced stores ----------------------------------------------------
-    if (kTableLate && !kTabIn) {
-        if (!ABL(p, 32)) tab_bad = fill_table(cellNx[lane], cellNy[lane], cellX0[lane], cellY0[lane]);
-        if (tab_bad && atomicOr(&cellFlag[lane], kCellSlow) == 0) atomicAdd(&hdr[4], 1);  // rare
-    }
     __syncthreads();
-    STAMP(10);
     if (kTabIn) {   // behind the barrier: nobody reads staged pixels any more, the table goes where they were (beside the D buffer)
-        if (!ABL(p, 32)) tab_bad = fill_table(cellNx[lane], cellNy[lane], cellX0[lane], cellY0[lane]);
+        const bool tab_bad = fill_table(cellNx[lane], cellNy[lane], cellX0[lane], cellY0[lane]);
         if (tab_bad && atomicOr(&cellFlag[lane], kCellSlow) == 0) atomicAdd(&hdr[4], 1);  // rare
     }
 #pragma unroll
@@ -580,19 +509,17 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
 #pragma unroll
         for (int t = 0; t < NP; ++t) {
             const int pp = s16 + 16 * t;
-            if (pp < P && !ABL(p, 16)) dbuf[cell * DS + rd * kSkew + pp] = acc[rd][t];
+            if (pp < P) dbuf[cell * DS + rd * kSkew + pp] = acc[rd][t];
         }
     }
-    STAMP(11);
     __syncthreads();
-    STAMP(12);
     {
         // lane -> cell so that a wave stores whole 64-byte grid-row segments: tile row lane >> 4, column lane & 15
         const int er = lane >> 4, ec = lane & 15;
         const int cell = ((ec >> 3) << 5) | (er << 3) | (ec & 7);
         const int gi = row0 + er, gj = col0 + ec;
         const int flag = cellFlag[cell];
-        if ((gi < G) & (gj < G) & !(flag & kCellSlow) & !ABL(p, 8)) {
+        if ((gi < G) & (gj < G) & !(flag & kCellSlow)) {
             const bool empty = (flag & kCellEmpty) != 0;
             const float *dc = dbuf + cell * DS + (ec >> 3) * kSkew;
             const float *tc = tab + cell * TS + (ec >> 3) * kSkew;
@@ -617,27 +544,14 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
 #pragma unroll
                     for (int kx = 0; kx < D; ++kx) {
                         const float val = fmaf(m[kx + 1], wx1[kx], m[kx] * wx0[kx]);
-                        if (!ABL(p, 128)) buf_st_nt(outr, goff, (unsigned)(ky * D + kx) * GG4, empty ? 0.f : val);
-                        else asm volatile("" :: "v"(val));  // streamed: nothing on the hot path reads it back
+                        buf_st_nt(outr, goff, (unsigned)(ky * D + kx) * GG4, empty ? 0.f : val);  // streamed: nothing on the hot path reads it back
                     }
                 }
             }
         }
     }
-    STAMP(13);
-#ifdef GFN_ABLATE
-    if (stamping)
-        printf("lean r%d wave %d (cycles from entry): all issued %lld | cells+table+f0 in LDS %lld | stage0 committed %lld | barrier %lld | addressing %lld | "
-               "D0 %lld | barrier %lld | stage1 committed+barrier %lld | D1 %lld | barrier %lld | dbuf %lld | barrier %lld | stores issued %lld\n",
-               R, tid >> 6, stamp[1] - stamp[0], stamp[2] - stamp[0], stamp[3] - stamp[0], stamp[4] - stamp[0], stamp[5] - stamp[0], stamp[6] - stamp[0],
-               stamp[7] - stamp[0], stamp[8] - stamp[0], stamp[9] - stamp[0], stamp[10] - stamp[0], stamp[11] - stamp[0], stamp[12] - stamp[0],
-               stamp[13] - stamp[0]);
-#endif
 
     // ---- flagged cells: general per-tap routine (about one cell in 10^4) ---------------------------------------------
-#ifdef GFN_LEAN_ANALYZE
-    return;
-#endif
     const int nslow = __builtin_amdgcn_readfirstlane(hdr[4]);
     if (nslow != 0) {  // block-uniform, rare
         __syncthreads();
@@ -668,15 +582,11 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
 // under wild flow (every tile listed, the tile workgroups leaving at once) they have the chip like the separate launch had.
 // Round 5 A/B: with the worker inlined the r >= 3 kernels' metadata shows 72-79 VGPR spills, ~160 SGPR spills and
 // ~300 bytes of scratch -- all of it in the worker branch (the ISA of the four lean_tile variants has no scratch access and 20 SGPR
-// spills, exactly what the -DGFN_LEAN_INLINE_WORKERS=0 build shows for the whole kernel: 117-123 VGPRs, no spills, no scratch).
-// As a launch of its own behind the tile kernel the worker costs nothing when the list is empty (94.7 vs 95.1 us, r = 4, 64
-// directions) but 12 us of serial tail when three tiles are listed, which is the bench's situation (95.9 vs 108.5 us): the inlined
-// form stays the default.
-#ifndef GFN_LEAN_INLINE_WORKERS
-#define GFN_LEAN_INLINE_WORKERS 1
-#endif
+// spills; without the worker the kernel takes 117-123 VGPRs, no spills, no scratch).  As a launch of its own behind the tile kernel
+// the worker costs nothing when the list is empty (94.7 vs 95.1 us, r = 4, 64 directions) but 12 us of serial tail when three tiles
+// are listed, which is the bench's situation (95.9 vs 108.5 us): the worker stays inlined.
 template <int R>
-constexpr int lean_workers() { return (GFN_LEAN_INLINE_WORKERS && R >= 3) ? 256 : 0; }  // a multiple of 8: the XCD of a tile's workgroup does not change
+constexpr int lean_workers() { return R >= 3 ? 256 : 0; }  // a multiple of 8: the XCD of a tile's workgroup does not change
 
 // one 4 x 16-cell tile `wid` from its plan record: the body of the tile kernel
 template <int R, int NCH, typename FT>
@@ -699,17 +609,8 @@ __device__ __forceinline__ void lean_small_tile(const LcParams &p, unsigned char
     // pitch, quads per row and items as the plan launch worked them out (region_fits, checked there)
     uA.pitch = pl[7] & 0xff; uA.nq = (pl[7] >> 8) & 0xff; uA.nitems = pl[7] >> 16;
     uB.pitch = pg[0] & 0xff; uB.nq = (pg[0] >> 8) & 0xff; uB.nitems = pg[0] >> 16;
-    if (ABL(p, 64)) {  // timing experiment: what a row ring would stage per tile
-        uA.h = min(uA.h, 7); uB.h = min(uB.h, 7);
-        (void)region_fits<R>(uA);
-        (void)region_fits<R>(uB);
-    }
     const int b = pg[1], row0 = pg[2] & 0xffff, col0 = pg[2] >> 16;
     const bool interior = (flags & kPlanInterior) != 0;
-#ifdef GFN_LEAN_ANALYZE  // ISA reading aid (tools/dump_isa.py): only the interior whole-tile variant, so that the hot path is straight-line code in the dump
-    lean_tile<R, NCH, false, false, FT>(p, smem, uA, uB, b, row0, col0, tid, lane, wave);
-    return;
-#endif
     if (flags & kPlanHalves) {
         if (interior) lean_tile<R, NCH, false, true, FT>(p, smem, uA, uB, b, row0, col0, tid, lane, wave);
         else lean_tile<R, NCH, true, true, FT>(p, smem, uA, uB, b, row0, col0, tid, lane, wave);

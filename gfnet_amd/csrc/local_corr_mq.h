@@ -16,18 +16,14 @@
 //   * no plan launch: the workgroup derives its region from the 32 flows itself (wave 0; the other waves' f0 loads cover the
 //     round trip); a tile whose windows do not fit the groups' accumulators runs the round-1 routine (fp32 FMAs) in this workgroup,
 //     which leaves what does not fit its stage either to the second launch (2 x 8-cell sub-tiles).
-// Where a tile's ~27 k cycles go (tools/stamp_local_corr.py 64 64 70 40 6, GFN_ABLATE build): 4.5-5 k until the region is known (kernel
+// Where a tile's ~27 k cycles go (s_memtime stamps at the phase boundaries): 4.5-5 k until the region is known (kernel
 // arguments, the flows' round trip to memory, ~400 instructions of one wave), 6 k until chunk 0 is filed, 4 x 2.8 k per chunk -- of which
 // the products are 0.3-0.6 k and the rest the next chunk's loads arriving and being split -- 4 k to file the accumulators and store.
 // The matrix core took the D-stage off the critical path; what is left is the latency of dependent loads with two workgroups per CU to
 // overlap it.  Tried without effect: the flows through the scalar cache (s_load_dwordx16 + v_writelane) and s_setprio for the set-up
 // wave (the wait is the memory round trip, not queueing or issue slots); skipping empty staging items by a branch.
 // Numerics: split-bf16 (local_corr_mstage.h; products exact in fp32 up to 2^-17 relative per term, fp32 accumulation; fp16 maps split
-// exactly), not bit-identical to the fp32 FMA kernels.  -DGFN_MQ=0 builds keep r >= 5 on the round-1 kernel.
-
-#ifndef GFN_MQ
-#define GFN_MQ 1
-#endif
+// exactly), not bit-identical to the fp32 FMA kernels (variant 4 of gfn_local_corr_fwd_dt keeps r >= 5 on them).
 
 constexpr int kMqLds = 80 * 1024;   // >= the round-1 routine's 68 KB stage + cells + f0 block at C = 64 (79 008 bytes)
 
@@ -84,11 +80,6 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_mq_kernel(LcParams p) 
     const int b = wid / tiles, tile = wid - b * tiles;
     const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
     const int row0 = ty * 2, col0 = tx * kTileW;
-#ifdef GFN_ABLATE
-    const bool stamping = ABL(p, 512) && blockIdx.x == 2000 && (tid & 63) == 0 && (tid >> 6) < 2;
-    long long stamp[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    STAMP(0);
 
     // ---- the f0 block: wave w takes channels 8 w .., lane = channel (lane >> 3) x quad of cells (tile row, four columns) ----------
     const int k8 = lane >> 3, fr = (lane & 7) >> 2, fc4 = (lane & 3) * 4;
@@ -150,9 +141,7 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_mq_kernel(LcParams p) 
             hdr[5] = fits ? 1 : ((long)w4r * h <= kStageBytes / (kSlotV4 * 16) - 1 ? 2 : 0);
         }
     }
-    STAMP(1);
     __syncthreads();
-    STAMP(2);
     MmRegion u;
     u.x0 = __builtin_amdgcn_readfirstlane(hdr[0]); u.y0 = __builtin_amdgcn_readfirstlane(hdr[1]);
     u.w = __builtin_amdgcn_readfirstlane(hdr[2]); u.h = __builtin_amdgcn_readfirstlane(hdr[3]);
@@ -180,7 +169,6 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_mq_kernel(LcParams p) 
     for (int n = 0; n < kMmPre; ++n) ml.it[n] = mm_item<M, NW, true, FT, true>(u, H, W, wave, lane, n);
     MmRegs<FT> pre;
     mm_issue<true, FT, true>(pre, f1r, 0u, H, W, u, ipw, ml);
-    STAMP(3);
 
     // ---- f0 block -> bf16 hi / lo: lanes k8 and k8 ^ 1 exchange, so that each files channel PAIRS (32-bit writes) of two cells -----
     {
@@ -255,9 +243,7 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_mq_kernel(LcParams p) 
 
     mm_commit<M, true, FT>(smem, pre, ipw, ml);
     mm_rest<M, NW, true, FT>(smem, f1r, 0u, H, W, u, ipw, wave, lane);
-    STAMP(4);
     __syncthreads();
-    STAMP(5);
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
         const bool more = ch + 1 < NCH;
@@ -290,7 +276,6 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_mq_kernel(LcParams p) 
             __syncthreads();
         }
     }
-    STAMP(6);
     __syncthreads();  // the D buffer aliases the stage
     if (__builtin_amdgcn_readfirstlane(hdr[6]) == 0) {  // border tile: window positions outside the image are zeros nobody computes
         float4 *d4 = reinterpret_cast<float4 *>(dbuf);
@@ -320,9 +305,7 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_mq_kernel(LcParams p) 
             }
         }
     }
-    STAMP(7);
     __syncthreads();
-    STAMP(8);
     {
         // lanes 0-31 -> the tile's cells so that a wave stores whole 64-byte grid-row segments; tap row ky = 2 wave + (lane >> 5)
         const int er = (lane >> 4) & 1, ec = lane & 15;
@@ -356,7 +339,6 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_mq_kernel(LcParams p) 
             }
         }
     }
-    STAMP(9);
     // ---- flagged cells: general per-tap routine (about one cell in 10^4) -----------------------------------------------------------
     const int nslow = __builtin_amdgcn_readfirstlane(hdr[4]);
     if (nslow != 0) {  // block-uniform, rare
@@ -377,11 +359,4 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_mq_kernel(LcParams p) 
                 tap_general<FT>(p, b, gi, gj, k / D, k % D, D, cellNx[cell], cellNy[cell]);
         }
     }
-#ifdef GFN_ABLATE
-    if (stamping)
-        printf("mq r%d wave %d (cycles): set-up %lld | barrier %lld | chunk 0 issued %lld | committed %lld | barrier %lld | products %lld | "
-               "filed %lld | barrier %lld | stores issued %lld\n",
-               R, tid >> 6, stamp[1] - stamp[0], stamp[2] - stamp[0], stamp[3] - stamp[0], stamp[4] - stamp[0], stamp[5] - stamp[0],
-               stamp[6] - stamp[0], stamp[7] - stamp[0], stamp[8] - stamp[0], stamp[9] - stamp[0]);
-#endif
 }

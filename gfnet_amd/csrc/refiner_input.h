@@ -167,10 +167,7 @@ __device__ __forceinline__ void refiner_input_cell(const RiArgs &args, int b, un
     const float lo = (float)(-1 + 1.0 / G), hi = (float)(1 - 1.0 / G);
     const unsigned plane = (unsigned)(Hs * Ws), GG = (unsigned)(G * G);
     if (cell >= GG) return;
-#ifndef GFN_RI_WAVE2D
-#define GFN_RI_WAVE2D 1
-#endif
-    if (GFN_RI_WAVE2D && (G & 31) == 0) {
+    if ((G & 31) == 0) {
         // Round 6: a wave's 64 cells are 2 grid rows x 32 columns instead of 1 x 64.  The x_hat gathers follow the flow: under the
         // bench's homographies a 64-lane pair gather of a 1 x 64 wave touches 13.9 128-byte lines (rows drift with the rotation), of a
         // 2 x 32 wave 11.3; the regular grid_feature gather goes from 4 to 5 lines, the stores stay two full lines per instruction

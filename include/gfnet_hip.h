@@ -132,12 +132,12 @@ int gfn_corr_softargmax_fwd(const float *f0, const float *f1, float *flow, int B
 int gfn_corr_softargmax_fwd_dt(const void *f0, const void *f1, int dtype, float *flow, int B, int C, int H0, int W0, int H1, int W1,
                                int symmetric, gfn_stream_t stream);
 /* The same with a caller-owned workspace (round 6).  On 33..64-channel maps whose rows are 32..64 positions wide (GFNet's stride-16
- * features, model/network.py:251-252) the products run on the bf16 matrix core instruction with both operands split three ways
- * (x = h + m + l exactly; six of the nine piece products kept, the dropped ones <= 2^-23 of |a||b|: measured closer to a float64
- * evaluation than the fp32 fma chains of the calls above); with ws_bytes >= gfn_corr_softargmax_ws_bytes(B, C, H1, W1) the
- * B-positions' operand is split ONCE into ws (16-byte aligned device memory, contents undefined afterwards) instead of by every
- * wave that walks it.  ws == NULL or too small: same results, slower.  gfn_corr_softargmax_ws_bytes returns 0 for shapes that
- * take no workspace. */
+ * features, model/network.py:251-252) the products of all three flow calls run on the bf16 matrix core instruction with both operands
+ * split three ways (x = h + m + l exactly; six of the nine piece products kept, the dropped ones <= 2^-23 of |a||b|: measured closer
+ * to a float64 evaluation than fp32 fma chains).  gfn_corr_softargmax_fwd and _dt split the operands inside the kernel, every wave
+ * again; here, with ws_bytes >= gfn_corr_softargmax_ws_bytes(B, C, H1, W1), the B-positions' operand is split ONCE into ws (16-byte
+ * aligned device memory, contents undefined afterwards).  ws == NULL or too small: same results as the in-kernel split, slower.
+ * gfn_corr_softargmax_ws_bytes returns 0 for shapes that take no workspace. */
 int64_t gfn_corr_softargmax_ws_bytes(int B, int C, int H1, int W1);
 int gfn_corr_softargmax_fwd_ws(const void *f0, const void *f1, int dtype, float *flow, int B, int C, int H0, int W0, int H1, int W1,
                                int symmetric, void *ws, int64_t ws_bytes, gfn_stream_t stream);
@@ -339,10 +339,8 @@ int gfn_pointwise_conv_fwd(const float *w, const float *bias, const float *t, fl
  *   between two blocks is a float16 tensor (torch.autocast around block1 + hidden_blocks, model/network.py:560-562).
  *   Arithmetic = the autocast class: the depthwise 5x5 runs on the matrix core too (v_mfma_f32_16x16x32_f16: the input halo --
  *   also a first block's fp32 concat -- and the folded taps rounded to fp16, fp32 accumulation), BatchNorm + ReLU fp32, ReLU output
- *   and 1x1 weights fp16, fp32 accumulation; builds with -DGFN_CONV_VALU_DW keep the depthwise in fp32 as gfn_conv_block_fwd
- *   variant 2 does.  A map of
- *   dtype GFN_F16 is (B, ceil(C/2), G, G) of half2: channels 2p and 2p+1 of a cell side by side, the odd channel past C zero
- *   (the kernel writes it so).  x_dtype / y_dtype: GFN_F32 (B, C, G, G) floats or GFN_F16; at least one of them GFN_F16 (a
+ *   and 1x1 weights fp16, fp32 accumulation.  A map of dtype GFN_F16 is (B, ceil(C/2), G, G) of half2: channels 2p and 2p+1 of
+ *   a cell side by side, the odd channel past C zero (the kernel writes it so).  x_dtype / y_dtype: GFN_F32 (B, C, G, G) floats or GFN_F16; at least one of them GFN_F16 (a
  *   stack's first block reads the fp32 concat, its last one writes fp32).  G must be a multiple of 4. */
 int gfn_conv_block_half_fwd(const void *x, int x_dtype, const float *packed, void *y, int y_dtype, int B, int C, int M, int G,
                             gfn_stream_t stream);

@@ -136,8 +136,8 @@ def test_product_kernels_keep_their_register_budget():
     """spills of the product kernels are tracked, not discovered.  From the metadata of the built objects
     (tools/kernel_regs.py): the fp32 instantiations of the default local-correlation paths stay spill-free where they are today
     (lean r <= 2, the r >= 5 matrix-core kernel), the known exceptions stay bounded -- the lean r = 3 / 4 kernels carry the
-    second-launch worker path (<= 80 spilled registers, all in the worker branch: the -DGFN_LEAN_INLINE_WORKERS=0 build of the same
-    kernels has no spills and no scratch, csrc/local_corr_lean.h; round 5 measured the separate launch 12 us slower under the
+    second-launch worker path (<= 80 spilled registers, all in the worker branch: round 5 built the same kernels without the
+    worker: no spills and no scratch, csrc/local_corr_lean.h; it measured the separate launch 12 us slower under the
     bench's flows and kept the inlined form).  The fp16 instantiations of the r >= 5 kernels (pyramids
     stored in fp16, BASELINE configs[4]) spilled 16-39 registers until round 4: the choice between the two staging forms was a run-time
     flag for fp16 maps (even / odd width) and both forms' load registers were live at once; it is a template parameter now (QOK) and
