@@ -1,5 +1,4 @@
-// local_corr_lean.h -- the round-2 tile path of the local correlation (r <= 4).  Included by local_corr.hip inside its
-// anonymous namespace (shares LcParams, cell_coords, tap_general, lane_group, wave_min_i32, unnorm, f1_of).
+// local_corr_lean.h -- the round-2 tile path of the local correlation (r <= 4).
 //
 // Same tile (4 x 16 cells), LDS slot layout, D-stage and arithmetic as process_tile<R, 2, true, 16, false>: results are
 // bit-identical to the round-1 kernel (tests/test_local_corr_gpu.py).  What changed is everything around the D-stage.
@@ -22,8 +21,13 @@
 //     slot; cells whose window misses the image entirely never enter the box and get exact zeros from the epilogue;
 //   * tile = two 4 x 8-cell halves (cells 0-31 / 32-63), the epilogue still stores 64-byte row segments;
 //   * fraction table: lane = cell, wave = tap index (no division); stores use scalar plane offsets.
+#pragma once
+#include "local_corr_common.h"
+#include "local_corr_stage.h"
+#include "local_corr_tile.h"
+#include "refiner_input.h"
 
-constexpr int kMmNBW = 10;  // local_corr_mq.h: accumulator blocks per wave of the matrix-core kernel (a group's box: <= 2 kMmNBW rows)
+namespace {
 
 constexpr int kPlanInts = 16;  // per tile: region A x0, y0, (h << 16) | w, flags; region B x0, y0, (h << 16) | w, geometry of A;
                                // geometry of B, direction b, row0 | col0 << 16, spare ...  (geometry = pitch | quads per row << 8 | items << 16:
@@ -60,6 +64,8 @@ struct Lean {
     static constexpr int kTabOff = (kDbuf + 15) & ~15;                         // table offset inside the stage (kTabInStage)
     static_assert(!kTabInStage || kTabOff + kTabBytes <= kStageLds, "the late table lies behind the D buffer");
     static constexpr int kCap = kStageLds / (kSlotV4 * 16);
+    // dynamic LDS of the tile kernel: stage (with the table at r = 3, 4), cell arrays, (r <= 2) the table, the f0 block
+    static constexpr size_t lds(int C) { return kStageLds + ((64 * 20 + 32 + 15) & ~15) + (kTabInStage ? 0 : kTabBytes) + (size_t)64 * (C + 4) * 4; }
     static constexpr int kMinWaves = R <= 2 ? 6 : 4;  // waves per SIMD the register allocation must allow
     static constexpr int PW = 2 * R + 2;
 };
@@ -98,7 +104,6 @@ __device__ __forceinline__ CellBox cell_box(bool ok, float nx, float ny, float x
     return c;
 }
 
-
 template <int R>
 __device__ __forceinline__ bool region_fits(RowPlan &u) {
     constexpr int PW = Lean<R>::PW;
@@ -111,15 +116,6 @@ __device__ __forceinline__ bool region_fits(RowPlan &u) {
     // branches around loads, exact wait counts)
     u.nitems = ((u.h * u.nq + 15) / 16 + 7) & ~7;
     return true;
-}
-
-// min over each row of 16 lanes (a 2 x 8-cell group), valid in lane 15 of the row
-__device__ __forceinline__ int row_min_i32(int v) {
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x111, 0xf, 0xf, false));  // row_shr:1
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x112, 0xf, 0xf, false));  // row_shr:2
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x114, 0xf, 0xf, false));  // row_shr:4
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x118, 0xf, 0xf, false));  // row_shr:8
-    return v;
 }
 
 // ---- plan launch: a wave plans kPlanPerWave tiles (all their flow loads in flight together) -----------------------------
@@ -189,18 +185,16 @@ __device__ __forceinline__ void plan_tiles(const LcParams &p, unsigned wid0, uns
                 return region_fits<R>(u);
             };
             RowPlan ua, ub;
-            const bool border_ok = true;
             int flags = all_in ? kPlanInterior : 0;
-            const bool full = region(min(hx0[0], hx0[1]), min(hy0[0], hy0[1]), max(hx1[0], hx1[1]), max(hy1[0], hy1[1]), ua) && border_ok;
+            const bool full = region(min(hx0[0], hx0[1]), min(hy0[0], hy0[1]), max(hx1[0], hx1[1]), max(hy1[0], hy1[1]), ua);
             ub = ua;
             if (!full) {
                 const bool fa = region(hx0[0], hy0[0], hx1[0], hy1[0], ua), fb = region(hx0[1], hy0[1], hx1[1], hy1[1], ub);
-                flags |= (fa && fb && border_ok) ? kPlanHalves : kPlanSecond;
+                flags |= (fa && fb) ? kPlanHalves : kPlanSecond;
             }
             int4 pl0, pl1;
             pl0.x = ua.x0; pl0.y = ua.y0; pl0.z = (ua.h << 16) | ua.w; pl0.w = flags;
-            pl1.x = ub.x0; pl1.y = ub.y0; pl1.z = (ub.h << 16) | ub.w; pl1.w = 0;
-            pl1.w = plan_geometry(ua);
+            pl1.x = ub.x0; pl1.y = ub.y0; pl1.z = (ub.h << 16) | ub.w; pl1.w = plan_geometry(ua);
             const int wb = (int)(wid / (unsigned)tiles), wt = (int)(wid - (unsigned)wb * (unsigned)tiles);
             const int wty = wt / p.tiles_x, wtx = wt - wty * p.tiles_x;
             reinterpret_cast<int4 *>(p.plan)[kPlanV4 * wid] = pl0;
@@ -386,7 +380,7 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
     auto fill_table = [&](float cnx, float cny, int cX0, int cY0) {
         // fraction table: the reference's fp32 coordinate of every tap column / row of every cell (local_correlation.py:55 adds
         // window offsets in normalised units, grid_sample un-normalises).  lane = cell, wave = tap index: no division.  Read by the
-        // epilogue, barriers from here.
+        // epilogue, barriers from here.  A cell whose taps do not start where its patch says is flagged for the per-tap routine.
         bool tab_bad = false;
         constexpr int NTAB = (2 * D + kWaves - 1) / kWaves;
 #pragma unroll
@@ -404,7 +398,7 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
                 tab[lane * TS + (lane >> 5) * kSkew + a] = pix - fl;
             }
         }
-        return tab_bad;
+        if (tab_bad && atomicOr(&cellFlag[lane], kCellSlow) == 0) atomicAdd(&hdr[4], 1);  // rare
     };
     // ---- per-lane D-stage addressing: the float4 index of every (round, pass) patch position of the lane's cell ----------------------
     int g, s16;
@@ -431,10 +425,7 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
     quad_commit<PRE, CHECK, FT>(s4, pre, H, W, uA, wave, lane, qlA, 0);
     quad_rest<CHECK, FT>(s4, f1r, 0u, H, W, uA, wave, lane, qlA, PRE);
     __syncthreads();
-    if (!kTabIn) {
-        const bool tab_bad = fill_table(cellNx[lane], cellNy[lane], cellX0[lane], cellY0[lane]);
-        if (tab_bad && atomicOr(&cellFlag[lane], kCellSlow) == 0) atomicAdd(&hdr[4], 1);  // rare
-    }
+    if (!kTabIn) fill_table(cellNx[lane], cellNy[lane], cellX0[lane], cellY0[lane]);
 
 #pragma unroll
     for (int rd = 0; rd < ROUNDS; ++rd) addressing(rd, cellX0[rd * 32 + cr], cellY0[rd * 32 + cr]);
@@ -499,10 +490,8 @@ __device__ __forceinline__ void lean_tile(const LcParams &p, unsigned char *smem
 
     // ---- epilogue: D -> LDS, bilinear combination, coalesced stores ----------------------------------------------------
     __syncthreads();
-    if (kTabIn) {   // behind the barrier: nobody reads staged pixels any more, the table goes where they were (beside the D buffer)
-        const bool tab_bad = fill_table(cellNx[lane], cellNy[lane], cellX0[lane], cellY0[lane]);
-        if (tab_bad && atomicOr(&cellFlag[lane], kCellSlow) == 0) atomicAdd(&hdr[4], 1);  // rare
-    }
+    // behind the barrier: nobody reads staged pixels any more, the table goes where they were (beside the D buffer)
+    if (kTabIn) fill_table(cellNx[lane], cellNy[lane], cellX0[lane], cellY0[lane]);
 #pragma unroll
     for (int rd = 0; rd < ROUNDS; ++rd) {
         const int cell = rd * 32 + cr;
@@ -635,3 +624,5 @@ __global__ __launch_bounds__(kThreads, Lean<R>::kMinWaves) void local_corr_tile2
     const unsigned wid = gfn::xcd_remap(blockIdx.x - kLeanWorkers, gridDim.x - kLeanWorkers);
     lean_small_tile<R, NCH, FT>(p, smem, wid, tid, lane, wave);
 }
+
+}  // namespace

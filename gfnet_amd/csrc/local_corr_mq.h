@@ -1,7 +1,7 @@
 // local_corr_mq.h -- round 3: large windows (r >= 5 on 64-channel maps: GFNet's r = 6 at stride 8 and r = 7 at stride 16) with the
-// D-stage on the matrix core.  Included by local_corr.hip after local_corr_mstage.h: the split-bf16 formulation, the swizzled slots,
-// the staging helpers (mm_item / mm_issue / mm_commit) and the guarded D buffer are that file's; what differs is the shape of the
-// kernel around them.
+// D-stage on the matrix core.  The split-bf16 formulation, the swizzled slots, the staging helpers (mm_item / mm_issue / mm_commit) and
+// the guarded D buffer are local_corr_mstage.h's, the cell boxes local_corr_lean.h's; what differs is the shape of the kernel around
+// them.
 //
 // Why here and not at r = 3, 4: a cell at r = 6 / 7 takes 196 / 256 products per channel (r = 4: 100) and the round-1 kernel's
 // D-stage feeds every v_fma_f32 with an LDS dword of its own -- at these radii that stage is ~2 k cycles per 16-channel chunk and
@@ -24,7 +24,16 @@
 // wave (the wait is the memory round trip, not queueing or issue slots); skipping empty staging items by a branch.
 // Numerics: split-bf16 (local_corr_mstage.h; products exact in fp32 up to 2^-17 relative per term, fp32 accumulation; fp16 maps split
 // exactly), not bit-identical to the fp32 FMA kernels (variant 4 of gfn_local_corr_fwd_dt keeps r >= 5 on them).
+#pragma once
+#include "local_corr_common.h"
+#include "local_corr_lean.h"
+#include "local_corr_mstage.h"
+#include "local_corr_stage.h"
+#include "local_corr_tile.h"
 
+namespace {
+
+constexpr int kMmNBW = 10;  // accumulator blocks per wave (a group's box: <= 2 kMmNBW rows)
 constexpr int kMqLds = 80 * 1024;   // >= the round-1 routine's 68 KB stage + cells + f0 block at C = 64 (79 008 bytes)
 
 template <int R, int C>
@@ -43,8 +52,7 @@ struct Mq {
     static constexpr int kStage = (kMqLds - kCellBytes - kTabBytes - kF0Bytes) & ~127;
     static constexpr int kCap = kStage / SLOT - 32;             // positions that fit (a block may read 31 slots past the region's end)
     static_assert(kDbufBytes <= kStage, "the D buffer aliases the stage");
-    // what process_tile<R, 1, true, kTileW, false> lays out when this kernel hands it a tile: stage + cell arrays + f0 block [32][C + 4]
-    static_assert(kStageBytes + ((32 * 20 + 32 + 15) & ~15) + 32 * (C + 4) * 4 <= kMqLds, "the round-1 routine must fit this kernel's LDS");
+    static_assert(round1_lds(R, C) <= kMqLds, "the round-1 routine (process_tile) must fit this kernel's LDS: it hands it tiles");
     static_assert(C % 16 == 0 && C == 64, "built for 64-channel maps (8 waves x 8 channels of the f0 block)");
 };
 
@@ -360,3 +368,5 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_mq_kernel(LcParams p) 
         }
     }
 }
+
+}  // namespace

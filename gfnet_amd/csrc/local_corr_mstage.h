@@ -1,6 +1,5 @@
 // local_corr_mstage.h -- split-bf16 operands and quad staging for the matrix-core local-correlation kernel (local_corr_mq.h, r >= 5 on
-// 64-channel maps).  Included by local_corr.hip after local_corr_lean.h (same namespace: cell boxes, buffer addressing, the fraction
-// table and the epilogue arithmetic are the lean path's).
+// 64-channel maps).  Buffer addressing and the quad loads are local_corr_stage.h's.
 //
 // The product: D[cell][position] = sum_c f0[cell][c] * f1[c][position] is (positions x channels) . (channels x cells).  fp32 accuracy
 // from bf16 operands: every value is split x = hi + lo when it is filed in LDS (both pieces round-to-nearest bf16: residual <=
@@ -14,6 +13,12 @@
 // kernel of local_corr_lean.h (profiles/r03_local_corr_mm.md: a quarter of a box's products are useful, and the bf16 split plus the
 // filing of the accumulators put back the vector instructions the FMAs freed); they stayed parked behind a build flag through round
 // 4 and were deleted in round 5 (git history: csrc/local_corr_mm.h, csrc/local_corr_mw.h at e0234d8).
+#pragma once
+#include "local_corr_common.h"
+#include "local_corr_stage.h"
+
+namespace {
+
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
@@ -26,7 +31,6 @@ __device__ __forceinline__ void split_pair(float a, float b, unsigned &hi, unsig
     const f32x2_t h = {__builtin_bit_cast(float, hi << 16), __builtin_bit_cast(float, hi & 0xffff0000u)};
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(v - h, bf16x2_t));
 }
-
 
 // swizzle of a slot's 16-byte pieces: piece p of slot s lives at physical piece p ^ mm_swz<KC>(s).  KC = 32 (8 pieces, slot stride
 // 32 dwords): (s >> 1) & 7 -- 16 consecutive slots reading one piece pair (p, p ^ 1) in the hardware's b128 lane groups
@@ -159,3 +163,5 @@ __device__ __forceinline__ void mm_rest(unsigned char *stage, rsrc_t f1r, unsign
         if ((it.meta >> 22) & 1u) mm_commit_one<M, CHECK, FT>(stage, a, it.meta);
     }
 }
+
+}  // namespace

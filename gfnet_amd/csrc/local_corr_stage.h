@@ -1,6 +1,9 @@
-// local_corr_stage.h -- staging of f1 into the LDS stage by 16-byte quads through buffer descriptors.  Included by local_corr.hip in
-// front of the round-1 tile routine (r >= 5 stages this way since round 3) and of local_corr_lean.h (whose tile kernels it was
-// written for in round 2).  Shares kSlotV4 / kWaves with local_corr.hip.
+// local_corr_stage.h -- staging of f1 into the LDS stage by 16-byte quads through buffer descriptors: the round-1 tile routine
+// (local_corr_tile.h: r >= 5 stages this way since round 3) and the lean tile kernels (local_corr_lean.h, written for them in round 2).
+#pragma once
+#include "local_corr_common.h"
+
+namespace {
 
 // region geometry from the box, identically in the plan kernel and the tile kernel
 struct RowPlan {  // block-uniform (scalars)
@@ -13,8 +16,6 @@ struct RowPlan {  // block-uniform (scalars)
 // ---- buffer addressing --------------------------------------------------------------------------------------------
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i32x4 make_i32x4(int a, int b, int c, int d) { i32x4 v = {a, b, c, d}; return v; }
 __device__ __forceinline__ rsrc_t make_rsrc(const void *base, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);  // raw buffer, 32-bit data format
 }
@@ -160,3 +161,4 @@ __device__ __forceinline__ void quad_rest(float4 *s4, rsrc_t f1r, unsigned chunk
     }
 }
 
+}  // namespace
