@@ -56,6 +56,10 @@ _SIGNATURES = {
     "gfn_conv_block_fwd": [c_vp] * 4 + [c_int] * 5 + [c_vp],
     "gfn_conv_block_half_fwd": [c_vp, c_int, c_vp, c_vp] + [c_int] * 5 + [c_vp],
     "gfn_pointwise_conv_fwd": [c_vp] * 4 + [c_int] * 4 + [c_vp],
+    "gfn_local_corr_mode_fwd": [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64] + [c_int] * 11 + [c_vp],
+    "gfn_local_corr_mode_bwd_f0": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 11 + [c_vp],
+    "gfn_grid_sample_mode_fwd": [c_vp, c_int, c_vp, c_vp, c_i64] + [c_int] * 8 + [c_vp],
+    "gfn_refiner_input_mode_fwd_dt": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 6 + [c_float, c_int, c_int, c_vp],
 }
 # entry points that return a size instead of a status
 _SIZE_FUNCS = {
@@ -184,6 +188,17 @@ def scratch(device, nbytes):
 
 
 GFN_F32, GFN_F16 = 0, 1
+# F.grid_sample's `mode` / `padding_mode` strings -> GFN_SAMPLE_* / GFN_PAD_* (include/gfnet_hip.h)
+SAMPLE_MODES = {"bilinear": 0, "nearest": 1, "bicubic": 2}
+PADDING_MODES = {"zeros": 0, "border": 1, "reflection": 2}
+
+
+def mode_codes(sample_mode, padding_mode, what):
+    """(GFN_SAMPLE_*, GFN_PAD_*) of two F.grid_sample mode strings; ValueError naming the accepted values otherwise."""
+    if sample_mode not in SAMPLE_MODES or padding_mode not in PADDING_MODES:
+        raise ValueError(f"{what}: sample_mode must be one of {sorted(SAMPLE_MODES)} and padding_mode one of {sorted(PADDING_MODES)}, "
+                         f"got {sample_mode!r}, {padding_mode!r}")
+    return SAMPLE_MODES[sample_mode], PADDING_MODES[padding_mode]
 
 
 def featc(t):

@@ -46,8 +46,9 @@ class ConvRefiner(nn.Module):
                  disable_local_corr_grad=False, is_classifier=False, sample_mode="bilinear", norm_type=nn.BatchNorm2d,
                  bn_momentum=0.1, amp_dtype=torch.float16):
         super().__init__()
-        if sample_mode != "bilinear":
-            raise ValueError("only bilinear sampling is implemented (the reference's setting)")
+        if sample_mode not in ("bilinear", "nearest", "bicubic"):
+            # the reference hands it to F.grid_sample (network.py:537, 547) and local_correlation (:553-554), zeros padding
+            raise ValueError(f"sample_mode must be 'bilinear', 'nearest' or 'bicubic', got {sample_mode!r}")
         # the reference stores these flags (network.py:496-501) and its forward (network.py:533-564) never reads any of them: they are
         # kept the same way -- attributes without effect -- so that a constructor call written for the reference behaves identically
         # here (rounds 1-4 raised NotImplementedError for them; VERDICT r4 "missing" 5)
@@ -107,7 +108,8 @@ class ConvRefiner(nn.Module):
         if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad or self.disp_emb.weight.requires_grad):
             return self._assemble_autograd(num_grid, x, y, flow, scale_factor)
         d = ops.refiner_input(num_grid, x, y, flow, self.disp_emb.weight, self.disp_emb.bias,
-                              self.local_corr_radius if use_corr else 0, scale_factor=scale_factor, corr_in_other=use_corr, reuse=reuse)
+                              self.local_corr_radius if use_corr else 0, scale_factor=scale_factor, corr_in_other=use_corr, reuse=reuse,
+                              sample_mode=self.sample_mode)
         return d, (d[:, 2 * c + dd:] if use_corr else None)
 
     def _assemble_autograd(self, num_grid, x, y, flow, scale_factor):
@@ -124,11 +126,11 @@ class ConvRefiner(nn.Module):
         if flow.shape[0] != b:
             raise NotImplementedError("training-mode refiner input needs a plain batch (flow and features of equal batch size)")
         x, y, flow = x.float(), y.float(), flow.float()
-        x_hat = F.grid_sample(y, flow.permute(0, 2, 3, 1), align_corners=False, mode="bilinear")              # :537
+        x_hat = F.grid_sample(y, flow.permute(0, 2, 3, 1), align_corners=False, mode=self.sample_mode)        # :537
         lin = torch.linspace(-1 + 1 / G, 1 - 1 / G, G, device=x.device)
         gy, gx = torch.meshgrid(lin, lin, indexing="ij")
         coords = torch.stack((gx, gy))[None].expand(b, 2, G, G)                                                 # :539-546
-        grid_feature = F.grid_sample(x, coords.permute(0, 2, 3, 1), align_corners=False, mode="bilinear")      # :547
+        grid_feature = F.grid_sample(x, coords.permute(0, 2, 3, 1), align_corners=False, mode=self.sample_mode)  # :547
         emb = self.disp_emb(40 / 32 * scale_factor * (flow - coords))                                           # :548-549
         parts = [grid_feature, x_hat, emb]
         lc = None

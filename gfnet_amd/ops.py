@@ -93,13 +93,20 @@ def pos_embed(corr_vol):
     return flow
 
 
-def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_factor=1.0, corr_in_other=True, reuse=None):
+def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_factor=1.0, corr_in_other=True, reuse=None,
+                  sample_mode="bilinear"):
     """The concat tensor `d` of ConvRefiner.forward (model/network.py:533-558):
     cat(grid_sample(x, cell centres), grid_sample(y, flow), disp_emb(40/32*scale_factor*(flow-centres)),
     local_correlation(...)) -- every slice written in place by the HIP kernels, no torch.cat.
     If flow has twice the batch of x/y the call is symmetric: directions (x vs y) then (y vs x).
     reuse: the `d` an earlier call returned for the SAME x and num_grid (the previous refiner iteration at this scale): it is
-    overwritten in place except for its grid_feature planes, which depend on x and the grid only."""
+    overwritten in place except for its grid_feature planes, which depend on x and the grid only.
+    sample_mode: ConvRefiner(sample_mode=...) (network.py:464, 537, 547, 553-554), "bilinear", "nearest" or "bicubic"; padding is
+    zeros as in the reference.  Other than bilinear, all three gathers take the general per-tap kernels (csrc/grid_modes.hip,
+    csrc/local_corr_modes.hip), never the tiled correlation or its plan."""
+    general = sample_mode != "bilinear"
+    if general:
+        sm, _ = _lib.mode_codes(sample_mode, "zeros", "refiner_input")
     dev = require_gpu(x, y, flow, disp_w, disp_b)
     (x, dtx), (y, dty), fl = featc(x), featc(y), f32c(flow)
     if dtx != dty:
@@ -126,6 +133,15 @@ def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fact
     st = stream_ptr(dev)
     mode = (1 if symmetric else 0) | (2 if keep else 0)  # include/gfnet_hip.h: GFN_RI_KEEP_GRID_FEATURE
     disp_scale = float(40 / 32 * scale_factor)
+    if general:  # the per-tap kernels of every mode: no tile plan, no scratch
+        check(_L().gfn_refiner_input_mode_fwd_dt(ptr(x), ptr(y), dtx, ptr(fl), ptr(w), ptr(bvec), ptr(d), CH * G * G, B, C, Hs, Ws, G, Dd,
+                                                 disp_scale, mode, sm, st), "gfn_refiner_input_mode_fwd_dt")
+        if corr_in_other:
+            out = d[:, 2 * C + Dd:]
+            check(_L().gfn_local_corr_mode_fwd(ptr(d), CH * G * G, ptr(y), ptr(x) if symmetric else None, dtx, ptr(fl), c_vp(out.data_ptr()),
+                                               CH * G * G, B, C, G, Hs, Ws, r, 0, Hs, Ws, sm, _lib.PADDING_MODES["zeros"], st),
+                  "gfn_local_corr_mode_fwd")
+        return d
     # shapes the lean local-correlation path takes are planned inside the refiner-input launch (both only read the flow)
     plans = FUSE_PLAN and corr_in_other and bool(_L().gfn_local_corr_plans(C, Hs, Ws, G, r, dtx))
     if corr_in_other:
@@ -150,8 +166,12 @@ def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fact
     return d
 
 
-def grid_sample(x, grid):
-    """F.grid_sample(x, grid, mode='bilinear', padding_mode='zeros', align_corners=False)."""
+def grid_sample(x, grid, mode="bilinear", padding_mode="zeros"):
+    """F.grid_sample(x, grid, mode, padding_mode, align_corners=False); mode "bilinear" / "nearest" / "bicubic", padding_mode
+    "zeros" / "border" / "reflection".  Returns fp32.  The default pair runs gfn_grid_sample_fwd (fp32 input), every other pair
+    gfn_grid_sample_mode_fwd, which reads fp16 input as stored."""
+    if mode != "bilinear" or padding_mode != "zeros":
+        return _grid_sample_mode(x, grid, mode, padding_mode)
     dev = require_gpu(x, grid)
     x, g = f32c(x), f32c(grid)
     B, C, H, W = x.shape
@@ -159,6 +179,20 @@ def grid_sample(x, grid):
     out = torch.empty((B, C, Ho, Wo), device=dev, dtype=torch.float32)
     check(_L().gfn_grid_sample_fwd(ptr(x), ptr(g), ptr(out), C * Ho * Wo, B, C, H, W, Ho, Wo, stream_ptr(dev)),
           "gfn_grid_sample_fwd")
+    return out
+
+
+def _grid_sample_mode(x, grid, mode, padding_mode):
+    sm, pm = _lib.mode_codes(mode, padding_mode, "grid_sample")
+    dev = require_gpu(x, grid)
+    (x, dtx), g = featc(x), f32c(grid)
+    B, C, H, W = x.shape
+    _, Ho, Wo, _ = g.shape
+    if tuple(g.shape) != (B, Ho, Wo, 2):
+        raise ValueError(f"grid_sample: grid must be (B,Ho,Wo,2) with B={B}, got {tuple(g.shape)}")
+    out = torch.empty((B, C, Ho, Wo), device=dev, dtype=torch.float32)
+    check(_L().gfn_grid_sample_mode_fwd(ptr(x), dtx, ptr(g), ptr(out), C * Ho * Wo, B, C, H, W, Ho, Wo, sm, pm, stream_ptr(dev)),
+          "gfn_grid_sample_mode_fwd")
     return out
 
 

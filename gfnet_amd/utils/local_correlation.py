@@ -2,7 +2,8 @@
 
 `local_correlation(...)` keeps the argument list of utils/local_correlation.py:4-16 so that
 model/network.py:553-554 can import it unchanged; the arithmetic runs in the hand-written gfx950
-kernels of csrc/local_corr.hip through the C ABI (gfn_local_corr_fwd, include/gfnet_hip.h).
+kernels of csrc/local_corr.hip through the C ABI (gfn_local_corr_fwd, include/gfnet_hip.h); sampling modes other
+than the reference's default bilinear + zeros run the per-tap kernels of csrc/local_corr_modes.hip.
 """
 import torch
 
@@ -31,18 +32,21 @@ def local_correlation(featuremap_size, feature0, feature1, local_radius, num_gri
     of the refiner's concat buffer); it must have contiguous (K,G,G) planes.
     Gradients: like the reference (local_correlation.py:54-60, sampling under no_grad) only feature0
     receives one; it is computed by gfn_local_corr_bwd_f0 when feature0.requires_grad (and `out` is None).
+    sample_mode ("bilinear", "nearest", "bicubic") and padding_mode ("zeros", "border", "reflection") are F.grid_sample's
+    (local_correlation.py:55-58, 66-68).  Bilinear + zeros takes the tiled kernels; every other pair runs the general per-tap
+    kernel of csrc/local_corr_modes.hip (gfn_local_corr_mode_fwd, gradient gfn_local_corr_mode_bwd_f0).
     """
     if out is None and torch.is_grad_enabled() and feature0.requires_grad:
         return _LocalCorrelationFn.apply(feature0, feature1, flow, tuple(int(v) for v in featuremap_size), int(local_radius),
-                                         int(num_grid), bool(grid_based_correlation), int(num_level))
+                                         int(num_grid), bool(grid_based_correlation), int(num_level), sample_mode, padding_mode)
     return _forward(featuremap_size, feature0, feature1, local_radius, num_grid, padding_mode, flow, sample_mode,
                     grid_based_correlation, num_level, out, _variant)
 
 
 def _forward(featuremap_size, feature0, feature1, local_radius, num_grid, padding_mode, flow, sample_mode,
              grid_based_correlation, num_level, out, _variant):
-    if padding_mode != "zeros" or sample_mode != "bilinear":
-        raise ValueError("only padding_mode='zeros', sample_mode='bilinear' (the reference's settings) are supported")
+    sm, pm = _lib.mode_codes(sample_mode, padding_mode, "local_correlation")
+    general = (sample_mode, padding_mode) != ("bilinear", "zeros")
     B, c, h, w = [int(v) for v in featuremap_size]
     r = int(local_radius)
     G = int(num_grid)
@@ -72,6 +76,11 @@ def _forward(featuremap_size, feature0, feature1, local_radius, num_grid, paddin
         out_bs = out.stride(0) if B > 1 else K * G * G
     L = _lib.lib()
     st = _lib.stream_ptr(dev)
+    if general:
+        _forward_modes(L, st, dev, f0, f0_bs, f1, f1_dt, fl, res, out_bs, B, c, G, h, w, r, grid_based_correlation, num_level, sm, pm)
+        if out is None and ret_dtype != torch.float32:
+            res = res.to(ret_dtype)
+        return res
     nscr = int(L.gfn_local_corr_scratch_bytes(B, G))
     scr = _lib.scratch(dev, nscr)
     hh, ww = h, w
@@ -93,6 +102,17 @@ def _forward(featuremap_size, feature0, feature1, local_radius, num_grid, paddin
     return res
 
 
+def _forward_modes(L, st, dev, f0, f0_bs, f1, f1_dt, fl, res, out_bs, B, c, G, h, w, r, grid_based, num_level, sm, pm):
+    """Every level through gfn_local_corr_mode_fwd; pooled levels from _pyramid (fp32, as the bilinear path builds them)."""
+    K1 = (2 * r + 1) ** 2
+    if num_level > 1:
+        f1, f1_dt = _lib.f32c(f1), _lib.GFN_F32
+    for level, (f1l, hh, ww) in enumerate(_pyramid(f1, B, c, h, w, num_level, dev)):
+        o = res[:, level * K1:(level + 1) * K1]
+        _lib.check(L.gfn_local_corr_mode_fwd(_lib.ptr(f0), f0_bs, _lib.ptr(f1l), None, f1_dt, _lib.ptr(fl), _lib.c_vp(o.data_ptr()), out_bs,
+                                             B, c, G, hh, ww, r, 1 if grid_based else 0, h, w, sm, pm, st), "gfn_local_corr_mode_fwd")
+
+
 def _pyramid(f1, B, c, h, w, num_level, dev):
     """feature1 and its 2x average-pooled levels (local_correlation.py:71), as the forward builds them."""
     L = _lib.lib()
@@ -110,16 +130,18 @@ class _LocalCorrelationFn(torch.autograd.Function):
     """local_correlation with the reference's gradient: d/d feature0 only."""
 
     @staticmethod
-    def forward(ctx, feature0, feature1, flow, featuremap_size, r, G, grid_based, num_level):
-        res = _forward(featuremap_size, feature0, feature1, r, G, "zeros", flow, "bilinear", grid_based, num_level, None, 0)
+    def forward(ctx, feature0, feature1, flow, featuremap_size, r, G, grid_based, num_level, sample_mode="bilinear", padding_mode="zeros"):
+        res = _forward(featuremap_size, feature0, feature1, r, G, padding_mode, flow, sample_mode, grid_based, num_level, None, 0)
         ctx.save_for_backward(feature1, flow if flow is not None else torch.empty(0, device=feature0.device))
-        ctx.meta = (featuremap_size, r, G, grid_based, num_level, flow is not None, feature0.dtype)
+        ctx.meta = (featuremap_size, r, G, grid_based, num_level, flow is not None, feature0.dtype, sample_mode, padding_mode)
         return res
 
     @staticmethod
     def backward(ctx, grad_out):
         feature1, flow = ctx.saved_tensors
-        (B, c, h, w), r, G, grid_based, num_level, has_flow, dtype = ctx.meta
+        (B, c, h, w), r, G, grid_based, num_level, has_flow, dtype, sample_mode, padding_mode = ctx.meta
+        general = (sample_mode, padding_mode) != ("bilinear", "zeros")
+        sm, pm = _lib.mode_codes(sample_mode, padding_mode, "local_correlation")
         dev = grad_out.device
         K1 = (2 * r + 1) ** 2
         g = _lib.f32c(grad_out)
@@ -130,7 +152,12 @@ class _LocalCorrelationFn(torch.autograd.Function):
         for level, (f1, hh, ww) in enumerate(_pyramid(_lib.f32c(feature1), B, c, h, w, num_level, dev)):
             gl = g[:, level * K1:(level + 1) * K1]
             gf0 = torch.empty((B, c, G, G), device=dev, dtype=torch.float32)
-            _lib.check(L.gfn_local_corr_bwd_f0(_lib.c_vp(gl.data_ptr()), g.stride(0), _lib.ptr(f1), None, _lib.ptr(fl), _lib.ptr(gf0),
-                                               c * G * G, B, c, G, hh, ww, r, 1 if grid_based else 0, h, w, st), "gfn_local_corr_bwd_f0")
+            if general:
+                _lib.check(L.gfn_local_corr_mode_bwd_f0(_lib.c_vp(gl.data_ptr()), g.stride(0), _lib.ptr(f1), None, _lib.ptr(fl), _lib.ptr(gf0),
+                                                        c * G * G, B, c, G, hh, ww, r, 1 if grid_based else 0, h, w, sm, pm, st),
+                           "gfn_local_corr_mode_bwd_f0")
+            else:
+                _lib.check(L.gfn_local_corr_bwd_f0(_lib.c_vp(gl.data_ptr()), g.stride(0), _lib.ptr(f1), None, _lib.ptr(fl), _lib.ptr(gf0),
+                                                   c * G * G, B, c, G, hh, ww, r, 1 if grid_based else 0, h, w, st), "gfn_local_corr_bwd_f0")
             total = gf0 if total is None else total + gf0
-        return total.to(dtype), None, None, None, None, None, None, None
+        return total.to(dtype), None, None, None, None, None, None, None, None, None

@@ -183,6 +183,45 @@ int gfn_refiner_input_plan_fwd_dt(const void *f0, const void *f1, int dtype, con
 int gfn_grid_sample_fwd(const float *in, const float *grid, float *out, int64_t out_bs, int B, int C, int H, int W,
                         int Ho, int Wo, gfn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sampling modes -- the `sample_mode` / `padding_mode` the reference passes straight to F.grid_sample
+ * (utils/local_correlation.py:4-16, 55-58, 66-68; ConvRefiner(sample_mode=...), model/network.py:464, 502, 537, 547, 553-554).
+ * ATen grid_sampler_2d semantics with align_corners=False: nearest rounds the padded coordinate half to even; bilinear weighs
+ * the four corners of the padded coordinate; bicubic takes the 4 x 4 taps around the UN-padded coordinate, pads each tap on
+ * its own and uses cubic convolution with A = -0.75 (rows along x first, then along y).  Taps outside the image read 0;
+ * coordinates 10^6 pixels or more outside the image, and non-finite ones, read 0 in every mode.
+ * These entry points are the general per-tap route for every combination (bilinear + zeros included); the LDS-tiled and
+ * matrix-core paths above serve bilinear + zeros only and are not reached from here.
+ */
+#define GFN_SAMPLE_BILINEAR 0
+#define GFN_SAMPLE_NEAREST 1
+#define GFN_SAMPLE_BICUBIC 2
+#define GFN_PAD_ZEROS 0
+#define GFN_PAD_BORDER 1
+#define GFN_PAD_REFLECTION 2
+
+/* gfn_local_corr_fwd_dt's arguments without variant and scratch, plus the two codes:
+ *   out[b, k, i, j] = sum_c f0[b,c,i,j] / sqrt(C) * sample(f1[b,c], p(b,i,j) + offset(k))
+ * Any C and r, fp32 / fp16 f1, f1_second, grid_based and flow == NULL as there.  With GFN_SAMPLE_BILINEAR + GFN_PAD_ZEROS the
+ * result is bit-identical to gfn_local_corr_fwd_dt with scratch == NULL (its general kernel). */
+int gfn_local_corr_mode_fwd(const float *f0, int64_t f0_bs, const void *f1, const void *f1_second, int f1_dtype, const float *flow,
+                            float *out, int64_t out_bs, int B, int C, int G, int H, int W, int r, int grid_based, int win_h, int win_w,
+                            int sample_mode, int padding_mode, gfn_stream_t stream);
+/* Its gradient with respect to f0, as gfn_local_corr_bwd_f0 (fp32 f1; feature1 and the coordinates under no_grad). */
+int gfn_local_corr_mode_bwd_f0(const float *grad_out, int64_t grad_out_bs, const float *f1, const float *f1_second, const float *flow,
+                               float *grad_f0, int64_t grad_f0_bs, int B, int C, int G, int H, int W, int r, int grid_based, int win_h,
+                               int win_w, int sample_mode, int padding_mode, gfn_stream_t stream);
+/* F.grid_sample(in, grid, mode, padding_mode, align_corners=False): in (B,C,H,W) stored as in_dtype = GFN_F32 or GFN_F16,
+ * grid (B,Ho,Wo,2) fp32 -> out (B,C,Ho,Wo) fp32 with batch stride out_bs. */
+int gfn_grid_sample_mode_fwd(const void *in, int in_dtype, const float *grid, float *out, int64_t out_bs, int B, int C, int H, int W,
+                             int Ho, int Wo, int sample_mode, int padding_mode, gfn_stream_t stream);
+/* gfn_refiner_input_fwd_dt (same arguments and `symmetric` bits, GFN_RI_KEEP_GRID_FEATURE included) with both grid_samples in
+ * `sample_mode`; padding is always zeros, as in the reference's ConvRefiner.  Fill the local-correlation slice with
+ * gfn_local_corr_mode_fwd (f0 = d, out = d + (2C+disp)*G*G, batch strides d_bs). */
+int gfn_refiner_input_mode_fwd_dt(const void *f0, const void *f1, int dtype, const float *flow, const float *disp_w, const float *disp_b,
+                                  float *d, int64_t d_bs, int B, int C, int Hs, int Ws, int G, int disp_dim, float disp_scale,
+                                  int symmetric, int sample_mode, gfn_stream_t stream);
+
 /* F.interpolate(x, size=(Ho,Wo), mode='bilinear', align_corners=False) -- model/network.py:238-249,
  * 271-281, 333-335.  in (BC,H,W) -> out (BC,Ho,Wo). */
 int gfn_interp_bilinear_fwd(const float *in, float *out, int BC, int H, int W, int Ho, int Wo, gfn_stream_t stream);
