@@ -262,15 +262,21 @@ __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restri
             mt = fmaxf(mt, sv[r]);
         }
         if (WRITE_FLOW) {
-            const float mn = fmaxf(m, mt);
-            const float sc = __expf(m - mn);  // m = -inf on the first tile -> 0
+            // a half-wave whose first tile is all padding (N1 <= 4 leaves rows 4..7 of every k-group empty) keeps m = -inf: shift by
+            // 0 then, not by -inf, or (-inf) - (-inf) turns its sums into NaN
+            const float mn = fmaxf(m, mt), ms = mn == -INFINITY ? 0.f : mn;
+            const float sc = __expf(m - ms);  // m = -inf on the first tile -> 0
             l *= sc; ax *= sc; ay *= sc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int j = j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const int jy = (int)(((float)j + 0.5f) * inv_w1);
-                const int jx = j - jy * W1;
-                const float e = __expf(sv[r] - mn);  // exp(-inf) = 0 for the padded rows
+                // the float quotient is off by one row for some j >= 2^22 (j + 0.5 and the product round); one integer step
+                // either way makes (jx, jy) exact for every j < 2^24 (tests/test_host_cpu.py runs this formula over all of them)
+                int jy = (int)(((float)j + 0.5f) * inv_w1);
+                int jx = j - jy * W1;
+                if (jx < 0) { --jy; jx += W1; }
+                else if (jx >= W1) { ++jy; jx -= W1; }
+                const float e = __expf(sv[r] - ms);  // exp(-inf) = 0 for the padded rows
                 l += e;
                 ax = fmaf(e, gfn::linspace_at(x_lo, x_hi, W1, jx), ax);
                 ay = fmaf(e, gfn::linspace_at(y_lo, y_hi, H1, min(jy, H1 - 1)), ay);

@@ -37,6 +37,80 @@ def test_argument_errors_return_codes_without_a_gpu():
     assert L.gfn_homography_scratch_bytes(2, 100) >= 2 * 100 * 76
 
 
+def test_corr_entry_points_refuse_bad_arguments_without_a_gpu():
+    """csrc/corr_softargmax.hip: every call below has exactly one bad argument and must be refused by the host checks, before a
+    launch (the feature / output pointers are a host buffer that no kernel may ever see)."""
+    import ctypes
+
+    from gfnet_amd import _lib
+
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.c_void_p(ctypes.addressof(buf))
+    F32, F16 = _lib.GFN_F32, _lib.GFN_F16
+
+    def refused(code, what):
+        assert code == -1, what
+        assert L.gfn_last_error(), what
+
+    def fused(f0=p, f1=p, flow=p, B=2, C=16, H0=4, W0=4, H1=4, W1=4, sym=0):
+        """every fused entry point and dtype with the same arguments"""
+        yield L.gfn_corr_softargmax_fwd(f0, f1, flow, B, C, H0, W0, H1, W1, sym, None)
+        for dt in (F32, F16):
+            yield L.gfn_corr_softargmax_fwd_dt(f0, f1, dt, flow, B, C, H0, W0, H1, W1, sym, None)
+            yield L.gfn_corr_softargmax_fwd_ws(f0, f1, dt, flow, B, C, H0, W0, H1, W1, sym, p, 64, None)
+            yield L.gfn_corr_softargmax_fwd_ws(f0, f1, dt, flow, B, C, H0, W0, H1, W1, sym, None, 0, None)
+
+    def volume(f0=p, f1=p, vol=p, flow=p, B=2, C=16, H0=4, W0=4, H1=4, W1=4):
+        yield L.gfn_corr_volume_fwd(f0, f1, vol, flow, B, C, H0, W0, H1, W1, None)
+        yield L.gfn_corr_volume_fwd(f0, f1, vol, None, B, C, H0, W0, H1, W1, None)
+
+    bad = {"C = 0": dict(C=0), "C = 129": dict(C=129), "B < 0": dict(B=-1), "null f0": dict(f0=None), "null f1": dict(f1=None),
+           "H0 = 0": dict(H0=0), "W1 = 0": dict(W1=0), "A map of 2^24 positions": dict(H0=4096, W0=4096),
+           "B map of 2^24 positions": dict(H1=1, W1=1 << 24), "B map of 2^24 + 2^12 positions": dict(H1=4097, W1=4096)}
+    for what, kw in bad.items():
+        for code in fused(**kw):
+            refused(code, what)
+        for code in volume(**kw):
+            refused(code, what)
+    for what, kw in {"symmetric, odd batch": dict(B=3, sym=1), "symmetric, unequal widths": dict(W1=5, sym=1),
+                     "symmetric, unequal heights": dict(H0=5, sym=1), "null flow": dict(flow=None)}.items():
+        for code in fused(**kw):
+            refused(code, what)
+    for code in volume(vol=None):
+        refused(code, "null volume")
+    refused(L.gfn_corr_softargmax_fwd_dt(p, p, 7, p, 2, 16, 4, 4, 4, 4, 0, None), "unknown dtype")
+    refused(L.gfn_corr_softargmax_fwd_ws(p, p, 7, p, 2, 16, 4, 4, 4, 4, 0, None, 0, None), "unknown dtype")
+    for args in [(None, p, 1, 4, 4, 4, 4), (p, None, 1, 4, 4, 4, 4), (p, p, -1, 4, 4, 4, 4), (p, p, 1, 0, 4, 4, 4), (p, p, 1, 4, 4, 4, 0)]:
+        refused(L.gfn_pos_embed_fwd(*args, None), f"pos_embed {args[2:]}")
+    # an empty batch is valid and returns before any launch
+    assert all(code == 0 for code in fused(B=0)) and all(code == 0 for code in volume(B=0))
+    assert L.gfn_pos_embed_fwd(p, p, 0, 4, 4, 4, 4, None) == 0
+
+
+def test_corr_general_loop_row_index_is_exact_below_2_pow_24():
+    """corr_softargmax_kernel's general loop turns a B-position j into (jx, jy) with a float quotient and one integer correction
+    step (csrc/corr_softargmax.hip).  This is that formula in float32 / int32 arithmetic, with inv_w1 = 1.0f / W1 correctly rounded,
+    for every j below check_args' 2^24 limit.  The quotient alone is a row too high at some j >= 2^22 (W1 = 4095: x = W1 - 2,
+    W1 - 1 from row 1025 on), which put a B-position at x = -1 or -2 of the next row."""
+    j = np.arange(1 << 24, dtype=np.int32)
+    jf = j.astype(np.float32) + np.float32(0.5)
+    for W1 in (1, 2, 3, 5, 31, 33, 63, 65, 80, 1000, 4095, 4096, 65535, (1 << 24) - 1):
+        inv_w1 = np.float32(1.0) / np.float32(W1)
+        jy = (jf * inv_w1).astype(np.int32)                  # (int)(((float)j + 0.5f) * inv_w1): a float32 product, truncated
+        jx = j - jy * np.int32(W1)
+        if W1 in (1, 3, 63, 4095, 65535):
+            assert (jx < 0).any()                            # the float quotient alone is wrong here ...
+        assert jx.min() >= -W1 and jx.max() < 2 * W1         # ... by at most one row either way, which one step corrects
+        lo, hi = jx < 0, jx >= W1
+        jy[lo] -= 1
+        jx[lo] += W1
+        jy[hi] += 1
+        jx[hi] -= W1
+        assert np.array_equal(jy, j // W1), W1
+        assert np.array_equal(jx, j % W1), W1
+
+
 def test_product_ops_refuse_cpu_tensors():
     from gfnet_amd import ops
     from gfnet_amd._lib import GfnError
