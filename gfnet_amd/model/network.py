@@ -19,6 +19,14 @@ GFNet.extract_features (model/network.py:156-201), or feed pyramids directly to
 "fp32" exact fp32 products, "fp16" fp16 1x1 operands, "amp" the class the reference's amp=True refiners run in under
 torch.autocast -- fp16 maps between the blocks); training mode keeps the nn modules and assembles the refiner input with
 differentiable torch ops (the HIP assembly has no backward).
+
+Training (`model.train()`, grad mode on, pyramids or parameters that require grad): forward_pyramids returns flows and
+certainties with an autograd graph, as the reference's forward does (network.py:230-281).  The scale-16 global match is
+differentiable with respect to both feature maps (ops.corr_softargmax: backward in csrc/corr_softargmax_bwd.hip, which never
+writes the volume), every flow update passes its gradient to the previous flow, the refiner's outputs and the certainty
+(ops.flow_update), and the refiners see the flow through their differentiable input assembly.  Detached as in the reference:
+the resize between scales (network.py:271-281) and the local correlation's feature1 / flow (utils/local_correlation.py:54).
+Calls without grad (inference, bench.py) take the plain launches: no extra work.
 """
 import math
 import os

@@ -50,7 +50,15 @@ def corr_softargmax(feat0, feat1, symmetric=False):
     """pos_embed(corr_volume(feat0, feat1)) without writing the volume (model/network.py:251-252, 415-440).
     feat0 (B,C,H0,W0), feat1 (B,C,H1,W1) -> flow (B,2,H0,W0).  symmetric=True: the result has 2B
     directions, (feat0 vs feat1) then (feat1 vs feat0) -- the reference's concatenated batch
-    (network.py:213-222) without copying the features."""
+    (network.py:213-222) without copying the features.  With grad mode on and a map that requires grad, the flow is
+    differentiable (gfn_corr_softargmax_bwd); every other call is the plain launch."""
+    if torch.is_grad_enabled() and (feat0.requires_grad or feat1.requires_grad):
+        return _CorrSoftargmaxFn.apply(feat0, feat1, symmetric)
+    return _corr_softargmax(feat0, feat1, symmetric)[0]
+
+
+def _corr_softargmax(feat0, feat1, symmetric):
+    """The forward launch; returns (flow, f0, f1, dtype code) with the maps as the kernel read them."""
     dev = require_gpu(feat0, feat1)
     (f0, dt0), (f1, dt1) = featc(feat0), featc(feat1)
     if dt0 != dt1:
@@ -67,7 +75,49 @@ def corr_softargmax(feat0, feat1, symmetric=False):
     ws = torch.empty(nws, device=dev, dtype=torch.uint8) if nws > 0 else None
     check(_L().gfn_corr_softargmax_fwd_ws(ptr(f0), ptr(f1), dt0, ptr(flow), nb, C, H0, W0, H1, W1, 1 if symmetric else 0,
                                           ptr(ws), nws, stream_ptr(dev)), "gfn_corr_softargmax_fwd")
-    return flow
+    return flow, f0, f1, dt0
+
+
+def corr_softargmax_bwd(f0, f1, flow, grad_flow, symmetric=False, need_f0=True, need_f1=True):
+    """Gradients of corr_softargmax's flow with respect to f0 and f1 (fp32, None where not asked for) given grad_flow = dL/dflow:
+    the backward of the reference's pos_embed(corr_volume(f0, f1)) (model/network.py:415-440) without the volume or its gradient
+    (csrc/corr_softargmax_bwd.hip).  f0 / f1 as the forward read them (fp32 or fp16, same dtype), flow its output."""
+    dev = require_gpu(f0, f1, flow, grad_flow)
+    (a, dt0), (b, dt1) = featc(f0), featc(f1)
+    if dt0 != dt1:
+        a, b, dt0 = f32c(a), f32c(b), _lib.GFN_F32
+    B, C, H0, W0 = a.shape
+    _, _, H1, W1 = b.shape
+    nb = 2 * B if symmetric else B
+    fl, g = f32c(flow), f32c(grad_flow)
+    if tuple(fl.shape) != (nb, 2, H0, W0) or tuple(g.shape) != (nb, 2, H0, W0):
+        raise ValueError("corr_softargmax_bwd: flow / grad_flow must be (B,2,H0,W0) of the forward")
+    g0 = torch.empty(a.shape, device=dev, dtype=torch.float32) if need_f0 else None
+    g1 = torch.empty(b.shape, device=dev, dtype=torch.float32) if need_f1 else None
+    nws = int(_L().gfn_corr_softargmax_bwd_ws_bytes(nb, C, H0, W0, H1, W1))
+    ws = torch.empty(nws, device=dev, dtype=torch.uint8) if nws > 0 else None
+    check(_L().gfn_corr_softargmax_bwd(ptr(a), ptr(b), dt0, ptr(fl), ptr(g), ptr(g0), ptr(g1), nb, C, H0, W0, H1, W1,
+                                       1 if symmetric else 0, ptr(ws), nws, stream_ptr(dev)), "gfn_corr_softargmax_bwd")
+    return g0, g1
+
+
+class _CorrSoftargmaxFn(torch.autograd.Function):
+    """corr_softargmax with a backward: the same launch forward (same bits), gfn_corr_softargmax_bwd backward."""
+
+    @staticmethod
+    def forward(ctx, feat0, feat1, symmetric):
+        flow, f0, f1, _ = _corr_softargmax(feat0, feat1, symmetric)
+        ctx.save_for_backward(f0, f1, flow)
+        ctx.symmetric = symmetric
+        ctx.dtypes = (feat0.dtype, feat1.dtype)
+        return flow
+
+    @staticmethod
+    def backward(ctx, grad_flow):
+        f0, f1, flow = ctx.saved_tensors
+        n0, n1 = ctx.needs_input_grad[:2]
+        g0, g1 = corr_softargmax_bwd(f0, f1, flow, grad_flow, ctx.symmetric, need_f0=n0, need_f1=n1)
+        return (g0.to(ctx.dtypes[0]) if g0 is not None else None, g1.to(ctx.dtypes[1]) if g1 is not None else None, None)
 
 
 def corr_volume(feat0, feat1, with_flow=False):
@@ -253,7 +303,14 @@ def _plane_view(t, planes, G):
 def flow_update(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero_small=True, first_iteration=True):
     """model/network.py:262-268 out of place: returns (flow + displacement(d_flow), certainty + d_cert) as new tensors (the
     reference keeps every iteration's result); d_flow (B,2,G,G) / d_cert (B,1,G,G) may be channel slices of one tensor.
-    disp_prev=None (first iteration of a scale that has only one): the displacement is not stored."""
+    disp_prev=None (first iteration of a scale that has only one): the displacement is not stored.  With grad mode on and an
+    input that requires grad, both results are differentiable (_FlowUpdateFn); every other call is the plain launch."""
+    if torch.is_grad_enabled() and (flow.requires_grad or certainty.requires_grad or d_flow.requires_grad or d_cert.requires_grad):
+        return _FlowUpdateFn.apply(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero_small, first_iteration)
+    return _flow_update(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero_small, first_iteration)
+
+
+def _flow_update(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero_small, first_iteration):
     dev = require_gpu(flow, certainty, d_flow, d_cert, *(() if disp_prev is None else (disp_prev,)))
     B, _, G, _ = flow.shape
     if tuple(certainty.shape) != (B, 1, G, G) or tuple(d_flow.shape) != (B, 2, G, G) or tuple(d_cert.shape) != (B, 1, G, G) or \
@@ -272,6 +329,38 @@ def flow_update(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero_
                                        ptr(disp_prev), B, G, int(scale), int(W0), int(H0), 1 if zero_small else 0,
                                        1 if first_iteration else 0, stream_ptr(dev)), "gfn_flow_update_out_fwd")
     return fo, co
+
+
+class _FlowUpdateFn(torch.autograd.Function):
+    """flow_update with a backward.  displacement = scale * (d_flow / (4 W0, 4 H0)) (network.py:262-263), so d flow_out / d d_flow
+    = scale / (4 W0) and scale / (4 H0); flow and both certainty terms pass their gradient through.  With zero_small (eval with
+    grad: network.py:264-265, `displacement[mask] = 0`) the cells the kernel zeroed get no gradient: the kernel stores the
+    displacement it applied in disp_prev (a scratch plane when the caller has none), and a zeroed cell is a stored 0 from a
+    d_flow that is not 0."""
+
+    @staticmethod
+    def forward(ctx, flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero_small, first_iteration):
+        dp = disp_prev
+        if zero_small and dp is None:
+            dp = torch.empty(flow.shape, device=flow.device, dtype=torch.float32)
+        fo, co = _flow_update(flow, certainty, d_flow, d_cert, dp, scale, W0, H0, zero_small, first_iteration)
+        mask = ((dp == 0) & (d_flow != 0)) if zero_small else None
+        ctx.save_for_backward(mask)
+        ctx.factors = (float(scale) / (4 * W0), float(scale) / (4 * H0))
+        ctx.dtypes = (flow.dtype, certainty.dtype, d_flow.dtype, d_cert.dtype)
+        return fo, co
+
+    @staticmethod
+    def backward(ctx, g_flow, g_cert):
+        (mask,) = ctx.saved_tensors
+        fx, fy = ctx.factors
+        g_d = torch.stack((g_flow[:, 0] * fx, g_flow[:, 1] * fy), dim=1)
+        if mask is not None:
+            g_d = g_d.masked_fill(mask, 0.0)
+        n = ctx.needs_input_grad
+        dt = ctx.dtypes
+        return (g_flow.to(dt[0]) if n[0] else None, g_cert.to(dt[1]) if n[1] else None, g_d.to(dt[2]) if n[2] else None,
+                g_cert.to(dt[3]) if n[3] else None, None, None, None, None, None, None)
 
 
 def match_post(flow, certainty, cert16=None, symmetric=True):

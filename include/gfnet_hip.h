@@ -141,6 +141,18 @@ int gfn_corr_softargmax_fwd_dt(const void *f0, const void *f1, int dtype, float 
 int64_t gfn_corr_softargmax_ws_bytes(int B, int C, int H1, int W1);
 int gfn_corr_softargmax_fwd_ws(const void *f0, const void *f1, int dtype, float *flow, int B, int C, int H0, int W0, int H1, int W1,
                                int symmetric, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+/* Backward of gfn_corr_softargmax_fwd_ws (training: the reference differentiates pos_embed(corr_volume(f0, f1)),
+ * model/network.py:251-252, 415-440, through torch autograd).  flow = the forward's output, grad_flow = dL/dflow, both (B,2,H0,W0)
+ * fp32.  grad_f0 (B',C,H0,W0) / grad_f1 (B',C,H1,W1) fp32 (B' = B, or B/2 with symmetric != 0) are OVERWRITTEN with the gradients
+ * with respect to the caller's f0 / f1 (fp32 or fp16 as dtype; fp16 maps give the gradient of their widened fp32 copy); either may
+ * be NULL, and its share is then not computed.  Symmetric batches are indexed as in the forward and each image's gradient is the sum
+ * over both directions it takes part in.  Same limits as the forward (C <= 128; symmetric: even batch, equal map sizes).  ws:
+ * >= gfn_corr_softargmax_bwd_ws_bytes(...) bytes of 16-byte aligned device memory (per-position softmax statistics; contents
+ * undefined afterwards).  Never writes the volume or its gradient; no atomics, so two calls give the same bits. */
+int64_t gfn_corr_softargmax_bwd_ws_bytes(int B, int C, int H0, int W0, int H1, int W1);
+int gfn_corr_softargmax_bwd(const void *f0, const void *f1, int dtype, const float *flow, const float *grad_flow, float *grad_f0,
+                            float *grad_f1, int B, int C, int H0, int W0, int H1, int W1, int symmetric, void *ws, int64_t ws_bytes,
+                            gfn_stream_t stream);
 int gfn_corr_volume_fwd(const float *f0, const float *f1, float *vol, float *flow_or_null, int B, int C, int H0, int W0,
                         int H1, int W1, gfn_stream_t stream);
 int gfn_pos_embed_fwd(const float *vol, float *flow, int B, int H0, int W0, int H1, int W1, gfn_stream_t stream);
