@@ -626,6 +626,11 @@ GFN_EXPORT int gfn_kde_density_sorted(const float *x, const float *y, float *out
                                       int round_fp16, float *scratch, int64_t scratch_floats, gfn_stream_t stream) {
     if (!x || !y || !out || !scratch) return gfn::fail(GFN_ERR_INVALID_ARG, "kde_sorted: null pointer");
     if (Bt < 0 || N < 0 || M <= 0 || !(std > 0) || Bt > 65535) return gfn::fail(GFN_ERR_INVALID_ARG, "kde_sorted: bad argument");
+    // the expanded exponent carries scale^2 (|x|^2 + |y|^2) = 0.72 * 8 (E / std)^2 in fp32 for coordinates within +-E: below 2048
+    // (one ulp = 2^-13, 8.5e-5 on a term) up to E = 16 std.  Coordinates are image coordinates, E = 1: refuse what cannot hold 1e-4.
+    if (std < GFN_KDE_SORTED_MIN_STD)
+        return gfn::fail(GFN_ERR_INVALID_ARG, "kde_sorted: std=%g below %g, the expanded exponent loses the 1e-4 parity: use gfn_kde_density",
+                         std, GFN_KDE_SORTED_MIN_STD);
     if (scratch_floats < gfn_kde_sorted_scratch_floats(Bt, N, M) || ((uintptr_t)scratch & 15) || ((uintptr_t)x & 15))
         return gfn::fail(GFN_ERR_SCRATCH, "kde_sorted: scratch too small or misaligned");
     if (Bt == 0 || N == 0) return GFN_OK;

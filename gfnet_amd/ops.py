@@ -381,11 +381,18 @@ def match_post(flow, certainty, cert16=None, symmetric=True):
     return warp, cout
 
 
+KDE_CULL_MIN_STD = 0.0625  # GFN_KDE_SORTED_MIN_STD (include/gfnet_hip.h)
+
+
 def kde_density(x, y=None, std=0.1, y_row_stride=None, cull=None, round_fp16=False):
     """sum_m exp(-|x_n - y_m|^2/(2 std^2)); x (N,D) or (Bt,N,D); y defaults to x.  fp32.
     round_fp16: coordinates rounded to fp16 first (what GFNet.sample hands to kde(); sums stay fp32).
     cull (default: automatic for 4-D points, N >= 4096): sort the points along a Morton curve of the
-    A-image coordinates and skip blocks of reference points beyond 6.7 std (terms < 2^-32)."""
+    A-image coordinates and skip blocks of reference points beyond 6.7 std (terms < 2^-32).
+    The culled routes form the exponent on the matrix core as |x|^2 + |y|^2 - 2 x.y; they hold the 1e-4 parity for
+    |coordinate| <= 16 std (include/gfnet_hip.h).  For image coordinates in [-1, 1] that is std >= KDE_CULL_MIN_STD: below it
+    the automatic rule takes the dense difference-form kernels (exact at any std and extent) and cull=True is refused.  The
+    extent of the points is not checked: points far outside the image at a small std belong on cull=False."""
     dev = require_gpu(x, y)
     xs = f32c(x)
     squeeze = xs.dim() == 2
@@ -403,7 +410,10 @@ def kde_density(x, y=None, std=0.1, y_row_stride=None, cull=None, round_fp16=Fal
         rs = int(y_row_stride)
         M = (ys.shape[1] * D + rs - 1) // rs
     if cull is None:
-        cull = D == 4 and N >= 4096 and M >= 4096 and std <= 0.2
+        cull = D == 4 and N >= 4096 and M >= 4096 and KDE_CULL_MIN_STD <= std <= 0.2
+    elif cull and D == 4 and not std >= KDE_CULL_MIN_STD:
+        raise ValueError(f"kde_density: cull=True needs std >= {KDE_CULL_MIN_STD} (got {std}): the matrix-core exponent loses the "
+                         "1e-4 parity below it; use cull=False")
     if cull and D == 4:
         if y_row_stride is not None:
             ys = ys[:, ::rs // D].contiguous()

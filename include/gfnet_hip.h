@@ -280,7 +280,13 @@ int gfn_kde_density(const float *x, const float *y, float *out, int Bt, int N, i
 /* Spatially culled KDE for 4-D matches (same sum as gfn_kde_density up to terms below 2^-32): the
  * caller orders x and y by gfn_kde_morton_keys (any stable sort of the int keys) and passes the
  * sorted arrays; out is in the order of the sorted x (or the original one, see perm).  scratch: gfn_kde_sorted_scratch_floats().
- * Blocks of 64 reference points farther than 6.7 std from a wave's 64 queries are skipped. */
+ * Blocks of 64 reference points farther than 6.7 std from a wave's 64 queries are skipped.
+ * Supported domain: the exponent is formed on the matrix core as |x|^2 + |y|^2 - 2 x.y with fp32 accumulators, so its error
+ * grows with (|coordinate| / std)^2 and not with the distance.  The 1e-4 relative parity with float64 holds for
+ * |coordinate| <= 16 std (measured 6e-5 at that edge; 2e-4 at 30 std, 3e-3 at 100 std: DESIGN.md).  The extent is data and
+ * is not checked; std is: gfn_kde_density_sorted refuses std < GFN_KDE_SORTED_MIN_STD = 1/16, the edge for image coordinates
+ * in [-1, 1].  gfn_kde_density (difference form) has no such limit. */
+#define GFN_KDE_SORTED_MIN_STD 0.0625
 int gfn_kde_morton_keys(const float *x, int *keys, int64_t n, gfn_stream_t stream);
 /* The order itself: rows of x (Bt,N,4) stably sorted by their Morton key, one launch.  x_sorted (Bt,N,4),
  * perm (Bt,N): x_sorted[b][i] = x[b][perm[b][i]]; scratch: Bt*N ints. */

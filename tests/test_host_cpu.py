@@ -88,6 +88,95 @@ def test_corr_entry_points_refuse_bad_arguments_without_a_gpu():
     assert L.gfn_pos_embed_fwd(p, p, 0, 4, 4, 4, 4, None) == 0
 
 
+def test_kde_entry_points_refuse_bad_arguments_without_a_gpu():
+    """csrc/kde.hip: every call below has exactly one bad argument and must be refused by the host checks before any launch (all
+    pointers are host buffers that no kernel may ever see)."""
+    import ctypes
+
+    from gfnet_amd import _lib
+
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(4096)
+    base = (ctypes.addressof(buf) + 15) & ~15
+    p, odd = ctypes.c_void_p(base), ctypes.c_void_p(base + 4)  # 16-byte aligned / float aligned only
+    INVALID, SCRATCH = -1, -3
+    nan = float("nan")
+
+    def density(x=p, y=p, out=p, Bt=1, N=8, M=8, D=4, rs=4, bs=32, std=0.1, scratch=None, n=0):
+        return L.gfn_kde_density(x, y, out, Bt, N, M, D, rs, bs, std, scratch, n, None)
+
+    for what, kw in {"std = 0": dict(std=0.0), "std < 0": dict(std=-0.1), "std NaN": dict(std=nan), "row stride < D": dict(rs=3),
+                     "row stride < D = 5": dict(D=5, rs=4), "Bt > 65535": dict(Bt=65536), "D = 0": dict(D=0), "N < 0": dict(N=-1),
+                     "M < 0": dict(M=-1), "null x": dict(x=None), "null y": dict(y=None), "null out": dict(out=None)}.items():
+        assert density(**kw) == INVALID, what
+        assert L.gfn_last_error(), what
+    assert density(Bt=0) == 0 and density(N=0) == 0  # empty: valid, returns before any launch
+
+    need = int(L.gfn_kde_sorted_scratch_floats(1, 8, 8))
+
+    def dsorted(x=p, y=p, out=p, perm=None, Bt=1, N=8, M=8, std=0.1, scratch=p, n=None):
+        return L.gfn_kde_density_sorted(x, y, out, perm, Bt, N, M, std, 0, scratch, need if n is None else n, None)
+
+    for what, kw in {"std = 0": dict(std=0.0), "std < 0": dict(std=-1.0), "std NaN": dict(std=nan), "M = 0": dict(M=0), "M < 0": dict(M=-5),
+                     "N < 0": dict(N=-1), "Bt > 65535": dict(Bt=65536), "null x": dict(x=None), "null y": dict(y=None),
+                     "null out": dict(out=None), "null scratch": dict(scratch=None),
+                     "std below the matrix-core domain": dict(std=0.06), "std far below": dict(std=0.01)}.items():
+        assert dsorted(**kw) == INVALID, what
+        assert L.gfn_last_error(), what
+    assert b"std" in L.gfn_last_error()
+    for what, kw in {"misaligned x": dict(x=odd), "misaligned scratch": dict(scratch=odd), "scratch one float short": dict(n=need - 1),
+                     "no scratch floats": dict(n=0)}.items():
+        assert dsorted(**kw) == SCRATCH, what
+    assert dsorted(Bt=0, n=int(L.gfn_kde_sorted_scratch_floats(0, 8, 8))) == 0 and dsorted(N=0) == 0
+    assert dsorted(std=0.0625, N=0) == 0  # the edge of the domain is inside it
+
+    def msort(x=p, xs=p, perm=p, scratch=p, Bt=1, N=8):
+        return L.gfn_kde_morton_sort(x, xs, perm, scratch, Bt, N, None)
+
+    for what, kw in {"row longer than 65535 * 16": dict(N=65535 * 16 + 1), "misaligned x": dict(x=odd), "misaligned x_sorted": dict(xs=odd),
+                     "null perm": dict(perm=None), "null scratch": dict(scratch=None), "null x": dict(x=None), "Bt < 0": dict(Bt=-1),
+                     "N < 0": dict(N=-1)}.items():
+        assert msort(**kw) == INVALID, what
+    assert b"too long" in (L.gfn_kde_morton_sort(p, p, p, p, 1, 65535 * 16 + 1, None), L.gfn_last_error())[1]
+    assert msort(Bt=0) == 0 and msort(N=0) == 0
+    assert L.gfn_kde_morton_keys(odd, p, 4, None) == INVALID and L.gfn_kde_morton_keys(None, p, 4, None) == INVALID
+    assert L.gfn_kde_morton_keys(p, None, 4, None) == INVALID and L.gfn_kde_morton_keys(p, p, -1, None) == INVALID
+    assert L.gfn_kde_morton_keys(p, p, 0, None) == 0
+
+
+def test_kde_sorted_scratch_covers_the_carve_up():
+    """gfn_kde_sorted_scratch_floats against the carve-up of gfn_kde_density_sorted, recomputed here (offsets in floats): pre-scaled
+    x and point pairs, 64- and 32-point boxes, up to 32 split-M partials, the bf16x8 operand images (16 bytes per entry, 128 per
+    64-row / 64-column tile pair), the 64-bit column sums.  Every region 16-byte aligned where the kernels read vectors, the last
+    byte inside the buffer, for every edge size and the production call."""
+    from gfnet_amd import _lib
+
+    L = _lib.lib()
+    sizes = [1, 2, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 4095, 4096, 4097, 10000]
+    for Bt in (1, 3, 32):
+        for N in sizes:
+            for M in {N, 1, 63, 333, 4097, sizes[(sizes.index(N) + 5) % len(sizes)]}:
+                Mp = (M + 1) & ~1
+                nblk = (Mp + 63) // 64
+                NT, MT = (N + 63) // 64 * 2, nblk * 2
+                xs = 0
+                ys = xs + Bt * N * 4
+                box = ys + Bt * Mp * 4
+                box32 = box + ((Bt * nblk * 8 + 3) & ~3)
+                part = box32 + Bt * nblk * 16
+                aop = part + ((Bt * 32 * N + 3) & ~3)       # room for MS = 32 partial rows
+                bop = aop + Bt * NT * 128 * 4
+                colacc = bop + Bt * MT * 128 * 4
+                end = colacc + Bt * N * 2
+                assert all(o % 4 == 0 for o in (ys, box, box32, part, aop, bop)) and colacc % 2 == 0, (Bt, N, M)
+                assert end <= int(L.gfn_kde_sorted_scratch_floats(Bt, N, M)), (Bt, N, M)
+                # the split never exceeds the 32 partial rows the carve-up leaves room for
+                blocks, ms = Bt * ((N + 255) // 256), 1
+                while blocks * ms < 2048 and nblk // (ms * 2) >= 8 and ms < 32:
+                    ms *= 2
+                assert ms <= 32
+
+
 def test_corr_general_loop_row_index_is_exact_below_2_pow_24():
     """corr_softargmax_kernel's general loop turns a B-position j into (jx, jy) with a float quotient and one integer correction
     step (csrc/corr_softargmax.hip).  This is that formula in float32 / int32 arithmetic, with inv_w1 = 1.0f / W1 correctly rounded,
