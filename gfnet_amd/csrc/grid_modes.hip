@@ -6,7 +6,9 @@
 //                                  (:548-549) with ConvRefiner(sample_mode=...) (:464, 502); the reference's refiner always pads with zeros
 //
 // One thread per output pixel / grid cell: the sampling set-up (sample_modes.h) once, then the channels in groups with all loads
-// of a group in flight.  The bilinear product path (grid_ops.hip, refiner_input.h) is not routed through here.
+// of a group in flight.  gfn_grid_sample_fwd (bilinear, zeros, fp32) is gfn_grid_sample_mode_fwd; the bilinear refiner input of the
+// product path keeps its own pair-gather kernel (grid_ops.hip, refiner_input.h), built on the same set-up.
+#include "refiner_input.h"
 #include "sample_modes.h"
 
 namespace {
@@ -119,20 +121,13 @@ GFN_EXPORT int gfn_grid_sample_mode_fwd(const void *in, int in_dtype, const floa
 GFN_EXPORT int gfn_refiner_input_mode_fwd_dt(const void *f0, const void *f1, int dtype, const float *flow, const float *disp_w,
                                              const float *disp_b, float *d, int64_t d_bs, int B, int C, int Hs, int Ws, int G, int disp_dim,
                                              float disp_scale, int symmetric, int sample_mode, gfn_stream_t stream) {
-    if (dtype != GFN_F32 && dtype != GFN_F16) return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input_mode: feature dtype must be GFN_F32 or GFN_F16");
     if (!gfn_sm::valid_modes(sample_mode, GFN_PAD_ZEROS))
         return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input_mode: sample_mode %d is not a GFN_SAMPLE_* code", sample_mode);
-    if (!f0 || !f1 || !flow || !d || (disp_dim > 0 && (!disp_w || !disp_b)))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input_mode: null pointer");
-    if (B < 0 || C <= 0 || Hs <= 0 || Ws <= 0 || G <= 0 || disp_dim < 0 || d_bs < (int64_t)(2 * C + disp_dim) * G * G ||
-        ((symmetric & 1) && (B & 1)) || (symmetric & ~3) || (long)C * Hs * Ws >= (1L << 31))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input_mode: bad size");
-    if (B == 0) return GFN_OK;
-    if (B > 65535 || (long)G * G >= (1L << 31)) return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input_mode: batch > 65535 or grid too large");
     gfn_ri::RiArgs q;
-    q.fa = f0; q.fb = f1; q.flow = flow; q.dw = disp_w; q.db = disp_b; q.d = d; q.d_bs = (long)d_bs;
-    q.B = B; q.Bh = (symmetric & 1) ? B / 2 : B; q.C = C; q.Hs = Hs; q.Ws = Ws; q.G = G; q.Dd = disp_dim; q.disp_scale = disp_scale;
-    const bool keep = (symmetric & GFN_RI_KEEP_GRID_FEATURE) != 0;
+    bool keep;
+    if (int e = gfn_ri::ri_args("refiner_input_mode", f0, f1, dtype, flow, disp_w, disp_b, d, d_bs, B, C, Hs, Ws, G, disp_dim, disp_scale, symmetric, q, keep))
+        return e;
+    if (B == 0) return GFN_OK;
     const dim3 grid((unsigned)(((long)G * G + 255) / 256), (unsigned)B);
     const hipStream_t s = (hipStream_t)stream;
     return gfn_sm::with_modes(sample_mode, GFN_PAD_ZEROS, [&](auto m, auto) {

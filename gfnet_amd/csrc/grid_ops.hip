@@ -6,7 +6,7 @@
 //                          written straight into the channel slices of the concat buffer `d`
 //                          (the local-correlation kernel fills the last slice), so the
 //                          reference's torch.cat copy of up to 417 channels disappears.
-//   gfn_grid_sample_fwd    F.grid_sample(bilinear, zeros, align_corners=False)
+//   gfn_grid_sample_fwd    F.grid_sample(bilinear, zeros, align_corners=False): gfn_grid_sample_mode_fwd (grid_modes.hip)
 //   gfn_interp_bilinear_fwd F.interpolate(mode='bilinear', align_corners=False), network.py:238-249,271-281
 //   gfn_flow_update_fwd    displacement scaling / eval-time zeroing / accumulation, network.py:262-268
 //   gfn_match_post_fwd     certainty attenuation, sigmoid, out-of-range masking, clamp, warp
@@ -29,23 +29,6 @@ __global__ __launch_bounds__(256) void refiner_input_kernel(RiArgs q, unsigned q
     refiner_input_cell<FT, KEEP>(q, ri_direction(q.B, q.Bh, blockIdx.y), blockIdx.x * 256u + threadIdx.x);
 }
 
-__global__ __launch_bounds__(256) void grid_sample_kernel(const float *__restrict__ in, const float *__restrict__ grid,
-                                                          float *__restrict__ out, long out_bs, int B, int C, int H, int W,
-                                                          int Ho, int Wo) {
-    const long total = (long)B * C * Ho * Wo;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const int j = (int)(idx % Wo);
-        long t = idx / Wo;
-        const int i = (int)(t % Ho);
-        t /= Ho;
-        const int c = (int)(t % C);
-        const int b = (int)(t / C);
-        const float *g = grid + (((size_t)b * Ho + i) * Wo + j) * 2;
-        const Bilin s = bilin_setup(g[0], g[1], W, H);
-        out[(size_t)b * out_bs + ((size_t)c * Ho + i) * Wo + j] = bilin_fetch(in + ((size_t)b * C + c) * H * W, W, s);
-    }
-}
-
 // ATen upsample_bilinear2d, align_corners=False: src = max(0, (dst+0.5)*in/out - 0.5)
 __device__ __forceinline__ float interp_at(const float *pl, int H, int W, int Ho, int Wo, int y, int x) {
     const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
@@ -61,7 +44,8 @@ __device__ __forceinline__ float interp_at(const float *pl, int H, int W, int Ho
 
 // ---- image resize + normalise ----------------------------------------------------
 // ATen upsample_bicubic2d, align_corners=False: src = (dst+0.5)*in/out - 0.5 (not clamped), taps floor(src)-1 .. +2 with
-// clamped indices, cubic convolution coefficients with A = -0.75, rows first then columns.
+// clamped indices, cubic convolution coefficients with A = -0.75, rows first then columns.  (sample_modes.h has the same
+// polynomials in ATen's grid_sampler argument order, cubic_conv2((1 - t) + 1) for cubic2(2 - t): other bits, kept apart.)
 __device__ __forceinline__ float cubic1(float x) { return ((-0.75f + 2.f) * x - (-0.75f + 3.f)) * x * x + 1.f; }
 __device__ __forceinline__ float cubic2(float x) { return ((-0.75f * x - 5.f * -0.75f) * x + 8.f * -0.75f) * x - 4.f * -0.75f; }
 __device__ __forceinline__ void cubic_coeffs(float t, float c[4]) {
@@ -247,19 +231,11 @@ GFN_EXPORT int gfn_refiner_input_fwd(const float *f0, const float *f1, const flo
 GFN_EXPORT int gfn_refiner_input_fwd_dt(const void *f0, const void *f1, int dtype, const float *flow, const float *disp_w,
                                         const float *disp_b, float *d, int64_t d_bs, int B, int C, int Hs, int Ws, int G,
                                         int disp_dim, float disp_scale, int symmetric, gfn_stream_t stream) {
-    if (dtype != GFN_F32 && dtype != GFN_F16) return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input: feature dtype must be GFN_F32 or GFN_F16");
-    if (!f0 || !f1 || !flow || !d || (disp_dim > 0 && (!disp_w || !disp_b)))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input: null pointer");
-    if (B < 0 || C <= 0 || Hs <= 0 || Ws <= 0 || G <= 0 || disp_dim < 0 || d_bs < (int64_t)(2 * C + disp_dim) * G * G ||
-        ((symmetric & 1) && (B & 1)) || (symmetric & ~3) || (long)C * Hs * Ws >= (1L << 31))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input: bad size");
-    if (B == 0) return GFN_OK;
-    if (B > 65535 || (long)G * G >= (1L << 31)) return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input: batch > 65535 or grid too large");
-    const unsigned q_blocks = (unsigned)(((long)G * G + 255) / 256);
     RiArgs q;
-    q.fa = f0; q.fb = f1; q.flow = flow; q.dw = disp_w; q.db = disp_b; q.d = d; q.d_bs = (long)d_bs;
-    q.B = B; q.Bh = (symmetric & 1) ? B / 2 : B; q.C = C; q.Hs = Hs; q.Ws = Ws; q.G = G; q.Dd = disp_dim; q.disp_scale = disp_scale;
-    const bool keep = (symmetric & 2) != 0;  // the grid_feature planes are already in d (GFN_RI_KEEP_GRID_FEATURE)
+    bool keep;
+    if (int e = ri_args("refiner_input", f0, f1, dtype, flow, disp_w, disp_b, d, d_bs, B, C, Hs, Ws, G, disp_dim, disp_scale, symmetric, q, keep)) return e;
+    if (B == 0) return GFN_OK;
+    const unsigned q_blocks = (unsigned)(((long)G * G + 255) / 256);
     const int banded = gfn_ri::ri_bands(q.B, q.Bh, q_blocks) ? 1 : 0;
     const dim3 grid = banded ? dim3(gfn_ri::ri_banded_blocks(B, q_blocks)) : dim3(q_blocks, (unsigned)B);
     if (dtype == GFN_F16) {
@@ -274,12 +250,7 @@ GFN_EXPORT int gfn_refiner_input_fwd_dt(const void *f0, const void *f1, int dtyp
 
 GFN_EXPORT int gfn_grid_sample_fwd(const float *in, const float *grid, float *out, int64_t out_bs, int B, int C, int H,
                                    int W, int Ho, int Wo, gfn_stream_t stream) {
-    if (!in || !grid || !out || B < 0 || C <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || out_bs < (int64_t)C * Ho * Wo)
-        return gfn::fail(GFN_ERR_INVALID_ARG, "grid_sample: bad argument");
-    if (B == 0) return GFN_OK;
-    hipLaunchKernelGGL(grid_sample_kernel, dim3(grid_for((long)B * C * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, in,
-                       grid, out, (long)out_bs, B, C, H, W, Ho, Wo);
-    return gfn::check_launch("grid_sample_kernel");
+    return gfn_grid_sample_mode_fwd(in, GFN_F32, grid, out, out_bs, B, C, H, W, Ho, Wo, GFN_SAMPLE_BILINEAR, GFN_PAD_ZEROS, stream);
 }
 
 GFN_EXPORT int gfn_interp_bilinear_fwd(const float *in, float *out, int BC, int H, int W, int Ho, int Wo,

@@ -29,7 +29,10 @@
 //   * tiles whose bounding box does not fit the stage (wild flow) are staged per 2x16 round, and
 //     rounds that still do not fit use the general per-tap routine inside the same launch.
 // General path (any C, radius, non-integer tap spacing: grid_based_correlation, pooled levels):
-//   one thread per (cell, tap), per-tap bilinear gather exactly as grid_sample does it.
+//   one thread per (cell, tap), per-tap bilinear gather exactly as grid_sample does it: the bilinear + zeros instantiation of
+//   local_corr_mode_kernel (local_corr_modes.hip), whose per-tap routine (tap_dot on Taps<MODE>, local_corr_common.h,
+//   sample_modes.h) is also what the tiled kernels call for flagged cells.  The feature0 gradient (gfn_local_corr_bwd_f0) is
+//   gfn_local_corr_mode_bwd_f0 for bilinear + zeros.
 //
 // Block->tile mapping is XCD-aware (common.h): consecutive tiles of one image stay on one XCD so
 // the 3-4x halo re-reads of f1 are served by that XCD's L2, not HBM.
@@ -40,91 +43,6 @@
 #include "local_corr_mq.h"
 
 namespace {
-
-template <typename FT>
-__global__ __launch_bounds__(256) void local_corr_general_kernel(LcParams p) {
-    const int D = 2 * p.r + 1, K = D * D;
-    const long total = (long)p.B * K * p.G * p.G;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const int j = (int)(idx % p.G);
-        long t = idx / p.G;
-        const int i = (int)(t % p.G);
-        t /= p.G;
-        const int k = (int)(t % K);
-        const int b = (int)(t / K);
-        float nx, ny;
-        cell_coords(p, b, i, j, nx, ny);
-        p.out[(size_t)b * p.out_bs + ((size_t)k * p.G + i) * p.G + j] = tap_general<FT>(p, b, i, j, k / D, k % D, D, nx, ny);
-    }
-}
-
-// ---- backward w.r.t. feature0 ---------------------------------------------------
-// out[b,k,i,j] = sum_c (f0[b,c,i,j] / sqrt(c)) * S_c(k) with S_c(k) the bilinear sample of f1[b,c] at tap k; the reference
-// lets gradients reach feature0 only (local_correlation.py:54-60: the sampling runs under no_grad).  Hence
-//   grad_f0[b,c,i,j] = (sum_k grad_out[b,k,i,j] * S_c(k)) / sqrt(c):
-// one thread per (cell, 8-channel group) walks the K taps with the forward's own coordinate arithmetic.
-constexpr int kBwdCh = 8;
-__global__ __launch_bounds__(256) void local_corr_bwd_f0_kernel(LcParams p, const float *__restrict__ gout, long gout_bs,
-                                                                float *__restrict__ gf0, long gf0_bs) {
-    const int D = 2 * p.r + 1, K = D * D;
-    const int groups = (p.C + kBwdCh - 1) / kBwdCh;
-    const long total = (long)p.B * groups * p.G * p.G;
-    float ylo, yhi, xlo, xhi;
-    if (p.grid_based) {
-        ylo = (float)(-2.0 * p.r / p.G); yhi = (float)(2.0 * p.r / p.G);
-        xlo = ylo; xhi = yhi;
-    } else {
-        ylo = (float)(-2.0 * p.r / p.win_h); yhi = (float)(2.0 * p.r / p.win_h);
-        xlo = (float)(-2.0 * p.r / p.win_w); xhi = (float)(2.0 * p.r / p.win_w);
-    }
-    const size_t plane = (size_t)p.H * p.W, cs = (size_t)p.G * p.G;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const int j = (int)(idx % p.G);
-        long t = idx / p.G;
-        const int i = (int)(t % p.G);
-        t /= p.G;
-        const int cg = (int)(t % groups);
-        const int b = (int)(t / groups);
-        const int c0 = cg * kBwdCh, nc = min(kBwdCh, p.C - c0);
-        float nx, ny;
-        cell_coords(p, b, i, j, nx, ny);
-        const float *f1p = f1_of<float>(p, b) + (size_t)c0 * plane;
-        const float *g = gout + (size_t)b * gout_bs + (size_t)i * p.G + j;
-        float acc[kBwdCh];
-#pragma unroll
-        for (int c = 0; c < kBwdCh; ++c) acc[c] = 0.f;
-        for (int k = 0; k < K; ++k) {
-            const int ky = k / D, kx = k - ky * D;
-            const float gx = nx + gfn::linspace_at(xlo, xhi, D, kx);
-            const float gy = ny + gfn::linspace_at(ylo, yhi, D, ky);
-            const float ix = unnorm(gx, p.W), iy = unnorm(gy, p.H);
-            const float fx = floorf(ix), fy = floorf(iy);
-            const bool sane = (fx > -1e6f) & (fx < 1e6f) & (fy > -1e6f) & (fy < 1e6f);
-            const int x0 = sane ? (int)fx : -4, y0 = sane ? (int)fy : -4;
-            const float w00 = (fx + 1.f - ix) * (fy + 1.f - iy), w01 = (ix - fx) * (fy + 1.f - iy);
-            const float w10 = (fx + 1.f - ix) * (iy - fy), w11 = (ix - fx) * (iy - fy);
-            const bool xa = (unsigned)x0 < (unsigned)p.W, xb = (unsigned)(x0 + 1) < (unsigned)p.W;
-            const bool ya = (unsigned)y0 < (unsigned)p.H, yb = (unsigned)(y0 + 1) < (unsigned)p.H;
-            const long o00 = (long)y0 * p.W + x0;
-            const float gk = g[(size_t)k * cs];
-#pragma unroll
-            for (int c = 0; c < kBwdCh; ++c) {
-                if (c >= nc) break;
-                const float *pl = f1p + c * plane;
-                float sv = 0.f;
-                if (ya & xa) sv += pl[o00] * w00;
-                if (ya & xb) sv += pl[o00 + 1] * w01;
-                if (yb & xa) sv += pl[o00 + p.W] * w10;
-                if (yb & xb) sv += pl[o00 + p.W + 1] * w11;
-                acc[c] = fmaf(gk, sv, acc[c]);
-            }
-        }
-        float *dst = gf0 + (size_t)b * gf0_bs + (size_t)c0 * cs + (size_t)i * p.G + j;
-#pragma unroll
-        for (int c = 0; c < kBwdCh; ++c)
-            if (c < nc) dst[c * cs] = acc[c] / p.sqrt_c;
-    }
-}
 
 // shapes the lean tile path takes (it keeps at most 8 channels of the f0 block per wave in registers, addresses planes with
 // 32-bit byte offsets, and reads fp16 quads at 4-byte alignment)
@@ -171,7 +89,7 @@ LcVariant decode_variant(int variant) {
 
 enum class LcRoute {
     Refused,       // variant 8 on a call the lean path does not take
-    General,       // local_corr_general_kernel
+    General,       // local_corr_mode_kernel<FT, bilinear, zeros> (local_corr_modes.hip)
     Lean,          // (plan kernel) + local_corr_tile2_kernel (+ r <= 2: local_corr_irregular_kernel)
     Round1,        // local_corr_tile_kernel + local_corr_irregular_kernel, 16-byte quad staging at r >= 5 (QOK)
     Round1Narrow,  // the same with the narrow stage loads (!QOK): r >= 5 on fp16 maps of odd width
@@ -198,19 +116,6 @@ LcRoute lc_route(const LcParams &p, const void *scratch, int64_t scratch_bytes, 
     // fp16 maps of odd width (35 x 35: scale 8 of a 280-pixel refinement pass) keep the narrow stage loads at r >= 5: an 8-byte quad
     // of such a row is not 4-byte aligned.  A kernel instantiation of its own, so that the staging form is a compile-time constant.
     return (p.r >= 5 && p.f16 && (p.W & 1)) ? LcRoute::Round1Narrow : LcRoute::Round1;
-}
-
-// what the forward, backward and plan entry points fill alike
-LcParams lc_params(const void *f1, const void *f1_second, bool f16, const float *flow, int B, int C, int G, int H, int W, int r,
-                   int grid_based, int win_h, int win_w) {
-    LcParams p{};
-    p.f1 = f1; p.f1_second = f1_second; p.f16 = f16 ? 1 : 0; p.Bh = f1_second ? B / 2 : B;
-    p.flow = flow;
-    p.B = B; p.C = C; p.G = G; p.H = H; p.W = W;
-    p.sqrt_c = (float)sqrt((double)C);
-    p.inv_sqrt_c = (float)(1.0 / sqrt((double)C));
-    p.r = r; p.win_h = win_h; p.win_w = win_w; p.grid_based = grid_based;
-    return p;
 }
 
 // the tile grid and the window parameters every tiled launch needs (what tap_general, the plan and the fraction tables read)
@@ -333,18 +238,9 @@ GFN_EXPORT int gfn_local_corr_fwd_dt(const float *f0, int64_t f0_bs, const void 
                                      int r, int grid_based, int win_h, int win_w, int variant, void *scratch,
                                      int64_t scratch_bytes, gfn_stream_t stream) {
     if (f1_dtype != GFN_F32 && f1_dtype != GFN_F16) return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr: feature dtype must be GFN_F32 or GFN_F16");
-    if (!f0 || !f1 || !out) return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr: null tensor pointer");
-    if (f1_second && (B & 1)) return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr: symmetric batch must be even");
-    if (B < 0 || C <= 0 || G <= 0 || H <= 0 || W <= 0 || r < 0 || win_h <= 0 || win_w <= 0)
-        return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr: bad size B=%d C=%d G=%d H=%d W=%d r=%d", B, C, G, H, W, r);
-    const long K = (long)(2 * r + 1) * (2 * r + 1);
-    if (f0_bs < (long)C * G * G || out_bs < K * G * G)
-        return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr: batch stride smaller than one batch element");
-    if (!flow && !(G == win_h && G == win_w))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr: flow=NULL needs num_grid == h == w (got G=%d h=%d w=%d)", G,
-                         win_h, win_w);
-    if ((long)B * K * G * G >= (1L << 40) || (long)C * H * W >= (1L << 31))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr: tensor too large");
+    if (int e = check_args("local_corr", !f0 || !f1 || !out, f1_second && (B & 1), B, C, G, H, W, r, win_h, win_w, f0_bs, out_bs, flow != nullptr,
+                           GFN_SAMPLE_BILINEAR, GFN_PAD_ZEROS))
+        return e;
     if (B == 0) return GFN_OK;
     hipStream_t s = (hipStream_t)stream;
     LcParams p = lc_params(f1, f1_second, f1_dtype == GFN_F16, flow, B, C, G, H, W, r, grid_based, win_h, win_w);
@@ -352,13 +248,7 @@ GFN_EXPORT int gfn_local_corr_fwd_dt(const float *f0, int64_t f0_bs, const void 
     const LcVariant v = decode_variant(variant);
     const LcRoute route = lc_route(p, scratch, scratch_bytes, v);
     if (route == LcRoute::Refused) return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr: variant 8 (plan present) on a call the lean path does not take");
-    if (route == LcRoute::General) {
-        const long total = (long)B * K * G * G;
-        const unsigned grid = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-        if (p.f16) hipLaunchKernelGGL(local_corr_general_kernel<_Float16>, dim3(grid), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(local_corr_general_kernel<float>, dim3(grid), dim3(256), 0, s, p);
-        return gfn::check_launch("local_corr_general_kernel");
-    }
+    if (route == LcRoute::General) return gfn_lc_launch_taps(p, GFN_SAMPLE_BILINEAR, GFN_PAD_ZEROS, s);
     tiled_window(p);
     p.todo = reinterpret_cast<int *>(scratch);
     p.todo_ints = scratch_bytes / 4;
@@ -404,20 +294,15 @@ GFN_EXPORT int gfn_refiner_input_plan_fwd_dt(const void *f0, const void *f1, int
                                              const float *disp_b, float *d, int64_t d_bs, int B, int C, int Hs, int Ws, int G, int disp_dim,
                                              float disp_scale, int symmetric, int r, void *scratch, int64_t scratch_bytes,
                                              gfn_stream_t stream) {
-    if (dtype != GFN_F32 && dtype != GFN_F16) return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input_plan: feature dtype must be GFN_F32 or GFN_F16");
-    if (!f0 || !f1 || !flow || !d || (disp_dim > 0 && (!disp_w || !disp_b))) return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input_plan: null pointer");
-    if (B < 0 || C <= 0 || Hs <= 0 || Ws <= 0 || G <= 0 || disp_dim < 0 || d_bs < (int64_t)(2 * C + disp_dim) * G * G || ((symmetric & 1) && (B & 1)) ||
-        (symmetric & ~3) || (long)C * Hs * Ws >= (1L << 31) || B > 65535 || (long)G * G >= (1L << 31))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input_plan: bad size");
+    gfn_ri::RiArgs q;
+    bool keep;
+    if (int e = gfn_ri::ri_args("refiner_input_plan", f0, f1, dtype, flow, disp_w, disp_b, d, d_bs, B, C, Hs, Ws, G, disp_dim, disp_scale, symmetric, q, keep))
+        return e;
     if (!lean_shape(C, Hs, Ws, G, r, dtype == GFN_F16))
         return gfn::fail(GFN_ERR_INVALID_ARG, "refiner_input_plan: the local correlation of this shape takes no plan (ask gfn_local_corr_plans first)");
     if (!scratch || scratch_bytes < gfn_local_corr_scratch_bytes(B, G) || ((uintptr_t)scratch & 3))
         return gfn::fail(GFN_ERR_SCRATCH, "refiner_input_plan: scratch too small");
     if (B == 0) return GFN_OK;
-    gfn_ri::RiArgs q;
-    q.fa = f0; q.fb = f1; q.flow = flow; q.dw = disp_w; q.db = disp_b; q.d = d; q.d_bs = (long)d_bs;
-    q.B = B; q.Bh = (symmetric & 1) ? B / 2 : B; q.C = C; q.Hs = Hs; q.Ws = Ws; q.G = G; q.Dd = disp_dim; q.disp_scale = disp_scale;
-    const bool keep = (symmetric & 2) != 0;  // the grid_feature planes are already in d
     LcParams p = lc_params(nullptr, nullptr, dtype == GFN_F16, flow, B, C, G, Hs, Ws, r, 0, Hs, Ws);
     tiled_window(p);
     p.todo = reinterpret_cast<int *>(scratch);
@@ -428,23 +313,8 @@ GFN_EXPORT int gfn_refiner_input_plan_fwd_dt(const void *f0, const void *f1, int
 GFN_EXPORT int gfn_local_corr_bwd_f0(const float *grad_out, int64_t grad_out_bs, const float *f1, const float *f1_second,
                                     const float *flow, float *grad_f0, int64_t grad_f0_bs, int B, int C, int G, int H, int W, int r,
                                     int grid_based, int win_h, int win_w, gfn_stream_t stream) {
-    if (!grad_out || !f1 || !grad_f0) return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr_bwd: null tensor pointer");
-    if (f1_second && (B & 1)) return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr_bwd: symmetric batch must be even");
-    if (B < 0 || C <= 0 || G <= 0 || H <= 0 || W <= 0 || r < 0 || win_h <= 0 || win_w <= 0)
-        return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr_bwd: bad size B=%d C=%d G=%d H=%d W=%d r=%d", B, C, G, H, W, r);
-    const long K = (long)(2 * r + 1) * (2 * r + 1);
-    if (grad_f0_bs < (long)C * G * G || grad_out_bs < K * G * G)
-        return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr_bwd: batch stride smaller than one batch element");
-    if (!flow && !(G == win_h && G == win_w))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr_bwd: flow=NULL needs num_grid == h == w");
-    if ((long)C * H * W >= (1L << 31)) return gfn::fail(GFN_ERR_INVALID_ARG, "local_corr_bwd: tensor too large");
-    if (B == 0) return GFN_OK;
-    const LcParams p = lc_params(f1, f1_second, false, flow, B, C, G, H, W, r, grid_based, win_h, win_w);
-    const long total = (long)B * ((C + kBwdCh - 1) / kBwdCh) * G * G;
-    const unsigned grid = (unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-    hipLaunchKernelGGL(local_corr_bwd_f0_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, grad_out, (long)grad_out_bs, grad_f0,
-                       (long)grad_f0_bs);
-    return gfn::check_launch("local_corr_bwd_f0_kernel");
+    return gfn_local_corr_mode_bwd_f0(grad_out, grad_out_bs, f1, f1_second, flow, grad_f0, grad_f0_bs, B, C, G, H, W, r, grid_based, win_h, win_w,
+                                      GFN_SAMPLE_BILINEAR, GFN_PAD_ZEROS, stream);
 }
 
 namespace {

@@ -1,24 +1,8 @@
-// local_corr_common.h -- what every local-correlation kernel shares: the launch constants, the kernel argument block (LcParams),
-// and the device helpers of the per-tap routine, the cell coordinates and the wave reductions.
+// local_corr_common.h -- what every local-correlation kernel shares: the launch constants, the kernel argument block (LcParams)
+// with its host-side checks and filler, and the device helpers of the per-tap routine, the cell coordinates and the wave reductions.
 #pragma once
 #include "common.h"
-#include "refiner_input.h"
-
-namespace {
-
-constexpr int kThreads = 512;
-constexpr int kWaves = kThreads / 64;
-constexpr int kChunk = 16;                // channels staged per pass
-constexpr int kSlotV4 = kChunk / 4 + 1;   // float4s per staged pixel: 4 data + 1 pad = 80 B
-constexpr int kStageBytes = 68 * 1024;    // stage buffer (aliased by the D buffer in the epilogue)
-constexpr int kCapSlots = kStageBytes / (kSlotV4 * 16) - 1;  // pixels that fit, minus the zero slot
-static_assert((kCapSlots + 1) * kSlotV4 < 65536, "stage indices are packed in 16 bits");
-constexpr int kTileW = 16;
-constexpr int kMaxLds = 150 * 1024;       // dynamic LDS a tiled launch may ask for
-constexpr int kFar = 1 << 28;             // patch origin of a cell that samples nothing
-constexpr int kTodoHdr = 8;               // ints in front of the tile list in scratch: [0] tiles left to the second launch, [1] its queue head,
-                                          // [2] its finished workgroups, [3] last call's [0], [4] cells redone per tap (running call),
-                                          // [5] last call's [4], [6] tiles staged in halves (running call), [7] last call's [6]; [0..2], [4] and [6] are zero between calls
+#include "sample_modes.h"
 
 struct LcParams {
     const float *f0;
@@ -42,6 +26,26 @@ struct LcParams {
     int *plan;                        // lean path: [4 * B*tiles] per-tile staging regions written by the plan launch (16-byte aligned)
 };
 
+// host: launches the per-(cell, tap) kernel of local_corr_modes.hip for validated mode codes; the general route of
+// gfn_local_corr_fwd_dt (bilinear, zeros) and gfn_local_corr_mode_fwd end here
+int gfn_lc_launch_taps(const LcParams &p, int sample_mode, int padding_mode, hipStream_t s);
+
+namespace {
+
+constexpr int kThreads = 512;
+constexpr int kWaves = kThreads / 64;
+constexpr int kChunk = 16;                // channels staged per pass
+constexpr int kSlotV4 = kChunk / 4 + 1;   // float4s per staged pixel: 4 data + 1 pad = 80 B
+constexpr int kStageBytes = 68 * 1024;    // stage buffer (aliased by the D buffer in the epilogue)
+constexpr int kCapSlots = kStageBytes / (kSlotV4 * 16) - 1;  // pixels that fit, minus the zero slot
+static_assert((kCapSlots + 1) * kSlotV4 < 65536, "stage indices are packed in 16 bits");
+constexpr int kTileW = 16;
+constexpr int kMaxLds = 150 * 1024;       // dynamic LDS a tiled launch may ask for
+constexpr int kFar = 1 << 28;             // patch origin of a cell that samples nothing
+constexpr int kTodoHdr = 8;               // ints in front of the tile list in scratch: [0] tiles left to the second launch, [1] its queue head,
+                                          // [2] its finished workgroups, [3] last call's [0], [4] cells redone per tap (running call),
+                                          // [5] last call's [4], [6] tiles staged in halves (running call), [7] last call's [6]; [0..2], [4] and [6] are zero between calls
+
 // f1 map of direction b.  Symmetric batches are virtual: the second half of the directions reads
 // the other image's features (f1_second) instead of a concatenated copy (model/network.py:213-222).
 template <typename FT>
@@ -50,8 +54,7 @@ __device__ __forceinline__ const FT *f1_of(const LcParams &p, int b) {
     return (b < p.Bh) ? static_cast<const FT *>(p.f1) + (size_t)b * chw : static_cast<const FT *>(p.f1_second) + (size_t)(b - p.Bh) * chw;
 }
 // a feature value as fp32 (fp16 storage is widened in registers; every sum stays fp32)
-__device__ __forceinline__ float ldf(const float *q) { return *q; }
-__device__ __forceinline__ float ldf(const _Float16 *q) { return (float)*q; }
+using gfn_sm::ldf;
 
 // lane -> (b128 hardware lane group, index inside the group).  ds_read_b128 is serviced in four
 // 16-lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, and the same +32.
@@ -84,13 +87,11 @@ __device__ __forceinline__ int wave_min_i32(int v) {
     return __builtin_amdgcn_readlane(v, 63);
 }
 
-// Normalised -> pixel coordinate exactly as grid_sample(align_corners=False) un-normalises (refiner_input.h).
-using gfn_ri::unnorm;
+// Normalised -> pixel coordinate exactly as grid_sample(align_corners=False) un-normalises.
+using gfn_sm::unnorm;
 
-// ---- general per-tap evaluation (mirrors the reference op for op) ---------------------------
-template <typename FT>
-__device__ __forceinline__ float tap_general(const LcParams &p, int b, int i, int j, int ky, int kx, int D, float nx, float ny) {
-    float ylo, yhi, xlo, xhi;
+// the window's end points in normalised units: +-2r / G (grid_based) or +-2r / (win_w, win_h)
+__device__ __forceinline__ void window_ends(const LcParams &p, float &xlo, float &xhi, float &ylo, float &yhi) {
     if (p.grid_based) {
         ylo = (float)(-2.0 * p.r / p.G); yhi = (float)(2.0 * p.r / p.G);
         xlo = ylo; xhi = yhi;
@@ -98,48 +99,41 @@ __device__ __forceinline__ float tap_general(const LcParams &p, int b, int i, in
         ylo = (float)(-2.0 * p.r / p.win_h); yhi = (float)(2.0 * p.r / p.win_h);
         xlo = (float)(-2.0 * p.r / p.win_w); xhi = (float)(2.0 * p.r / p.win_w);
     }
-    const float gx = nx + gfn::linspace_at(xlo, xhi, D, kx);
-    const float gy = ny + gfn::linspace_at(ylo, yhi, D, ky);
-    const float ix = unnorm(gx, p.W), iy = unnorm(gy, p.H);
-    float fx = floorf(ix), fy = floorf(iy);
-    const bool sane = (fx > -1e6f) & (fx < 1e6f) & (fy > -1e6f) & (fy < 1e6f);
-    const int x0 = sane ? (int)fx : -4, y0 = sane ? (int)fy : -4;
-    const float w00 = (fx + 1.f - ix) * (fy + 1.f - iy), w01 = (ix - fx) * (fy + 1.f - iy);
-    const float w10 = (fx + 1.f - ix) * (iy - fy), w11 = (ix - fx) * (iy - fy);
-    const bool xa = (unsigned)x0 < (unsigned)p.W, xb = (unsigned)(x0 + 1) < (unsigned)p.W;
-    const bool ya = (unsigned)y0 < (unsigned)p.H, yb = (unsigned)(y0 + 1) < (unsigned)p.H;
+}
+
+// sum_c f0[b,c,i,j] / sqrt(C) * (the sample of f1[b,c] through the set-up tp), as the reference forms it op for op: channels in
+// groups with all gathers of a group in flight -- a corner outside the image reads pixel 0 with weight 0 (adds an exact 0), the
+// branchy form exposed one L2 round trip per channel
+template <typename FT, int MODE>
+__device__ __forceinline__ float tap_dot(const LcParams &p, int b, int i, int j, const gfn_sm::Taps<MODE> &tp) {
+    constexpr int UC = gfn_sm::group_channels<MODE>();
     const float *f0p = p.f0 + (size_t)b * p.f0_bs + (size_t)i * p.G + j;
     const FT *f1p = f1_of<FT>(p, b);
     const size_t plane = (size_t)p.H * p.W, cs = (size_t)p.G * p.G;
-    const long o00 = (long)y0 * p.W + x0;
-    // zero padding without branches: a corner outside the image reads pixel 0 with weight 0 (adds an exact 0), so the
-    // gathers of 8 channels can all be in flight at once -- the branchy form exposed one L2 round trip per channel
-    const long oa = (ya & xa) ? o00 : 0, ob = (ya & xb) ? o00 + 1 : 0, oc = (yb & xa) ? o00 + p.W : 0, od = (yb & xb) ? o00 + p.W + 1 : 0;
-    const float wa = (ya & xa) ? w00 : 0.f, wb = (ya & xb) ? w01 : 0.f, wc = (yb & xa) ? w10 : 0.f, wd = (yb & xb) ? w11 : 0.f;
     float acc = 0.f;
-    constexpr int UC = 8;
     for (int c0 = 0; c0 < p.C; c0 += UC) {
-        float va[UC], vb[UC], vc[UC], vd[UC], q[UC];
+        float v[UC][gfn_sm::Taps<MODE>::N], q[UC];
 #pragma unroll
         for (int u = 0; u < UC; ++u) {
             const int c = min(c0 + u, p.C - 1);
-            const FT *pl = f1p + c * plane;
-            va[u] = ldf(pl + oa); vb[u] = ldf(pl + ob); vc[u] = ldf(pl + oc); vd[u] = ldf(pl + od);
+            tp.load(f1p + c * plane, v[u]);
             q[u] = f0p[c * cs];
         }
 #pragma unroll
-        for (int u = 0; u < UC; ++u) {
-            if (c0 + u < p.C) {
-                float s = 0.f;
-                s += va[u] * wa;
-                s += vb[u] * wb;
-                s += vc[u] * wc;
-                s += vd[u] * wd;
-                acc += (q[u] / p.sqrt_c) * s;
-            }
-        }
+        for (int u = 0; u < UC; ++u)
+            if (c0 + u < p.C) acc += (q[u] / p.sqrt_c) * tp.value(v[u]);
     }
     return acc;
+}
+
+// ---- general per-tap evaluation of the tiled kernels (flagged cells, rounds that do not fit the stage): bilinear, zeros ---------
+template <typename FT>
+__device__ __forceinline__ float tap_general(const LcParams &p, int b, int i, int j, int ky, int kx, int D, float nx, float ny) {
+    float xlo, xhi, ylo, yhi;
+    window_ends(p, xlo, xhi, ylo, yhi);
+    gfn_sm::Taps<GFN_SAMPLE_BILINEAR> tp;
+    tp.setup<GFN_PAD_ZEROS>(nx + gfn::linspace_at(xlo, xhi, D, kx), ny + gfn::linspace_at(ylo, yhi, D, ky), p.W, p.H);
+    return tap_dot<FT>(p, b, i, j, tp);
 }
 
 __device__ __forceinline__ void cell_coords(const LcParams &p, int b, int i, int j, float &nx, float &ny) {
@@ -150,6 +144,40 @@ __device__ __forceinline__ void cell_coords(const LcParams &p, int b, int i, int
         nx = gfn::linspace_at((float)(-1 + 1.0 / p.win_w), (float)(1 - 1.0 / p.win_w), p.win_w, j);
         ny = gfn::linspace_at((float)(-1 + 1.0 / p.win_h), (float)(1 - 1.0 / p.win_h), p.win_h, i);
     }
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------
+// the argument checks of the local-correlation entry points (`what` names the caller in the error text); in / out: the tensor
+// of C and of K planes per batch element (f0 and out forwards, grad_f0 and grad_out backwards)
+inline int check_args(const char *what, bool null_ptr, bool odd_symmetric, int B, int C, int G, int H, int W, int r, int win_h, int win_w,
+                      int64_t in_bs, int64_t out_bs, bool has_flow, int sample_mode, int padding_mode) {
+    if (!gfn_sm::valid_modes(sample_mode, padding_mode))
+        return gfn::fail(GFN_ERR_INVALID_ARG, "%s: sample_mode %d / padding_mode %d is not a GFN_SAMPLE_* / GFN_PAD_* code", what,
+                         sample_mode, padding_mode);
+    if (null_ptr) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: null tensor pointer", what);
+    if (odd_symmetric) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: symmetric batch must be even", what);
+    if (B < 0 || C <= 0 || G <= 0 || H <= 0 || W <= 0 || r < 0 || win_h <= 0 || win_w <= 0)
+        return gfn::fail(GFN_ERR_INVALID_ARG, "%s: bad size B=%d C=%d G=%d H=%d W=%d r=%d", what, B, C, G, H, W, r);
+    const long K = (long)(2 * r + 1) * (2 * r + 1);
+    if (in_bs < (long)C * G * G || out_bs < K * G * G)
+        return gfn::fail(GFN_ERR_INVALID_ARG, "%s: batch stride smaller than one batch element", what);
+    if (!has_flow && !(G == win_h && G == win_w))
+        return gfn::fail(GFN_ERR_INVALID_ARG, "%s: flow=NULL needs num_grid == h == w (got G=%d h=%d w=%d)", what, G, win_h, win_w);
+    if ((long)B * K * G * G >= (1L << 40) || (long)C * H * W >= (1L << 31)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: tensor too large", what);
+    return GFN_OK;
+}
+
+// what the forward, backward and plan entry points fill alike
+inline LcParams lc_params(const void *f1, const void *f1_second, bool f16, const float *flow, int B, int C, int G, int H, int W, int r,
+                          int grid_based, int win_h, int win_w) {
+    LcParams p{};
+    p.f1 = f1; p.f1_second = f1_second; p.f16 = f16 ? 1 : 0; p.Bh = f1_second ? B / 2 : B;
+    p.flow = flow;
+    p.B = B; p.C = C; p.G = G; p.H = H; p.W = W;
+    p.sqrt_c = (float)sqrt((double)C);
+    p.inv_sqrt_c = (float)(1.0 / sqrt((double)C));
+    p.r = r; p.win_h = win_h; p.win_w = win_w; p.grid_based = grid_based;
+    return p;
 }
 
 }  // namespace

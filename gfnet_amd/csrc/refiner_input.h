@@ -3,68 +3,9 @@
 // also plans the tiles of the local correlation that follows, so that call needs no plan launch of its own).
 #pragma once
 #include "common.h"
+#include "sample_modes.h"
 
 namespace gfn_ri {
-
-__device__ __forceinline__ float unnorm(float g, int size) { return ((g + 1.f) * (float)size - 1.f) / 2.f; }
-
-struct Bilin {
-    int x0, y0;
-    float w00, w01, w10, w11;
-    bool xa, xb, ya, yb;
-};
-
-// grid_sample's bilinear set-up (ATen grid_sampler_2d): corners nw,ne,sw,se; zeros padding.
-__device__ __forceinline__ Bilin bilin_setup(float gx, float gy, int W, int H) {
-    Bilin s;
-    const float ix = unnorm(gx, W), iy = unnorm(gy, H);
-    const float fx = floorf(ix), fy = floorf(iy);
-    const bool sane = (fx > -1e6f) & (fx < 1e6f) & (fy > -1e6f) & (fy < 1e6f);
-    s.x0 = sane ? (int)fx : -4;
-    s.y0 = sane ? (int)fy : -4;
-    s.w00 = (fx + 1.f - ix) * (fy + 1.f - iy);
-    s.w01 = (ix - fx) * (fy + 1.f - iy);
-    s.w10 = (fx + 1.f - ix) * (iy - fy);
-    s.w11 = (ix - fx) * (iy - fy);
-    s.xa = (unsigned)s.x0 < (unsigned)W;
-    s.xb = (unsigned)(s.x0 + 1) < (unsigned)W;
-    s.ya = (unsigned)s.y0 < (unsigned)H;
-    s.yb = (unsigned)(s.y0 + 1) < (unsigned)H;
-    return s;
-}
-
-__device__ __forceinline__ float bilin_fetch(const float *pl, int W, const Bilin &s) {
-    const long o = (long)s.y0 * W + s.x0;
-    float v = 0.f;
-    if (s.ya & s.xa) v += pl[o] * s.w00;
-    if (s.ya & s.xb) v += pl[o + 1] * s.w01;
-    if (s.yb & s.xa) v += pl[o + W] * s.w10;
-    if (s.yb & s.xb) v += pl[o + W + 1] * s.w11;
-    return v;
-}
-
-// Clamped form of a bilinear set-up: four always-valid offsets and four weights that are zero for
-// out-of-image corners, so the gathers need no branches (a zero weight times any finite value adds
-// an exact 0; corner order nw, ne, sw, se is kept).
-struct BilinC {
-    int o[4];
-    float w[4];
-};
-
-__device__ __forceinline__ BilinC bilin_clamped(float gx, float gy, int W, int H) {
-    const Bilin s = bilin_setup(gx, gy, W, H);
-    BilinC c;
-    const int o00 = s.y0 * W + s.x0;
-    c.o[0] = (s.ya & s.xa) ? o00 : 0;
-    c.o[1] = (s.ya & s.xb) ? o00 + 1 : 0;
-    c.o[2] = (s.yb & s.xa) ? o00 + W : 0;
-    c.o[3] = (s.yb & s.xb) ? o00 + W + 1 : 0;
-    c.w[0] = (s.ya & s.xa) ? s.w00 : 0.f;
-    c.w[1] = (s.ya & s.xb) ? s.w01 : 0.f;
-    c.w[2] = (s.yb & s.xa) ? s.w10 : 0.f;
-    c.w[3] = (s.yb & s.xb) ? s.w11 : 0.f;
-    return c;
-}
 
 // Pair form of a bilinear set-up: the two corners of an image row are adjacent, so one 8-byte gather (4-byte aligned)
 // fetches both.  o[0]/o[1] = offsets of the pair in rows y0 / y0+1, always inside the map (column clamped to 0..W-2, an
@@ -78,7 +19,7 @@ struct BilinP {
 typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
 
 __device__ __forceinline__ BilinP bilin_pairs(float gx, float gy, int W, int H) {
-    const Bilin s = bilin_setup(gx, gy, W, H);
+    const gfn_sm::Bilin s = gfn_sm::bilin_setup<GFN_PAD_ZEROS>(gx, gy, W, H);  // the set-up of Taps<GFN_SAMPLE_BILINEAR> (sample_modes.h)
     BilinP c;
     const int ox = min(max(s.x0, 0), W - 2);
     // fetched left pixel = column ox, right = ox + 1; corner columns are x0 (weights w*0) and x0+1 (weights w*1)
@@ -152,6 +93,23 @@ struct RiArgs {
     float disp_scale;
 };
 
+// host: the argument checks of the refiner-input entry points (`what` names the caller in the error text) and their RiArgs;
+// `keep`: the grid_feature planes are already in d (GFN_RI_KEEP_GRID_FEATURE)
+inline int ri_args(const char *what, const void *f0, const void *f1, int dtype, const float *flow, const float *disp_w, const float *disp_b,
+                   float *d, int64_t d_bs, int B, int C, int Hs, int Ws, int G, int disp_dim, float disp_scale, int symmetric, RiArgs &q,
+                   bool &keep) {
+    if (dtype != GFN_F32 && dtype != GFN_F16) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: feature dtype must be GFN_F32 or GFN_F16", what);
+    if (!f0 || !f1 || !flow || !d || (disp_dim > 0 && (!disp_w || !disp_b))) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: null pointer", what);
+    if (B < 0 || C <= 0 || Hs <= 0 || Ws <= 0 || G <= 0 || disp_dim < 0 || d_bs < (int64_t)(2 * C + disp_dim) * G * G ||
+        ((symmetric & 1) && (B & 1)) || (symmetric & ~3) || (long)C * Hs * Ws >= (1L << 31))
+        return gfn::fail(GFN_ERR_INVALID_ARG, "%s: bad size", what);
+    if (B > 0 && (B > 65535 || (long)G * G >= (1L << 31))) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: batch > 65535 or grid too large", what);
+    q.fa = f0; q.fb = f1; q.flow = flow; q.dw = disp_w; q.db = disp_b; q.d = d; q.d_bs = (long)d_bs;
+    q.B = B; q.Bh = (symmetric & 1) ? B / 2 : B; q.C = C; q.Hs = Hs; q.Ws = Ws; q.G = G; q.Dd = disp_dim; q.disp_scale = disp_scale;
+    keep = (symmetric & GFN_RI_KEEP_GRID_FEATURE) != 0;
+    return GFN_OK;
+}
+
 // KEEP: the grid_feature planes (first C channels of d: grid_sample(x, cell centres), a function of x and the grid only) are
 // already in d from an earlier call with the same x and G -- the second refiner iteration at a scale (num_itr = 2,
 // model/network.py:257-268, calls the refiner again with a new flow): only x_hat and the displacement embedding are rewritten.
@@ -217,17 +175,15 @@ __device__ __forceinline__ void refiner_input_cell(const RiArgs &args, int b, un
             }
         }
     } else {  // one-column maps: no pair to fetch
-        const BilinC sa = bilin_clamped(cx, cy, Ws, Hs);
-        const BilinC sb = bilin_clamped(fx, fy, Ws, Hs);
+        gfn_sm::Taps<GFN_SAMPLE_BILINEAR> sa, sb;
+        sa.setup<GFN_PAD_ZEROS>(cx, cy, Ws, Hs);
+        sb.setup<GFN_PAD_ZEROS>(fx, fy, Ws, Hs);
         for (int c = 0; c < C; ++c) {
-            float ra = 0.f, rb = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (!KEEP) ra += (float)(q + (size_t)c * plane)[sa.o[e]] * sa.w[e];
-                rb += (float)(sm + (size_t)c * plane)[sb.o[e]] * sb.w[e];
-            }
-            if (!KEEP) (o + (size_t)c * GG)[cell] = ra;
-            (o + (size_t)(C + c) * GG)[cell] = rb;
+            float va[4], vb[4];
+            if (!KEEP) sa.load(q + (size_t)c * plane, va);
+            sb.load(sm + (size_t)c * plane, vb);
+            if (!KEEP) (o + (size_t)c * GG)[cell] = sa.value(va);
+            (o + (size_t)(C + c) * GG)[cell] = sb.value(vb);
         }
     }
     // disp_emb(40/32 * scale_factor * (flow - im_A_coords))                                  network.py:548-549

@@ -5,8 +5,11 @@
 //
 // A sampling point becomes a Taps<MODE> set-up once: the in-image offsets of its 1, 4 or 16 pixels (a pixel outside the image
 // reads pixel 0, whose contribution is then dropped) and its weights; every channel plane is then read through the same set-up
-// with all loads of a channel group in flight (load(), then value()).  For bilinear with zeros padding the arithmetic is
-// exactly that of tap_general (local_corr_common.h) and bilin_setup (refiner_input.h), operation for operation.
+// with all loads of a channel group in flight (load(), then value()).  This is the one definition of a sample: the per-tap
+// routine of the tiled local-correlation kernels (tap_general, local_corr_common.h), every per-tap kernel (local_corr_modes.hip,
+// grid_modes.hip) and the pair gathers of the refiner input (bilin_pairs, refiner_input.h) take their arithmetic from here.
+// The zero-weight form reads pixel 0 of a plane for a corner outside the image and multiplies it by 0: exact for finite feature
+// maps (include/gfnet_hip.h, conventions).
 //
 // Coordinates whose floor lies 10^6 pixels or more outside the image, and non-finite ones, read zeros in every mode (the
 // `sane` guard of the bilinear kernels); F.grid_sample's CPU and GPU implementations disagree with each other there.
@@ -14,11 +17,11 @@
 #include <type_traits>
 
 #include "common.h"
-#include "refiner_input.h"
 
 namespace gfn_sm {
 
-using gfn_ri::unnorm;
+// normalised -> pixel coordinate exactly as grid_sample(align_corners=False) un-normalises
+__device__ __forceinline__ float unnorm(float g, int size) { return ((g + 1.f) * (float)size - 1.f) / 2.f; }
 
 __device__ __forceinline__ float ldf(const float *q) { return *q; }
 __device__ __forceinline__ float ldf(const _Float16 *q) { return (float)*q; }
@@ -46,7 +49,8 @@ __device__ __forceinline__ float pad_coord(float x, int size) {
 // the bilinear kernels' guard, on the floor of the un-padded coordinate (false for NaN)
 __device__ __forceinline__ bool sane_floor(float fx, float fy) { return (fx > -1e6f) & (fx < 1e6f) & (fy > -1e6f) & (fy < 1e6f); }
 
-// get_cubic_upsample_coefficients, A = -0.75 (the polynomials of cubic_coeffs in grid_ops.hip, ATen's argument order)
+// get_cubic_upsample_coefficients, A = -0.75.  The polynomials of cubic_coeffs in grid_ops.hip (resize_normalise) in ATen's
+// argument order -- cubic_conv2((1 - t) + 1) here, cubic2(2 - t) there: not the same bits, so the two stay apart.
 __device__ __forceinline__ float cubic_conv1(float x) { return ((-0.75f + 2.f) * x - (-0.75f + 3.f)) * x * x + 1.f; }
 __device__ __forceinline__ float cubic_conv2(float x) { return ((-0.75f * x - 5.f * -0.75f) * x + 8.f * -0.75f) * x - 4.f * -0.75f; }
 __device__ __forceinline__ void cubic_coeffs(float t, float c[4]) {
@@ -81,7 +85,36 @@ struct Taps<GFN_SAMPLE_NEAREST> {
     __device__ __forceinline__ float value(const float v[N]) const { return ok ? v[0] : 0.f; }
 };
 
-// bilinear: corners nw, ne, sw, se of the padded coordinate, zero weight outside the image (tap_general's form)
+// grid_sample's bilinear set-up (ATen grid_sampler_2d): the nw corner (x0, y0) of the padded coordinate, the weights of the corners
+// nw, ne, sw, se and which corner columns / rows lie inside the image.  An insane coordinate has every corner outside.
+struct Bilin {
+    int x0, y0;
+    float w00, w01, w10, w11;
+    bool xa, xb, ya, yb;
+};
+template <int PAD>
+__device__ __forceinline__ Bilin bilin_setup(float gx, float gy, int W, int H) {
+    Bilin s;
+    float ix = unnorm(gx, W), iy = unnorm(gy, H);
+    const bool sane = sane_floor(floorf(ix), floorf(iy));
+    ix = pad_coord<PAD>(ix, W);
+    iy = pad_coord<PAD>(iy, H);
+    const float fx = floorf(ix), fy = floorf(iy);
+    s.x0 = sane ? (int)fx : -4;
+    s.y0 = sane ? (int)fy : -4;
+    s.w00 = (fx + 1.f - ix) * (fy + 1.f - iy);
+    s.w01 = (ix - fx) * (fy + 1.f - iy);
+    s.w10 = (fx + 1.f - ix) * (iy - fy);
+    s.w11 = (ix - fx) * (iy - fy);
+    s.xa = (unsigned)s.x0 < (unsigned)W;
+    s.xb = (unsigned)(s.x0 + 1) < (unsigned)W;
+    s.ya = (unsigned)s.y0 < (unsigned)H;
+    s.yb = (unsigned)(s.y0 + 1) < (unsigned)H;
+    return s;
+}
+
+// bilinear: four always-valid offsets and four weights that are zero for a corner outside the image, so the gathers need no
+// branches (a zero weight times any finite value adds an exact 0; corner order nw, ne, sw, se is kept)
 template <>
 struct Taps<GFN_SAMPLE_BILINEAR> {
     static constexpr int N = 4;
@@ -89,24 +122,15 @@ struct Taps<GFN_SAMPLE_BILINEAR> {
     float w[4];
     template <int PAD>
     __device__ __forceinline__ void setup(float gx, float gy, int W, int H) {
-        float ix = unnorm(gx, W), iy = unnorm(gy, H);
-        const bool sane = sane_floor(floorf(ix), floorf(iy));
-        ix = pad_coord<PAD>(ix, W);
-        iy = pad_coord<PAD>(iy, H);
-        const float fx = floorf(ix), fy = floorf(iy);
-        const int x0 = sane ? (int)fx : -4, y0 = sane ? (int)fy : -4;
-        const float w00 = (fx + 1.f - ix) * (fy + 1.f - iy), w01 = (ix - fx) * (fy + 1.f - iy);
-        const float w10 = (fx + 1.f - ix) * (iy - fy), w11 = (ix - fx) * (iy - fy);
-        const bool xa = (unsigned)x0 < (unsigned)W, xb = (unsigned)(x0 + 1) < (unsigned)W;
-        const bool ya = (unsigned)y0 < (unsigned)H, yb = (unsigned)(y0 + 1) < (unsigned)H;
-        o[0] = (ya & xa) ? y0 * W + x0 : 0;  // (each offset is formed only for a corner inside the image)
-        o[1] = (ya & xb) ? y0 * W + x0 + 1 : 0;
-        o[2] = (yb & xa) ? (y0 + 1) * W + x0 : 0;
-        o[3] = (yb & xb) ? (y0 + 1) * W + x0 + 1 : 0;
-        w[0] = (ya & xa) ? w00 : 0.f;
-        w[1] = (ya & xb) ? w01 : 0.f;
-        w[2] = (yb & xa) ? w10 : 0.f;
-        w[3] = (yb & xb) ? w11 : 0.f;
+        const Bilin s = bilin_setup<PAD>(gx, gy, W, H);
+        o[0] = (s.ya & s.xa) ? s.y0 * W + s.x0 : 0;  // (each offset is formed only for a corner inside the image)
+        o[1] = (s.ya & s.xb) ? s.y0 * W + s.x0 + 1 : 0;
+        o[2] = (s.yb & s.xa) ? (s.y0 + 1) * W + s.x0 : 0;
+        o[3] = (s.yb & s.xb) ? (s.y0 + 1) * W + s.x0 + 1 : 0;
+        w[0] = (s.ya & s.xa) ? s.w00 : 0.f;
+        w[1] = (s.ya & s.xb) ? s.w01 : 0.f;
+        w[2] = (s.yb & s.xa) ? s.w10 : 0.f;
+        w[3] = (s.yb & s.xb) ? s.w11 : 0.f;
     }
     template <typename FT>
     __device__ __forceinline__ void load(const FT *pl, float v[N]) const {
@@ -177,7 +201,7 @@ struct Taps<GFN_SAMPLE_BICUBIC> {
     }
 };
 
-// channels unrolled per group: 8 for nearest and bilinear (as the general kernel), 4 for bicubic (16 loads per channel)
+// channels unrolled per group: 8 for nearest and bilinear, 4 for bicubic (16 loads per channel)
 template <int MODE>
 constexpr int group_channels() { return MODE == GFN_SAMPLE_BICUBIC ? 4 : 8; }
 

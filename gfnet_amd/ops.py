@@ -183,9 +183,9 @@ def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fact
     st = stream_ptr(dev)
     mode = (1 if symmetric else 0) | (2 if keep else 0)  # include/gfnet_hip.h: GFN_RI_KEEP_GRID_FEATURE
     disp_scale = float(40 / 32 * scale_factor)
+    ri_args = (ptr(x), ptr(y), dtx, ptr(fl), ptr(w), ptr(bvec), ptr(d), CH * G * G, B, C, Hs, Ws, G, Dd, disp_scale, mode)
     if general:  # the per-tap kernels of every mode: no tile plan, no scratch
-        check(_L().gfn_refiner_input_mode_fwd_dt(ptr(x), ptr(y), dtx, ptr(fl), ptr(w), ptr(bvec), ptr(d), CH * G * G, B, C, Hs, Ws, G, Dd,
-                                                 disp_scale, mode, sm, st), "gfn_refiner_input_mode_fwd_dt")
+        check(_L().gfn_refiner_input_mode_fwd_dt(*ri_args, sm, st), "gfn_refiner_input_mode_fwd_dt")
         if corr_in_other:
             out = d[:, 2 * C + Dd:]
             check(_L().gfn_local_corr_mode_fwd(ptr(d), CH * G * G, ptr(y), ptr(x) if symmetric else None, dtx, ptr(fl), c_vp(out.data_ptr()),
@@ -198,11 +198,9 @@ def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fact
         nscr = int(_L().gfn_local_corr_scratch_bytes(B, G))
         scr = _lib.scratch(dev, nscr)
     if plans:
-        check(_L().gfn_refiner_input_plan_fwd_dt(ptr(x), ptr(y), dtx, ptr(fl), ptr(w), ptr(bvec), ptr(d), CH * G * G, B, C, Hs, Ws, G, Dd,
-                                                 disp_scale, mode, r, ptr(scr), nscr, st), "gfn_refiner_input_plan_fwd")
+        check(_L().gfn_refiner_input_plan_fwd_dt(*ri_args, r, ptr(scr), nscr, st), "gfn_refiner_input_plan_fwd")
     else:
-        check(_L().gfn_refiner_input_fwd_dt(ptr(x), ptr(y), dtx, ptr(fl), ptr(w), ptr(bvec), ptr(d), CH * G * G, B, C, Hs, Ws, G, Dd,
-                                            disp_scale, mode, st), "gfn_refiner_input_fwd")
+        check(_L().gfn_refiner_input_fwd_dt(*ri_args, st), "gfn_refiner_input_fwd")
     if corr_in_other:
         out = d[:, 2 * C + Dd:]
         name = f"local_corr_c{C}_h{Hs}_g{G}_r{r}"
@@ -218,21 +216,7 @@ def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fact
 
 def grid_sample(x, grid, mode="bilinear", padding_mode="zeros"):
     """F.grid_sample(x, grid, mode, padding_mode, align_corners=False); mode "bilinear" / "nearest" / "bicubic", padding_mode
-    "zeros" / "border" / "reflection".  Returns fp32.  The default pair runs gfn_grid_sample_fwd (fp32 input), every other pair
-    gfn_grid_sample_mode_fwd, which reads fp16 input as stored."""
-    if mode != "bilinear" or padding_mode != "zeros":
-        return _grid_sample_mode(x, grid, mode, padding_mode)
-    dev = require_gpu(x, grid)
-    x, g = f32c(x), f32c(grid)
-    B, C, H, W = x.shape
-    _, Ho, Wo, _ = g.shape
-    out = torch.empty((B, C, Ho, Wo), device=dev, dtype=torch.float32)
-    check(_L().gfn_grid_sample_fwd(ptr(x), ptr(g), ptr(out), C * Ho * Wo, B, C, H, W, Ho, Wo, stream_ptr(dev)),
-          "gfn_grid_sample_fwd")
-    return out
-
-
-def _grid_sample_mode(x, grid, mode, padding_mode):
+    "zeros" / "border" / "reflection".  Returns fp32; fp16 input is read as stored (the widening is exact)."""
     sm, pm = _lib.mode_codes(mode, padding_mode, "grid_sample")
     dev = require_gpu(x, grid)
     (x, dtx), g = featc(x), f32c(grid)

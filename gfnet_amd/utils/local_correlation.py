@@ -31,10 +31,10 @@ def local_correlation(featuremap_size, feature0, feature1, local_radius, num_gri
     Extra keyword `out`: a (B, K*num_level, G, G) fp32 view to write into (e.g. the channel slice
     of the refiner's concat buffer); it must have contiguous (K,G,G) planes.
     Gradients: like the reference (local_correlation.py:54-60, sampling under no_grad) only feature0
-    receives one; it is computed by gfn_local_corr_bwd_f0 when feature0.requires_grad (and `out` is None).
+    receives one; it is computed by gfn_local_corr_mode_bwd_f0 when feature0.requires_grad (and `out` is None).
     sample_mode ("bilinear", "nearest", "bicubic") and padding_mode ("zeros", "border", "reflection") are F.grid_sample's
-    (local_correlation.py:55-58, 66-68).  Bilinear + zeros takes the tiled kernels; every other pair runs the general per-tap
-    kernel of csrc/local_corr_modes.hip (gfn_local_corr_mode_fwd, gradient gfn_local_corr_mode_bwd_f0).
+    (local_correlation.py:55-58, 66-68).  Bilinear + zeros takes the tiled kernels (gfn_local_corr_fwd_dt); every other pair
+    runs the general per-tap kernel of csrc/local_corr_modes.hip (gfn_local_corr_mode_fwd).
     """
     if out is None and torch.is_grad_enabled() and feature0.requires_grad:
         return _LocalCorrelationFn.apply(feature0, feature1, flow, tuple(int(v) for v in featuremap_size), int(local_radius),
@@ -76,41 +76,24 @@ def _forward(featuremap_size, feature0, feature1, local_radius, num_grid, paddin
         out_bs = out.stride(0) if B > 1 else K * G * G
     L = _lib.lib()
     st = _lib.stream_ptr(dev)
-    if general:
-        _forward_modes(L, st, dev, f0, f0_bs, f1, f1_dt, fl, res, out_bs, B, c, G, h, w, r, grid_based_correlation, num_level, sm, pm)
-        if out is None and ret_dtype != torch.float32:
-            res = res.to(ret_dtype)
-        return res
-    nscr = int(L.gfn_local_corr_scratch_bytes(B, G))
-    scr = _lib.scratch(dev, nscr)
-    hh, ww = h, w
-    for level in range(int(num_level)):
-        o = res[:, level * K1:(level + 1) * K1]
+    if not general:  # the tiled routes exist for bilinear + zeros only
         from .. import ops  # (LOCAL_CORR_FP32: fp32 FMA arithmetic at every radius instead of the matrix-core kernel for r >= 5)
         variant = 4 if (int(_variant) == 0 and ops.LOCAL_CORR_FP32) else int(_variant)
-        _lib.check(L.gfn_local_corr_fwd_dt(_lib.ptr(f0), f0_bs, _lib.ptr(f1), None, f1_dt, _lib.ptr(fl), _lib.c_vp(o.data_ptr()),
-                                           out_bs, B, c, G, hh, ww, r, 1 if grid_based_correlation else 0, h, w,
-                                           variant, _lib.ptr(scr), nscr, st), "gfn_local_corr_fwd")
-        if level + 1 < num_level:
-            if f1_dt != _lib.GFN_F32:  # pooled levels (unused by GFNet) are built in fp32
-                f1, f1_dt = _lib.f32c(f1), _lib.GFN_F32
-            pooled = torch.empty((B, c, hh // 2, ww // 2), device=dev, dtype=torch.float32)
-            _lib.check(L.gfn_avg_pool2(_lib.ptr(f1), _lib.ptr(pooled), B * c, hh, ww, st), "gfn_avg_pool2")
-            f1, hh, ww = pooled, hh // 2, ww // 2
+        nscr = int(L.gfn_local_corr_scratch_bytes(B, G))
+        scr = _lib.scratch(dev, nscr)
+    if num_level > 1 and f1_dt != _lib.GFN_F32:  # pooled levels (unused by GFNet) are built in fp32
+        f1, f1_dt = _lib.f32c(f1), _lib.GFN_F32
+    for level, (f1l, hh, ww) in enumerate(_pyramid(f1, B, c, h, w, int(num_level), dev)):
+        o = res[:, level * K1:(level + 1) * K1]
+        args = (_lib.ptr(f0), f0_bs, _lib.ptr(f1l), None, f1_dt, _lib.ptr(fl), _lib.c_vp(o.data_ptr()), out_bs, B, c, G, hh, ww, r,
+                1 if grid_based_correlation else 0, h, w)
+        if general:
+            _lib.check(L.gfn_local_corr_mode_fwd(*args, sm, pm, st), "gfn_local_corr_mode_fwd")
+        else:
+            _lib.check(L.gfn_local_corr_fwd_dt(*args, variant, _lib.ptr(scr), nscr, st), "gfn_local_corr_fwd")
     if out is None and ret_dtype != torch.float32:
         res = res.to(ret_dtype)
     return res
-
-
-def _forward_modes(L, st, dev, f0, f0_bs, f1, f1_dt, fl, res, out_bs, B, c, G, h, w, r, grid_based, num_level, sm, pm):
-    """Every level through gfn_local_corr_mode_fwd; pooled levels from _pyramid (fp32, as the bilinear path builds them)."""
-    K1 = (2 * r + 1) ** 2
-    if num_level > 1:
-        f1, f1_dt = _lib.f32c(f1), _lib.GFN_F32
-    for level, (f1l, hh, ww) in enumerate(_pyramid(f1, B, c, h, w, num_level, dev)):
-        o = res[:, level * K1:(level + 1) * K1]
-        _lib.check(L.gfn_local_corr_mode_fwd(_lib.ptr(f0), f0_bs, _lib.ptr(f1l), None, f1_dt, _lib.ptr(fl), _lib.c_vp(o.data_ptr()), out_bs,
-                                             B, c, G, hh, ww, r, 1 if grid_based else 0, h, w, sm, pm, st), "gfn_local_corr_mode_fwd")
 
 
 def _pyramid(f1, B, c, h, w, num_level, dev):
@@ -140,7 +123,6 @@ class _LocalCorrelationFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         feature1, flow = ctx.saved_tensors
         (B, c, h, w), r, G, grid_based, num_level, has_flow, dtype, sample_mode, padding_mode = ctx.meta
-        general = (sample_mode, padding_mode) != ("bilinear", "zeros")
         sm, pm = _lib.mode_codes(sample_mode, padding_mode, "local_correlation")
         dev = grad_out.device
         K1 = (2 * r + 1) ** 2
@@ -152,12 +134,8 @@ class _LocalCorrelationFn(torch.autograd.Function):
         for level, (f1, hh, ww) in enumerate(_pyramid(_lib.f32c(feature1), B, c, h, w, num_level, dev)):
             gl = g[:, level * K1:(level + 1) * K1]
             gf0 = torch.empty((B, c, G, G), device=dev, dtype=torch.float32)
-            if general:
-                _lib.check(L.gfn_local_corr_mode_bwd_f0(_lib.c_vp(gl.data_ptr()), g.stride(0), _lib.ptr(f1), None, _lib.ptr(fl), _lib.ptr(gf0),
-                                                        c * G * G, B, c, G, hh, ww, r, 1 if grid_based else 0, h, w, sm, pm, st),
-                           "gfn_local_corr_mode_bwd_f0")
-            else:
-                _lib.check(L.gfn_local_corr_bwd_f0(_lib.c_vp(gl.data_ptr()), g.stride(0), _lib.ptr(f1), None, _lib.ptr(fl), _lib.ptr(gf0),
-                                                   c * G * G, B, c, G, hh, ww, r, 1 if grid_based else 0, h, w, st), "gfn_local_corr_bwd_f0")
+            _lib.check(L.gfn_local_corr_mode_bwd_f0(_lib.c_vp(gl.data_ptr()), g.stride(0), _lib.ptr(f1), None, _lib.ptr(fl), _lib.ptr(gf0),
+                                                    c * G * G, B, c, G, hh, ww, r, 1 if grid_based else 0, h, w, sm, pm, st),
+                       "gfn_local_corr_mode_bwd_f0")
             total = gf0 if total is None else total + gf0
         return total.to(dtype), None, None, None, None, None, None, None, None, None

@@ -15,7 +15,9 @@
  *     the call returns without synchronising; it is safe to capture into a hipGraph;
  *   - return value: GFN_OK (0) or a negative GFN_ERR_* code; gfn_last_error() gives the text
  *     (thread-local).  Nothing is launched when an argument error is returned;
- *   - no global mutable state; single host thread per stream is assumed, as in the reference.
+ *   - no global mutable state; single host thread per stream is assumed, as in the reference;
+ *   - sampled maps are finite feature maps: a sampling corner outside the image reads pixel 0 of its plane with weight 0, so
+ *     a non-finite value there would turn the zero it stands for into NaN.
  */
 #ifndef GFNET_HIP_H
 #define GFNET_HIP_H
@@ -105,7 +107,8 @@ int gfn_local_corr_fwd_dt(const float *f0, int64_t f0_bs, const void *f1, const 
 /* Backward of gfn_local_corr_fwd with respect to f0 -- the only gradient the reference lets through
  * (utils/local_correlation.py:54-60: sampling coordinates and feature1 are used under no_grad):
  *   grad_f0[b,c,i,j] = (sum_k grad_out[b,k,i,j] * bilinear(f1[b,c], tap k of cell (i,j))) / sqrt(C).
- * Same arguments as the forward; grad_out (B,K,G,G) with batch stride grad_out_bs, grad_f0 (B,C,G,G) with grad_f0_bs. */
+ * Same arguments as the forward; grad_out (B,K,G,G) with batch stride grad_out_bs, grad_f0 (B,C,G,G) with grad_f0_bs.
+ * This is gfn_local_corr_mode_bwd_f0 with GFN_SAMPLE_BILINEAR and GFN_PAD_ZEROS. */
 int gfn_local_corr_bwd_f0(const float *grad_out, int64_t grad_out_bs, const float *f1, const float *f1_second, const float *flow,
                           float *grad_f0, int64_t grad_f0_bs, int B, int C, int G, int H, int W, int r, int grid_based, int win_h,
                           int win_w, gfn_stream_t stream);
@@ -191,7 +194,8 @@ int gfn_refiner_input_plan_fwd_dt(const void *f0, const void *f1, int dtype, con
                                   int symmetric, int r, void *scratch, int64_t scratch_bytes, gfn_stream_t stream);
 
 /* F.grid_sample(in, grid, mode='bilinear', padding_mode='zeros', align_corners=False):
- * in (B,C,H,W), grid (B,Ho,Wo,2) -> out (B,C,Ho,Wo) with batch stride out_bs. */
+ * in (B,C,H,W), grid (B,Ho,Wo,2) -> out (B,C,Ho,Wo) with batch stride out_bs.  This is gfn_grid_sample_mode_fwd with GFN_F32,
+ * GFN_SAMPLE_BILINEAR and GFN_PAD_ZEROS; like it, it refuses H * W >= 2^31 (pixel offsets are 32-bit). */
 int gfn_grid_sample_fwd(const float *in, const float *grid, float *out, int64_t out_bs, int B, int C, int H, int W,
                         int Ho, int Wo, gfn_stream_t stream);
 
@@ -214,12 +218,13 @@ int gfn_grid_sample_fwd(const float *in, const float *grid, float *out, int64_t 
 
 /* gfn_local_corr_fwd_dt's arguments without variant and scratch, plus the two codes:
  *   out[b, k, i, j] = sum_c f0[b,c,i,j] / sqrt(C) * sample(f1[b,c], p(b,i,j) + offset(k))
- * Any C and r, fp32 / fp16 f1, f1_second, grid_based and flow == NULL as there.  With GFN_SAMPLE_BILINEAR + GFN_PAD_ZEROS the
- * result is bit-identical to gfn_local_corr_fwd_dt with scratch == NULL (its general kernel). */
+ * Any C and r, fp32 / fp16 f1, f1_second, grid_based and flow == NULL as there.  With GFN_SAMPLE_BILINEAR + GFN_PAD_ZEROS this
+ * is the general kernel of gfn_local_corr_fwd_dt (what that runs with scratch == NULL). */
 int gfn_local_corr_mode_fwd(const float *f0, int64_t f0_bs, const void *f1, const void *f1_second, int f1_dtype, const float *flow,
                             float *out, int64_t out_bs, int B, int C, int G, int H, int W, int r, int grid_based, int win_h, int win_w,
                             int sample_mode, int padding_mode, gfn_stream_t stream);
-/* Its gradient with respect to f0, as gfn_local_corr_bwd_f0 (fp32 f1; feature1 and the coordinates under no_grad). */
+/* Its gradient with respect to f0 (fp32 f1; feature1 and the coordinates under no_grad); gfn_local_corr_bwd_f0 is this call with
+ * GFN_SAMPLE_BILINEAR + GFN_PAD_ZEROS. */
 int gfn_local_corr_mode_bwd_f0(const float *grad_out, int64_t grad_out_bs, const float *f1, const float *f1_second, const float *flow,
                                float *grad_f0, int64_t grad_f0_bs, int B, int C, int G, int H, int W, int r, int grid_based, int win_h,
                                int win_w, int sample_mode, int padding_mode, gfn_stream_t stream);

@@ -185,6 +185,51 @@ def test_bilinear_zeros_through_the_mode_kernel_is_bit_identical_to_the_general_
         assert torch.equal(a, b), (B, c, h, w, G, r, dt, symmetric, grid_based)
 
 
+def test_bwd_f0_is_bit_identical_to_the_mode_gradient_with_bilinear_zeros():
+    from gfnet_amd import _lib
+
+    L, st = _lib.lib(), _lib.stream_ptr(torch.device("cuda"))
+    cases = [  # B, c, h, w, G, r, symmetric, grid_based, flow
+        (2, 13, 20, 28, 6, 2, False, 0, True),  # C not a multiple of 8
+        (4, 32, 40, 40, 16, 3, True, 0, True),  # symmetric: f1_second
+        (2, 16, 36, 52, 20, 7, True, 1, True),  # grid_based
+        (1, 12, 12, 12, 12, 1, False, 0, False),  # flow == NULL
+    ]
+    for B, c, h, w, G, r, symmetric, grid_based, has_flow in cases:
+        K = (2 * r + 1) ** 2
+        gout = dev(synth.lattice_normalish((B, K, G, G), 1511))
+        nmaps = B // 2 if symmetric else B
+        f1 = dev(synth.lattice_normalish((nmaps, c, h, w), 1512))
+        f1s = dev(synth.lattice_normalish((nmaps, c, h, w), 1513)) if symmetric else None
+        flow = uniform((B, 2, G, G), 1514, 1.3) if has_flow else None
+        a = torch.full((B, c, G, G), float("nan"), device="cuda")
+        b = torch.full((B, c, G, G), float("nan"), device="cuda")
+        _lib.check(L.gfn_local_corr_bwd_f0(_lib.ptr(gout), K * G * G, _lib.ptr(f1), _lib.ptr(f1s), _lib.ptr(flow), _lib.ptr(a), c * G * G,
+                                           B, c, G, h, w, r, grid_based, h, w, st), "bwd_f0")
+        _lib.check(L.gfn_local_corr_mode_bwd_f0(_lib.ptr(gout), K * G * G, _lib.ptr(f1), _lib.ptr(f1s), _lib.ptr(flow), _lib.ptr(b), c * G * G,
+                                                B, c, G, h, w, r, grid_based, h, w, 0, 0, st), "mode bwd_f0")
+        torch.cuda.synchronize()
+        assert torch.isfinite(a).all()
+        assert torch.equal(a, b), (B, c, h, w, G, r, symmetric, grid_based)
+
+
+def test_grid_sample_fwd_is_bit_identical_to_the_mode_entry_point_with_bilinear_zeros():
+    from gfnet_amd import _lib
+
+    L, st = _lib.lib(), _lib.stream_ptr(torch.device("cuda"))
+    for B, C, H, W, Ho, Wo in [(2, 5, 13, 17, 9, 11), (3, 16, 24, 24, 32, 32), (1, 3, 7, 1, 4, 6)]:
+        x = dev(synth.lattice_normalish((B, C, H, W), 1521))  # fp32 input
+        grid = uniform((B, Ho, Wo, 2), 1522, 3.0)  # out to +-3: far outside the image on every side
+        a = torch.full((B, C, Ho, Wo), float("nan"), device="cuda")
+        b = torch.full((B, C, Ho, Wo), float("nan"), device="cuda")
+        _lib.check(L.gfn_grid_sample_fwd(_lib.ptr(x), _lib.ptr(grid), _lib.ptr(a), C * Ho * Wo, B, C, H, W, Ho, Wo, st), "grid_sample")
+        _lib.check(L.gfn_grid_sample_mode_fwd(_lib.ptr(x), _lib.GFN_F32, _lib.ptr(grid), _lib.ptr(b), C * Ho * Wo, B, C, H, W, Ho, Wo, 0, 0, st),
+                   "grid_sample_mode")
+        torch.cuda.synchronize()
+        assert torch.isfinite(a).all()
+        assert torch.equal(a, b), (B, C, H, W, Ho, Wo)
+
+
 def test_non_finite_and_far_flows_read_zeros_in_every_mode():
     B, c, h, w, G, r = 1, 8, 16, 16, 8, 1
     f0 = dev(synth.lattice_normalish((B, c, G, G), 1601))

@@ -4,7 +4,7 @@
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/probe_sampling_modes.py [--reps N]
 
 local correlation: nearest / bicubic (zeros padding) and bilinear + border on local_corr_mode_kernel, bilinear + zeros on the general
-per-tap kernel (local_corr_general_kernel, `_variant=1`) and on the product's tiled path; refiner input: ops.refiner_input with
+per-tap kernel (local_corr_mode_kernel, `_variant=1`) and on the product's tiled path; refiner input: ops.refiner_input with
 sample_mode nearest / bicubic (refiner_input_mode_kernel + local_corr_mode_kernel) and bilinear (the product path)."""
 import argparse
 import os
