@@ -32,6 +32,14 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned n) {
     return start + local;
 }
 
+// counter-based random bits (sample.hip, homography.hip; restated in oracle/homography_oracle.c)
+__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
 // The same with the step (end - start) / (steps - 1) supplied by the caller (computed once on the host in fp32: an IEEE
 // division there and here give the same bits; on the device it costs a dozen vector instructions per call).
 __device__ __forceinline__ float linspace_step_at(float start, float end, float step, int steps, int i) {

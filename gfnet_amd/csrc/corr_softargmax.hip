@@ -14,19 +14,148 @@
 // coalesced loads from the NCHW maps (positions contiguous), no LDS and no transposition.
 // Accumulator register r of lane l holds S[j = (r&3)+8(r>>2)+4(l>>5)][i = l&31]: the column
 // (i) sits on the lane, so the softmax over j is lane-local apart from one final lane^32 merge.
-#include "common.h"
+//
+// A tile is defined once: the accumulator layout, the fp32 tile product, the cell of a position and the virtual symmetric direction
+// in corr_common.h (shared with the backward); the row-tile soft-argmax (RowTiles), the split-bf16 product (split_columns,
+// split_products) and the half-wave merge (finish_flow) below, shared by corr_softargmax_kernel, corr_softargmax_img_kernel and
+// split_rows_kernel.
+#include "corr_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using namespace gfn;
 
-// x = h + m + l exactly (three round-to-nearest bf16 pieces of 8 significant bits each cover the 24 of an fp32 value)
-__device__ __forceinline__ void split3(float v, __bf16 &h, __bf16 &m, __bf16 &l) {
-    h = (__bf16)v;
-    const float r1 = v - (float)h;
-    m = (__bf16)r1;
-    l = (__bf16)(r1 - (float)m);
+// merge the two half-waves (same column i, disjoint rows j) and write flow[b, :, i]
+__device__ __forceinline__ void finish_flow(float m, float l, float ax, float ay, float *__restrict__ flow, int b, int N0, int i, int h) {
+    const float m2 = __shfl_xor(m, 32), l2 = __shfl_xor(l, 32), ax2 = __shfl_xor(ax, 32), ay2 = __shfl_xor(ay, 32);
+    const float mn = fmaxf(m, m2);
+    const float s1 = __expf(m - mn), s2 = __expf(m2 - mn);
+    const float lt = l * s1 + l2 * s2;
+    const float fx = (ax * s1 + ax2 * s2) / lt, fy = (ay * s1 + ay2 * s2) / lt;
+    if (h == 0 && i < N0) {
+        flow[((size_t)b * 2 + 0) * N0 + i] = fx;
+        flow[((size_t)b * 2 + 1) * N0 + i] = fy;
+    }
+}
+
+// ---- row tiles (flow only, 32 <= W1 <= 64: the 448 and 672 configurations) -------------------------------------------------
+// A tile of 32 B-positions is (part of) ONE grid row: positions x = 32 p .. 32 p + 31 of row y, those past the row's end
+// masked out (W1 = 48: the second tile of a row is half empty -- a third more matrix work).  Its y coordinate is then
+// wave-uniform, the 16 x coordinates of a lane's accumulator rows are two constant sets, and the 1/sqrt(C) scale folds into
+// the exponent: ~6 VALU instructions per value instead of ~40.  The kernel is VALU-bound (the fp32 MFMA shares the vector
+// ALUs): 48x48 maps, which took the general path below, ran 6.5x longer than 32x32 ones for 2.5x the work.
+
+// B-position that lane column col reads in row tile t (parts = tiles per grid row; tile t = part t % parts of row t / parts)
+__device__ __forceinline__ int row_tile_pos(int t, int parts, int W1, int col) {
+    const int y = parts == 1 ? t : t >> 1, pp = parts == 1 ? 0 : t & 1;
+    return y * W1 + min(32 * pp + col, W1 - 1);
+}
+
+// one lane's online soft-argmax over the row tiles of a direction
+struct RowTiles {
+    float gxA[16], gxB[16];  // x coordinate of the lane's accumulator rows in the first / second tile of a grid row
+    unsigned maskB;          // accumulator rows of the second tile that lie inside the grid row
+    float y_lo, y_hi, e_scale;
+    int H1;
+    float m, l, ax, ay;      // running maximum (in unscaled units), sum, weighted coordinate sums
+
+    // second: the grid rows have a second tile (W1 > 32), so gxB / maskB are wanted
+    __device__ __forceinline__ RowTiles(int H1_, int W1, bool second, int h, float sqrt_c)
+        : maskB(0), y_lo((float)(-1 + 1.0 / H1_)), y_hi((float)(1 - 1.0 / H1_)),
+          e_scale(1.4426950408889634f / sqrt_c),  // exp(v / sqrt(C)) = exp2(v * log2(e) / sqrt(C))
+          H1(H1_), m(-INFINITY), l(0.f), ax(0.f), ay(0.f) {
+        const float x_lo = (float)(-1 + 1.0 / W1), x_hi = (float)(1 - 1.0 / W1);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int o = acc_row(r, h);
+            gxA[r] = linspace_at(x_lo, x_hi, W1, min(o, W1 - 1));
+            if (second) {
+                gxB[r] = linspace_at(x_lo, x_hi, W1, min(32 + o, W1 - 1));
+                maskB |= (32 + o < W1 ? 1u : 0u) << r;
+            }
+        }
+    }
+
+    __device__ __forceinline__ void softmax_tile(f32x16 acc, const float (&gx)[16], int y) {
+        float mt = acc[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) mt = fmaxf(mt, acc[r]);
+        const float mn = fmaxf(m, mt);
+        const float sc = __builtin_amdgcn_exp2f((m - mn) * e_scale);  // m = -inf on the first tile -> 0
+        float lt = 0.f, axt = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float e = __builtin_amdgcn_exp2f((acc[r] - mn) * e_scale);  // masked positions: exp2(-inf) = 0
+            lt += e;
+            axt = fmaf(e, gx[r], axt);
+        }
+        const float gy = linspace_at(y_lo, y_hi, H1, y);
+        l = fmaf(l, sc, lt);
+        ax = fmaf(ax, sc, axt);
+        ay = fmaf(ay, sc, lt * gy);
+        m = mn;
+    }
+
+    // the products of row tile t
+    __device__ __forceinline__ void add_tile(f32x16 acc, int parts, int t) {
+        if (parts == 1 || !(t & 1)) {
+            softmax_tile(acc, gxA, parts == 1 ? t : t >> 1);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = ((maskB >> r) & 1u) ? acc[r] : -INFINITY;
+            softmax_tile(acc, gxB, t >> 1);
+        }
+    }
+
+    __device__ __forceinline__ void finish(float sqrt_c, float *__restrict__ flow, int b, int N0, int i, int h) {
+        finish_flow(m / sqrt_c, l, ax, ay, flow, b, N0, i, h);  // the running maximum was kept in unscaled units
+    }
+};
+
+// Round 6, 64-channel maps (GFNet's stride-16 features): the products on the bf16 matrix core instruction with both operands
+// split three ways (x = h + m + l, exact).  Six of the nine piece products are kept -- h.h, h.m, m.h, m.m, h.l, l.h; the dropped
+// m.l, l.m, l.l are <= 2^-23 of |a||b|, the size of an fp32 product's own rounding -- in 24 v_mfma_f32_32x32x16_bf16 per tile
+// (768 matrix cycles) instead of 32 v_mfma_f32_32x32x2_f32 (2 048), and unlike the fp32 instruction they leave the vector ALUs
+// to the softmax and to the next tile's splitting.  Same accumulator layout, same softmax.  Lane l supplies row / column
+// l & 31 and channels 16 c + 8 (l >> 5) + e, e = 0..7, of chunk c: plain coalesced NCHW loads as before.
+
+// the wave's own 32 columns (position ic of f0b, all channels, zero for channels >= C), split
+template <typename FT>
+__device__ __forceinline__ void split_columns(const FT *__restrict__ f0b, int C, int N0, int ic, int h, bf16x8 (&bh)[4], bf16x8 (&bm)[4],
+                                              bf16x8 (&bl)[4]) {
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int c = 16 * c4 + 8 * h + e;
+            const float v = c < C ? (float)f0b[(size_t)min(c, C - 1) * N0 + ic] : 0.f;
+            __bf16 ph, pm, pl;
+            split3(v, ph, pm, pl);
+            bh[c4][e] = ph; bm[c4][e] = pm; bl[c4][e] = pl;
+        }
+}
+
+// one tile's products from the pieces of its rows (ah, am, al: four 16-channel chunks each) and of the wave's columns
+__device__ __forceinline__ f32x16 split_products(const bf16x8 *ah, const bf16x8 *am, const bf16x8 *al, const bf16x8 (&bh)[4],
+                                                 const bf16x8 (&bm)[4], const bf16x8 (&bl)[4]) {
+    // two chains: the small classes and the large ones, smallest terms first inside each; summed at the end
+    f32x16 accs = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc = accs;
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+        accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[c4], bm[c4], accs, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[c4], bm[c4], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+        accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[c4], bl[c4], accs, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[c4], bh[c4], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+        accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[c4], bh[c4], accs, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[c4], bh[c4], acc, 0, 0, 0);
+    }
+    return acc + accs;
 }
 
 // KS = k-steps of 2 channels held in registers (compile-time so that the operand array stays in
@@ -45,11 +174,8 @@ __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restri
     const int col = lane & 31, h = lane >> 5;
     const int i = i0 + col;
     const int ic = min(i, N0 - 1);
-
-    // symmetric batches are virtual (Bh = B/2 images per side): direction b >= Bh swaps the roles of
-    // the two feature arrays instead of reading a concatenated copy (model/network.py:213-222)
-    const FT *f0b = b < Bh ? f0 + (size_t)b * C * N0 : f1 + (size_t)(b - Bh) * C * N0;
-    const FT *f1b = b < Bh ? f1 + (size_t)b * C * N1 : f0 + (size_t)(b - Bh) * C * N1;
+    const FT *f0b = dir_image(f0, f1, b, Bh, (size_t)C * N0);
+    const FT *f1b = dir_image(f1, f0, b, Bh, (size_t)C * N1);
 
     // B operand: this wave's 32 columns of f0, all channels, kept in registers
     float bop[KS];
@@ -60,76 +186,15 @@ __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restri
         bop[s] = c < C ? v : 0.f;
     }
 
-    const float x_lo = (float)(-1 + 1.0 / W1), x_hi = (float)(1 - 1.0 / W1);
-    const float y_lo = (float)(-1 + 1.0 / H1), y_hi = (float)(1 - 1.0 / H1);
-    const float inv_w1 = 1.0f / (float)W1;
-    float m = -INFINITY, l = 0.f, ax = 0.f, ay = 0.f;
-    const float e_scale = 1.4426950408889634f / sqrt_c;    // exp(v / sqrt(C)) = exp2(v * log2(e) / sqrt(C))
-
-    // ---- row tiles (flow only, 32 <= W1 <= 64: the 448 and 672 configurations) ---------------------------------------------
-    // A tile of 32 B-positions is (part of) ONE grid row: positions x = 32 p .. 32 p + 31 of row y, those past the row's end
-    // masked out (W1 = 48: the second tile of a row is half empty -- a third more matrix work).  Its y coordinate is then
-    // wave-uniform, the 16 x coordinates of a lane's accumulator rows are two constant sets, and the 1/sqrt(C) scale folds into
-    // the exponent: ~6 VALU instructions per value instead of ~40.  The kernel is VALU-bound (the fp32 MFMA shares the vector
-    // ALUs): 48x48 maps, which took the general path below, ran 6.5x longer than 32x32 ones for 2.5x the work.
-    if (WRITE_FLOW && !WRITE_VOL && W1 >= 32 && W1 <= 64) {  // wave-uniform
+    if (WRITE_FLOW && !WRITE_VOL && W1 >= 32 && W1 <= 64) {  // row tiles; wave-uniform
         const int parts = W1 > 32 ? 2 : 1;
-        float gxA[16], gxB[16];
-        unsigned maskB = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
-            gxA[r] = gfn::linspace_at(x_lo, x_hi, W1, min(o, W1 - 1));
-            gxB[r] = gfn::linspace_at(x_lo, x_hi, W1, min(32 + o, W1 - 1));
-            maskB |= (32 + o < W1 ? 1u : 0u) << r;
-        }
-        auto load_row_tile = [&](float (&a)[KS], int t) {
-            const int y = parts == 1 ? t : t >> 1, pp = parts == 1 ? 0 : t & 1;
-            const int jl = y * W1 + min(32 * pp + col, W1 - 1);
-#pragma unroll
-            for (int s = 0; s < KS; ++s) a[s] = (float)f1b[(size_t)min(2 * s + h, C - 1) * N1 + jl];  // channels >= C meet a zero in bop
-        };
-        auto softmax_tile = [&](f32x16 acc, const float (&gx)[16], int y) {
-            float mt = acc[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mt = fmaxf(mt, acc[r]);
-            const float mn = fmaxf(m, mt);
-            const float sc = __builtin_amdgcn_exp2f((m - mn) * e_scale);  // m = -inf on the first tile -> 0
-            float lt = 0.f, axt = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float e = __builtin_amdgcn_exp2f((acc[r] - mn) * e_scale);  // masked positions: exp2(-inf) = 0
-                lt += e;
-                axt = fmaf(e, gx[r], axt);
-            }
-            const float gy = gfn::linspace_at(y_lo, y_hi, H1, y);
-            l = fmaf(l, sc, lt);
-            ax = fmaf(ax, sc, axt);
-            ay = fmaf(ay, sc, lt * gy);
-            m = mn;
-        };
+        RowTiles rt(H1, W1, true, h, sqrt_c);
         const int ntiles = H1 * parts;
-        if constexpr (KS == 32) {
-            // Round 6, 64-channel maps (GFNet's stride-16 features): the products on the bf16 matrix core instruction with both operands
-            // split three ways (x = h + m + l, exact).  Six of the nine piece products are kept -- h.h, h.m, m.h, m.m, h.l, l.h; the dropped
-            // m.l, l.m, l.l are <= 2^-23 of |a||b|, the size of an fp32 product's own rounding -- in 24 v_mfma_f32_32x32x16_bf16 per tile
-            // (768 matrix cycles) instead of 32 v_mfma_f32_32x32x2_f32 (2 048), and unlike the fp32 instruction they leave the vector ALUs
-            // to the softmax and to the next tile's splitting.  Same accumulator layout, same softmax.  Lane l supplies row / column
-            // l & 31 and channels 16 c + 8 (l >> 5) + e, e = 0..7, of chunk c: plain coalesced NCHW loads as before.
+        if constexpr (KS == 32) {  // split-bf16 products, the operand split here (no workspace: corr_softargmax_img_kernel otherwise)
             bf16x8 bh[4], bm[4], bl[4];
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int c = 16 * c4 + 8 * h + e;
-                    const float v = c < C ? (float)f0b[(size_t)min(c, C - 1) * N0 + ic] : 0.f;
-                    __bf16 ph, pm, pl;
-                    split3(v, ph, pm, pl);
-                    bh[c4][e] = ph; bm[c4][e] = pm; bl[c4][e] = pl;
-                }
+            split_columns(f0b, C, N0, ic, h, bh, bm, bl);
             auto load_raw = [&](float (&a)[32], int t) {
-                const int y = parts == 1 ? t : t >> 1, pp = parts == 1 ? 0 : t & 1;
-                const int jl = y * W1 + min(32 * pp + col, W1 - 1);
+                const int jl = row_tile_pos(t, parts, W1, col);
 #pragma unroll
                 for (int c4 = 0; c4 < 4; ++c4)
 #pragma unroll
@@ -150,73 +215,32 @@ __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restri
                         split3(r_cur[8 * c4 + e], ph, pm, pl);
                         ah[c4][e] = ph; am[c4][e] = pm; al[c4][e] = pl;
                     }
-                // two chains: the small classes and the large ones, smallest terms first inside each; summed at the end
-                f32x16 accs = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc = accs;
-#pragma unroll
-                for (int c4 = 0; c4 < 4; ++c4) {
-                    accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[c4], bm[c4], accs, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[c4], bm[c4], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int c4 = 0; c4 < 4; ++c4) {
-                    accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[c4], bl[c4], accs, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[c4], bh[c4], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int c4 = 0; c4 < 4; ++c4) {
-                    accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[c4], bh[c4], accs, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[c4], bh[c4], acc, 0, 0, 0);
-                }
-                acc += accs;
+                const f32x16 acc = split_products(ah, am, al, bh, bm, bl);
 #pragma unroll
                 for (int k = 0; k < 32; ++k) r_cur[k] = r_nxt[k];
-                if (parts == 1 || !(t & 1)) {
-                    softmax_tile(acc, gxA, parts == 1 ? t : t >> 1);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] = ((maskB >> r) & 1u) ? acc[r] : -INFINITY;
-                    softmax_tile(acc, gxB, t >> 1);
-                }
+                rt.add_tile(acc, parts, t);
             }
         } else {
-        float a_cur[KS], a_nxt[KS];
-        load_row_tile(a_cur, 0);
-        // land the first tile before the loop: otherwise the wait-count pass assumes 64 loads in flight at the loop head and
-        // makes every MFMA of every tile wait for the *prefetch* it was meant to overlap with
+            auto load_row_tile = [&](float (&a)[KS], int t) {
+                const int jl = row_tile_pos(t, parts, W1, col);
 #pragma unroll
-        for (int s = 0; s < KS; ++s) asm volatile("" : "+v"(a_cur[s]));
-        for (int t = 0; t < ntiles; ++t) {
-            if (t + 1 < ntiles) load_row_tile(a_nxt, t + 1);
-            // two independent accumulation chains (even / odd k-steps): a single chain left the matrix pipe waiting on its own
-            // result between issues (0.152 -> 0.122 ms for 64 directions; four chains: 0.131); summed at the end
-            f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc2 = acc;
+                for (int s = 0; s < KS; ++s) a[s] = (float)f1b[(size_t)min(2 * s + h, C - 1) * N1 + jl];  // channels >= C meet a zero in bop
+            };
+            float a_cur[KS], a_nxt[KS];
+            load_row_tile(a_cur, 0);
+            // land the first tile before the loop: otherwise the wait-count pass assumes 64 loads in flight at the loop head and
+            // makes every MFMA of every tile wait for the *prefetch* it was meant to overlap with
 #pragma unroll
-            for (int s = 0; s < KS; s += 2) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[s], bop[s], acc, 0, 0, 0);
-                if (s + 1 < KS) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[s + 1], bop[s + 1], acc2, 0, 0, 0);
-            }
-            acc += acc2;
+            for (int s = 0; s < KS; ++s) asm volatile("" : "+v"(a_cur[s]));
+            for (int t = 0; t < ntiles; ++t) {
+                if (t + 1 < ntiles) load_row_tile(a_nxt, t + 1);
+                const f32x16 acc = corr_tile<KS>(a_cur, bop);
 #pragma unroll
-            for (int s = 0; s < KS; ++s) a_cur[s] = a_nxt[s];
-            if (parts == 1 || !(t & 1)) {
-                softmax_tile(acc, gxA, parts == 1 ? t : t >> 1);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = ((maskB >> r) & 1u) ? acc[r] : -INFINITY;
-                softmax_tile(acc, gxB, t >> 1);
+                for (int s = 0; s < KS; ++s) a_cur[s] = a_nxt[s];
+                rt.add_tile(acc, parts, t);
             }
         }
-        }
-        m = m / sqrt_c;  // the running maximum was kept in unscaled units
-        const float m2 = __shfl_xor(m, 32), l2 = __shfl_xor(l, 32), ax2 = __shfl_xor(ax, 32), ay2 = __shfl_xor(ay, 32);
-        const float mn = fmaxf(m, m2);
-        const float s1 = __expf(m - mn), s2 = __expf(m2 - mn);
-        const float lt = l * s1 + l2 * s2;
-        const float fx = (ax * s1 + ax2 * s2) / lt, fy = (ay * s1 + ay2 * s2) / lt;
-        if (h == 0 && i < N0) {
-            flow[((size_t)b * 2 + 0) * N0 + i] = fx;
-            flow[((size_t)b * 2 + 1) * N0 + i] = fy;
-        }
+        rt.finish(sqrt_c, flow, b, N0, i, h);
         return;
     }
 
@@ -230,6 +254,10 @@ __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restri
             a[s] = (float)f1b[(size_t)min(2 * s + h, C - 1) * N1 + jl];  // channels >= C meet a zero in bop
         }
     };
+    const float x_lo = (float)(-1 + 1.0 / W1), x_hi = (float)(1 - 1.0 / W1);
+    const float y_lo = (float)(-1 + 1.0 / H1), y_hi = (float)(1 - 1.0 / H1);
+    const float inv_w1 = 1.0f / (float)W1;
+    float m = -INFINITY, l = 0.f, ax = 0.f, ay = 0.f;
     float a_cur[KS], a_nxt[KS];
     load_tile(a_cur, 0);
     // land the first tile before the loop: otherwise the wait-count pass assumes 64 loads in flight at the loop head and
@@ -238,22 +266,14 @@ __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restri
     for (int s = 0; s < KS; ++s) asm volatile("" : "+v"(a_cur[s]));
     for (int j0 = 0; j0 < N1; j0 += 32) {
         if (j0 + 32 < N1) load_tile(a_nxt, j0 + 32);
-        // two independent accumulation chains (even / odd k-steps): a single chain left the matrix pipe waiting on its own
-        // result between issues (0.152 -> 0.122 ms for 64 directions; four chains: 0.131); summed at the end
-        f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc2 = acc;
-#pragma unroll
-        for (int s = 0; s < KS; s += 2) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[s], bop[s], acc, 0, 0, 0);
-            if (s + 1 < KS) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[s + 1], bop[s + 1], acc2, 0, 0, 0);
-        }
-        acc += acc2;
+        const f32x16 acc = corr_tile<KS>(a_cur, bop);
 #pragma unroll
         for (int s = 0; s < KS; ++s) a_cur[s] = a_nxt[s];
         float sv[16];
         float mt = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int j = j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int j = j0 + acc_row(r, h);
             const float v = acc[r] / sqrt_c;
             if (WRITE_VOL) {
                 if (j < N1 && i < N0) vol[((size_t)b * N1 + j) * N0 + i] = v;
@@ -269,33 +289,17 @@ __global__ __launch_bounds__(256) void corr_softargmax_kernel(const FT *__restri
             l *= sc; ax *= sc; ay *= sc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int j = j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                // the float quotient is off by one row for some j >= 2^22 (j + 0.5 and the product round); one integer step
-                // either way makes (jx, jy) exact for every j < 2^24 (tests/test_host_cpu.py runs this formula over all of them)
-                int jy = (int)(((float)j + 0.5f) * inv_w1);
-                int jx = j - jy * W1;
-                if (jx < 0) { --jy; jx += W1; }
-                else if (jx >= W1) { ++jy; jx -= W1; }
+                int jx, jy;
+                cell_of(j0 + acc_row(r, h), W1, inv_w1, jx, jy);
                 const float e = __expf(sv[r] - ms);  // exp(-inf) = 0 for the padded rows
                 l += e;
-                ax = fmaf(e, gfn::linspace_at(x_lo, x_hi, W1, jx), ax);
-                ay = fmaf(e, gfn::linspace_at(y_lo, y_hi, H1, min(jy, H1 - 1)), ay);
+                ax = fmaf(e, linspace_at(x_lo, x_hi, W1, jx), ax);
+                ay = fmaf(e, linspace_at(y_lo, y_hi, H1, min(jy, H1 - 1)), ay);
             }
             m = mn;
         }
     }
-    if (WRITE_FLOW) {
-        // merge the two half-waves (same column i, disjoint rows j)
-        const float m2 = __shfl_xor(m, 32), l2 = __shfl_xor(l, 32), ax2 = __shfl_xor(ax, 32), ay2 = __shfl_xor(ay, 32);
-        const float mn = fmaxf(m, m2);
-        const float s1 = __expf(m - mn), s2 = __expf(m2 - mn);
-        const float lt = l * s1 + l2 * s2;
-        const float fx = (ax * s1 + ax2 * s2) / lt, fy = (ay * s1 + ay2 * s2) / lt;
-        if (h == 0 && i < N0) {
-            flow[((size_t)b * 2 + 0) * N0 + i] = fx;
-            flow[((size_t)b * 2 + 1) * N0 + i] = fy;
-        }
-    }
+    if (WRITE_FLOW) finish_flow(m, l, ax, ay, flow, b, N0, i, h);
 }
 
 // The row-tile path on pre-split operand images as a kernel of its own (round 6).  Every wave that walks a direction's tiles would
@@ -316,57 +320,14 @@ __global__ __launch_bounds__(256, 2) void corr_softargmax_img_kernel(const FT *_
     const int col = lane & 31, h = lane >> 5;
     const int i = i0 + col;
     const int ic = min(i, N0 - 1);
-    const FT *f0b = b < Bh ? f0 + (size_t)b * C * N0 : f1 + (size_t)(b - Bh) * C * N0;
     bf16x8 bh[4], bm[4], bl[4];
-#pragma unroll
-    for (int c4 = 0; c4 < 4; ++c4)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int c = 16 * c4 + 8 * h + e;
-            const float v = c < C ? (float)f0b[(size_t)min(c, C - 1) * N0 + ic] : 0.f;
-            __bf16 ph, pm, pl;
-            split3(v, ph, pm, pl);
-            bh[c4][e] = ph; bm[c4][e] = pm; bl[c4][e] = pl;
-        }
-    const float x_lo = (float)(-1 + 1.0 / W1), x_hi = (float)(1 - 1.0 / W1);
-    const float y_lo = (float)(-1 + 1.0 / H1), y_hi = (float)(1 - 1.0 / H1);
-    float m = -INFINITY, l = 0.f, ax = 0.f, ay = 0.f;
-    const float e_scale = 1.4426950408889634f / sqrt_c;
-    float gxA[16], gxB[PARTS == 2 ? 16 : 1];
-    unsigned maskB = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
-        gxA[r] = gfn::linspace_at(x_lo, x_hi, W1, min(o, W1 - 1));
-        if (PARTS == 2) {
-            gxB[r] = gfn::linspace_at(x_lo, x_hi, W1, min(32 + o, W1 - 1));
-            maskB |= (32 + o < W1 ? 1u : 0u) << r;
-        }
-    }
-    auto softmax_tile = [&](f32x16 acc, const float *gx, int y) {   // as in corr_softargmax_kernel
-        float mt = acc[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mt = fmaxf(mt, acc[r]);
-        const float mn = fmaxf(m, mt);
-        const float sc = __builtin_amdgcn_exp2f((m - mn) * e_scale);
-        float lt = 0.f, axt = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float e = __builtin_amdgcn_exp2f((acc[r] - mn) * e_scale);
-            lt += e;
-            axt = fmaf(e, gx[r], axt);
-        }
-        const float gy = gfn::linspace_at(y_lo, y_hi, H1, y);
-        l = fmaf(l, sc, lt);
-        ax = fmaf(ax, sc, axt);
-        ay = fmaf(ay, sc, lt * gy);
-        m = mn;
-    };
+    split_columns(dir_image(f0, f1, b, Bh, (size_t)C * N0), C, N0, ic, h, bh, bm, bl);
+    RowTiles rt(H1, W1, PARTS == 2, h, sqrt_c);
     const int ntiles = H1 * PARTS;
     const bf16x8 *img = aimg + (size_t)b * ntiles * 12 * 64 + lane;
     // (issuing the products of tile t + 1 in front of the softmax of tile t -- a software pipeline over the tiles, 238 registers -- measured
     // SLOWER: 72 against 64 us; the second wave of the SIMD already fills the matrix pipe under this wave's exponentials)
-    bf16x8 a_cur[12], a_nxt[12];
+    bf16x8 a_cur[12], a_nxt[12];  // pieces h, m, l of the tile's rows, four chunks each (split_rows_kernel)
 #pragma unroll
     for (int k = 0; k < 12; ++k) a_cur[k] = img[k * 64];
 #pragma unroll
@@ -376,44 +337,12 @@ __global__ __launch_bounds__(256, 2) void corr_softargmax_img_kernel(const FT *_
 #pragma unroll
             for (int k = 0; k < 12; ++k) a_nxt[k] = img[((size_t)(t + 1) * 12 + k) * 64];
         }
-        // two chains: the small classes and the large ones, smallest terms first inside each; summed at the end
-        f32x16 accs = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc = accs;
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) {
-            accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[4 + c4], bm[c4], accs, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[c4], bm[c4], acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) {
-            accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[c4], bl[c4], accs, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[4 + c4], bh[c4], acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) {
-            accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[8 + c4], bh[c4], accs, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[c4], bh[c4], acc, 0, 0, 0);
-        }
-        acc += accs;
+        const f32x16 acc = split_products(a_cur, a_cur + 4, a_cur + 8, bh, bm, bl);
 #pragma unroll
         for (int k = 0; k < 12; ++k) a_cur[k] = a_nxt[k];
-        if (PARTS == 1 || !(t & 1)) {
-            softmax_tile(acc, gxA, PARTS == 1 ? t : t >> 1);
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = ((maskB >> r) & 1u) ? acc[r] : -INFINITY;
-            softmax_tile(acc, gxB, t >> 1);
-        }
+        rt.add_tile(acc, PARTS, t);
     }
-    m = m / sqrt_c;  // the running maximum was kept in unscaled units
-    const float m2 = __shfl_xor(m, 32), l2 = __shfl_xor(l, 32), ax2 = __shfl_xor(ax, 32), ay2 = __shfl_xor(ay, 32);
-    const float mn = fmaxf(m, m2);
-    const float s1 = __expf(m - mn), s2 = __expf(m2 - mn);
-    const float lt = l * s1 + l2 * s2;
-    const float fx = (ax * s1 + ax2 * s2) / lt, fy = (ay * s1 + ay2 * s2) / lt;
-    if (h == 0 && i < N0) {
-        flow[((size_t)b * 2 + 0) * N0 + i] = fx;
-        flow[((size_t)b * 2 + 1) * N0 + i] = fy;
-    }
+    rt.finish(sqrt_c, flow, b, N0, i, h);
 }
 
 // Workspace of the split-bf16 row-tile path: the B-positions' operand of every direction, split once.  Image of direction b, row tile t
@@ -429,9 +358,8 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const FT *__restrict__ 
     const long bt = idx >> 8;
     const int t = (int)(bt % ntiles), b = (int)(bt / ntiles);
     const int col = lane & 31, h = lane >> 5;
-    const FT *f1b = b < Bh ? f1 + (size_t)b * C * N1 : f0 + (size_t)(b - Bh) * C * N1;  // (symmetric: equal map sizes, checked by the caller)
-    const int y = parts == 1 ? t : t >> 1, pp = parts == 1 ? 0 : t & 1;
-    const int jl = y * W1 + min(32 * pp + col, W1 - 1);
+    const FT *f1b = dir_image(f1, f0, b, Bh, (size_t)C * N1);  // (symmetric: equal map sizes, checked by the caller)
+    const int jl = row_tile_pos(t, parts, W1, col);
     bf16x8 ph, pm, pl;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -484,16 +412,6 @@ __global__ __launch_bounds__(256) void pos_embed_kernel(const float *__restrict_
     flow[((size_t)b * 2 + 1) * N0 + i] = ay / l;
 }
 
-int check_args(const void *f0, const void *f1, int B, int C, int H0, int W0, int H1, int W1) {
-    if (!f0 || !f1) return gfn::fail(GFN_ERR_INVALID_ARG, "corr: null feature pointer");
-    if (B < 0 || C <= 0 || H0 <= 0 || W0 <= 0 || H1 <= 0 || W1 <= 0)
-        return gfn::fail(GFN_ERR_INVALID_ARG, "corr: bad size B=%d C=%d %dx%d vs %dx%d", B, C, H0, W0, H1, W1);
-    if (C > 128) return gfn::fail(GFN_ERR_INVALID_ARG, "corr: C=%d > 128 channels not supported", C);
-    if ((long)H0 * W0 >= (1L << 24) || (long)H1 * W1 >= (1L << 24))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "corr: map too large");
-    return GFN_OK;
-}
-
 template <bool WV, bool WF, typename FT>
 int launch_corr(const FT *f0, const FT *f1, float *vol, float *flow, int B, int Bh, int C, int H0, int W0, int H1,
                 int W1, hipStream_t stream, void *ws = nullptr, int64_t ws_bytes = 0) {
@@ -531,41 +449,11 @@ int launch_corr(const FT *f0, const FT *f1, float *vol, float *flow, int B, int 
     return gfn::check_launch("corr_softargmax_kernel");
 }
 
-}  // namespace
-
-GFN_EXPORT int gfn_corr_softargmax_fwd(const float *f0, const float *f1, float *flow, int B, int C, int H0, int W0,
-                                       int H1, int W1, int symmetric, gfn_stream_t stream) {
-    if (int e = check_args(f0, f1, B, C, H0, W0, H1, W1)) return e;
-    if (!flow) return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax: null flow");
-    if (symmetric && ((B & 1) || H0 != H1 || W0 != W1))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax: symmetric needs an even batch and equal map sizes");
-    if (B == 0) return GFN_OK;
-    return launch_corr<false, true>(f0, f1, nullptr, flow, B, symmetric ? B / 2 : B, C, H0, W0, H1, W1, (hipStream_t)stream);
-}
-
-GFN_EXPORT int gfn_corr_softargmax_fwd_dt(const void *f0, const void *f1, int dtype, float *flow, int B, int C, int H0, int W0,
-                                          int H1, int W1, int symmetric, gfn_stream_t stream) {
-    if (dtype == GFN_F32)
-        return gfn_corr_softargmax_fwd(static_cast<const float *>(f0), static_cast<const float *>(f1), flow, B, C, H0, W0, H1, W1, symmetric, stream);
-    if (dtype != GFN_F16) return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax: feature dtype must be GFN_F32 or GFN_F16");
-    if (int e = check_args(static_cast<const float *>(f0), static_cast<const float *>(f1), B, C, H0, W0, H1, W1)) return e;
-    if (!flow) return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax: null flow");
-    if (symmetric && ((B & 1) || H0 != H1 || W0 != W1))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax: symmetric needs an even batch and equal map sizes");
-    if (B == 0) return GFN_OK;
-    return launch_corr<false, true>(static_cast<const _Float16 *>(f0), static_cast<const _Float16 *>(f1), nullptr, flow, B, symmetric ? B / 2 : B, C,
-                                    H0, W0, H1, W1, (hipStream_t)stream);
-}
-
-GFN_EXPORT int64_t gfn_corr_softargmax_ws_bytes(int B, int C, int H1, int W1) { return split_ws_bytes(B, C, H1, W1); }
-
-GFN_EXPORT int gfn_corr_softargmax_fwd_ws(const void *f0, const void *f1, int dtype, float *flow, int B, int C, int H0, int W0, int H1,
-                                          int W1, int symmetric, void *ws, int64_t ws_bytes, gfn_stream_t stream) {
+// every flow-only entry point: checks in the order they refuse, then the launch for the dtype
+int softargmax_fwd(const void *f0, const void *f1, int dtype, float *flow, int B, int C, int H0, int W0, int H1, int W1, int symmetric, void *ws,
+                   int64_t ws_bytes, gfn_stream_t stream) {
     if (dtype != GFN_F32 && dtype != GFN_F16) return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax: feature dtype must be GFN_F32 or GFN_F16");
-    if (int e = check_args(f0, f1, B, C, H0, W0, H1, W1)) return e;
-    if (!flow) return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax: null flow");
-    if (symmetric && ((B & 1) || H0 != H1 || W0 != W1))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax: symmetric needs an even batch and equal map sizes");
+    if (int e = corr_check("corr_softargmax", f0, f1, flow, B, C, H0, W0, H1, W1, symmetric)) return e;
     if (B == 0) return GFN_OK;
     const int Bh = symmetric ? B / 2 : B;
     if (dtype == GFN_F16)
@@ -575,10 +463,28 @@ GFN_EXPORT int gfn_corr_softargmax_fwd_ws(const void *f0, const void *f1, int dt
                                     (hipStream_t)stream, ws, ws_bytes);
 }
 
+}  // namespace
+
+GFN_EXPORT int gfn_corr_softargmax_fwd(const float *f0, const float *f1, float *flow, int B, int C, int H0, int W0,
+                                       int H1, int W1, int symmetric, gfn_stream_t stream) {
+    return softargmax_fwd(f0, f1, GFN_F32, flow, B, C, H0, W0, H1, W1, symmetric, nullptr, 0, stream);
+}
+
+GFN_EXPORT int gfn_corr_softargmax_fwd_dt(const void *f0, const void *f1, int dtype, float *flow, int B, int C, int H0, int W0,
+                                          int H1, int W1, int symmetric, gfn_stream_t stream) {
+    return softargmax_fwd(f0, f1, dtype, flow, B, C, H0, W0, H1, W1, symmetric, nullptr, 0, stream);
+}
+
+GFN_EXPORT int64_t gfn_corr_softargmax_ws_bytes(int B, int C, int H1, int W1) { return split_ws_bytes(B, C, H1, W1); }
+
+GFN_EXPORT int gfn_corr_softargmax_fwd_ws(const void *f0, const void *f1, int dtype, float *flow, int B, int C, int H0, int W0, int H1,
+                                          int W1, int symmetric, void *ws, int64_t ws_bytes, gfn_stream_t stream) {
+    return softargmax_fwd(f0, f1, dtype, flow, B, C, H0, W0, H1, W1, symmetric, ws, ws_bytes, stream);
+}
+
 GFN_EXPORT int gfn_corr_volume_fwd(const float *f0, const float *f1, float *vol, float *flow_or_null, int B, int C,
                                    int H0, int W0, int H1, int W1, gfn_stream_t stream) {
-    if (int e = check_args(f0, f1, B, C, H0, W0, H1, W1)) return e;
-    if (!vol) return gfn::fail(GFN_ERR_INVALID_ARG, "corr_volume: null volume");
+    if (int e = corr_check("corr_volume", f0, f1, vol, B, C, H0, W0, H1, W1, 0)) return e;
     if (B == 0) return GFN_OK;
     if (flow_or_null) return launch_corr<true, true>(f0, f1, vol, flow_or_null, B, B, C, H0, W0, H1, W1, (hipStream_t)stream);
     return launch_corr<true, false>(f0, f1, vol, nullptr, B, B, C, H0, W0, H1, W1, (hipStream_t)stream);

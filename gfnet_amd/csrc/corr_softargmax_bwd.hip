@@ -9,43 +9,18 @@
 //   bwd_f0_kernel  one wave per 32 A-positions streams every B-position: online max / sum and the unnormalised
 //                  sum_j e_ji (G_i . gamma_j - D_i) f1[:,j]  ->  dF0, and the row statistics (m_i, 1/(l_i sqrt C), G_i, D_i) into ws;
 //   bwd_f1_kernel  one wave per 32 B-positions streams every A-position: recomputes s_ji, takes P_ji from the statistics, dF1.
-// Every product is on the exact-fp32 matrix core (v_mfma_f32_32x32x2_f32: fp32 fmaf chains).  The correlation tile S is computed as in
-// the forward's general path (rows = streamed positions, columns = the wave's own); its weights W, still in the accumulator layout,
+// Every product is on the exact-fp32 matrix core (v_mfma_f32_32x32x2_f32: fp32 fmaf chains).  The correlation tile S is the forward's
+// (corr_tile, acc_row, cell_centre and dir_image of corr_common.h: rows = streamed positions, columns = the wave's own); its weights W, still in the accumulator layout,
 // are the B operand of the second product out[c][p] += sum_q Y[c][q] W[q][p] as they stand: lane (col, h) supplies W[q(r, h)][col]
 // = acc[r] for k-step r, q(r, h) = (r & 3) + 8 (r >> 2) + 4 h.  Its A operand Y[c][q(r, h)] has the channel on the lane, the
 // transpose of the coalesced tile load: the tile goes through LDS (one wave per workgroup, row stride 33: conflict-free both ways).
-#include "common.h"
+#include "corr_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace gfn;
 
 constexpr int LDS_STRIDE = 33;
-
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// B-grid cell centre of position j (torch.linspace as the forward fills it; the integer correction as in corr_softargmax.hip)
-__device__ __forceinline__ void cell_centre(int j, int H1, int W1, float inv_w1, float &gx, float &gy) {
-    int jy = (int)(((float)j + 0.5f) * inv_w1);
-    int jx = j - jy * W1;
-    if (jx < 0) { --jy; jx += W1; }
-    else if (jx >= W1) { ++jy; jx -= W1; }
-    gx = gfn::linspace_at((float)(-1 + 1.0 / W1), (float)(1 - 1.0 / W1), W1, jx);
-    gy = gfn::linspace_at((float)(-1 + 1.0 / H1), (float)(1 - 1.0 / H1), H1, min(jy, H1 - 1));
-}
-
-// S[q][p] = sum_c Y[c][q] X[c][p] for one tile: y = the lane's KS values Y[2 s + h][q0 + col], x = X[2 s + h][p0 + col] (zero for
-// channels >= C); two accumulation chains as in the forward
-template <int KS>
-__device__ __forceinline__ f32x16 corr_tile(const float (&y)[KS], const float (&x)[KS]) {
-    f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc2 = acc;
-#pragma unroll
-    for (int s = 0; s < KS; s += 2) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(y[s], x[s], acc, 0, 0, 0);
-        if (s + 1 < KS) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(y[s + 1], x[s + 1], acc2, 0, 0, 0);
-    }
-    return acc + acc2;
-}
 
 // out[cb][c][p] += sum_q Y[c][q] W[q][p] with Y staged in lds ([c][q], row stride LDS_STRIDE) and w[r] = W[q(r, h)][col]
 template <int NCB>
@@ -74,10 +49,9 @@ __global__ __launch_bounds__(64) void bwd_f0_kernel(const FT *__restrict__ f0, c
     const int col = lane & 31, h = lane >> 5;
     const int i = i0 + col, ic = min(i, N0 - 1);
     // symmetric batches are virtual (Bh = B/2): direction b >= Bh swaps the two arrays, and its dF0 is the gradient of f1[b - Bh]
-    const FT *f0b = b < Bh ? f0 + (size_t)b * C * N0 : f1 + (size_t)(b - Bh) * C * N0;
-    const FT *f1b = b < Bh ? f1 + (size_t)b * C * N1 : f0 + (size_t)(b - Bh) * C * N1;
-    float *gbase = b < Bh ? g0 : g1;
-    float *gout = gbase ? gbase + (size_t)(b < Bh ? b : b - Bh) * C * N0 : nullptr;
+    const FT *f0b = dir_image(f0, f1, b, Bh, (size_t)C * N0);
+    const FT *f1b = dir_image(f1, f0, b, Bh, (size_t)C * N1);
+    float *gout = (b < Bh ? g0 : g1) ? dir_image(g0, g1, b, Bh, (size_t)C * N0) : nullptr;
     const bool want = gout != nullptr;  // workgroup-uniform; without it only the statistics are made
 
     float xop[KS];
@@ -178,11 +152,10 @@ __global__ __launch_bounds__(64) void bwd_f1_kernel(const FT *__restrict__ f0, c
     const int b = blockIdx.x / jtiles, j0 = (blockIdx.x - b * jtiles) << 5;
     const int col = lane & 31, h = lane >> 5;
     const int j = j0 + col, jc = min(j, N1 - 1);
-    float *gbase = b < Bh ? g1 : g0;
-    if (!gbase) return;  // whole workgroup
-    float *gout = gbase + (size_t)(b < Bh ? b : b - Bh) * C * N1;
-    const FT *f0b = b < Bh ? f0 + (size_t)b * C * N0 : f1 + (size_t)(b - Bh) * C * N0;
-    const FT *f1b = b < Bh ? f1 + (size_t)b * C * N1 : f0 + (size_t)(b - Bh) * C * N1;
+    if (!(b < Bh ? g1 : g0)) return;  // whole workgroup
+    float *gout = dir_image(g1, g0, b, Bh, (size_t)C * N1);
+    const FT *f0b = dir_image(f0, f1, b, Bh, (size_t)C * N0);
+    const FT *f1b = dir_image(f1, f0, b, Bh, (size_t)C * N1);
 
     float xop[KS];
 #pragma unroll
@@ -289,13 +262,8 @@ GFN_EXPORT int gfn_corr_softargmax_bwd(const void *f0, const void *f1, int dtype
                                        float *grad_f1, int B, int C, int H0, int W0, int H1, int W1, int symmetric, void *ws,
                                        int64_t ws_bytes_, gfn_stream_t stream) {
     if (dtype != GFN_F32 && dtype != GFN_F16) return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax_bwd: feature dtype must be GFN_F32 or GFN_F16");
-    if (!f0 || !f1 || !flow || !grad_flow) return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax_bwd: null input pointer");
-    if (B < 0 || C <= 0 || H0 <= 0 || W0 <= 0 || H1 <= 0 || W1 <= 0)
-        return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax_bwd: bad size B=%d C=%d %dx%d vs %dx%d", B, C, H0, W0, H1, W1);
-    if (C > 128) return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax_bwd: C=%d > 128 channels not supported", C);
-    if ((long)H0 * W0 >= (1L << 24) || (long)H1 * W1 >= (1L << 24)) return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax_bwd: map too large");
-    if (symmetric && ((B & 1) || H0 != H1 || W0 != W1))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax_bwd: symmetric needs an even batch and equal map sizes");
+    if (!grad_flow) return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax_bwd: null grad_flow");
+    if (int e = corr_check("corr_softargmax_bwd", f0, f1, flow, B, C, H0, W0, H1, W1, symmetric)) return e;
     if (B == 0 || (!grad_f0 && !grad_f1)) return GFN_OK;
     if (!ws || ws_bytes_ < ws_bytes(B, H0, W0) || ((uintptr_t)ws & 15))
         return gfn::fail(GFN_ERR_INVALID_ARG, "corr_softargmax_bwd: workspace missing, misaligned or smaller than gfn_corr_softargmax_bwd_ws_bytes");

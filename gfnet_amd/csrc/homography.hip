@@ -29,16 +29,9 @@
 
 namespace {
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
 __device__ __forceinline__ uint32_t draw_index(uint64_t seed, uint32_t b, uint32_t t, uint32_t k, uint32_t a, uint32_t s, uint32_t N) {
-    uint64_t h = splitmix64(seed ^ splitmix64(((uint64_t)b << 32) | t));
-    h = splitmix64(h + ((uint64_t)s << 16) + ((uint64_t)k << 8) + a);
+    uint64_t h = gfn::splitmix64(seed ^ gfn::splitmix64(((uint64_t)b << 32) | t));
+    h = gfn::splitmix64(h + ((uint64_t)s << 16) + ((uint64_t)k << 8) + a);
     return (uint32_t)(h % N);
 }
 

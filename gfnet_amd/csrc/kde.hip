@@ -12,7 +12,7 @@
 // matrix product); fp32 accumulation.  When N is too small to fill the chip the M range is split
 // over blockIdx.y and the partial sums are reduced by a second tiny kernel (deterministic, no
 // float atomics).
-#include "common.h"
+#include "corr_common.h"  // split3, bf16x8, f32x16, acc_row
 #include <cstdlib>
 
 namespace {
@@ -277,15 +277,9 @@ __global__ __launch_bounds__(256) void kde4_bbox_kernel(const float *__restrict_
 // norms (3 + 3 slots against ones) fill K = 32, so D comes out as the exponent itself (error ~1e-5 from the
 // fp32 accumulation of +-300 magnitudes, i.e. 1e-5 relative on a term).  What is left on the VALU per pair
 // is v_exp_f32 and half a packed add -- 2.4x fewer vector cycles than the difference form (kde4_kernel).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void split3(float v, __bf16 &h, __bf16 &l, __bf16 &ll) {
-    h = (__bf16)v;
-    const float r1 = v - (float)h;
-    l = (__bf16)r1;
-    ll = (__bf16)(r1 - (float)l);
-}
+using gfn::bf16x8;
+using gfn::f32x16;
+using gfn::split3;  // (h, l, ll here are its h, m, l)
 
 // Operand images: op[(bt*T + tile)*4 + g][row 0..31] = 8 bf16, g = MFMA (0/1) * 2 + k half; one thread per point.
 //   MFMA 0  k 0-7 : A xh  nxh 1 nxl 1   B yh  1 nyh 1 nyl      k 8-15: A xh xl    B yl yh
@@ -506,7 +500,7 @@ __global__ __launch_bounds__(kKdeThreads, 4) void kde4_mfma_kernel(const float *
             v0 += xor_lane(v0, o);
             v1 += xor_lane(v1, o);
         }
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
+        const int row = gfn::acc_row(r, kh);
         if (col == 0 && q0 + row < N) dst[q0 + row] = v0;
         if (col == 0 && q0 + 32 + row < N) dst[q0 + 32 + row] = v1;
     }

@@ -16,13 +16,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
 // One workgroup = kKeysPerBlock consecutive elements of one row; besides the keys it accumulates the row's histogram of
 // the top 11 key bits (the first radix-select pass) -- in LDS, flushed with one global atomic per occupied bin.
 constexpr int kKeysPerBlock = 8192;
@@ -37,7 +30,7 @@ __global__ __launch_bounds__(256) void race_keys_kernel(const float *__restrict_
     for (int i = i0 + threadIdx.x; i < i1; i += 256) {
         float wi = w[(size_t)row * w_rs + i];
         wi = wi > one_above ? 1.f : wi;  // GFNet.sample's certainty threshold (network.py:391-393); +inf = off
-        const uint64_t h = splitmix64(seed ^ splitmix64(((uint64_t)(unsigned)row << 32) | (unsigned)i));
+        const uint64_t h = gfn::splitmix64(seed ^ gfn::splitmix64(((uint64_t)(unsigned)row << 32) | (unsigned)i));
         const float u = ((float)(unsigned)(h >> 40) + 1.0f) * 5.9604644775390625e-08f;  // (0, 1], 24 bits
         const float e = -__logf(u);                                                      // Exp(1); 0 only for u == 1
         float key = wi > 0.f ? wi / fmaxf(e, 1e-30f) : 0.f;
