@@ -61,12 +61,14 @@ _SIGNATURES = {
     "gfn_local_corr_mode_bwd_f0": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 11 + [c_vp],
     "gfn_grid_sample_mode_fwd": [c_vp, c_int, c_vp, c_vp, c_i64] + [c_int] * 8 + [c_vp],
     "gfn_refiner_input_mode_fwd_dt": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 6 + [c_float, c_int, c_int, c_vp],
+    "gfn_refiner_input_bwd": [c_vp, c_i64, c_vp, c_int] + [c_vp] * 8 + [c_int] * 7 + [c_float, c_vp, c_i64, c_vp],
 }
 # entry points that return a size instead of a status
 _SIZE_FUNCS = {
     "gfn_local_corr_scratch_bytes": [c_int, c_int],
     "gfn_corr_softargmax_ws_bytes": [c_int] * 4,
     "gfn_corr_softargmax_bwd_ws_bytes": [c_int] * 6,
+    "gfn_refiner_input_bwd_scratch_bytes": [c_int] * 3,
     "gfn_local_corr_plans": [c_int] * 6,
     "gfn_kde_scratch_floats": [c_int, c_int, c_int, c_int],
     "gfn_kde_sorted_scratch_floats": [c_int, c_int, c_int],

@@ -17,14 +17,16 @@ GFNet.extract_features (model/network.py:156-201), or feed pyramids directly to
 `forward_pyramids` / `match_pyramids`.  The refiner's depthwise/pointwise conv stack
 (model/network.py:560-563) runs on csrc/conv_stack.hip / conv_stack_half.hip in eval mode (`conv_precision`:
 "fp32" exact fp32 products, "fp16" fp16 1x1 operands, "amp" the class the reference's amp=True refiners run in under
-torch.autocast -- fp16 maps between the blocks); training mode keeps the nn modules and assembles the refiner input with
-differentiable torch ops (the HIP assembly has no backward).
+torch.autocast -- fp16 maps between the blocks); training mode keeps the nn modules (BatchNorm uses batch statistics there)
+and assembles the refiner input with the same HIP launch as inference, which has a HIP backward (ops.refiner_input;
+csrc/refiner_input_bwd.hip).  Refiners with sample_mode "nearest" / "bicubic" train through differentiable torch ops instead.
 
 Training (`model.train()`, grad mode on, pyramids or parameters that require grad): forward_pyramids returns flows and
 certainties with an autograd graph, as the reference's forward does (network.py:230-281).  The scale-16 global match is
 differentiable with respect to both feature maps (ops.corr_softargmax: backward in csrc/corr_softargmax_bwd.hip, which never
 writes the volume), every flow update passes its gradient to the previous flow, the refiner's outputs and the certainty
-(ops.flow_update), and the refiners see the flow through their differentiable input assembly.  Detached as in the reference:
+(ops.flow_update), and the refiner input (ops.refiner_input) passes its gradient to both feature maps, the flow and disp_emb --
+also when only the flow asks for one.  Detached as in the reference:
 the resize between scales (network.py:271-281) and the local correlation's feature1 / flow (utils/local_correlation.py:54).
 Calls without grad (inference, bench.py) take the plain launches: no extra work.
 """
@@ -113,7 +115,10 @@ class ConvRefiner(nn.Module):
         c = x.shape[1]
         dd = self.disp_emb.weight.shape[0]
         use_corr = bool(self.corr_in_other)
-        if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad or self.disp_emb.weight.requires_grad):
+        emb = self.disp_emb
+        needs_grad = torch.is_grad_enabled() and (x.requires_grad or y.requires_grad or flow.requires_grad or
+                                                  emb.weight.requires_grad or emb.bias.requires_grad)
+        if needs_grad and self.sample_mode != "bilinear":
             return self._assemble_autograd(num_grid, x, y, flow, scale_factor)
         d = ops.refiner_input(num_grid, x, y, flow, self.disp_emb.weight, self.disp_emb.bias,
                               self.local_corr_radius if use_corr else 0, scale_factor=scale_factor, corr_in_other=use_corr, reuse=reuse,
@@ -121,9 +126,10 @@ class ConvRefiner(nn.Module):
         return d, (d[:, 2 * c + dd:] if use_corr else None)
 
     def _assemble_autograd(self, num_grid, x, y, flow, scale_factor):
-        """The same tensor from differentiable torch ops (network.py:537-555), for training: gradients reach the backbone
+        """The same tensor from differentiable torch ops (network.py:537-555), for training with sample_mode "nearest" or
+        "bicubic" (bilinear refiners train through ops.refiner_input's HIP backward): gradients reach the backbone
         features through both grid_samples, disp_emb's parameters, and feature0 of the local correlation (through the HIP
-        backward gfn_local_corr_bwd_f0; the reference samples feature1 under no_grad, utils/local_correlation.py:54-60).
+        backward gfn_local_corr_mode_bwd_f0; the reference samples feature1 under no_grad, utils/local_correlation.py:54-60).
         Only plain (non-symmetric) batches: training concatenates the pyramids itself."""
         import torch.nn.functional as F
 

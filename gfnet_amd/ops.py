@@ -153,7 +153,19 @@ def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fact
     overwritten in place except for its grid_feature planes, which depend on x and the grid only.
     sample_mode: ConvRefiner(sample_mode=...) (network.py:464, 537, 547, 553-554), "bilinear", "nearest" or "bicubic"; padding is
     zeros as in the reference.  Other than bilinear, all three gathers take the general per-tap kernels (csrc/grid_modes.hip,
-    csrc/local_corr_modes.hip), never the tiled correlation or its plan."""
+    csrc/local_corr_modes.hip), never the tiled correlation or its plan.
+    With grad mode on and any of x, y, flow, disp_w, disp_b requiring grad, a bilinear call on a plain batch is differentiable
+    (_RefinerInputFn: the same launches forward, gfn_refiner_input_bwd backward; `reuse` is not taken, an autograd graph keeps d);
+    a symmetric batch that needs gradients raises NotImplementedError, as training does.  Every other call is the plain launch."""
+    if sample_mode == "bilinear" and torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, flow, disp_w, disp_b)):
+        if flow.shape[0] != x.shape[0]:
+            raise NotImplementedError("training-mode refiner input needs a plain batch (flow and features of equal batch size)")
+        return _RefinerInputFn.apply(x, y, flow, disp_w, disp_b, int(num_grid), int(local_radius), float(scale_factor), bool(corr_in_other))
+    return _refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_factor, corr_in_other, reuse, sample_mode)[0]
+
+
+def _refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_factor, corr_in_other, reuse, sample_mode):
+    """The forward launches; returns (d, y, flow, disp_w) with the inputs as the kernels read them."""
     general = sample_mode != "bilinear"
     if general:
         sm, _ = _lib.mode_codes(sample_mode, "zeros", "refiner_input")
@@ -191,7 +203,7 @@ def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fact
             check(_L().gfn_local_corr_mode_fwd(ptr(d), CH * G * G, ptr(y), ptr(x) if symmetric else None, dtx, ptr(fl), c_vp(out.data_ptr()),
                                                CH * G * G, B, C, G, Hs, Ws, r, 0, Hs, Ws, sm, _lib.PADDING_MODES["zeros"], st),
                   "gfn_local_corr_mode_fwd")
-        return d
+        return d, y, fl, w
     # shapes the lean local-correlation path takes are planned inside the refiner-input launch (both only read the flow)
     plans = FUSE_PLAN and corr_in_other and bool(_L().gfn_local_corr_plans(C, Hs, Ws, G, r, dtx))
     if corr_in_other:
@@ -211,7 +223,67 @@ def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fact
         if kernel_counters is not None:
             hdr = scr[:8].cpu()  # synchronises; header layout: csrc/local_corr.hip kTodoHdr
             kernel_counters.setdefault(name, []).append((int(hdr[3]), int(hdr[5]), int(hdr[7])))
-    return d
+    return d, y, fl, w
+
+
+def refiner_input_bwd(grad_d, y, flow, disp_w, local_radius, scale_factor=1.0, corr_in_other=True, need=(True,) * 5):
+    """Gradients of refiner_input's d (bilinear, plain batch) with respect to (x, y, flow, disp_w, disp_b) given grad_d = dL/dd:
+    fp32 tensors, None where `need` says so (csrc/refiner_input_bwd.hip).  y (B,C,Hs,Ws) fp32 or fp16, flow (B,2,G,G) and disp_w
+    (Dd,2) as the forward read them.  The local correlation passes its feature0 gradient on to x (gfn_local_corr_mode_bwd_f0 on
+    grad_d's last planes); its feature1 and coordinates are detached, as in the reference (utils/local_correlation.py:54-60).
+    dy is accumulated with fp32 atomics: its last bits can differ between runs; every other result is reproducible."""
+    dev = require_gpu(grad_d, y, flow, disp_w)
+    (y, dt), fl, g = featc(y), f32c(flow), f32c(grad_d)
+    w = f32c(disp_w).reshape(-1, 2)
+    B, C, Hs, Ws = y.shape
+    G, Dd, r = fl.shape[-1], w.shape[0], int(local_radius)
+    K = (2 * r + 1) ** 2 if corr_in_other else 0
+    CH = 2 * C + Dd + K
+    if tuple(fl.shape) != (B, 2, G, G) or tuple(g.shape) != (B, CH, G, G):
+        raise ValueError(f"refiner_input_bwd: flow must be (B,2,G,G) and grad_d {(B, CH, G, G)}, got {tuple(fl.shape)}, {tuple(g.shape)}")
+    st = stream_ptr(dev)
+    n_x, n_y, n_f, n_w, n_b = need
+    gf0 = None
+    if n_x and corr_in_other:
+        gk = g[:, 2 * C + Dd:]
+        gf0 = torch.empty((B, C, G, G), device=dev, dtype=torch.float32)
+        check(_L().gfn_local_corr_mode_bwd_f0(c_vp(gk.data_ptr()), CH * G * G, ptr(f32c(y)), None, ptr(fl), ptr(gf0), C * G * G, B, C, G,
+                                              Hs, Ws, r, 0, Hs, Ws, _lib.SAMPLE_MODES["bilinear"], _lib.PADDING_MODES["zeros"], st),
+              "gfn_local_corr_mode_bwd_f0")
+
+    def out(wanted, *shape):
+        return torch.empty(shape, device=dev, dtype=torch.float32) if wanted else None
+
+    dx, dy, dfl = out(n_x, B, C, Hs, Ws), out(n_y, B, C, Hs, Ws), out(n_f, B, 2, G, G)
+    dw, db = out(n_w, Dd, 2), out(n_b, Dd)
+    nscr = int(_L().gfn_refiner_input_bwd_scratch_bytes(B, G, Dd)) if (n_w or n_b) else 0
+    scr = torch.empty(nscr, device=dev, dtype=torch.uint8) if nscr > 0 else None  # (not the per-stream scratch: its header stays zeroed)
+    check(_L().gfn_refiner_input_bwd(ptr(g), CH * G * G, ptr(y), dt, ptr(fl), ptr(w), ptr(gf0), ptr(dx), ptr(dy), ptr(dfl), ptr(dw), ptr(db),
+                                     B, C, Hs, Ws, G, Dd, K, float(40 / 32 * scale_factor), ptr(scr), nscr, st), "gfn_refiner_input_bwd")
+    return dx, dy, dfl, dw, db
+
+
+class _RefinerInputFn(torch.autograd.Function):
+    """refiner_input with a backward: the same launches forward (same bits, the planned lean route included), saving only y, flow
+    and disp_w; refiner_input_bwd backward."""
+
+    @staticmethod
+    def forward(ctx, x, y, flow, disp_w, disp_b, num_grid, local_radius, scale_factor, corr_in_other):
+        d, yk, fl, w = _refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_factor, corr_in_other, None, "bilinear")
+        ctx.save_for_backward(yk, fl, w)
+        ctx.meta = (local_radius, scale_factor, corr_in_other, tuple(t.dtype for t in (x, y, flow, disp_w, disp_b)), disp_w.shape, disp_b.shape)
+        return d
+
+    @staticmethod
+    def backward(ctx, grad_d):
+        yk, fl, w = ctx.saved_tensors
+        r, scale_factor, corr_in_other, dtypes, w_shape, b_shape = ctx.meta
+        grads = list(refiner_input_bwd(grad_d, yk, fl, w, r, scale_factor, corr_in_other, need=ctx.needs_input_grad[:5]))
+        if grads[3] is not None:
+            grads[3] = grads[3].reshape(w_shape)
+        if grads[4] is not None:
+            grads[4] = grads[4].reshape(b_shape)
+        return tuple(None if t is None else t.to(dt) for t, dt in zip(grads, dtypes)) + (None,) * 4
 
 
 def grid_sample(x, grid, mode="bilinear", padding_mode="zeros"):

@@ -193,6 +193,29 @@ int gfn_refiner_input_plan_fwd_dt(const void *f0, const void *f1, int dtype, con
                                   float *d, int64_t d_bs, int B, int C, int Hs, int Ws, int G, int disp_dim, float disp_scale,
                                   int symmetric, int r, void *scratch, int64_t scratch_bytes, gfn_stream_t stream);
 
+/* Backward of gfn_refiner_input_fwd_dt (+ the local correlation that fills d's last K planes) on a plain batch, bilinear sampling
+ * with zeros padding (training: the reference differentiates model/network.py:537-555 through torch autograd).  grad_d = dL/dd,
+ * (B, 2C+disp_dim+K, G, G) with batch stride d_bs; f1 (B,C,Hs,Ws) as the forward read it (dtype = GFN_F32 or GFN_F16), flow and
+ * disp_w the forward's.  gf0 (B,C,G,G) contiguous or NULL: the gradient the local correlation sends to its feature0 = d[:, 0:C]
+ * (gfn_local_corr_bwd_f0 on grad_d's last K planes); NULL when there is no correlation slice.  Outputs, all fp32 and OVERWRITTEN,
+ * each may be NULL and is then not computed:
+ *   dx      (B,C,Hs,Ws)  adjoint of sampling f0 at the cell centres, applied to grad_d[:, 0:C] + gf0: a gather, no atomics
+ *   dy      (B,C,Hs,Ws)  adjoint of sampling f1 along the flow: a scatter with fp32 atomic adds; the call clears dy on `stream`
+ *                        first.  The one output whose last bits can differ from run to run (the order the adds arrive in)
+ *   dflow   (B,2,G,G)    derivative of x_hat with respect to the sampling coordinate (ATen's grid_sampler rule: corners outside
+ *                        the image count as zeros; cells 10^6 pixels outside or non-finite get none) plus
+ *                        disp_scale * disp_w^T grad_emb.  The local correlation adds nothing: the reference samples its window
+ *                        under no_grad (utils/local_correlation.py:54-60)
+ *   ddisp_w (disp_dim,2) disp_scale * sum grad_emb * (flow - centres), ddisp_b (disp_dim) sum grad_emb: per-workgroup partial sums
+ *                        in `scratch` and a second-stage sum, both in a fixed order (no atomics)
+ * scratch: >= gfn_refiner_input_bwd_scratch_bytes(B, G, disp_dim) bytes of 4-byte aligned device memory when ddisp_w or ddisp_b is
+ * wanted (contents undefined afterwards), unused otherwise.  Same size limits as the forward (C * Hs * Ws < 2^31). */
+int64_t gfn_refiner_input_bwd_scratch_bytes(int B, int G, int disp_dim);
+int gfn_refiner_input_bwd(const float *grad_d, int64_t d_bs, const void *f1, int dtype, const float *flow, const float *disp_w,
+                          const float *gf0, float *dx, float *dy, float *dflow, float *ddisp_w, float *ddisp_b, int B, int C, int Hs,
+                          int Ws, int G, int disp_dim, int K, float disp_scale, void *scratch, int64_t scratch_bytes,
+                          gfn_stream_t stream);
+
 /* F.grid_sample(in, grid, mode='bilinear', padding_mode='zeros', align_corners=False):
  * in (B,C,H,W), grid (B,Ho,Wo,2) -> out (B,C,Ho,Wo) with batch stride out_bs.  This is gfn_grid_sample_mode_fwd with GFN_F32,
  * GFN_SAMPLE_BILINEAR and GFN_PAD_ZEROS; like it, it refuses H * W >= 2^31 (pixel offsets are 32-bit). */
