@@ -62,6 +62,8 @@ _SIGNATURES = {
     "gfn_grid_sample_mode_fwd": [c_vp, c_int, c_vp, c_vp, c_i64] + [c_int] * 8 + [c_vp],
     "gfn_refiner_input_mode_fwd_dt": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 6 + [c_float, c_int, c_int, c_vp],
     "gfn_refiner_input_bwd": [c_vp, c_i64, c_vp, c_int] + [c_vp] * 8 + [c_int] * 7 + [c_float, c_vp, c_i64, c_vp],
+    "gfn_conv_block_train_fwd": [c_vp] * 13 + [c_int] * 4 + [c_double, c_double, c_vp, c_i64, c_vp],
+    "gfn_conv_block_train_bwd": [c_vp] * 16 + [c_int] * 5 + [c_vp, c_i64, c_vp],
 }
 # entry points that return a size instead of a status
 _SIZE_FUNCS = {
@@ -74,7 +76,10 @@ _SIZE_FUNCS = {
     "gfn_kde_sorted_scratch_floats": [c_int, c_int, c_int],
     "gfn_homography_scratch_bytes": [c_int, c_int],
     "gfn_conv_block_packed_floats": [c_int, c_int],
+    "gfn_conv_block_train_ws_bytes": [c_int] * 5,
 }
+# `need` bits of gfn_conv_block_train_bwd (GFN_CBT_NEED_* in include/gfnet_hip.h)
+CBT_NEED_X, CBT_NEED_DW, CBT_NEED_BN, CBT_NEED_PW = 1, 2, 4, 8
 
 
 class GfnError(RuntimeError):

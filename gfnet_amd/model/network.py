@@ -17,9 +17,13 @@ GFNet.extract_features (model/network.py:156-201), or feed pyramids directly to
 `forward_pyramids` / `match_pyramids`.  The refiner's depthwise/pointwise conv stack
 (model/network.py:560-563) runs on csrc/conv_stack.hip / conv_stack_half.hip in eval mode (`conv_precision`:
 "fp32" exact fp32 products, "fp16" fp16 1x1 operands, "amp" the class the reference's amp=True refiners run in under
-torch.autocast -- fp16 maps between the blocks); training mode keeps the nn modules (BatchNorm uses batch statistics there)
-and assembles the refiner input with the same HIP launch as inference, which has a HIP backward (ops.refiner_input;
-csrc/refiner_input_bwd.hip).  Refiners with sample_mode "nearest" / "bicubic" train through differentiable torch ops instead.
+torch.autocast -- fp16 maps between the blocks).  Training mode keeps the nn modules by default (BatchNorm uses batch statistics
+there); with `train_conv_impl = "hip"` on a refiner its nine blocks run on csrc/conv_stack_train.hip instead (ops.conv_block_train:
+batch-statistic forward, running-buffer update and backward in HIP) -- the fp32 class only; the autocast training class,
+GroupNorm or other norm types, non-depthwise blocks and symmetric batches beyond what the nn path does are out of scope and
+keep the modules.  Either way the refiner input is assembled with the same HIP launch as inference, which has a HIP backward
+(ops.refiner_input; csrc/refiner_input_bwd.hip).  Refiners with sample_mode "nearest" / "bicubic" train through differentiable
+torch ops instead.
 
 Training (`model.train()`, grad mode on, pyramids or parameters that require grad): forward_pyramids returns flows and
 certainties with an autograd graph, as the reference's forward does (network.py:230-281).  The scale-16 global match is
@@ -47,7 +51,8 @@ class ConvRefiner(nn.Module):
 
     forward(num_grid, x, y, flow, scale_factor=1, logits=None) -> (delta_flow, delta_certainty,
     local_corr).  Input assembly (network.py:533-558) and, in eval mode, the conv stack
-    (network.py:560-563) run in HIP; training mode keeps the nn modules.
+    (network.py:560-563) run in HIP; training mode keeps the nn modules unless `train_conv_impl`
+    is "hip" (fp32 class, csrc/conv_stack_train.hip).
     """
 
     def __init__(self, in_dim=6, hidden_dim=16, out_dim=2, dw=False, kernel_size=5, hidden_blocks=3,
@@ -95,6 +100,9 @@ class ConvRefiner(nn.Module):
         # 1x1 conv operands on the HIP path: "fp32" (exact fp32 products, the CPU reference's class) or "fp16"
         # (operands rounded to fp16, fp32 accumulation: the autocast class the reference runs these refiners in on GPU)
         self.conv_precision = "fp32"
+        # training mode: "torch" keeps the nn modules (the default); "hip" runs block1 + hidden_blocks through
+        # ops.conv_block_train where _hip_train_stack_supported() holds, the modules otherwise
+        self.train_conv_impl = "torch"
         self.fold_out_conv = True  # multiply out_conv into the last block's 1x1 conv (see folded_stack)
 
     supports_reuse_d = True  # forward(..., reuse_d=): see GFNet.forward_pyramids
@@ -165,6 +173,32 @@ class ConvRefiner(nn.Module):
                 return False
         return True
 
+    def _hip_train_stack_supported(self, d):
+        """Training mode on csrc/conv_stack_train.hip: opt-in (`train_conv_impl = "hip"`), the fp32 class, depthwise blocks whose
+        norm is an affine BatchNorm2d that tracks running statistics with a float momentum; anything else keeps the modules."""
+        if not self.training or self.train_conv_impl != "hip" or self.conv_precision != "fp32":
+            return False
+        if d.dim() != 4 or d.shape[-1] != d.shape[-2] or d.dtype != torch.float32 or not d.is_cuda:
+            return False
+        for blk in [self.block1] + list(self.hidden_blocks):
+            conv, norm, _, pw = blk
+            if not isinstance(norm, nn.BatchNorm2d) or conv.groups != conv.in_channels or conv.out_channels != conv.in_channels \
+                    or conv.kernel_size != (5, 5) or pw.in_channels != conv.out_channels:
+                return False
+            if not norm.affine or not norm.track_running_stats or not isinstance(norm.momentum, float) or norm.running_mean is None:
+                return False
+            if any(p.dtype != torch.float32 for p in blk.parameters()):
+                return False
+        return True
+
+    def _train_stack_hip(self, d):
+        """hidden_blocks(block1(d)) in training mode, network.py:560-562, one ops.conv_block_train per block"""
+        h = d
+        for conv, norm, _, pw in [self.block1] + list(self.hidden_blocks):
+            h = ops.conv_block_train(h, conv.weight, conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var,
+                                     norm.num_batches_tracked, norm.momentum, norm.eps, pw.weight, pw.bias)
+        return h
+
     def folded_stack(self):
         """Per block the packed parameters of ops.conv_block (eval-mode BatchNorm folded to
         y = x*alpha + beta in float64); cached until a parameter or running statistic changes.
@@ -234,13 +268,19 @@ class ConvRefiner(nn.Module):
         d, local_corr = self.assemble(num_grid, x, y, flow, scale_factor, reuse=prev if reusable else None)
         if reuse_d is not None:
             reuse_d[0] = d if reusable else None
-        if self._hip_stack_supported():
-            out = self.conv_stack(d)
-        else:
-            with torch.autocast("cuda", enabled=bool(self.amp), dtype=self.amp_dtype):
-                h = self.hidden_blocks(self.block1(d))
-            out = self.out_conv(h.float())
+        out = self.apply_stack(d)
         return out[:, :2], out[:, 2:3], local_corr
+
+    def apply_stack(self, d):
+        """out_conv(hidden_blocks(block1(d))), network.py:560-563, on whichever path this refiner's mode and settings select"""
+        if self._hip_stack_supported():
+            return self.conv_stack(d)
+        if self._hip_train_stack_supported(d):
+            # out_conv is not folded here: its parameters take their own gradients, and a 3-channel 1x1 needs no kernel
+            return self.out_conv(self._train_stack_hip(d).float())
+        with torch.autocast("cuda", enabled=bool(self.amp), dtype=self.amp_dtype):
+            h = self.hidden_blocks(self.block1(d))
+        return self.out_conv(h.float())
 
 
 def _refiner_for(feat_dim, disp_dim, radius):

@@ -732,3 +732,127 @@ def pointwise_conv(t, w, bias, out=None):
     check(_timed("pw_m%d_k%d_g%d" % (M, K, G), lambda: _L().gfn_pointwise_conv_fwd(
         ptr(w), ptr(bias), ptr(t), ptr(out), B, M, K, G * G2, stream_ptr(dev))), "gfn_pointwise_conv_fwd")
     return out
+
+
+def _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b):
+    """Shape and dtype checks of conv_block_train; returns (B, C, M, G)."""
+    what = "conv_block_train"
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise ValueError(f"{what}: x must be (B,C,G,G) on a square grid, got {tuple(x.shape)}")
+    B, C, G, _ = x.shape
+    M = pw_w.shape[0]
+    params = {"dw_w": (dw_w, C * 25), "bn_weight": (bn_weight, C), "bn_bias": (bn_bias, C), "running_mean": (running_mean, C),
+              "running_var": (running_var, C), "pw_w": (pw_w, M * C), "pw_b": (pw_b, M)}
+    if dw_b is not None:
+        params["dw_b"] = (dw_b, C)
+    for name, (t, n) in params.items():
+        if t is None:
+            raise ValueError(f"{what}: {name} is missing")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be float32 (the fp32 training class), got {t.dtype}")
+        if t.numel() != n:
+            raise ValueError(f"{what}: {name} has {t.numel()} elements, C={C} and M={M} need {n}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{what}: x must be float32, got {x.dtype}")
+    if B * G * G < 2:
+        raise ValueError(f"{what}: batch statistics need more than one value per channel")
+    return B, C, M, G
+
+
+def conv_block_train_fwd(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, momentum, eps, pw_w, pw_b):
+    """The forward launches of conv_block_train: returns (y, u, mean, invstd) and updates running_mean / running_var in place
+    (csrc/conv_stack_train.hip).  Tensors as the kernels read them: contiguous float32."""
+    dev = require_gpu(x, dw_w, pw_w, running_mean, running_var)
+    B, C, M, G = _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b)
+    if not (running_mean.is_contiguous() and running_var.is_contiguous()):
+        raise ValueError("conv_block_train: the running statistics are updated in place and must be contiguous")
+    x, dw_w, pw_w = x.contiguous(), dw_w.contiguous(), pw_w.contiguous()
+    u, y = torch.empty_like(x), torch.empty((B, M, G, G), device=dev, dtype=torch.float32)
+    mean, invstd = torch.empty(C, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
+    nws = int(_L().gfn_conv_block_train_ws_bytes(B, C, M, G, 0))
+    ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
+    check(_timed("conv_block_train_fwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_fwd(
+        ptr(x), ptr(dw_w), ptr(dw_b.contiguous()) if dw_b is not None else None, ptr(bn_weight.contiguous()), ptr(bn_bias.contiguous()),
+        ptr(running_mean), ptr(running_var), ptr(pw_w), ptr(pw_b.contiguous()), ptr(u), ptr(mean), ptr(invstd), ptr(y), B, C, M, G,
+        float(momentum), float(eps), ptr(ws), nws, stream_ptr(dev))), "gfn_conv_block_train_fwd")
+    return y, u, mean, invstd
+
+
+def conv_block_train_bwd(gy, x, u, mean, invstd, dw_w, bn_weight, bn_bias, pw_w, need=(True,) * 7, has_dw_bias=True):
+    """Gradients of conv_block_train's y with respect to (x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b) given gy = dL/dy and what
+    the forward saved; None where `need` says so.  Weight and bias of one layer come from the same launches (the C ABI's need
+    mask has one bit per pair); every result is reproducible bit for bit."""
+    dev = require_gpu(gy, x, u)
+    gy = f32c(gy)
+    B, C, G, _ = x.shape
+    M = pw_w.shape[0]
+    if tuple(gy.shape) != (B, M, G, G):
+        raise ValueError(f"conv_block_train_bwd: grad_y must be {(B, M, G, G)}, got {tuple(gy.shape)}")
+    n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb = need
+    n_dwb = n_dwb and has_dw_bias
+    mask = (_lib.CBT_NEED_X if n_x else 0) | (_lib.CBT_NEED_DW if (n_dww or n_dwb) else 0) | \
+        (_lib.CBT_NEED_BN if (n_g or n_b) else 0) | (_lib.CBT_NEED_PW if (n_pww or n_pwb) else 0)
+
+    def out(bit, *shape):
+        return torch.empty(shape, device=dev, dtype=torch.float32) if mask & bit else None
+
+    gx = out(_lib.CBT_NEED_X, B, C, G, G)
+    d_dww, d_dwb = out(_lib.CBT_NEED_DW, C, 25), (out(_lib.CBT_NEED_DW, C) if has_dw_bias else None)
+    d_g, d_b = out(_lib.CBT_NEED_BN, C), out(_lib.CBT_NEED_BN, C)
+    d_pww, d_pwb = out(_lib.CBT_NEED_PW, M, C), out(_lib.CBT_NEED_PW, M)
+    if mask:
+        nws = int(_L().gfn_conv_block_train_ws_bytes(B, C, M, G, 1))
+        ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
+        check(_timed("conv_block_train_bwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_bwd(
+            ptr(gy), ptr(x), ptr(u), ptr(mean), ptr(invstd), ptr(dw_w), ptr(bn_weight), ptr(bn_bias), ptr(pw_w), ptr(gx), ptr(d_dww),
+            ptr(d_dwb), ptr(d_g), ptr(d_b), ptr(d_pww), ptr(d_pwb), B, C, M, G, mask, ptr(ws), nws, stream_ptr(dev))),
+            "gfn_conv_block_train_bwd")
+    grads = (gx, d_dww, d_dwb, d_g, d_b, d_pww, d_pwb)
+    return tuple(g if want else None for g, want in zip(grads, (n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb)))
+
+
+class _ConvBlockTrainFn(torch.autograd.Function):
+    """conv_block_train: saves x, u, mean, invstd and the parameters the backward reads -- not t = relu(bn(u)), which both
+    directions recompute from u."""
+
+    @staticmethod
+    def forward(ctx, x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b, running_mean, running_var, momentum, eps):
+        C, M = x.shape[1], pw_w.shape[0]
+        xk, dww, pww = x.contiguous(), dw_w.reshape(C, 25).contiguous(), pw_w.reshape(M, C).contiguous()
+        bnw, bnb = bn_weight.contiguous(), bn_bias.contiguous()
+        y, u, mean, invstd = conv_block_train_fwd(xk, dww, dw_b, bnw, bnb, running_mean, running_var, momentum, eps, pww, pw_b)
+        ctx.save_for_backward(xk, u, mean, invstd, dww, bnw, bnb, pww)
+        ctx.meta = (dw_w.shape, pw_w.shape, dw_b is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xk, u, mean, invstd, dww, bnw, bnb, pww = ctx.saved_tensors
+        dw_shape, pw_shape, has_bias = ctx.meta
+        g = list(conv_block_train_bwd(gy, xk, u, mean, invstd, dww, bnw, bnb, pww, need=ctx.needs_input_grad[:7], has_dw_bias=has_bias))
+        if g[1] is not None:
+            g[1] = g[1].reshape(dw_shape)
+        if g[5] is not None:
+            g[5] = g[5].reshape(pw_shape)
+        return tuple(g) + (None,) * 4
+
+
+def conv_block_train(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, pw_w, pw_b):
+    """Conv2d(C,C,5,pad 2,groups=C[,bias]) -> BatchNorm2d in training mode -> ReLU -> Conv2d(C,M,1) with a backward, all in
+    csrc/conv_stack_train.hip: one block of ConvRefiner under model.train() (model/network.py:471-487, 560-563), the fp32 class.
+    x (B,C,G,G); dw_w (C,1,5,5) or (C,25); dw_b (C) or None (use_bias_block_1=False); bn_weight, bn_bias (C); pw_w (M,C[,1,1]);
+    pw_b (M); everything float32.  The batch's statistics normalise; running_mean / running_var (C) are updated in place with
+    `momentum` (a float) as torch does (unbiased variance) and num_batches_tracked, when given, is incremented -- also without grad
+    mode (train() under no_grad).  The buffers' version counters are bumped, so whatever caches on them (ConvRefiner.folded_stack)
+    sees the change.  Gradients flow to x and the seven parameters; identical calls give identical bits."""
+    if momentum is None:
+        raise ValueError("conv_block_train: momentum must be a float (cumulative averaging, momentum=None, is not supported)")
+    require_gpu(x, dw_w, pw_w, running_mean, running_var)
+    _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b)
+    y = _ConvBlockTrainFn.apply(x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b, running_mean, running_var, float(momentum), float(eps))
+    # the kernels wrote the buffers through raw pointers: tell autograd's version counters
+    torch.autograd.graph.increment_version(running_mean)
+    torch.autograd.graph.increment_version(running_var)
+    if num_batches_tracked is not None:
+        num_batches_tracked.add_(1)
+    return y

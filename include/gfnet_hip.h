@@ -430,6 +430,37 @@ int gfn_pointwise_conv_fwd(const float *w, const float *bias, const float *t, fl
 int gfn_conv_block_half_fwd(const void *x, int x_dtype, const float *packed, void *y, int y_dtype, int B, int C, int M, int G,
                             gfn_stream_t stream);
 
+/* One conv block in TRAINING mode (model.train(); ConvRefiner.create_block / forward, model/network.py:471-487, 560-563, which
+ * torch autograd differentiates in the reference): Conv2d(C,C,5,pad 2,groups=C[,bias]) -> BatchNorm2d on the batch's own
+ * statistics -> ReLU -> Conv2d(C,M,1), fp32 throughout on contiguous maps; csrc/conv_stack_train.hip.  Every reduction is
+ * two-stage in a fixed order (no floating-point atomics): identical calls give identical bits.
+ *
+ * gfn_conv_block_train_fwd: x (B,C,G,G) -> u = dw5x5(x) + dw_b (B,C,G,G; kept for the backward), mean and invstd (C) of u over
+ *   the batch (biased variance; per-tile shifted sums merged with Chan's formula in double), y = pw(relu(bn(u))) (B,M,G,G) with
+ *   the 1x1 products on the exact-fp32 matrix core.  dw_w (C,25), dw_b (C) or NULL, bn_w / bn_b (C) BatchNorm's weight and bias,
+ *   pw_w (M,C), pw_b (M).  running_mean / running_var (C) are updated in place as torch does: (1 - momentum) * old + momentum *
+ *   batch value, the variance unbiased (n / (n - 1)); B*G*G >= 2.  x, u and y must be three different maps.
+ * gfn_conv_block_train_bwd: gy = dL/dy (B,M,G,G), and x, u, mean, invstd, dw_w, bn_w, bn_b, pw_w as the forward had them ->
+ *   gx (B,C,G,G), d_dw_w (C,25), d_dw_b (C), d_bn_w, d_bn_b (C), d_pw_w (M,C), d_pw_b (M), all OVERWRITTEN.  `need` is a sum of
+ *   GFN_CBT_NEED_*: only what it names is computed and only those pointers are touched (d_dw_b may be NULL with GFN_CBT_NEED_DW:
+ *   a block without depthwise bias); need = 0 launches nothing.  The ReLU mask is recomputed from u with the forward's expression.
+ * ws: gfn_conv_block_train_ws_bytes(B, C, M, G, backward = 0 / 1) bytes of 16-byte aligned device memory, contents undefined
+ *   before and after (the backward keeps its gz map there).  Limits: B <= 65535, C*G*G and M*G*G <= 2^29 - 1. */
+#define GFN_CBT_NEED_X 1  /* gx */
+#define GFN_CBT_NEED_DW 2 /* d_dw_w, d_dw_b */
+#define GFN_CBT_NEED_BN 4 /* d_bn_w, d_bn_b */
+#define GFN_CBT_NEED_PW 8 /* d_pw_w, d_pw_b */
+#define GFN_CBT_NEED_ALL 15
+int64_t gfn_conv_block_train_ws_bytes(int B, int C, int M, int G, int backward);
+int gfn_conv_block_train_fwd(const float *x, const float *dw_w, const float *dw_b, const float *bn_w, const float *bn_b,
+                             float *running_mean, float *running_var, const float *pw_w, const float *pw_b, float *u, float *mean,
+                             float *invstd, float *y, int B, int C, int M, int G, double momentum, double eps, void *ws,
+                             int64_t ws_bytes, gfn_stream_t stream);
+int gfn_conv_block_train_bwd(const float *gy, const float *x, const float *u, const float *mean, const float *invstd,
+                             const float *dw_w, const float *bn_w, const float *bn_b, const float *pw_w, float *gx, float *d_dw_w,
+                             float *d_dw_b, float *d_bn_w, float *d_bn_b, float *d_pw_w, float *d_pw_b, int B, int C, int M, int G,
+                             int need, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
