@@ -64,6 +64,11 @@ _SIGNATURES = {
     "gfn_refiner_input_bwd": [c_vp, c_i64, c_vp, c_int] + [c_vp] * 8 + [c_int] * 7 + [c_float, c_vp, c_i64, c_vp],
     "gfn_conv_block_train_fwd": [c_vp] * 13 + [c_int] * 4 + [c_double, c_double, c_vp, c_i64, c_vp],
     "gfn_conv_block_train_bwd": [c_vp] * 16 + [c_int] * 5 + [c_vp, c_i64, c_vp],
+    "gfn_robust_loss_fwd": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_double, c_vp, c_vp] + [c_int] * 3 + [c_double] * 7
+                           + [c_vp, c_i64, c_vp],
+    "gfn_robust_loss_bwd": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_double, c_vp, c_vp, c_vp, c_vp] + [c_int] * 4
+                           + [c_double] * 6 + [c_vp],
+    "gfn_gt_warp_homography_fwd": [c_vp] * 5 + [c_int] * 3 + [c_double, c_double, c_int, c_vp],
 }
 # entry points that return a size instead of a status
 _SIZE_FUNCS = {
@@ -77,7 +82,10 @@ _SIZE_FUNCS = {
     "gfn_homography_scratch_bytes": [c_int, c_int],
     "gfn_conv_block_packed_floats": [c_int, c_int],
     "gfn_conv_block_train_ws_bytes": [c_int] * 5,
+    "gfn_robust_loss_ws_bytes": [c_int] * 4,
 }
+# gfn_robust_loss_fwd's `stats` vector (GFN_RL_STAT_* in include/gfnet_hip.h) and the most iterations a scale may have
+RL_STAT_LOSS, RL_STAT_CE, RL_STAT_REG, RL_STAT_COUNT, RL_STAT_PCK, RL_STATS, RL_MAX_ITR = 0, 1, 2, 3, 4, 8, 8
 # `need` bits of gfn_conv_block_train_bwd (GFN_CBT_NEED_* in include/gfnet_hip.h)
 CBT_NEED_X, CBT_NEED_DW, CBT_NEED_BN, CBT_NEED_PW = 1, 2, 4, 8
 
@@ -176,11 +184,13 @@ def release_retired():
     _retired.clear()
 
 
-def scratch(device, nbytes):
+def scratch(device, nbytes, pool=""):
     """A per-(device, stream), grow-only int32 scratch buffer.  Reuse is stream-ordered: any number of models may share it on
     one stream (their launches cannot overlap), work on different streams gets different buffers; one host thread per
-    stream.  Dropped as a whole after any failed call (check())."""
-    key = (device.type, device.index, current_stream_handle(device) if device.type == "cuda" else 0)
+    stream.  Dropped as a whole after any failed call (check()).  `pool` names a buffer of its own: the default one belongs to the
+    local correlation, whose counters must be zero on entry, so an op that leaves other contents behind (the loss's partial sums)
+    takes another."""
+    key = (device.type, device.index, current_stream_handle(device) if device.type == "cuda" else 0, pool)
     buf = _scratch.get(key)
     if buf is None or buf.numel() * 4 < nbytes:
         # a buffer that is outgrown is RETIRED, not freed: a hipGraph captured on this stream keeps launching kernels with its

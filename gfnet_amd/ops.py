@@ -856,3 +856,160 @@ def conv_block_train(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_va
     if num_batches_tracked is not None:
         num_batches_tracked.add_(1)
     return y
+
+
+# ---- the training loss (losses/robust_loss.py) -------------------------------------------------------------------------------------
+def _ptr_array(tensors):
+    """A host array of RL_MAX_ITR device pointers (NULL where `tensors` has None or ends)."""
+    arr = (c_vp * _lib.RL_MAX_ITR)()
+    for k, t in enumerate(tensors):
+        arr[k] = t.data_ptr() if t is not None else None
+    return arr
+
+
+def _robust_loss_scale_args(what, flows, certs, H, prev_epe, im_A_coords):
+    """Shape and dtype checks of one scale; returns (B, h, w, ph, pw).  Tensors as the kernels read them: contiguous float32."""
+    n = len(flows)
+    if not 1 <= n <= _lib.RL_MAX_ITR or len(certs) != n:
+        raise ValueError(f"{what}: a scale has 1..{_lib.RL_MAX_ITR} iterations, each with a flow and a certainty; got {n} flows, {len(certs)} certainties")
+    if flows[0].dim() != 4 or flows[0].shape[1] != 2:
+        raise ValueError(f"{what}: a flow must be (B,2,h,w), got {tuple(flows[0].shape)}")
+    B, _, h, w = flows[0].shape
+    maps = [("flow", f, (B, 2, h, w)) for f in flows] + [("certainty", c, (B, 1, h, w)) for c in certs] + [("H", H, (B, 3, 3))]
+    if prev_epe is not None:
+        if prev_epe.dim() != 3 or prev_epe.shape[0] != B:
+            raise ValueError(f"{what}: prev_epe must be (B,ph,pw) with B = {B}, got {tuple(prev_epe.shape)}")
+        maps.append(("prev_epe", prev_epe, tuple(prev_epe.shape)))
+    if im_A_coords is not None:
+        maps.append(("im_A_coords", im_A_coords, (B, 2, h, w)))
+    for name, t, shape in maps:
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{what}: {name} must be {shape}, got {tuple(t.shape)} (flows and certainties of one scale share a grid)")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous float32, got {t.dtype}")
+    ph, pw = (prev_epe.shape[1], prev_epe.shape[2]) if prev_epe is not None else (0, 0)
+    return B, h, w, ph, pw
+
+
+def robust_loss_scale_fwd(flows, certs, H, ext_a, ext_b, a, cs, ce_weight, iteration_base, pck_thresh, prev_epe=None, prev_thresh=0.0,
+                          im_A_coords=None, want_epe=False, stats=None):
+    """One scale of RobustLosses (losses/robust_loss.py:65-90 and the body of :97-127) in csrc/robust_loss.hip: flows / certs are
+    the scale's iterations in order, (B,2,h,w) and (B,1,h,w); H (B,3,3) is H_s2t; ext_a / ext_b are im_A.shape[2] - 1 and
+    im_B.shape[2] - 1.  Returns (stats, epe_last): stats the _lib.RL_STATS floats of include/gfnet_hip.h (loss, ce, reg, count,
+    pck_05, ...), written into `stats` when given; epe_last (B,h,w) when want_epe, else None."""
+    dev = require_gpu(*flows, *certs, H, prev_epe, im_A_coords, stats)
+    B, h, w, ph, pw = _robust_loss_scale_args("robust_loss_scale_fwd", flows, certs, H, prev_epe, im_A_coords)
+    if stats is None:
+        stats = torch.empty(_lib.RL_STATS, device=dev, dtype=torch.float32)
+    epe = torch.empty((B, h, w), device=dev, dtype=torch.float32) if want_epe else None
+    nws = int(_L().gfn_robust_loss_ws_bytes(B, h, w, len(flows)))
+    ws = _lib.scratch(dev, nws, pool="robust_loss")  # (not the local correlation's: its counters must stay zero)
+    check(_timed("robust_loss_fwd_%dx%d" % (h, w), lambda: _L().gfn_robust_loss_fwd(
+        _ptr_array(flows), _ptr_array(certs), len(flows), ptr(H), ptr(im_A_coords), ptr(prev_epe), ph, pw, float(prev_thresh), ptr(epe),
+        ptr(stats), B, h, w, float(ext_a), float(ext_b), float(a), float(cs), float(ce_weight), float(iteration_base), float(pck_thresh),
+        ptr(ws), nws, stream_ptr(dev))), "gfn_robust_loss_fwd")
+    return stats, epe
+
+
+def robust_loss_scale_bwd(grad_out, stats, flows, certs, H, ext_a, ext_b, a, cs, ce_weight, iteration_base, prev_epe=None,
+                          prev_thresh=0.0, im_A_coords=None, need_flow=None, need_cert=None):
+    """Gradients of robust_loss_scale_fwd's loss with respect to the flows and certainties, times grad_out (a 0-dim float32 DEVICE
+    tensor: no host round trip); `stats` as the forward left it.  need_flow / need_cert: one bool per iteration (default: all).
+    Returns (g_flows, g_certs), lists with None where not asked for.  One launch; none when nothing is asked for."""
+    n = len(flows)
+    need_flow = [True] * n if need_flow is None else list(need_flow)
+    need_cert = [True] * n if need_cert is None else list(need_cert)
+    dev = require_gpu(grad_out, stats, *flows, *certs, H, prev_epe, im_A_coords)
+    B, h, w, ph, pw = _robust_loss_scale_args("robust_loss_scale_bwd", flows, certs, H, prev_epe, im_A_coords)
+    if grad_out.numel() != 1 or grad_out.dtype != torch.float32:
+        raise ValueError(f"robust_loss_scale_bwd: grad_out must be one float32 value, got {tuple(grad_out.shape)} {grad_out.dtype}")
+    g_flows = [torch.empty_like(f) if nf else None for f, nf in zip(flows, need_flow)]
+    g_certs = [torch.empty_like(c) if nc else None for c, nc in zip(certs, need_cert)]
+    mask = sum(1 << k for k in range(n) if need_flow[k]) | sum(1 << (_lib.RL_MAX_ITR + k) for k in range(n) if need_cert[k])
+    if mask:
+        check(_timed("robust_loss_bwd_%dx%d" % (h, w), lambda: _L().gfn_robust_loss_bwd(
+            _ptr_array(flows), _ptr_array(certs), n, ptr(H), ptr(im_A_coords), ptr(prev_epe), ph, pw, float(prev_thresh), ptr(stats),
+            ptr(grad_out), _ptr_array(g_flows), _ptr_array(g_certs), mask, B, h, w, float(ext_a), float(ext_b), float(a), float(cs),
+            float(ce_weight), float(iteration_base), stream_ptr(dev))), "gfn_robust_loss_bwd")
+    return g_flows, g_certs
+
+
+def gt_warp_homography(H, h, w, ext_a, ext_b, im_A_coords=None, normalized=True, return_x1_n=False):
+    """get_gt_warp_homography (losses/robust_loss.py:9-42) for an h x w grid: H (B,3,3) -> (x2_n or x2 (B,h,w,2), prob (B,h,w),
+    x1_n (B,h,w,2) or None).  ext_a / ext_b: im_A.shape[2] - 1 and im_B.shape[2] - 1."""
+    dev = require_gpu(H, im_A_coords)
+    if H.dim() != 3 or tuple(H.shape[1:]) != (3, 3):
+        raise ValueError(f"gt_warp_homography: H must be (B,3,3), got {tuple(H.shape)}")
+    B = H.shape[0]
+    H = f32c(H)
+    if im_A_coords is not None:
+        if tuple(im_A_coords.shape) != (B, 2, h, w):
+            raise ValueError(f"gt_warp_homography: im_A_coords must be {(B, 2, h, w)}, got {tuple(im_A_coords.shape)}")
+        im_A_coords = f32c(im_A_coords)
+    out = torch.empty((B, h, w, 2), device=dev, dtype=torch.float32)
+    prob = torch.empty((B, h, w), device=dev, dtype=torch.float32)
+    x1n = torch.empty((B, h, w, 2), device=dev, dtype=torch.float32) if return_x1_n else None
+    check(_L().gfn_gt_warp_homography_fwd(ptr(H), ptr(im_A_coords), ptr(out), ptr(prob), ptr(x1n), B, h, w, float(ext_a), float(ext_b),
+                                          1 if normalized else 0, stream_ptr(dev)), "gfn_gt_warp_homography_fwd")
+    return out, prob, x1n
+
+
+class _RobustLossFn(torch.autograd.Function):
+    """The whole loss: forward runs the scales in order (each hands its last end-point error to the next), backward issues one launch
+    per scale.  `scales` is a tuple of per-scale dicts (n, a, cs, pck, narrowed, prev_thresh), `common` = (ext_a, ext_b, ce_weight,
+    iteration_base); `maps` the flat list per scale of its flows, then its certainties.  Saved: the maps, H, each scale's prev_epe,
+    the statistics."""
+
+    @staticmethod
+    def forward(ctx, scales, common, H, stats, *maps):
+        ext_a, ext_b, ce_weight, iteration_base = common
+        maps = [m.detach() for m in maps]
+        prev, prevs, at = None, [], 0
+        for i, sc in enumerate(scales):
+            n = sc["n"]
+            flows, certs = maps[at:at + n], maps[at + n:at + 2 * n]
+            at += 2 * n
+            pe = prev if sc["narrowed"] else None
+            prevs.append(pe)
+            want = i + 1 < len(scales) and scales[i + 1]["narrowed"]
+            _, prev = robust_loss_scale_fwd(flows, certs, H, ext_a, ext_b, sc["a"], sc["cs"], ce_weight, iteration_base, sc["pck"], prev_epe=pe,
+                                            prev_thresh=sc["prev_thresh"], want_epe=want, stats=stats[i])
+        ctx.save_for_backward(H, stats, *maps)
+        ctx.prevs, ctx.scales, ctx.common = prevs, scales, common
+        return stats[:, _lib.RL_STAT_LOSS].sum()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        H, stats, *maps = ctx.saved_tensors
+        ext_a, ext_b, ce_weight, iteration_base = ctx.common
+        grad_out = f32c(grad_out)
+        need = ctx.needs_input_grad[4:]
+        grads, at = [], 0
+        for i, sc in enumerate(ctx.scales):
+            n = sc["n"]
+            gf, gc = robust_loss_scale_bwd(grad_out, stats[i], maps[at:at + n], maps[at + n:at + 2 * n], H, ext_a, ext_b, sc["a"], sc["cs"],
+                                           ce_weight, iteration_base, prev_epe=ctx.prevs[i], prev_thresh=sc["prev_thresh"],
+                                           need_flow=need[at:at + n], need_cert=need[at + n:at + 2 * n])
+            grads += gf + gc
+            at += 2 * n
+        return (None, None, None, None) + tuple(grads)
+
+
+def robust_loss(scales, H, ext_a, ext_b, ce_weight, iteration_base, maps):
+    """The sum over `scales` of ce_weight * ce_s + reg_s (losses/robust_loss.py:92-128), differentiable in every flow and certainty.
+    scales: per scale a dict with n (iterations), a (alpha), cs (c * scale), pck (the pck_05 threshold), narrowed (multiply the mask
+    by the previous scale's end-point error below prev_thresh) and prev_thresh; maps: per scale its n flows (B,2,h,w), then its n
+    certainties (B,1,h,w).  Returns (loss, stats): a 0-dim tensor and the (len(scales), RL_STATS) statistics, one row per scale
+    (ce, reg, count, pck_05 ...: include/gfnet_hip.h).  No host synchronisation; valid under stream capture."""
+    dev = require_gpu(H, *maps)
+    if sum(2 * sc["n"] for sc in scales) != len(maps):
+        raise ValueError("robust_loss: every scale needs n flows followed by n certainties")
+    if scales and scales[0]["narrowed"]:
+        raise ValueError("robust_loss: the first scale cannot be narrowed, no previous end-point error exists")
+    if not scales:
+        raise ValueError("robust_loss: no scales")
+    stats = torch.empty((len(scales), _lib.RL_STATS), device=dev, dtype=torch.float32)
+    maps = [f32c(m) for m in maps]
+    loss = _RobustLossFn.apply(tuple(scales), (float(ext_a), float(ext_b), float(ce_weight), float(iteration_base)), f32c(H).detach(), stats,
+                               *maps)
+    return loss, stats

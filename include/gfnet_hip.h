@@ -461,6 +461,54 @@ int gfn_conv_block_train_bwd(const float *gy, const float *x, const float *u, co
                              float *d_dw_b, float *d_bn_w, float *d_bn_b, float *d_pw_w, float *d_pw_b, int B, int C, int M, int G,
                              int need, void *ws, int64_t ws_bytes, gfn_stream_t stream);
 
+/* The training objective on a homography ground truth (losses/robust_loss.py: get_gt_warp_homography :9-42,
+ * RobustLosses.regression_loss :65-90 and the per-scale body of RobustLosses.forward :92-128); csrc/robust_loss.hip.  One call
+ * is one scale with all of its iterations; fp32 contiguous maps on an h x w grid, batch B.
+ *
+ * The ground-truth warp of a cell (never stored by the loss): its centre x1_n = linspace(-1 + 1/n, 1 - 1/n, n) per axis (x from
+ *   w, y from h), or im_A_coords (B,2,h,w) when given; pixels x1 = (x1_n + 1) * ext_a * 0.5 with ext_a = im_A.shape[2] - 1 on BOTH
+ *   axes (:25); x2 = H (B,3,3) applied to (x1, 1), divided by z (by 1 where |z| <= 1e-8; kornia's transform_points :26);
+ *   x2_n = x2 / ext_b * 2 - 1 with ext_b = im_B.shape[2] - 1 > 0 (:28-29); prob = 1 where both coordinates of x2_n lie strictly
+ *   inside (-1, 1), else 0 (:31-33).  With prev_epe (B,ph,pw), the previous scale's last end-point error, prob is further
+ *   multiplied by [prev_epe at the nearest-exact source cell min(floor((i + 0.5) * in / out), in - 1) < prev_thresh] (:117-120).
+ * gfn_gt_warp_homography_fwd: out (B,h,w,2) = x2_n (normalized != 0) or x2, prob (B,h,w), x1_n (B,h,w,2) unless NULL.
+ * gfn_robust_loss_fwd: flows / certs are HOST arrays of n_itr (1..8) device pointers, flow_k (B,2,h,w) and cert_k (B,1,h,w) of
+ *   iteration k = 1..n_itr in order.  With w_k = iteration_base ** (n_itr - k), epe_k = ||flow_k - x2_n||:
+ *     ce  = sum_k w_k * mean over all B*h*w cells of binary_cross_entropy_with_logits(cert_k, prob)                  (:77-78)
+ *     reg = (sum over cells with prob = 1 of sum_k w_k * cs^a * ((epe_k / cs)^2 + 1)^(a/2)) / count, 0 when count = 0  (:81-84)
+ *   stats (8 floats, GFN_RL_STAT_*): loss = ce_weight * ce + reg, ce, reg, count, pck = the fraction of masked cells whose last
+ *   iteration has epe < pck_thresh (0 when count = 0; :73-74), the number of cells, the unnormalised regression sum, 0.
+ *   epe_last (B,h,w), unless NULL, receives the last iteration's epe of every cell: the next scale's prev_epe (:115, :127).
+ *   Two launches: the streaming pass leaves one partial per block and quantity in ws (reduced per wave, then per block, in a fixed
+ *   order), a single workgroup adds them in a fixed order in double.  No floating-point atomics: identical calls, identical bits.
+ * gfn_robust_loss_bwd: the same inputs, stats as the forward left them and grad_out, a DEVICE scalar (dL/dloss) ->
+ *     g_flows[k] (B,2,h,w) = grad_out * w_k / count * a * cs^(a-2) * ((epe_k / cs)^2 + 1)^(a/2 - 1) * (flow_k - x2_n), 0 off the mask
+ *     g_certs[k] (B,1,h,w) = grad_out * ce_weight * w_k * (sigmoid(cert_k) - prob) / (B*h*w)
+ *   OVERWRITTEN, for the iterations `need` names: bit k-1 asks for g_flows[k-1], bit 8+k-1 for g_certs[k-1]; other entries of the
+ *   two host arrays (or the arrays themselves) may be NULL.  need = 0 launches nothing.  H, prev_epe and the mask carry no gradient.
+ * Maps are read and written with 16- or 8-byte vector accesses when w is a multiple of 4 or 2 and every map pointer is so aligned.
+ * ws: gfn_robust_loss_ws_bytes(B, h, w, n_itr) bytes, 16-byte aligned, contents undefined before and after.
+ * Limits: h, w, ph, pw <= 32768, B*h*w <= 2^30, cs > 0; B = 0 is valid and launches nothing. */
+#define GFN_RL_STAT_LOSS 0
+#define GFN_RL_STAT_CE 1
+#define GFN_RL_STAT_REG 2
+#define GFN_RL_STAT_COUNT 3
+#define GFN_RL_STAT_PCK 4
+#define GFN_RL_STAT_CELLS 5
+#define GFN_RL_STAT_RHO_SUM 6
+#define GFN_RL_STATS 8
+int64_t gfn_robust_loss_ws_bytes(int B, int h, int w, int n_itr);
+int gfn_robust_loss_fwd(const float *const *flows, const float *const *certs, int n_itr, const float *H, const float *im_A_coords,
+                        const float *prev_epe, int ph, int pw, double prev_thresh, float *epe_last, float *stats, int B, int h, int w,
+                        double ext_a, double ext_b, double a, double cs, double ce_weight, double iteration_base, double pck_thresh,
+                        void *ws, int64_t ws_bytes, gfn_stream_t stream);
+int gfn_robust_loss_bwd(const float *const *flows, const float *const *certs, int n_itr, const float *H, const float *im_A_coords,
+                        const float *prev_epe, int ph, int pw, double prev_thresh, const float *stats, const float *grad_out,
+                        float *const *g_flows, float *const *g_certs, int need, int B, int h, int w, double ext_a, double ext_b,
+                        double a, double cs, double ce_weight, double iteration_base, gfn_stream_t stream);
+int gfn_gt_warp_homography_fwd(const float *H, const float *im_A_coords, float *out, float *prob, float *x1_n, int B, int h, int w,
+                               double ext_a, double ext_b, int normalized, gfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
