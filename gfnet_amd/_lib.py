@@ -69,6 +69,7 @@ _SIGNATURES = {
     "gfn_robust_loss_bwd": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_double, c_vp, c_vp, c_vp, c_vp] + [c_int] * 4
                            + [c_double] * 6 + [c_vp],
     "gfn_gt_warp_homography_fwd": [c_vp] * 5 + [c_int] * 3 + [c_double, c_double, c_int, c_vp],
+    "gfn_train_step": [c_vp, c_int, c_vp, c_int, c_vp, c_double, c_double, c_double, c_int, c_int, c_vp, c_vp, c_i64, c_vp],
 }
 # entry points that return a size instead of a status
 _SIZE_FUNCS = {
@@ -83,9 +84,13 @@ _SIZE_FUNCS = {
     "gfn_conv_block_packed_floats": [c_int, c_int],
     "gfn_conv_block_train_ws_bytes": [c_int] * 5,
     "gfn_robust_loss_ws_bytes": [c_int] * 4,
+    "gfn_train_step_ws_bytes": [c_int, c_int],
 }
 # gfn_robust_loss_fwd's `stats` vector (GFN_RL_STAT_* in include/gfnet_hip.h) and the most iterations a scale may have
 RL_STAT_LOSS, RL_STAT_CE, RL_STAT_REG, RL_STAT_COUNT, RL_STAT_PCK, RL_STATS, RL_MAX_ITR = 0, 1, 2, 3, 4, 8, 8
+# gfn_train_step (GFN_TS_* in include/gfnet_hip.h): elements per chunk, bytes of the device state, the head of `stats_out`
+TS_CHUNK, TS_STATE_BYTES, TS_STATS = 4096, 32, 8
+TS_STAT_GRAD_NORM, TS_STAT_PARAM_NORM, TS_STAT_GRAD_SCALE, TS_STAT_FOUND_INF, TS_STAT_CLIP_COEF = 0, 1, 2, 3, 4
 # `need` bits of gfn_conv_block_train_bwd (GFN_CBT_NEED_* in include/gfnet_hip.h)
 CBT_NEED_X, CBT_NEED_DW, CBT_NEED_BN, CBT_NEED_PW = 1, 2, 4, 8
 

@@ -509,6 +509,58 @@ int gfn_robust_loss_bwd(const float *const *flows, const float *const *certs, in
 int gfn_gt_warp_homography_fwd(const float *H, const float *im_A_coords, float *out, float *prob, float *x1_n, int B, int h, int w,
                                double ext_a, double ext_b, int normalized, gfn_stream_t stream);
 
+/* What a training step does after backward() (trainer/train.py:29-43: grad_scaler.unscale_, log_param_statistics :13-27,
+ * clip_grad_norm_, grad_scaler.step(optimizer) with torch.optim.AdamW, grad_scaler.update(), the floor of the scale at :40-41, and the
+ * optimizer.zero_grad() of the next step :30); csrc/train_step.hip.  One call is one step over every parameter tensor: three launches
+ * (ts_norm_kernel, ts_finish_kernel, ts_update_kernel), no host synchronisation, no atomics -- identical calls, identical bits.
+ *
+ * tensor_table: DEVICE array of n_tensors gfn_ts_tensor records, one per parameter that has a gradient.  p, g, exp_avg, exp_avg_sq are
+ *   fp32, contiguous, numel elements each; lr .. eps are the parameter group's AdamW hyperparameters (amsgrad = maximize = False);
+ *   first_chunk / n_chunks name the tensor's run of chunk records; vec16 != 0 allows 16-byte accesses and may be set only when all
+ *   four pointers are 16-byte aligned (otherwise every access is a single float: gradients that are views at odd element offsets).
+ * chunk_table: DEVICE array of n_chunks gfn_ts_chunk records, one per workgroup: elements first .. first + count - 1 of tensor
+ *   `tensor`, 1 <= count <= GFN_TS_CHUNK, first a multiple of GFN_TS_CHUNK; no chunk spans two tensors, the chunks of a tensor are
+ *   consecutive and ascending and cover it exactly once; a tensor of no elements has no chunk.
+ * state: GFN_TS_STATE_BYTES on the DEVICE, read and written: float scale, int32 tracker (clean steps since the scale last changed),
+ *   int64 step (AdamW's step count; it lives on the device because a skipped step must not advance it and the host does not look),
+ *   float min_scale (read only), 12 bytes reserved.
+ * The step: found_inf = any raw g is inf or nan; gu = g * (1 / scale); grad_norm = sqrt(sum gu^2) over all tensors and param_norm =
+ *   sqrt(sum p^2) (the norm of the per-tensor norms, :18), accumulated in double, so that finite gradients never overflow them;
+ *   clip_coef = min(1, max_norm / (grad_norm + 1e-6)).  Unless found_inf: step += 1 and per element, in fp32 and in the operation order
+ *   of torch.optim.adam._single_tensor_adam with each op associated as ATen's CPU kernel does (addcmul_ as (value * a) * b, addcdiv_
+ *   as (value * a) / b; ATen's device kernels associate the other way, one rounding apart), gu *= clip_coef, p *= 1 - lr * wd, m = lerp(m, gu, 1 - beta1), v = v * beta2 +
+ *   (1 - beta2) * gu * gu, p += -(lr / (1 - beta1^step)) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps); with found_inf none of p, m, v,
+ *   step is written.  Then the scale (torch's _amp_update_scale_): found_inf -> scale *= backoff, tracker = 0; else tracker += 1 and at
+ *   growth_interval scale *= growth (kept when that overflows), tracker = 0; then scale = max(scale, min_scale).
+ *   zero_grads != 0 stores 0 to every g after reading it, on skipped steps too; otherwise g is left as it came in, still scaled.
+ * stats_out: GFN_TS_STATS + n_tensors floats on the device: GFN_TS_STAT_* (grad_scale is the scale this step used), then one 0 / 1
+ *   flag per tensor: its raw gradient held an inf or nan.
+ * ws: gfn_train_step_ws_bytes(n_tensors, n_chunks) bytes, 16-byte aligned, contents undefined before and after.
+ * Limits: n_tensors <= 2^20 (the single workgroup of ts_finish_kernel loops over them), n_chunks <= 2^23 (the grid).  n_tensors = 0
+ *   is valid (the tables may be NULL): only the scale rule runs, with found_inf = 0, and the step count stays. */
+#define GFN_TS_CHUNK 4096
+#define GFN_TS_STATE_BYTES 32
+#define GFN_TS_STAT_GRAD_NORM 0
+#define GFN_TS_STAT_PARAM_NORM 1
+#define GFN_TS_STAT_GRAD_SCALE 2
+#define GFN_TS_STAT_FOUND_INF 3
+#define GFN_TS_STAT_CLIP_COEF 4
+#define GFN_TS_STATS 8
+typedef struct gfn_ts_tensor {
+    float *p, *g, *exp_avg, *exp_avg_sq;
+    int64_t numel;
+    double lr, wd, beta1, beta2, eps;
+    int32_t first_chunk, n_chunks, vec16, reserved;
+} gfn_ts_tensor; /* 96 bytes */
+typedef struct gfn_ts_chunk {
+    int32_t tensor, count;
+    int64_t first;
+} gfn_ts_chunk; /* 16 bytes */
+int64_t gfn_train_step_ws_bytes(int n_tensors, int n_chunks);
+int gfn_train_step(const gfn_ts_tensor *tensor_table, int n_tensors, const gfn_ts_chunk *chunk_table, int n_chunks, void *state,
+                   double max_norm, double growth, double backoff, int growth_interval, int zero_grads, float *stats_out, void *ws,
+                   int64_t ws_bytes, gfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
