@@ -9,6 +9,8 @@
 //   gfn_grid_sample_fwd    F.grid_sample(bilinear, zeros, align_corners=False): gfn_grid_sample_mode_fwd (grid_modes.hip)
 //   gfn_interp_bilinear_fwd F.interpolate(mode='bilinear', align_corners=False), network.py:238-249,271-281
 //   gfn_flow_update_fwd    displacement scaling / eval-time zeroing / accumulation, network.py:262-268
+//   gfn_flow_update_resize_fwd  a scale's last flow update and the resize to the next grid through one LDS tile,
+//                          network.py:262-268 + 271-281
 //   gfn_match_post_fwd     certainty attenuation, sigmoid, out-of-range masking, clamp, warp
 //                          assembly, network.py:332-338 + 358-384
 #include "common.h"
@@ -29,17 +31,30 @@ __global__ __launch_bounds__(256) void refiner_input_kernel(RiArgs q, unsigned q
     refiner_input_cell<FT, KEEP>(q, ri_direction(q.B, q.Bh, blockIdx.y), blockIdx.x * 256u + threadIdx.x);
 }
 
-// ATen upsample_bilinear2d, align_corners=False: src = max(0, (dst+0.5)*in/out - 0.5)
+// ATen upsample_bilinear2d, align_corners=False: src = max(0, (dst+0.5)*in/out - 0.5).  One axis of one output: the two
+// source indices and their weights.  Every bilinear resize below goes through interp_tap + bilerp, so they all round alike.
+struct Tap {
+    int i0, i1;
+    float l, h;
+};
+__device__ __forceinline__ Tap interp_tap(int n_in, int n_out, int o) {
+    const float s = (float)n_in / (float)n_out;
+    float f = ((float)o + 0.5f) * s - 0.5f;
+    f = f < 0.f ? 0.f : f;
+    Tap t;
+    t.i0 = (int)f;
+    t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
+    t.l = f - (float)t.i0;
+    t.h = 1.f - t.l;
+    return t;
+}
+__device__ __forceinline__ float bilerp(const Tap &ty, const Tap &tx, float v00, float v01, float v10, float v11) {
+    return ty.h * (tx.h * v00 + tx.l * v01) + ty.l * (tx.h * v10 + tx.l * v11);
+}
 __device__ __forceinline__ float interp_at(const float *pl, int H, int W, int Ho, int Wo, int y, int x) {
-    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-    float fy = ((float)y + 0.5f) * sy - 0.5f, fx = ((float)x + 0.5f) * sx - 0.5f;
-    fy = fy < 0.f ? 0.f : fy;
-    fx = fx < 0.f ? 0.f : fx;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
-    return hy * (hx * pl[(size_t)y0 * W + x0] + lx * pl[(size_t)y0 * W + x1]) +
-           ly * (hx * pl[(size_t)y1 * W + x0] + lx * pl[(size_t)y1 * W + x1]);
+    const Tap ty = interp_tap(H, Ho, y), tx = interp_tap(W, Wo, x);
+    return bilerp(ty, tx, pl[(size_t)ty.i0 * W + tx.i0], pl[(size_t)ty.i0 * W + tx.i1], pl[(size_t)ty.i1 * W + tx.i0],
+                  pl[(size_t)ty.i1 * W + tx.i1]);
 }
 
 // ---- image resize + normalise ----------------------------------------------------
@@ -108,22 +123,38 @@ __global__ __launch_bounds__(256) void resize_normalize_kernel(const float *__re
     }
 }
 
-// Four consecutive outputs of one row per thread (one 16-byte store when the row pitch allows), 32-bit index arithmetic,
-// planes on blockIdx.y: the one-output-per-thread form with 64-bit div/mod ran at 1 TB/s.  Same per-pixel arithmetic
-// (interp_at) as before.
-__device__ __forceinline__ void interp_quad(const float *__restrict__ pl, float *__restrict__ oplane, int H, int W, int Ho, int Wo,
-                                            unsigned q, int Wq) {
+// Four consecutive outputs of one row per thread (one 16-byte store per plane when the row pitch allows), 32-bit index
+// arithmetic inside a plane: the one-output-per-thread form with 64-bit div/mod ran at 1 TB/s.  A thread serves up to
+// kResizePlanes planes (a direction's two flow planes and its certainty, in the loop's calls) with ONE set of taps: the row's
+// tap and the four column taps do not depend on the plane.
+constexpr int kResizePlanes = 3;
+
+__device__ __forceinline__ void interp_quad(const float *(&pl)[kResizePlanes], float *(&oplane)[kResizePlanes], int np,
+                                            int H, int W, int Ho, int Wo, unsigned q, int Wq) {
     const int y = (int)(q / (unsigned)Wq), x0 = ((int)q - y * Wq) * 4;
-    float *o = oplane + (size_t)y * Wo + x0;
-    if (x0 + 3 < Wo && (Wo & 3) == 0 && (((uintptr_t)oplane & 15) == 0)) {
-        float4 v;
-        v.x = interp_at(pl, H, W, Ho, Wo, y, x0);
-        v.y = interp_at(pl, H, W, Ho, Wo, y, x0 + 1);
-        v.z = interp_at(pl, H, W, Ho, Wo, y, x0 + 2);
-        v.w = interp_at(pl, H, W, Ho, Wo, y, x0 + 3);
-        *reinterpret_cast<float4 *>(o) = v;
-    } else {
-        for (int k = 0; k < 4 && x0 + k < Wo; ++k) o[k] = interp_at(pl, H, W, Ho, Wo, y, x0 + k);
+    const Tap ty = interp_tap(H, Ho, y);
+    const int r0 = ty.i0 * W, r1 = ty.i1 * W;
+    Tap tx[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tx[k] = interp_tap(W, Wo, min(x0 + k, Wo - 1));  // past a ragged row end: the last column again, not stored
+    const bool quad = x0 + 3 < Wo && (Wo & 3) == 0;
+    const int o = y * Wo + x0;
+#pragma unroll
+    for (int p = 0; p < kResizePlanes; ++p) {
+        if (p >= np) break;
+        const float *__restrict__ s = pl[p];
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            v[k] = bilerp(ty, tx[k], s[r0 + tx[k].i0], s[r0 + tx[k].i1], s[r1 + tx[k].i0], s[r1 + tx[k].i1]);
+        float *d = oplane[p] + o;
+        if (quad && (((uintptr_t)oplane[p] & 15) == 0)) {
+            *reinterpret_cast<float4 *>(d) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x0 + k < Wo) d[k] = v[k];
+        }
     }
 }
 
@@ -132,53 +163,163 @@ __global__ __launch_bounds__(256) void interp_bilinear_kernel(const float *__res
     const int Wq = (Wo + 3) >> 2;
     const unsigned q = blockIdx.x * 256u + threadIdx.x;
     if (q >= (unsigned)(Wq * Ho)) return;
-    for (int pl = blockIdx.y; pl < BC; pl += gridDim.y)
-        interp_quad(in + (size_t)pl * H * W, out + (size_t)pl * Ho * Wo, H, W, Ho, Wo, q, Wq);
+    for (int g = blockIdx.y * kResizePlanes; g < BC; g += gridDim.y * kResizePlanes) {  // block-uniform
+        const float *pl[kResizePlanes];
+        float *op[kResizePlanes];
+#pragma unroll
+        for (int p = 0; p < kResizePlanes; ++p) {
+            const int i = min(g + p, BC - 1);
+            pl[p] = in + (size_t)i * H * W;
+            op[p] = out + (size_t)i * Ho * Wo;
+        }
+        interp_quad(pl, op, min(kResizePlanes, BC - g), H, W, Ho, Wo, q, Wq);
+    }
 }
 
 // two tensors of the same spatial size in one launch (flow + certainty between scales: half the launches of the loop)
 __global__ __launch_bounds__(256) void interp_bilinear_pair_kernel(const float *__restrict__ in_a, float *__restrict__ out_a, int BCa,
                                                                    const float *__restrict__ in_b, float *__restrict__ out_b, int BCb,
                                                                    int H, int W, int Ho, int Wo) {
-    const int Wq = (Wo + 3) >> 2;
+    const int Wq = (Wo + 3) >> 2, BC = BCa + BCb;
     const unsigned q = blockIdx.x * 256u + threadIdx.x;
     if (q >= (unsigned)(Wq * Ho)) return;
-    for (int pl = blockIdx.y; pl < BCa + BCb; pl += gridDim.y) {
-        const bool second = pl >= BCa;  // block-uniform
-        const float *in = second ? in_b + (size_t)(pl - BCa) * H * W : in_a + (size_t)pl * H * W;
-        float *out = second ? out_b + (size_t)(pl - BCa) * Ho * Wo : out_a + (size_t)pl * Ho * Wo;
-        interp_quad(in, out, H, W, Ho, Wo, q, Wq);
+    for (int g = blockIdx.y * kResizePlanes; g < BC; g += gridDim.y * kResizePlanes) {  // block-uniform
+        const float *pl[kResizePlanes];
+        float *op[kResizePlanes];
+#pragma unroll
+        for (int p = 0; p < kResizePlanes; ++p) {
+            const int i = min(g + p, BC - 1);
+            const bool second = i >= BCa;
+            pl[p] = second ? in_b + (size_t)(i - BCa) * H * W : in_a + (size_t)i * H * W;
+            op[p] = second ? out_b + (size_t)(i - BCa) * Ho * Wo : out_a + (size_t)i * Ho * Wo;
+        }
+        interp_quad(pl, op, min(kResizePlanes, BC - g), H, W, Ho, Wo, q, Wq);
     }
+}
+
+// One cell of network.py:262-268, the only copy of these expressions: the displacement from the refiner's increment, the
+// eval-time zeroing against the previous displacement (`pp`, planes GG apart; NULL on a single-iteration scale), the carry of
+// the displacement (when `store_prev`) and the accumulation.  f / c come in as the cell's flow and certainty and leave updated.
+__device__ __forceinline__ void flow_update_cell(float &fx, float &fy, float &c, float dlx, float dly, float dc, float *pp, int GG,
+                                                 bool store_prev, float scale, float div_x, float div_y, int zero_small, int first) {
+    float dx = scale * (dlx / div_x), dy = scale * (dly / div_y);  // network.py:262-263
+    if (zero_small) {  // network.py:256,264-265
+        const float px = first ? 1e-7f : pp[0], py = first ? 1e-7f : pp[GG];
+        if (fabsf(dx - px) / fabsf(px) < 1e-6f) dx = 0.f;
+        if (fabsf(dy - py) / fabsf(py) < 1e-6f) dy = 0.f;
+    }
+    if (pp && store_prev) {
+        pp[0] = dx;
+        pp[GG] = dy;
+    }
+    fx = fx + dx;
+    fy = fy + dy;
+    c = c + dc;
 }
 
 // dflow: (B, >=2, G, G) displacement increment with batch stride dflow_bs, dcert: (B, >=1, G, G) certainty increment with
 // dcert_bs (the refiner's two outputs; one (B,3,G,G) tensor or two).  flow_in/cert_in -> flow_out/cert_out (may alias).
-// flow_in / cert_in may be the same buffers as flow_out / cert_out (gfn_flow_update_fwd updates in place): no __restrict__ on them
+// flow_in / cert_in may be the same buffers as flow_out / cert_out (gfn_flow_update_fwd updates in place): no __restrict__ on them.
+// Cells of a direction on blockIdx.x, directions on blockIdx.y: no division, 32-bit offsets inside a direction.
+// MODE 0: the whole step.  MODE 1: only the carry of the displacement into disp_prev (behind the fused kernel below, which must
+// not store it while neighbouring workgroups still read it).
+template <int MODE>
 __global__ __launch_bounds__(256) void flow_update_kernel(const float *flow_in, const float *cert_in,
                                                           float *flow_out, float *cert_out, const float *__restrict__ dflow,
                                                           long dflow_bs, const float *__restrict__ dcert, long dcert_bs,
                                                           float *__restrict__ disp_prev, int B, int G, float scale, float div_x,
                                                           float div_y, int zero_small, int first) {
-    const long GG = (long)G * G, total = (long)B * GG;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const int b = (int)(idx / GG);
-        const long r = idx - (long)b * GG;
+    const int GG = G * G;
+    const int r = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (r >= GG) return;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
         const float *dl = dflow + (size_t)b * dflow_bs + r;
-        float dx = scale * (dl[0] / div_x), dy = scale * (dl[GG] / div_y);  // network.py:262-263
         float *pp = disp_prev ? disp_prev + (size_t)b * 2 * GG + r : nullptr;  // NULL: single-iteration scale, nothing to carry
-        if (zero_small) {  // network.py:256,264-265
-            const float px = first ? 1e-7f : pp[0], py = first ? 1e-7f : pp[GG];
-            if (fabsf(dx - px) / fabsf(px) < 1e-6f) dx = 0.f;
-            if (fabsf(dy - py) / fabsf(py) < 1e-6f) dy = 0.f;
+        if (MODE == 1) {
+            float fx = 0.f, fy = 0.f, c = 0.f;
+            flow_update_cell(fx, fy, c, dl[0], dl[GG], 0.f, pp, GG, true, scale, div_x, div_y, zero_small, first);
+            continue;
         }
-        if (pp) {
-            pp[0] = dx;
-            pp[GG] = dy;
+        const size_t o = (size_t)b * 2 * GG + r, oc = (size_t)b * GG + r;
+        float fx = flow_in[o], fy = flow_in[o + GG], c = cert_in[oc];
+        flow_update_cell(fx, fy, c, dl[0], dl[GG], dcert[(size_t)b * dcert_bs + r], pp, GG, true, scale, div_x, div_y, zero_small, first);
+        flow_out[o] = fx;
+        flow_out[o + GG] = fy;
+        cert_out[oc] = c;
+    }
+}
+
+// The last update of a scale and the resize of its result to the next grid (R = G_next / G, 1 or 2) in one launch.  A workgroup
+// owns 16 x 16 cells of one direction (blockIdx = tile column, tile row, direction): it updates them and the ring of cells
+// around them that lie inside the map into LDS -- every source cell of the tile's outputs once; interp_tap clamps at the
+// border, so no output needs a cell outside the map --, writes its own cells to flow_out / cert_out, and after one barrier
+// each thread interpolates four consecutive outputs of a row for the three planes from LDS with one set of taps.
+// LDS: three planes of 18 rows of 18 floats.  A half wave reads 4 output rows x 8 quads = source rows j..j+2 at even columns:
+// with an 18-float pitch those are banks {0..14}, {18..32}, {36..50} (mod 32), one 2-way conflict per read; a 19-float pitch
+// gives five.  Ring cells are another workgroup's own cells, so nothing here may store disp_prev where it is also read
+// (STORE_PREV false: the caller stores it with flow_update_kernel<1> afterwards), and the outputs must not alias the inputs.
+constexpr int kTile = 16, kPitch = kTile + 2;
+
+template <int R, bool STORE_PREV>
+__global__ __launch_bounds__(256) void flow_update_resize_kernel(const float *__restrict__ flow_in, const float *__restrict__ cert_in,
+                                                                 float *__restrict__ flow_out, float *__restrict__ cert_out,
+                                                                 const float *__restrict__ dflow, long dflow_bs,
+                                                                 const float *__restrict__ dcert, long dcert_bs, float *disp_prev, int G,
+                                                                 float scale, float div_x, float div_y, int zero_small, int first,
+                                                                 float *__restrict__ flow_next, float *__restrict__ cert_next) {
+    __shared__ float tile[3][kPitch][kPitch];
+    const int b = blockIdx.z, ty0 = blockIdx.y * kTile, tx0 = blockIdx.x * kTile, GG = G * G, Go = G * R;
+    const float *fin = flow_in + (size_t)b * 2 * GG, *cin = cert_in + (size_t)b * GG;
+    const float *dl = dflow + (size_t)b * dflow_bs, *dc = dcert + (size_t)b * dcert_bs;
+    float *fout = flow_out + (size_t)b * 2 * GG, *cout = cert_out + (size_t)b * GG;
+    float *prev = disp_prev ? disp_prev + (size_t)b * 2 * GG : nullptr;
+    for (int i = threadIdx.x; i < kPitch * kPitch; i += 256) {
+        const int ly = i / kPitch, lx = i - ly * kPitch, y = ty0 - 1 + ly, x = tx0 - 1 + lx;
+        if (y < 0 || y >= G || x < 0 || x >= G) continue;
+        const bool own = ly >= 1 && ly <= kTile && lx >= 1 && lx <= kTile;
+        const int r = y * G + x;
+        float fx = fin[r], fy = fin[r + GG], c = cin[r];
+        flow_update_cell(fx, fy, c, dl[r], dl[r + GG], dc[r], prev ? prev + r : nullptr, GG, STORE_PREV && own, scale, div_x, div_y,
+                         zero_small, first);
+        tile[0][ly][lx] = fx;
+        tile[1][ly][lx] = fy;
+        tile[2][ly][lx] = c;
+        if (own) {
+            fout[r] = fx;
+            fout[r + GG] = fy;
+            cout[r] = c;
         }
-        const size_t o = (size_t)b * 2 * GG + r;
-        flow_out[o] = flow_in[o] + dx;
-        flow_out[o + GG] = flow_in[o + GG] + dy;
-        cert_out[idx] = cert_in[idx] + dcert[(size_t)b * dcert_bs + r];
+    }
+    __syncthreads();
+    // the tile's outputs: 16 R rows of 4 R quads
+    if (threadIdx.x >= kTile * R * 4 * R) return;
+    const int oy = ty0 * R + (int)threadIdx.x / (4 * R), ox = tx0 * R + ((int)threadIdx.x % (4 * R)) * 4;
+    if (oy >= Go || ox >= Go) return;
+    const Tap ty = interp_tap(G, Go, oy);
+    const int r0 = ty.i0 - (ty0 - 1), r1 = ty.i1 - (ty0 - 1);
+    Tap tx[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        tx[k] = interp_tap(G, Go, min(ox + k, Go - 1));  // past a ragged row end: the last column again, not stored
+        tx[k].i0 -= tx0 - 1;
+        tx[k].i1 -= tx0 - 1;
+    }
+    const bool quad = ox + 3 < Go && (Go & 3) == 0;
+    const int o = oy * Go + ox;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            v[k] = bilerp(ty, tx[k], tile[p][r0][tx[k].i0], tile[p][r0][tx[k].i1], tile[p][r1][tx[k].i0], tile[p][r1][tx[k].i1]);
+        float *plane = p < 2 ? flow_next + ((size_t)b * 2 + p) * Go * Go : cert_next + (size_t)b * Go * Go;
+        if (quad && (((uintptr_t)plane & 15) == 0)) {
+            *reinterpret_cast<float4 *>(plane + o) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (ox + k < Go) plane[o + k] = v[k];
+        }
     }
 }
 
@@ -220,6 +361,11 @@ inline unsigned grid_for(long total, int cap = 16384) {
     return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
+// in-plane offsets are 32-bit in the resize and flow-update kernels
+constexpr int kMaxGrid = 46340;  // floor(sqrt(2^31))
+
+inline dim3 flow_update_grid(int B, int G) { return dim3((unsigned)(((long)G * G + 255) / 256), (unsigned)(B < 65535 ? B : 65535)); }
+
 }  // namespace
 
 GFN_EXPORT int gfn_refiner_input_fwd(const float *f0, const float *f1, const float *flow, const float *disp_w,
@@ -258,9 +404,10 @@ GFN_EXPORT int gfn_interp_bilinear_fwd(const float *in, float *out, int BC, int 
     if (!in || !out || BC < 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0)
         return gfn::fail(GFN_ERR_INVALID_ARG, "interp_bilinear: bad argument");
     if (BC == 0) return GFN_OK;
-    if ((long)Ho * ((Wo + 3) / 4) >= (1L << 31)) return gfn::fail(GFN_ERR_INVALID_ARG, "interp_bilinear: output too large");
+    if ((long)H * W >= (1L << 31) || (long)Ho * Wo >= (1L << 31)) return gfn::fail(GFN_ERR_INVALID_ARG, "interp_bilinear: plane too large");
     const unsigned gx = (unsigned)(((long)Ho * ((Wo + 3) / 4) + 255) / 256);
-    hipLaunchKernelGGL(interp_bilinear_kernel, dim3(gx, (unsigned)(BC < 65535 ? BC : 65535)), dim3(256), 0, (hipStream_t)stream, in,
+    const int groups = (BC + kResizePlanes - 1) / kResizePlanes;
+    hipLaunchKernelGGL(interp_bilinear_kernel, dim3(gx, (unsigned)(groups < 65535 ? groups : 65535)), dim3(256), 0, (hipStream_t)stream, in,
                        out, BC, H, W, Ho, Wo);
     return gfn::check_launch("interp_bilinear_kernel");
 }
@@ -270,10 +417,11 @@ GFN_EXPORT int gfn_interp_bilinear_pair_fwd(const float *in_a, float *out_a, int
     if (!in_a || !out_a || !in_b || !out_b || BCa < 0 || BCb < 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0)
         return gfn::fail(GFN_ERR_INVALID_ARG, "interp_bilinear_pair: bad argument");
     if (BCa + BCb == 0) return GFN_OK;
-    if ((long)Ho * ((Wo + 3) / 4) >= (1L << 31)) return gfn::fail(GFN_ERR_INVALID_ARG, "interp_bilinear_pair: output too large");
+    if ((long)H * W >= (1L << 31) || (long)Ho * Wo >= (1L << 31)) return gfn::fail(GFN_ERR_INVALID_ARG, "interp_bilinear_pair: plane too large");
     const unsigned gx = (unsigned)(((long)Ho * ((Wo + 3) / 4) + 255) / 256);
-    const long planes = (long)BCa + BCb;
-    hipLaunchKernelGGL(interp_bilinear_pair_kernel, dim3(gx, (unsigned)(planes < 65535 ? planes : 65535)), dim3(256), 0,
+    if ((long)BCa + BCb >= (1L << 31)) return gfn::fail(GFN_ERR_INVALID_ARG, "interp_bilinear_pair: too many planes");
+    const int groups = (BCa + BCb + kResizePlanes - 1) / kResizePlanes;
+    hipLaunchKernelGGL(interp_bilinear_pair_kernel, dim3(gx, (unsigned)(groups < 65535 ? groups : 65535)), dim3(256), 0,
                        (hipStream_t)stream, in_a, out_a, BCa, in_b, out_b, BCb, H, W, Ho, Wo);
     return gfn::check_launch("interp_bilinear_pair_kernel");
 }
@@ -300,8 +448,9 @@ GFN_EXPORT int gfn_flow_update_fwd(float *flow, float *certainty, const float *d
                                    gfn_stream_t stream) {
     if (!flow || !certainty || !delta || !disp_prev || B < 0 || G <= 0 || W0 <= 0 || H0 <= 0 || delta_bs < 3L * G * G)
         return gfn::fail(GFN_ERR_INVALID_ARG, "flow_update: bad argument");
+    if (G > kMaxGrid) return gfn::fail(GFN_ERR_INVALID_ARG, "flow_update: grid too large");
     if (B == 0) return GFN_OK;
-    hipLaunchKernelGGL(flow_update_kernel, dim3(grid_for((long)B * G * G)), dim3(256), 0, (hipStream_t)stream, flow, certainty, flow,
+    hipLaunchKernelGGL(flow_update_kernel<0>, flow_update_grid(B, G), dim3(256), 0, (hipStream_t)stream, flow, certainty, flow,
                        certainty, delta, (long)delta_bs, delta + 2L * G * G, (long)delta_bs, disp_prev, B, G, (float)scale,
                        (float)(4 * W0), (float)(4 * H0), zero_small, first_iteration);
     return gfn::check_launch("flow_update_kernel");
@@ -314,11 +463,52 @@ GFN_EXPORT int gfn_flow_update_out_fwd(const float *flow_in, const float *cert_i
     if (!flow_in || !cert_in || !flow_out || !cert_out || !dflow || !dcert || B < 0 || G <= 0 || W0 <= 0 || H0 <= 0 ||
         dflow_bs < 2L * G * G || dcert_bs < (long)G * G || (!disp_prev && !first_iteration))
         return gfn::fail(GFN_ERR_INVALID_ARG, "flow_update_out: bad argument");
+    if (G > kMaxGrid) return gfn::fail(GFN_ERR_INVALID_ARG, "flow_update_out: grid too large");
     if (B == 0) return GFN_OK;
-    hipLaunchKernelGGL(flow_update_kernel, dim3(grid_for((long)B * G * G)), dim3(256), 0, (hipStream_t)stream, flow_in, cert_in, flow_out,
+    hipLaunchKernelGGL(flow_update_kernel<0>, flow_update_grid(B, G), dim3(256), 0, (hipStream_t)stream, flow_in, cert_in, flow_out,
                        cert_out, dflow, (long)dflow_bs, dcert, (long)dcert_bs, disp_prev, B, G, (float)scale, (float)(4 * W0),
                        (float)(4 * H0), zero_small, first_iteration);
     return gfn::check_launch("flow_update_kernel");
+}
+
+GFN_EXPORT int gfn_flow_update_resize_fwd(const float *flow_in, const float *cert_in, float *flow_out, float *cert_out,
+                                          const float *dflow, int64_t dflow_bs, const float *dcert, int64_t dcert_bs, float *disp_prev,
+                                          int B, int G, int scale, int W0, int H0, int zero_small, int first_iteration,
+                                          float *flow_next, float *cert_next, int G_next, gfn_stream_t stream) {
+    if (!flow_in || !cert_in || !flow_out || !cert_out || !dflow || !dcert || !flow_next || !cert_next || B < 0 || G <= 0 || W0 <= 0 ||
+        H0 <= 0 || dflow_bs < 2L * G * G || dcert_bs < (long)G * G || (!disp_prev && !first_iteration))
+        return gfn::fail(GFN_ERR_INVALID_ARG, "flow_update_resize: bad argument");
+    if (G_next != G && (G > kMaxGrid || G_next != 2 * G))
+        return gfn::fail(GFN_ERR_INVALID_ARG, "flow_update_resize: G_next must be G or 2 G (use flow_update_out + interp_bilinear_pair)");
+    if (G_next > kMaxGrid) return gfn::fail(GFN_ERR_INVALID_ARG, "flow_update_resize: grid too large");
+    if (flow_in == flow_out || cert_in == cert_out)
+        return gfn::fail(GFN_ERR_INVALID_ARG, "flow_update_resize: outputs must not alias the inputs");
+    if (B > 65535) return gfn::fail(GFN_ERR_INVALID_ARG, "flow_update_resize: more than 65535 directions");
+    if (B == 0) return GFN_OK;
+    // disp_prev is read only by the zeroing test of a later iteration; there a ring cell would read what its owner stores
+    const bool deferred = disp_prev && zero_small && !first_iteration;
+    const unsigned tiles = (unsigned)((G + kTile - 1) / kTile);
+    const dim3 grid(tiles, tiles, (unsigned)B);
+    const float s = (float)scale, dx = (float)(4 * W0), dy = (float)(4 * H0);
+#define GFN_FUR_LAUNCH(R, SP)                                                                                                        \
+    hipLaunchKernelGGL((flow_update_resize_kernel<R, SP>), grid, dim3(256), 0, (hipStream_t)stream, flow_in, cert_in, flow_out,      \
+                       cert_out, dflow, (long)dflow_bs, dcert, (long)dcert_bs, disp_prev, G, s, dx, dy, zero_small, first_iteration, \
+                       flow_next, cert_next)
+    if (G_next == G) {
+        if (deferred) GFN_FUR_LAUNCH(1, false);
+        else GFN_FUR_LAUNCH(1, true);
+    } else {
+        if (deferred) GFN_FUR_LAUNCH(2, false);
+        else GFN_FUR_LAUNCH(2, true);
+    }
+#undef GFN_FUR_LAUNCH
+    if (int e = gfn::check_launch("flow_update_resize_kernel")) return e;
+    if (deferred) {
+        hipLaunchKernelGGL(flow_update_kernel<1>, flow_update_grid(B, G), dim3(256), 0, (hipStream_t)stream, nullptr, nullptr, nullptr,
+                           nullptr, dflow, (long)dflow_bs, dcert, (long)dcert_bs, disp_prev, B, G, s, dx, dy, zero_small, first_iteration);
+        return gfn::check_launch("flow_update_kernel");
+    }
+    return GFN_OK;
 }
 
 GFN_EXPORT int gfn_match_post_fwd(const float *flow, const float *certainty, const float *cert16_or_null, float *warp,

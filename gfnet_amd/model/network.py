@@ -420,6 +420,8 @@ class GFNet(nn.Module):
                     flow = ops.corr_softargmax(f0, f1, symmetric=symmetric)                      # :251-252
                     certainty = torch.zeros((flow.shape[0], 1) + tuple(flow.shape[2:]), device=flow.device)  # :253
             corresps[scale] = {}
+            fuse_resize = (ops.FUSE_UPDATE_RESIZE and not torch.is_grad_enabled() and scale != "1" and num_itr[idx] >= 1
+                           and num_grid[idx + 1] in (flow.shape[-1], 2 * flow.shape[-1]))
             disp_prev = torch.empty_like(flow) if num_itr[idx] > 1 else None  # carried between the iterations of one scale
             for itr in range(num_itr[idx]):
                 ref = self.conv_refiner[scale]
@@ -433,10 +435,17 @@ class GFNet(nn.Module):
                 else:
                     d_flow, d_cert, _ = ref(num_grid[idx], f0, f1, flow, scale_factor=scale_factor)
                 # each iteration's result is kept (corresps): out-of-place update straight from the refiner's outputs
-                flow, certainty = ops.flow_update(flow, certainty, d_flow, d_cert, disp_prev, int(scale), W0, H0,
-                                                  zero_small=not self.training, first_iteration=(itr == 0))  # :262-268
+                if itr == num_itr[idx] - 1 and fuse_resize:  # the scale's last update and the resize below in one launch
+                    flow, certainty, flow_next, cert_next = ops.flow_update_resize(
+                        flow, certainty, d_flow, d_cert, disp_prev, int(scale), W0, H0, num_grid[idx + 1],
+                        zero_small=not self.training, first_iteration=(itr == 0))                 # :262-268 + :271-281
+                else:
+                    flow, certainty = ops.flow_update(flow, certainty, d_flow, d_cert, disp_prev, int(scale), W0, H0,
+                                                      zero_small=not self.training, first_iteration=(itr == 0))  # :262-268
                 corresps[scale][itr + 1] = {"flow": flow, "certainty": certainty}
-            if scale != "1":                                                                      # :271-281
+            if fuse_resize:
+                flow, certainty = flow_next, cert_next
+            elif scale != "1":                                                                    # :271-281
                 flow, certainty = ops.interpolate_bilinear_pair(flow, certainty, num_grid[idx + 1])
         return corresps
 

@@ -366,7 +366,7 @@ def flow_update(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero_
     return _flow_update(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero_small, first_iteration)
 
 
-def _flow_update(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero_small, first_iteration):
+def _flow_update(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero_small, first_iteration, size_next=None):
     dev = require_gpu(flow, certainty, d_flow, d_cert, *(() if disp_prev is None else (disp_prev,)))
     B, _, G, _ = flow.shape
     if tuple(certainty.shape) != (B, 1, G, G) or tuple(d_flow.shape) != (B, 2, G, G) or tuple(d_cert.shape) != (B, 1, G, G) or \
@@ -381,10 +381,31 @@ def _flow_update(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero
     df, df_bs = _plane_view(d_flow, 2, G)
     dc, dc_bs = _plane_view(d_cert, 1, G)
     fo, co = torch.empty_like(fi), torch.empty_like(ci)
+    if size_next is not None:  # flow_update_resize
+        Gn = int(size_next)
+        fn = torch.empty((B, 2, Gn, Gn), device=dev, dtype=torch.float32)
+        cn = torch.empty((B, 1, Gn, Gn), device=dev, dtype=torch.float32)
+        check(_L().gfn_flow_update_resize_fwd(ptr(fi), ptr(ci), ptr(fo), ptr(co), c_vp(df.data_ptr()), df_bs, c_vp(dc.data_ptr()), dc_bs,
+                                              ptr(disp_prev), B, G, int(scale), int(W0), int(H0), 1 if zero_small else 0,
+                                              1 if first_iteration else 0, ptr(fn), ptr(cn), Gn, stream_ptr(dev)),
+              "gfn_flow_update_resize_fwd")
+        return fo, co, fn, cn
     check(_L().gfn_flow_update_out_fwd(ptr(fi), ptr(ci), ptr(fo), ptr(co), c_vp(df.data_ptr()), df_bs, c_vp(dc.data_ptr()), dc_bs,
                                        ptr(disp_prev), B, G, int(scale), int(W0), int(H0), 1 if zero_small else 0,
                                        1 if first_iteration else 0, stream_ptr(dev)), "gfn_flow_update_out_fwd")
     return fo, co
+
+
+# forward_pyramids ends a scale with flow_update_resize where it can; False keeps the two launches (the comparison the tests make)
+FUSE_UPDATE_RESIZE = True
+
+
+def flow_update_resize(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, size_next, zero_small=True, first_iteration=True):
+    """flow_update followed by interpolate_bilinear_pair of its results to the (size_next, size_next) grid in one launch
+    (model/network.py:262-268 + 271-281): returns (flow, certainty, flow_next, cert_next), bit for bit what the two calls
+    return, and leaves disp_prev as flow_update does.  size_next must be the grid size or twice it (anything else is an error:
+    make the two calls).  Inference only: no backward."""
+    return _flow_update(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero_small, first_iteration, size_next=size_next)
 
 
 class _FlowUpdateFn(torch.autograd.Function):

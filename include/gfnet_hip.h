@@ -284,6 +284,17 @@ int gfn_flow_update_fwd(float *flow, float *certainty, const float *delta, int64
 int gfn_flow_update_out_fwd(const float *flow_in, const float *cert_in, float *flow_out, float *cert_out, const float *dflow,
                             int64_t dflow_bs, const float *dcert, int64_t dcert_bs, float *disp_prev, int B, int G, int scale,
                             int W0, int H0, int zero_small, int first_iteration, gfn_stream_t stream);
+/* gfn_flow_update_out_fwd followed by gfn_interp_bilinear_pair_fwd of its two results to the next grid, in one launch --
+ * model/network.py:262-268 and 271-281: the last update of a scale and the resize that seeds the next one.  A workgroup
+ * updates 16 x 16 cells plus a one-cell halo into LDS, writes its cells to flow_out / cert_out (and disp_prev) and
+ * interpolates flow_next (B,2,G_next,G_next) / cert_next (B,1,G_next,G_next) from LDS; all five results are bit for bit
+ * those of the two calls.  G_next must be G or 2 * G (anything else: GFN_ERR_INVALID_ARG, use the two calls).  Outputs must
+ * NOT alias the inputs here (neighbouring workgroups read each other's input cells).  When disp_prev is read and written
+ * (zero_small, not first_iteration) it is stored by a second small launch for the same reason. */
+int gfn_flow_update_resize_fwd(const float *flow_in, const float *cert_in, float *flow_out, float *cert_out, const float *dflow,
+                               int64_t dflow_bs, const float *dcert, int64_t dcert_bs, float *disp_prev, int B, int G, int scale,
+                               int W0, int H0, int zero_small, int first_iteration, float *flow_next, float *cert_next, int G_next,
+                               gfn_stream_t stream);
 
 /* match() post-processing -- model/network.py:332-338 + 358-384.
  *   flow (nb,2,G,G), certainty (nb,1,G,G) finest-scale logits, nb = 2*B_images when symmetric;
