@@ -1,4 +1,8 @@
-"""ctypes binding of libgfnet_hip.so (C ABI: include/gfnet_hip.h).
+"""ctypes binding of libgfnet_hip.so, derived from its C ABI: include/gfnet_hip.h is read at import.
+
+Every `gfn_*` prototype of the header gives the argument and return ctypes of its symbol, every `#define GFN_<NAME> <number>` a
+constant of this module (`GFN_RL_STATS` -> `RL_STATS`; `GFN_F32` / `GFN_F16` keep their prefix): nothing of the boundary is typed
+a second time here.  A declaration the parser does not understand is an error at import, never a default.
 
 torch is imported first so that the library binds to the HIP runtime torch already loaded
 (same libamdhip64 SONAME); torch itself is only plumbing here: device memory and streams.
@@ -6,125 +10,101 @@ There is NO CPU fallback: if the library is missing or the tensors are not on a 
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GFNET_HIP_LIB") or os.path.join(_HERE, "csrc", "libgfnet_hip.so")
-_lib = None
+HEADER_PATH = os.environ.get("GFNET_HIP_HEADER") or os.path.join(_HERE, "..", "include", "gfnet_hip.h")
 
 c_int, c_i64, c_vp, c_float, c_double = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
-
-# name -> argtypes; every entry point returns int (GFN_OK or a negative error code)
-_SIGNATURES = {
-    "gfn_local_corr_fwd": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 9 + [c_vp, c_i64, c_vp],
-    "gfn_local_corr_fwd_ex": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 10 + [c_vp, c_i64, c_vp],
-    "gfn_local_corr_fwd_dt": [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64] + [c_int] * 10 + [c_vp, c_i64, c_vp],
-    "gfn_avg_pool2": [c_vp, c_vp, c_int, c_int, c_int, c_vp],
-    "gfn_corr_softargmax_fwd": [c_vp, c_vp, c_vp] + [c_int] * 7 + [c_vp],
-    "gfn_corr_volume_fwd": [c_vp, c_vp, c_vp, c_vp] + [c_int] * 6 + [c_vp],
-    "gfn_pos_embed_fwd": [c_vp, c_vp] + [c_int] * 5 + [c_vp],
-    "gfn_refiner_input_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 6 + [c_float, c_int, c_vp],
-    "gfn_refiner_input_fwd_dt": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 6 + [c_float, c_int, c_vp],
-    "gfn_refiner_input_plan_fwd_dt": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 6 + [c_float, c_int, c_int, c_vp, c_i64, c_vp],
-    "gfn_corr_softargmax_fwd_dt": [c_vp, c_vp, c_int, c_vp] + [c_int] * 7 + [c_vp],
-    "gfn_corr_softargmax_fwd_ws": [c_vp, c_vp, c_int, c_vp] + [c_int] * 7 + [c_vp, c_i64, c_vp],
-    "gfn_corr_softargmax_bwd": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp] + [c_int] * 7 + [c_vp, c_i64, c_vp],
-    "gfn_grid_sample_fwd": [c_vp, c_vp, c_vp, c_i64] + [c_int] * 6 + [c_vp],
-    "gfn_interp_bilinear_fwd": [c_vp, c_vp] + [c_int] * 5 + [c_vp],
-    "gfn_interp_bilinear_pair_fwd": [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp],
-    "gfn_flow_update_fwd": [c_vp, c_vp, c_vp, c_i64, c_vp] + [c_int] * 7 + [c_vp],
-    "gfn_flow_update_out_fwd": [c_vp] * 5 + [c_i64, c_vp, c_i64, c_vp] + [c_int] * 7 + [c_vp],
-    "gfn_flow_update_resize_fwd": [c_vp] * 5 + [c_i64, c_vp, c_i64, c_vp] + [c_int] * 7 + [c_vp, c_vp, c_int, c_vp],
-    "gfn_match_post_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp] + [c_int] * 4 + [c_vp],
-    "gfn_kde_msplit": [c_int, c_int, c_int],
-    "gfn_kde_density": [c_vp, c_vp, c_vp] + [c_int] * 4 + [c_i64, c_i64, c_double, c_vp, c_i64, c_vp],
-    "gfn_kde_morton_keys": [c_vp, c_vp, c_i64, c_vp],
-    "gfn_kde_morton_sort": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp],
-    "gfn_kde_density_sorted": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_double, c_int, c_vp, c_i64, c_vp],
-    "gfn_threshold_certainty": [c_vp, c_vp, c_i64, c_float, c_vp],
-    "gfn_balance_weights": [c_vp, c_vp, c_i64, c_float, c_float, c_int, c_vp],
-    "gfn_sample_without_replacement": [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, ctypes.c_uint64, c_float, c_vp],
-    "gfn_gather_matches": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_vp],
-    "gfn_convert_matches": [c_vp, c_vp, c_i64] + [c_float] * 4 + [c_vp],
-    "gfn_homography_ransac": [c_vp, c_int, c_int, c_double, c_int, ctypes.c_uint64, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
-                              c_vp, c_i64, c_vp],
-    "gfn_homography_ransac_ex": [c_vp, c_int, c_int, c_double, c_int, c_double, ctypes.c_uint64, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
-                                 c_vp, c_vp, c_i64, c_vp],
-    "gfn_homography_dlt": [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp],
-    "gfn_local_corr_bwd_f0": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 9 + [c_vp],
-    "gfn_resize_normalize_fwd": [c_vp, c_i64, c_vp] + [c_int] * 6 + [c_vp, c_vp, c_vp],
-    "gfn_conv_block_pack": [c_vp] * 7 + [c_int] * 2 + [c_vp],
-    "gfn_conv_block_fwd": [c_vp] * 4 + [c_int] * 5 + [c_vp],
-    "gfn_conv_block_half_fwd": [c_vp, c_int, c_vp, c_vp] + [c_int] * 5 + [c_vp],
-    "gfn_pointwise_conv_fwd": [c_vp] * 4 + [c_int] * 4 + [c_vp],
-    "gfn_local_corr_mode_fwd": [c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_i64] + [c_int] * 11 + [c_vp],
-    "gfn_local_corr_mode_bwd_f0": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 11 + [c_vp],
-    "gfn_grid_sample_mode_fwd": [c_vp, c_int, c_vp, c_vp, c_i64] + [c_int] * 8 + [c_vp],
-    "gfn_refiner_input_mode_fwd_dt": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_int] * 6 + [c_float, c_int, c_int, c_vp],
-    "gfn_refiner_input_bwd": [c_vp, c_i64, c_vp, c_int] + [c_vp] * 8 + [c_int] * 7 + [c_float, c_vp, c_i64, c_vp],
-    "gfn_conv_block_train_fwd": [c_vp] * 13 + [c_int] * 4 + [c_double, c_double, c_vp, c_i64, c_vp],
-    "gfn_conv_block_train_bwd": [c_vp] * 16 + [c_int] * 5 + [c_vp, c_i64, c_vp],
-    "gfn_robust_loss_fwd": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_double, c_vp, c_vp] + [c_int] * 3 + [c_double] * 7
-                           + [c_vp, c_i64, c_vp],
-    "gfn_robust_loss_bwd": [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_double, c_vp, c_vp, c_vp, c_vp] + [c_int] * 4
-                           + [c_double] * 6 + [c_vp],
-    "gfn_gt_warp_homography_fwd": [c_vp] * 5 + [c_int] * 3 + [c_double, c_double, c_int, c_vp],
-    "gfn_train_step": [c_vp, c_int, c_vp, c_int, c_vp, c_double, c_double, c_double, c_int, c_int, c_vp, c_vp, c_i64, c_vp],
-}
-# entry points that return a size instead of a status
-_SIZE_FUNCS = {
-    "gfn_local_corr_scratch_bytes": [c_int, c_int],
-    "gfn_corr_softargmax_ws_bytes": [c_int] * 4,
-    "gfn_corr_softargmax_bwd_ws_bytes": [c_int] * 6,
-    "gfn_refiner_input_bwd_scratch_bytes": [c_int] * 3,
-    "gfn_local_corr_plans": [c_int] * 6,
-    "gfn_kde_scratch_floats": [c_int, c_int, c_int, c_int],
-    "gfn_kde_sorted_scratch_floats": [c_int, c_int, c_int],
-    "gfn_homography_scratch_bytes": [c_int, c_int],
-    "gfn_conv_block_packed_floats": [c_int, c_int],
-    "gfn_conv_block_train_ws_bytes": [c_int] * 5,
-    "gfn_robust_loss_ws_bytes": [c_int] * 4,
-    "gfn_train_step_ws_bytes": [c_int, c_int],
-}
-# gfn_robust_loss_fwd's `stats` vector (GFN_RL_STAT_* in include/gfnet_hip.h) and the most iterations a scale may have
-RL_STAT_LOSS, RL_STAT_CE, RL_STAT_REG, RL_STAT_COUNT, RL_STAT_PCK, RL_STATS, RL_MAX_ITR = 0, 1, 2, 3, 4, 8, 8
-# gfn_train_step (GFN_TS_* in include/gfnet_hip.h): elements per chunk, bytes of the device state, the head of `stats_out`
-TS_CHUNK, TS_STATE_BYTES, TS_STATS = 4096, 32, 8
-TS_STAT_GRAD_NORM, TS_STAT_PARAM_NORM, TS_STAT_GRAD_SCALE, TS_STAT_FOUND_INF, TS_STAT_CLIP_COEF = 0, 1, 2, 3, 4
-# `need` bits of gfn_conv_block_train_bwd (GFN_CBT_NEED_* in include/gfnet_hip.h)
-CBT_NEED_X, CBT_NEED_DW, CBT_NEED_BN, CBT_NEED_PW = 1, 2, 4, 8
+_SCALARS = {"int": c_int, "int64_t": c_i64, "uint64_t": ctypes.c_uint64, "float": c_float, "double": c_double, "gfn_stream_t": c_vp}
 
 
 class GfnError(RuntimeError):
     pass
 
 
+def _ctype(decl, proto, is_return=False):
+    """The ctypes type of one parameter declaration (type and name) or of a return type: every pointer is a c_void_p (a returned
+    `const char *` a c_char_p), a scalar is looked up by its type name; anything else raises, naming the prototype."""
+    words = decl.replace("*", " * ").split()
+    if "*" in words:
+        if not is_return:
+            return c_vp
+        if words == ["const", "char", "*"]:
+            return ctypes.c_char_p
+    kind = [w for w in (words if is_return else words[:-1]) if w != "const"]
+    if len(kind) != 1 or kind[0] not in _SCALARS:
+        raise GfnError(f"{proto}: cannot bind {'return type' if is_return else 'parameter'} '{' '.join(decl.split())}' "
+                       f"(known: pointers, {', '.join(_SCALARS)})")
+    return _SCALARS[kind[0]]
+
+
+def parse_header(text):
+    """(prototypes, constants) of a C header written like include/gfnet_hip.h: prototypes maps every `gfn_*` function to (restype,
+    [argtypes]) in declaration order, constants every `#define GFN_<NAME> <int or float literal, possibly parenthesised>` to its
+    value under the header's name."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    constants = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(GFN_\w+)[ \t]+\(?[ \t]*([-+]?[0-9.][\w.+-]*)[ \t]*\)?[ \t]*$", text, flags=re.M):
+        try:
+            constants[name] = int(value, 0)
+        except ValueError:
+            constants[name] = float(value)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    prototypes = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(gfn_\w+)\s*\(([^()]*)\)\s*;", text):
+        params = [] if params.strip() == "void" else params.split(",")
+        prototypes[name] = (_ctype(ret, name, is_return=True), [_ctype(p, name) for p in params])
+    return prototypes, constants
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        PROTOTYPES, CONSTANTS = parse_header(_f.read())
+except OSError as e:
+    raise GfnError(f"the C ABI header is needed to bind the library: {e} (set GFNET_HIP_HEADER to include/gfnet_hip.h)") from None
+globals().update({name if name in ("GFN_F32", "GFN_F16") else name[len("GFN_"):]: value for name, value in CONSTANTS.items()})
+# F.grid_sample's `mode` / `padding_mode` strings -> GFN_SAMPLE_* / GFN_PAD_*
+SAMPLE_MODES = {mode: CONSTANTS["GFN_SAMPLE_" + mode.upper()] for mode in ("bilinear", "nearest", "bicubic")}
+PADDING_MODES = {mode: CONSTANTS["GFN_PAD_" + mode.upper()] for mode in ("zeros", "border", "reflection")}
+# The entry points whose int is a status (GFN_OK or a negative GFN_ERR_*): those that return int AND take a gfn_stream_t, i.e. that
+# enqueue work.  What takes no stream answers a question on the host (sizes, gfn_local_corr_plans' flag, gfn_kde_msplit's count,
+# the introspection calls) and its value is never an error code to raise on.
+STATUS_FUNCS = frozenset(name for name, (restype, argtypes) in PROTOTYPES.items() if restype is c_int and argtypes[-1:] == [c_vp])
+
+_handles = {}
+
+
+def _load(checked):
+    if not os.path.exists(LIB_PATH):
+        raise GfnError(f"{LIB_PATH} not found: build it with `python -m gfnet_amd.build` "
+                       "(there is no CPU fallback for the GFNet hot path)")
+    L = ctypes.CDLL(LIB_PATH)  # (a handle of its own per view: ctypes keeps one function object per handle and name)
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+        if checked and name in STATUS_FUNCS:
+            fn.errcheck = _raise_on_error
+    _handles[checked] = L
+    return L
+
+
 def lib():
-    """Load (once) and return the ctypes handle; raises if the HIP library has not been built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise GfnError(f"{LIB_PATH} not found: build it with `python -m gfnet_amd.build` "
-                           "(there is no CPU fallback for the GFNet hot path)")
-        L = ctypes.CDLL(LIB_PATH)
-        L.gfn_abi_version.restype = c_int
-        L.gfn_last_error.restype = ctypes.c_char_p
-        L.gfn_device_arch.argtypes = [ctypes.c_char_p, c_int]
-        for name, argtypes in _SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-        for name, argtypes in _SIZE_FUNCS.items():
-            fn = getattr(L, name)
-            fn.argtypes = argtypes
-            fn.restype = c_i64
-        _lib = L
-    return _lib
+    """Load (once) and return the raw ctypes handle: status codes come back as integers.  Raises if the HIP library has not been built."""
+    return _handles.get(False) or _load(False)
+
+
+def checked():
+    """The same library with every status-returning entry point (STATUS_FUNCS) raising GfnError by itself, under the name of the
+    symbol that was called; sizes, flags and counts come back as they are."""
+    return _handles.get(True) or _load(True)
 
 
 def exported_symbols():
-    return ["gfn_abi_version", "gfn_last_error", "gfn_device_arch"] + list(_SIGNATURES) + list(_SIZE_FUNCS)
+    return list(PROTOTYPES)
 
 
 def check(code, what):
@@ -136,6 +116,12 @@ def check(code, what):
             _retire(b)  # (not freed where a captured graph may still name them)
         _scratch.clear()
         raise GfnError(f"{what} failed ({code}): {msg}")
+
+
+def _raise_on_error(code, fn, args):
+    if code != 0:
+        check(code, fn.__name__)
+    return code
 
 
 def ptr(t):
@@ -210,12 +196,6 @@ def scratch(device, nbytes, pool=""):
     if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
         _in_graphs.add(buf.data_ptr())
     return buf
-
-
-GFN_F32, GFN_F16 = 0, 1
-# F.grid_sample's `mode` / `padding_mode` strings -> GFN_SAMPLE_* / GFN_PAD_* (include/gfnet_hip.h)
-SAMPLE_MODES = {"bilinear": 0, "nearest": 1, "bicubic": 2}
-PADDING_MODES = {"zeros": 0, "border": 1, "reflection": 2}
 
 
 def mode_codes(sample_mode, padding_mode, what):

@@ -18,7 +18,7 @@
 
 namespace {
 
-constexpr int kMaxItr = 8;
+constexpr int kMaxItr = GFN_RL_MAX_ITR;
 constexpr int kThreads = 256;
 constexpr int kQuant = 4;          // ce, rho, count, pck
 constexpr int kMaxSide = 32768;    // (2 * i + 1) * side of the nearest-exact index stays inside 32 bits

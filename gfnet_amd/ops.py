@@ -9,11 +9,9 @@ import math
 import torch
 
 from . import _lib
-from ._lib import c_vp, check, f32c, featc, ptr, require_gpu, stream_ptr
+from ._lib import c_vp, f32c, featc, ptr, require_gpu, stream_ptr
 
-
-def _L():
-    return _lib.lib()
+_L = _lib.checked  # every status-returning entry point raises GfnError by itself, under its own name
 
 
 # bench.py sets this to a dict {name: [(start_event, end_event), ...]} to time individual launches
@@ -73,8 +71,8 @@ def _corr_softargmax(feat0, feat1, symmetric):
     # (the caching allocator hands the same block back; not the per-stream scratch, whose header the local correlation keeps zeroed)
     nws = int(_L().gfn_corr_softargmax_ws_bytes(nb, C, H1, W1))
     ws = torch.empty(nws, device=dev, dtype=torch.uint8) if nws > 0 else None
-    check(_L().gfn_corr_softargmax_fwd_ws(ptr(f0), ptr(f1), dt0, ptr(flow), nb, C, H0, W0, H1, W1, 1 if symmetric else 0,
-                                          ptr(ws), nws, stream_ptr(dev)), "gfn_corr_softargmax_fwd")
+    _L().gfn_corr_softargmax_fwd_ws(ptr(f0), ptr(f1), dt0, ptr(flow), nb, C, H0, W0, H1, W1, 1 if symmetric else 0,
+                                    ptr(ws), nws, stream_ptr(dev))
     return flow, f0, f1, dt0
 
 
@@ -96,8 +94,8 @@ def corr_softargmax_bwd(f0, f1, flow, grad_flow, symmetric=False, need_f0=True, 
     g1 = torch.empty(b.shape, device=dev, dtype=torch.float32) if need_f1 else None
     nws = int(_L().gfn_corr_softargmax_bwd_ws_bytes(nb, C, H0, W0, H1, W1))
     ws = torch.empty(nws, device=dev, dtype=torch.uint8) if nws > 0 else None
-    check(_L().gfn_corr_softargmax_bwd(ptr(a), ptr(b), dt0, ptr(fl), ptr(g), ptr(g0), ptr(g1), nb, C, H0, W0, H1, W1,
-                                       1 if symmetric else 0, ptr(ws), nws, stream_ptr(dev)), "gfn_corr_softargmax_bwd")
+    _L().gfn_corr_softargmax_bwd(ptr(a), ptr(b), dt0, ptr(fl), ptr(g), ptr(g0), ptr(g1), nb, C, H0, W0, H1, W1,
+                                 1 if symmetric else 0, ptr(ws), nws, stream_ptr(dev))
     return g0, g1
 
 
@@ -128,8 +126,7 @@ def corr_volume(feat0, feat1, with_flow=False):
     _, _, H1, W1 = f1.shape
     vol = torch.empty((B, H1, W1, H0, W0), device=dev, dtype=torch.float32)
     flow = torch.empty((B, 2, H0, W0), device=dev, dtype=torch.float32) if with_flow else None
-    check(_L().gfn_corr_volume_fwd(ptr(f0), ptr(f1), ptr(vol), ptr(flow), B, C, H0, W0, H1, W1, stream_ptr(dev)),
-          "gfn_corr_volume_fwd")
+    _L().gfn_corr_volume_fwd(ptr(f0), ptr(f1), ptr(vol), ptr(flow), B, C, H0, W0, H1, W1, stream_ptr(dev))
     return (vol, flow) if with_flow else vol
 
 
@@ -139,7 +136,7 @@ def pos_embed(corr_vol):
     v = f32c(corr_vol)
     B, H1, W1, H0, W0 = v.shape
     flow = torch.empty((B, 2, H0, W0), device=dev, dtype=torch.float32)
-    check(_L().gfn_pos_embed_fwd(ptr(v), ptr(flow), B, H0, W0, H1, W1, stream_ptr(dev)), "gfn_pos_embed_fwd")
+    _L().gfn_pos_embed_fwd(ptr(v), ptr(flow), B, H0, W0, H1, W1, stream_ptr(dev))
     return flow
 
 
@@ -193,16 +190,15 @@ def _refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fac
     else:
         d = torch.empty((B, CH, G, G), device=dev, dtype=torch.float32)
     st = stream_ptr(dev)
-    mode = (1 if symmetric else 0) | (2 if keep else 0)  # include/gfnet_hip.h: GFN_RI_KEEP_GRID_FEATURE
+    mode = (1 if symmetric else 0) | (_lib.RI_KEEP_GRID_FEATURE if keep else 0)
     disp_scale = float(40 / 32 * scale_factor)
     ri_args = (ptr(x), ptr(y), dtx, ptr(fl), ptr(w), ptr(bvec), ptr(d), CH * G * G, B, C, Hs, Ws, G, Dd, disp_scale, mode)
     if general:  # the per-tap kernels of every mode: no tile plan, no scratch
-        check(_L().gfn_refiner_input_mode_fwd_dt(*ri_args, sm, st), "gfn_refiner_input_mode_fwd_dt")
+        _L().gfn_refiner_input_mode_fwd_dt(*ri_args, sm, st)
         if corr_in_other:
             out = d[:, 2 * C + Dd:]
-            check(_L().gfn_local_corr_mode_fwd(ptr(d), CH * G * G, ptr(y), ptr(x) if symmetric else None, dtx, ptr(fl), c_vp(out.data_ptr()),
-                                               CH * G * G, B, C, G, Hs, Ws, r, 0, Hs, Ws, sm, _lib.PADDING_MODES["zeros"], st),
-                  "gfn_local_corr_mode_fwd")
+            _L().gfn_local_corr_mode_fwd(ptr(d), CH * G * G, ptr(y), ptr(x) if symmetric else None, dtx, ptr(fl), c_vp(out.data_ptr()),
+                                         CH * G * G, B, C, G, Hs, Ws, r, 0, Hs, Ws, sm, _lib.PADDING_MODES["zeros"], st)
         return d, y, fl, w
     # shapes the lean local-correlation path takes are planned inside the refiner-input launch (both only read the flow)
     plans = FUSE_PLAN and corr_in_other and bool(_L().gfn_local_corr_plans(C, Hs, Ws, G, r, dtx))
@@ -210,16 +206,16 @@ def _refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fac
         nscr = int(_L().gfn_local_corr_scratch_bytes(B, G))
         scr = _lib.scratch(dev, nscr)
     if plans:
-        check(_L().gfn_refiner_input_plan_fwd_dt(*ri_args, r, ptr(scr), nscr, st), "gfn_refiner_input_plan_fwd")
+        _L().gfn_refiner_input_plan_fwd_dt(*ri_args, r, ptr(scr), nscr, st)
     else:
-        check(_L().gfn_refiner_input_fwd_dt(*ri_args, st), "gfn_refiner_input_fwd")
+        _L().gfn_refiner_input_fwd_dt(*ri_args, st)
     if corr_in_other:
         out = d[:, 2 * C + Dd:]
         name = f"local_corr_c{C}_h{Hs}_g{G}_r{r}"
-        check(_timed(name, lambda: _L().gfn_local_corr_fwd_dt(ptr(d), CH * G * G, ptr(y), ptr(x) if symmetric else None, dtx, ptr(fl),
-                                                              c_vp(out.data_ptr()), CH * G * G, B, C, G, Hs, Ws, r, 0, Hs, Ws,
-                                                              (8 if plans else 0) | (4 if LOCAL_CORR_FP32 and r >= 5 else 0),
-                                                              ptr(scr), nscr, st)), "gfn_local_corr_fwd")
+        _timed(name, lambda: _L().gfn_local_corr_fwd_dt(ptr(d), CH * G * G, ptr(y), ptr(x) if symmetric else None, dtx, ptr(fl),
+                                                        c_vp(out.data_ptr()), CH * G * G, B, C, G, Hs, Ws, r, 0, Hs, Ws,
+                                                        (8 if plans else 0) | (4 if LOCAL_CORR_FP32 and r >= 5 else 0),
+                                                        ptr(scr), nscr, st))
         if kernel_counters is not None:
             hdr = scr[:8].cpu()  # synchronises; header layout: csrc/local_corr.hip kTodoHdr
             kernel_counters.setdefault(name, []).append((int(hdr[3]), int(hdr[5]), int(hdr[7])))
@@ -247,9 +243,8 @@ def refiner_input_bwd(grad_d, y, flow, disp_w, local_radius, scale_factor=1.0, c
     if n_x and corr_in_other:
         gk = g[:, 2 * C + Dd:]
         gf0 = torch.empty((B, C, G, G), device=dev, dtype=torch.float32)
-        check(_L().gfn_local_corr_mode_bwd_f0(c_vp(gk.data_ptr()), CH * G * G, ptr(f32c(y)), None, ptr(fl), ptr(gf0), C * G * G, B, C, G,
-                                              Hs, Ws, r, 0, Hs, Ws, _lib.SAMPLE_MODES["bilinear"], _lib.PADDING_MODES["zeros"], st),
-              "gfn_local_corr_mode_bwd_f0")
+        _L().gfn_local_corr_mode_bwd_f0(c_vp(gk.data_ptr()), CH * G * G, ptr(f32c(y)), None, ptr(fl), ptr(gf0), C * G * G, B, C, G,
+                                        Hs, Ws, r, 0, Hs, Ws, _lib.SAMPLE_MODES["bilinear"], _lib.PADDING_MODES["zeros"], st)
 
     def out(wanted, *shape):
         return torch.empty(shape, device=dev, dtype=torch.float32) if wanted else None
@@ -258,8 +253,8 @@ def refiner_input_bwd(grad_d, y, flow, disp_w, local_radius, scale_factor=1.0, c
     dw, db = out(n_w, Dd, 2), out(n_b, Dd)
     nscr = int(_L().gfn_refiner_input_bwd_scratch_bytes(B, G, Dd)) if (n_w or n_b) else 0
     scr = torch.empty(nscr, device=dev, dtype=torch.uint8) if nscr > 0 else None  # (not the per-stream scratch: its header stays zeroed)
-    check(_L().gfn_refiner_input_bwd(ptr(g), CH * G * G, ptr(y), dt, ptr(fl), ptr(w), ptr(gf0), ptr(dx), ptr(dy), ptr(dfl), ptr(dw), ptr(db),
-                                     B, C, Hs, Ws, G, Dd, K, float(40 / 32 * scale_factor), ptr(scr), nscr, st), "gfn_refiner_input_bwd")
+    _L().gfn_refiner_input_bwd(ptr(g), CH * G * G, ptr(y), dt, ptr(fl), ptr(w), ptr(gf0), ptr(dx), ptr(dy), ptr(dfl), ptr(dw), ptr(db),
+                               B, C, Hs, Ws, G, Dd, K, float(40 / 32 * scale_factor), ptr(scr), nscr, st)
     return dx, dy, dfl, dw, db
 
 
@@ -297,8 +292,7 @@ def grid_sample(x, grid, mode="bilinear", padding_mode="zeros"):
     if tuple(g.shape) != (B, Ho, Wo, 2):
         raise ValueError(f"grid_sample: grid must be (B,Ho,Wo,2) with B={B}, got {tuple(g.shape)}")
     out = torch.empty((B, C, Ho, Wo), device=dev, dtype=torch.float32)
-    check(_L().gfn_grid_sample_mode_fwd(ptr(x), dtx, ptr(g), ptr(out), C * Ho * Wo, B, C, H, W, Ho, Wo, sm, pm, stream_ptr(dev)),
-          "gfn_grid_sample_mode_fwd")
+    _L().gfn_grid_sample_mode_fwd(ptr(x), dtx, ptr(g), ptr(out), C * Ho * Wo, B, C, H, W, Ho, Wo, sm, pm, stream_ptr(dev))
     return out
 
 
@@ -309,7 +303,7 @@ def interpolate_bilinear(x, size):
     B, C, H, W = x.shape
     Ho, Wo = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
     out = torch.empty((B, C, Ho, Wo), device=dev, dtype=torch.float32)
-    check(_L().gfn_interp_bilinear_fwd(ptr(x), ptr(out), B * C, H, W, Ho, Wo, stream_ptr(dev)), "gfn_interp_bilinear_fwd")
+    _L().gfn_interp_bilinear_fwd(ptr(x), ptr(out), B * C, H, W, Ho, Wo, stream_ptr(dev))
     return out
 
 
@@ -325,8 +319,7 @@ def interpolate_bilinear_pair(a, b, size):
     Ho, Wo = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
     oa = torch.empty((B, Ca, Ho, Wo), device=dev, dtype=torch.float32)
     ob = torch.empty((B, Cb, Ho, Wo), device=dev, dtype=torch.float32)
-    check(_L().gfn_interp_bilinear_pair_fwd(ptr(a), ptr(oa), B * Ca, ptr(b), ptr(ob), B * Cb, H, W, Ho, Wo, stream_ptr(dev)),
-          "gfn_interp_bilinear_pair_fwd")
+    _L().gfn_interp_bilinear_pair_fwd(ptr(a), ptr(oa), B * Ca, ptr(b), ptr(ob), B * Cb, H, W, Ho, Wo, stream_ptr(dev))
     return oa, ob
 
 
@@ -342,9 +335,8 @@ def flow_update_(flow, certainty, delta, disp_prev, scale, W0, H0, zero_small=Tr
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError("flow_update_: flow/certainty/disp_prev must be contiguous fp32 (updated in place)")
     dl = f32c(delta)
-    check(_L().gfn_flow_update_fwd(ptr(flow), ptr(certainty), ptr(dl), dl.shape[1] * G * G, ptr(disp_prev), B, G, int(scale),
-                                   int(W0), int(H0), 1 if zero_small else 0, 1 if first_iteration else 0, stream_ptr(dev)),
-          "gfn_flow_update_fwd")
+    _L().gfn_flow_update_fwd(ptr(flow), ptr(certainty), ptr(dl), dl.shape[1] * G * G, ptr(disp_prev), B, G, int(scale),
+                             int(W0), int(H0), 1 if zero_small else 0, 1 if first_iteration else 0, stream_ptr(dev))
     return flow, certainty
 
 
@@ -385,14 +377,13 @@ def _flow_update(flow, certainty, d_flow, d_cert, disp_prev, scale, W0, H0, zero
         Gn = int(size_next)
         fn = torch.empty((B, 2, Gn, Gn), device=dev, dtype=torch.float32)
         cn = torch.empty((B, 1, Gn, Gn), device=dev, dtype=torch.float32)
-        check(_L().gfn_flow_update_resize_fwd(ptr(fi), ptr(ci), ptr(fo), ptr(co), c_vp(df.data_ptr()), df_bs, c_vp(dc.data_ptr()), dc_bs,
-                                              ptr(disp_prev), B, G, int(scale), int(W0), int(H0), 1 if zero_small else 0,
-                                              1 if first_iteration else 0, ptr(fn), ptr(cn), Gn, stream_ptr(dev)),
-              "gfn_flow_update_resize_fwd")
+        _L().gfn_flow_update_resize_fwd(ptr(fi), ptr(ci), ptr(fo), ptr(co), c_vp(df.data_ptr()), df_bs, c_vp(dc.data_ptr()), dc_bs,
+                                        ptr(disp_prev), B, G, int(scale), int(W0), int(H0), 1 if zero_small else 0,
+                                        1 if first_iteration else 0, ptr(fn), ptr(cn), Gn, stream_ptr(dev))
         return fo, co, fn, cn
-    check(_L().gfn_flow_update_out_fwd(ptr(fi), ptr(ci), ptr(fo), ptr(co), c_vp(df.data_ptr()), df_bs, c_vp(dc.data_ptr()), dc_bs,
-                                       ptr(disp_prev), B, G, int(scale), int(W0), int(H0), 1 if zero_small else 0,
-                                       1 if first_iteration else 0, stream_ptr(dev)), "gfn_flow_update_out_fwd")
+    _L().gfn_flow_update_out_fwd(ptr(fi), ptr(ci), ptr(fo), ptr(co), c_vp(df.data_ptr()), df_bs, c_vp(dc.data_ptr()), dc_bs,
+                                 ptr(disp_prev), B, G, int(scale), int(W0), int(H0), 1 if zero_small else 0,
+                                 1 if first_iteration else 0, stream_ptr(dev))
     return fo, co
 
 
@@ -453,12 +444,12 @@ def match_post(flow, certainty, cert16=None, symmetric=True):
     Gc = c16.shape[-1] if c16 is not None else 0
     warp = torch.empty((B, G, Gw, 4), device=dev, dtype=torch.float32)
     cout = torch.empty((B, G, Gw), device=dev, dtype=torch.float32)
-    check(_L().gfn_match_post_fwd(ptr(fl), ptr(ce), ptr(c16), ptr(warp), ptr(cout), B, G, Gc, 1 if symmetric else 0,
-                                  stream_ptr(dev)), "gfn_match_post_fwd")
+    _L().gfn_match_post_fwd(ptr(fl), ptr(ce), ptr(c16), ptr(warp), ptr(cout), B, G, Gc, 1 if symmetric else 0,
+                            stream_ptr(dev))
     return warp, cout
 
 
-KDE_CULL_MIN_STD = 0.0625  # GFN_KDE_SORTED_MIN_STD (include/gfnet_hip.h)
+KDE_CULL_MIN_STD = _lib.KDE_SORTED_MIN_STD
 
 
 def kde_density(x, y=None, std=0.1, y_row_stride=None, cull=None, round_fp16=False):
@@ -504,8 +495,8 @@ def kde_density(x, y=None, std=0.1, y_row_stride=None, cull=None, round_fp16=Fal
     out = torch.empty((Bt, N), device=dev, dtype=torch.float32)
     nscr = int(_L().gfn_kde_scratch_floats(Bt, N, M, D))
     scratch = torch.empty((max(nscr, 4),), device=dev, dtype=torch.float32)
-    check(_L().gfn_kde_density(ptr(xs), ptr(ys), ptr(out), Bt, N, M, D, rs, bs, float(std), ptr(scratch), nscr,
-                               stream_ptr(dev)), "gfn_kde_density")
+    _L().gfn_kde_density(ptr(xs), ptr(ys), ptr(out), Bt, N, M, D, rs, bs, float(std), ptr(scratch), nscr,
+                         stream_ptr(dev))
     return out[0] if squeeze else out
 
 
@@ -517,7 +508,7 @@ def _morton_sorted(pts, dev, long_perm=True):
     out = torch.empty_like(pts)
     perm = torch.empty((Bt, N), device=dev, dtype=torch.int32)
     tmp = torch.empty((Bt, N), device=dev, dtype=torch.int32)
-    check(_L().gfn_kde_morton_sort(ptr(pts), ptr(out), ptr(perm), ptr(tmp), Bt, N, stream_ptr(dev)), "gfn_kde_morton_sort")
+    _L().gfn_kde_morton_sort(ptr(pts), ptr(out), ptr(perm), ptr(tmp), Bt, N, stream_ptr(dev))
     return out, (perm.long() if long_perm else perm)
 
 
@@ -530,8 +521,8 @@ def _kde_culled(xs, ys, std, same, dev, round_fp16=False):
     nscr = int(_L().gfn_kde_sorted_scratch_floats(Bt, N, M))
     scratch = torch.empty((nscr,), device=dev, dtype=torch.float32)
     # perm: the densities are written straight back in the caller's order
-    check(_L().gfn_kde_density_sorted(ptr(xsort), ptr(ysort), ptr(out), ptr(perm), Bt, N, M, float(std), 1 if round_fp16 else 0, ptr(scratch), nscr,
-                                      stream_ptr(dev)), "gfn_kde_density_sorted")
+    _L().gfn_kde_density_sorted(ptr(xsort), ptr(ysort), ptr(out), ptr(perm), Bt, N, M, float(std), 1 if round_fp16 else 0, ptr(scratch), nscr,
+                                stream_ptr(dev))
     return out
 
 
@@ -540,7 +531,7 @@ def threshold_certainty(certainty, thresh):
     dev = require_gpu(certainty)
     c = f32c(certainty)
     out = torch.empty_like(c)
-    check(_L().gfn_threshold_certainty(ptr(c), ptr(out), c.numel(), float(thresh), stream_ptr(dev)), "gfn_threshold_certainty")
+    _L().gfn_threshold_certainty(ptr(c), ptr(out), c.numel(), float(thresh), stream_ptr(dev))
     return out
 
 
@@ -550,8 +541,7 @@ def balance_weights(density, min_density=10.0, floor_p=1e-7, round_fp16=False):
     dev = require_gpu(density)
     d = f32c(density)
     p = torch.empty_like(d)
-    check(_L().gfn_balance_weights(ptr(d), ptr(p), d.numel(), float(min_density), float(floor_p), 1 if round_fp16 else 0, stream_ptr(dev)),
-          "gfn_balance_weights")
+    _L().gfn_balance_weights(ptr(d), ptr(p), d.numel(), float(min_density), float(floor_p), 1 if round_fp16 else 0, stream_ptr(dev))
     return p
 
 
@@ -567,8 +557,8 @@ def gather_matches(matches, certainty, idx, one_above=None):
     idx = idx.contiguous()
     om = torch.empty((Bt, K, 4), device=dev, dtype=torch.float32)
     oc = torch.empty((Bt, K), device=dev, dtype=torch.float32)
-    check(_L().gfn_gather_matches(ptr(m), ptr(c), ptr(idx), ptr(om), ptr(oc), Bt, N, K,
-                                  float("inf") if one_above is None else float(one_above), stream_ptr(dev)), "gfn_gather_matches")
+    _L().gfn_gather_matches(ptr(m), ptr(c), ptr(idx), ptr(om), ptr(oc), Bt, N, K,
+                            float("inf") if one_above is None else float(one_above), stream_ptr(dev))
     return om, oc
 
 
@@ -586,9 +576,8 @@ def sample_without_replacement(weights, num_samples, seed=None, one_above=None):
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     out = torch.empty((Bt, K), device=dev, dtype=torch.int64)
     scratch = torch.empty((Bt * (N + 2048),), device=dev, dtype=torch.int32)
-    check(_L().gfn_sample_without_replacement(ptr(w), N, ptr(out), ptr(scratch), Bt, N, K, int(seed) & (2 ** 64 - 1),
-                                              float("inf") if one_above is None else float(one_above), stream_ptr(dev)),
-          "gfn_sample_without_replacement")
+    _L().gfn_sample_without_replacement(ptr(w), N, ptr(out), ptr(scratch), Bt, N, K, int(seed) & (2 ** 64 - 1),
+                                        float("inf") if one_above is None else float(one_above), stream_ptr(dev))
     return out
 
 
@@ -598,8 +587,7 @@ def convert_matches(matches, wA, hA, wB, hB):
     m = f32c(matches)
     out = torch.empty_like(m)
     n = m.numel() // 4
-    check(_L().gfn_convert_matches(ptr(m), ptr(out), n, float(wA), float(hA), float(wB), float(hB), stream_ptr(dev)),
-          "gfn_convert_matches")
+    _L().gfn_convert_matches(ptr(m), ptr(out), n, float(wA), float(hA), float(wB), float(hB), stream_ptr(dev))
     return out
 
 
@@ -622,9 +610,8 @@ def find_homography(pts, thresh=3.0, iters=2000, seed=0, lm_iters=10, stage=0, r
     mask = torch.empty((Bt, N), device=dev, dtype=torch.uint8) if return_mask else None
     nb = int(_L().gfn_homography_scratch_bytes(Bt, int(iters)))
     scratch = torch.empty((nb // 8 + 1,), device=dev, dtype=torch.float64)
-    check(_L().gfn_homography_ransac_ex(ptr(p), Bt, N, float(thresh), int(iters), float(confidence or 0.0), int(seed), int(lm_iters),
-                                        int(stage), ptr(H), ptr(ninl), ptr(best), ptr(mask), ptr(used), ptr(scratch), nb, stream_ptr(dev)),
-          "gfn_homography_ransac")
+    _L().gfn_homography_ransac_ex(ptr(p), Bt, N, float(thresh), int(iters), float(confidence or 0.0), int(seed), int(lm_iters),
+                                  int(stage), ptr(H), ptr(ninl), ptr(best), ptr(mask), ptr(used), ptr(scratch), nb, stream_ptr(dev))
     out = (H, ninl, best)
     if return_mask:
         out = out + (mask,)
@@ -642,7 +629,7 @@ def homography_dlt(pts, weight=None):
     w = f32c(weight).reshape(Bt, N) if weight is not None else None
     H = torch.empty((Bt, 3, 3), device=dev, dtype=torch.float64)
     ok = torch.empty((Bt,), device=dev, dtype=torch.int32)
-    check(_L().gfn_homography_dlt(ptr(p), ptr(w), Bt, N, ptr(H), ptr(ok), stream_ptr(dev)), "gfn_homography_dlt")
+    _L().gfn_homography_dlt(ptr(p), ptr(w), Bt, N, ptr(H), ptr(ok), stream_ptr(dev))
     return H, ok
 
 
@@ -666,8 +653,8 @@ def resize_normalise(im, size, mode="bicubic", mean=IMAGENET_MEAN, std=IMAGENET_
     Ho, Wo = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
     out = torch.empty((B, 3, Ho, Wo), device=dev, dtype=torch.float32)
     m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-    check(_L().gfn_resize_normalize_fwd(ptr(x), C * H * W, ptr(out), B, H, W, Ho, Wo, 1 if mode == "bicubic" else 0, m3, s3,
-                                        stream_ptr(dev)), "gfn_resize_normalize_fwd")
+    _L().gfn_resize_normalize_fwd(ptr(x), C * H * W, ptr(out), B, H, W, Ho, Wo, 1 if mode == "bicubic" else 0, m3, s3,
+                                  stream_ptr(dev))
     return out
 
 
@@ -680,8 +667,8 @@ def conv_block_pack(dw_w, dw_b, bn_alpha, bn_beta, pw_w, pw_b):
     al, be, pb = f32c(bn_alpha), f32c(bn_beta), f32c(pw_b)
     db = f32c(dw_b) if dw_b is not None else None
     packed = torch.empty(int(_L().gfn_conv_block_packed_floats(C, M)), device=dev, dtype=torch.float32)
-    check(_L().gfn_conv_block_pack(ptr(dw_w), ptr(db) if db is not None else None, ptr(al), ptr(be), ptr(pw_w), ptr(pb), ptr(packed),
-                                   C, M, stream_ptr(dev)), "gfn_conv_block_pack")
+    _L().gfn_conv_block_pack(ptr(dw_w), ptr(db) if db is not None else None, ptr(al), ptr(be), ptr(pw_w), ptr(pb), ptr(packed),
+                             C, M, stream_ptr(dev))
     return packed
 
 
@@ -701,9 +688,9 @@ def conv_block(x, packed, M, out=None, variant=0, t_scratch=None):
         out = torch.empty((B, M, G, G), device=dev, dtype=torch.float32)
     if ((variant & 1) or G % 4) and t_scratch is None:
         t_scratch = torch.empty_like(x)
-    check(_timed("conv_block_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_fwd(
+    _timed("conv_block_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_fwd(
         ptr(x), ptr(packed), ptr(out), ptr(t_scratch) if t_scratch is not None else None, B, C, M, G, int(variant),
-        stream_ptr(dev))), "gfn_conv_block_fwd")
+        stream_ptr(dev)))
     return out
 
 
@@ -730,9 +717,9 @@ def conv_block_half(x, packed, C, M, out=None, out_half=True):
     dt = torch.float16 if out_half else torch.float32
     if out is None or tuple(out.shape) != shape or out.dtype != dt:
         out = torch.empty(shape, device=dev, dtype=dt)
-    check(_timed("conv_block_half_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_half_fwd(
+    _timed("conv_block_half_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_half_fwd(
         ptr(x), _lib.GFN_F16 if x_half else _lib.GFN_F32, ptr(packed), ptr(out), _lib.GFN_F16 if out_half else _lib.GFN_F32, B, C, M, G,
-        stream_ptr(dev))), "gfn_conv_block_half_fwd")
+        stream_ptr(dev)))
     return out
 
 
@@ -750,8 +737,8 @@ def pointwise_conv(t, w, bias, out=None):
     M = bias.shape[0]
     if out is None:
         out = torch.empty((B, M, G, G2), device=dev, dtype=torch.float32)
-    check(_timed("pw_m%d_k%d_g%d" % (M, K, G), lambda: _L().gfn_pointwise_conv_fwd(
-        ptr(w), ptr(bias), ptr(t), ptr(out), B, M, K, G * G2, stream_ptr(dev))), "gfn_pointwise_conv_fwd")
+    _timed("pw_m%d_k%d_g%d" % (M, K, G), lambda: _L().gfn_pointwise_conv_fwd(
+        ptr(w), ptr(bias), ptr(t), ptr(out), B, M, K, G * G2, stream_ptr(dev)))
     return out
 
 
@@ -792,10 +779,10 @@ def conv_block_train_fwd(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, runnin
     mean, invstd = torch.empty(C, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
     nws = int(_L().gfn_conv_block_train_ws_bytes(B, C, M, G, 0))
     ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
-    check(_timed("conv_block_train_fwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_fwd(
+    _timed("conv_block_train_fwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_fwd(
         ptr(x), ptr(dw_w), ptr(dw_b.contiguous()) if dw_b is not None else None, ptr(bn_weight.contiguous()), ptr(bn_bias.contiguous()),
         ptr(running_mean), ptr(running_var), ptr(pw_w), ptr(pw_b.contiguous()), ptr(u), ptr(mean), ptr(invstd), ptr(y), B, C, M, G,
-        float(momentum), float(eps), ptr(ws), nws, stream_ptr(dev))), "gfn_conv_block_train_fwd")
+        float(momentum), float(eps), ptr(ws), nws, stream_ptr(dev)))
     return y, u, mean, invstd
 
 
@@ -824,10 +811,9 @@ def conv_block_train_bwd(gy, x, u, mean, invstd, dw_w, bn_weight, bn_bias, pw_w,
     if mask:
         nws = int(_L().gfn_conv_block_train_ws_bytes(B, C, M, G, 1))
         ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
-        check(_timed("conv_block_train_bwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_bwd(
+        _timed("conv_block_train_bwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_bwd(
             ptr(gy), ptr(x), ptr(u), ptr(mean), ptr(invstd), ptr(dw_w), ptr(bn_weight), ptr(bn_bias), ptr(pw_w), ptr(gx), ptr(d_dww),
-            ptr(d_dwb), ptr(d_g), ptr(d_b), ptr(d_pww), ptr(d_pwb), B, C, M, G, mask, ptr(ws), nws, stream_ptr(dev))),
-            "gfn_conv_block_train_bwd")
+            ptr(d_dwb), ptr(d_g), ptr(d_b), ptr(d_pww), ptr(d_pwb), B, C, M, G, mask, ptr(ws), nws, stream_ptr(dev)))
     grads = (gx, d_dww, d_dwb, d_g, d_b, d_pww, d_pwb)
     return tuple(g if want else None for g, want in zip(grads, (n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb)))
 
@@ -925,10 +911,10 @@ def robust_loss_scale_fwd(flows, certs, H, ext_a, ext_b, a, cs, ce_weight, itera
     epe = torch.empty((B, h, w), device=dev, dtype=torch.float32) if want_epe else None
     nws = int(_L().gfn_robust_loss_ws_bytes(B, h, w, len(flows)))
     ws = _lib.scratch(dev, nws, pool="robust_loss")  # (not the local correlation's: its counters must stay zero)
-    check(_timed("robust_loss_fwd_%dx%d" % (h, w), lambda: _L().gfn_robust_loss_fwd(
+    _timed("robust_loss_fwd_%dx%d" % (h, w), lambda: _L().gfn_robust_loss_fwd(
         _ptr_array(flows), _ptr_array(certs), len(flows), ptr(H), ptr(im_A_coords), ptr(prev_epe), ph, pw, float(prev_thresh), ptr(epe),
         ptr(stats), B, h, w, float(ext_a), float(ext_b), float(a), float(cs), float(ce_weight), float(iteration_base), float(pck_thresh),
-        ptr(ws), nws, stream_ptr(dev))), "gfn_robust_loss_fwd")
+        ptr(ws), nws, stream_ptr(dev)))
     return stats, epe
 
 
@@ -948,10 +934,10 @@ def robust_loss_scale_bwd(grad_out, stats, flows, certs, H, ext_a, ext_b, a, cs,
     g_certs = [torch.empty_like(c) if nc else None for c, nc in zip(certs, need_cert)]
     mask = sum(1 << k for k in range(n) if need_flow[k]) | sum(1 << (_lib.RL_MAX_ITR + k) for k in range(n) if need_cert[k])
     if mask:
-        check(_timed("robust_loss_bwd_%dx%d" % (h, w), lambda: _L().gfn_robust_loss_bwd(
+        _timed("robust_loss_bwd_%dx%d" % (h, w), lambda: _L().gfn_robust_loss_bwd(
             _ptr_array(flows), _ptr_array(certs), n, ptr(H), ptr(im_A_coords), ptr(prev_epe), ph, pw, float(prev_thresh), ptr(stats),
             ptr(grad_out), _ptr_array(g_flows), _ptr_array(g_certs), mask, B, h, w, float(ext_a), float(ext_b), float(a), float(cs),
-            float(ce_weight), float(iteration_base), stream_ptr(dev))), "gfn_robust_loss_bwd")
+            float(ce_weight), float(iteration_base), stream_ptr(dev)))
     return g_flows, g_certs
 
 
@@ -970,8 +956,8 @@ def gt_warp_homography(H, h, w, ext_a, ext_b, im_A_coords=None, normalized=True,
     out = torch.empty((B, h, w, 2), device=dev, dtype=torch.float32)
     prob = torch.empty((B, h, w), device=dev, dtype=torch.float32)
     x1n = torch.empty((B, h, w, 2), device=dev, dtype=torch.float32) if return_x1_n else None
-    check(_L().gfn_gt_warp_homography_fwd(ptr(H), ptr(im_A_coords), ptr(out), ptr(prob), ptr(x1n), B, h, w, float(ext_a), float(ext_b),
-                                          1 if normalized else 0, stream_ptr(dev)), "gfn_gt_warp_homography_fwd")
+    _L().gfn_gt_warp_homography_fwd(ptr(H), ptr(im_A_coords), ptr(out), ptr(prob), ptr(x1n), B, h, w, float(ext_a), float(ext_b),
+                                    1 if normalized else 0, stream_ptr(dev))
     return out, prob, x1n
 
 

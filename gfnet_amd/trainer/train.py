@@ -139,10 +139,9 @@ class FusedAdamWStep(torch.optim.Optimizer):
     # ---- host side --------------------------------------------------------------------------------------------------------------
     def _launch(self, n):
         ptr = _lib.ptr
-        code = _lib.lib().gfn_train_step(ptr(self._tensor_table), n, ptr(self._chunk_table), self._n_chunks, ptr(self._dev_state), self.max_norm,
-                                         self.growth_factor, self.backoff_factor, self.growth_interval, int(self.zero_grads),
-                                         ptr(self._stats), ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr(self._device))
-        _lib.check(code, "train_step")
+        _lib.checked().gfn_train_step(ptr(self._tensor_table), n, ptr(self._chunk_table), self._n_chunks, ptr(self._dev_state), self.max_norm,
+                                      self.growth_factor, self.backoff_factor, self.growth_interval, int(self.zero_grads),
+                                      ptr(self._stats), ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr(self._device))
 
     def _check_param(self, p):
         if not p.is_cuda:

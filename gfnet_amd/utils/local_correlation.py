@@ -74,7 +74,7 @@ def _forward(featuremap_size, feature0, feature1, local_radius, num_grid, paddin
             raise ValueError("out must be a fp32 (B,K,G,G) view with contiguous (K,G,G) planes")
         res = out
         out_bs = out.stride(0) if B > 1 else K * G * G
-    L = _lib.lib()
+    L = _lib.checked()
     st = _lib.stream_ptr(dev)
     if not general:  # the tiled routes exist for bilinear + zeros only
         from .. import ops  # (LOCAL_CORR_FP32: fp32 FMA arithmetic at every radius instead of the matrix-core kernel for r >= 5)
@@ -88,9 +88,9 @@ def _forward(featuremap_size, feature0, feature1, local_radius, num_grid, paddin
         args = (_lib.ptr(f0), f0_bs, _lib.ptr(f1l), None, f1_dt, _lib.ptr(fl), _lib.c_vp(o.data_ptr()), out_bs, B, c, G, hh, ww, r,
                 1 if grid_based_correlation else 0, h, w)
         if general:
-            _lib.check(L.gfn_local_corr_mode_fwd(*args, sm, pm, st), "gfn_local_corr_mode_fwd")
+            L.gfn_local_corr_mode_fwd(*args, sm, pm, st)
         else:
-            _lib.check(L.gfn_local_corr_fwd_dt(*args, variant, _lib.ptr(scr), nscr, st), "gfn_local_corr_fwd")
+            L.gfn_local_corr_fwd_dt(*args, variant, _lib.ptr(scr), nscr, st)
     if out is None and ret_dtype != torch.float32:
         res = res.to(ret_dtype)
     return res
@@ -98,12 +98,12 @@ def _forward(featuremap_size, feature0, feature1, local_radius, num_grid, paddin
 
 def _pyramid(f1, B, c, h, w, num_level, dev):
     """feature1 and its 2x average-pooled levels (local_correlation.py:71), as the forward builds them."""
-    L = _lib.lib()
+    L = _lib.checked()
     st = _lib.stream_ptr(dev)
     levels, hh, ww = [(f1, h, w)], h, w
     for _ in range(1, num_level):
         pooled = torch.empty((B, c, hh // 2, ww // 2), device=dev, dtype=torch.float32)
-        _lib.check(L.gfn_avg_pool2(_lib.ptr(f1), _lib.ptr(pooled), B * c, hh, ww, st), "gfn_avg_pool2")
+        L.gfn_avg_pool2(_lib.ptr(f1), _lib.ptr(pooled), B * c, hh, ww, st)
         f1, hh, ww = pooled, hh // 2, ww // 2
         levels.append((f1, hh, ww))
     return levels
@@ -128,14 +128,13 @@ class _LocalCorrelationFn(torch.autograd.Function):
         K1 = (2 * r + 1) ** 2
         g = _lib.f32c(grad_out)
         fl = _lib.f32c(flow) if has_flow else None
-        L = _lib.lib()
+        L = _lib.checked()
         st = _lib.stream_ptr(dev)
         total = None
         for level, (f1, hh, ww) in enumerate(_pyramid(_lib.f32c(feature1), B, c, h, w, num_level, dev)):
             gl = g[:, level * K1:(level + 1) * K1]
             gf0 = torch.empty((B, c, G, G), device=dev, dtype=torch.float32)
-            _lib.check(L.gfn_local_corr_mode_bwd_f0(_lib.c_vp(gl.data_ptr()), g.stride(0), _lib.ptr(f1), None, _lib.ptr(fl), _lib.ptr(gf0),
-                                                    c * G * G, B, c, G, hh, ww, r, 1 if grid_based else 0, h, w, sm, pm, st),
-                       "gfn_local_corr_mode_bwd_f0")
+            L.gfn_local_corr_mode_bwd_f0(_lib.c_vp(gl.data_ptr()), g.stride(0), _lib.ptr(f1), None, _lib.ptr(fl), _lib.ptr(gf0),
+                                         c * G * G, B, c, G, hh, ww, r, 1 if grid_based else 0, h, w, sm, pm, st)
             total = gf0 if total is None else total + gf0
         return total.to(dtype), None, None, None, None, None, None, None, None, None

@@ -508,6 +508,7 @@ int gfn_conv_block_train_bwd(const float *gy, const float *x, const float *u, co
 #define GFN_RL_STAT_CELLS 5
 #define GFN_RL_STAT_RHO_SUM 6
 #define GFN_RL_STATS 8
+#define GFN_RL_MAX_ITR 8 /* the most iterations a scale may have: the length of the host pointer arrays, the stride of `need`'s halves */
 int64_t gfn_robust_loss_ws_bytes(int B, int h, int w, int n_itr);
 int gfn_robust_loss_fwd(const float *const *flows, const float *const *certs, int n_itr, const float *H, const float *im_A_coords,
                         const float *prev_epe, int ph, int pw, double prev_thresh, float *epe_last, float *stats, int B, int h, int w,

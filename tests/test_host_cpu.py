@@ -3,6 +3,7 @@
 network mirror's parameter layout against the reference's state_dict keys, the no-CPU-fallback rule."""
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -21,7 +22,12 @@ def test_library_exports_every_declared_symbol():
     L = _lib.lib()
     for name in sorted(declared):
         assert hasattr(L, name), f"{name} declared in include/gfnet_hip.h but not exported"
+    # the binding's parser against this test's own scan of the names: a prototype it skipped would show here
     assert declared == set(_lib.exported_symbols()), declared ^ set(_lib.exported_symbols())
+    # and the library itself: its defined dynamic gfn_* symbols are exactly the declared ones, in both directions
+    syms = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--dyn-syms", "-W", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    defined = {f[7].split("@")[0] for f in (ln.split() for ln in syms.splitlines()) if len(f) == 8 and f[6] != "UND" and f[7].startswith("gfn_")}
+    assert defined == declared, defined ^ declared
     assert L.gfn_abi_version() == 1
 
 

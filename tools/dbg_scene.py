@@ -3,15 +3,15 @@ ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
 sys.path.insert(0, ROOT)
 import torch
 from gfnet_amd import _lib, ops
-orig = _lib.check
-def check(code, what):
-    orig(code, what)
-    print("ok launch", what, flush=True)
+def traced(code, fn, args):
+    _lib._raise_on_error(code, fn, args)
+    print("ok launch", fn.__name__, flush=True)
     if os.environ.get("DBG_SYNC") == "1":
         torch.cuda.synchronize()
-        print("   synced", what, flush=True)
-_lib.check = check
-ops.check = check
+        print("   synced", fn.__name__, flush=True)
+    return code
+for name in _lib.STATUS_FUNCS:
+    getattr(_lib.checked(), name).errcheck = traced
 import gfnet_amd.utils.local_correlation as lc
 from gfnet_amd._synthetic import Scene
 S, pairs = int(sys.argv[1]), int(sys.argv[2])
