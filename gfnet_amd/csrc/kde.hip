@@ -288,10 +288,13 @@ using gfn::split3;  // (h, l, ll here are its h, m, l)
 // the norms) sit in ONE accumulation so that no intermediate sum is large (a +-400 intermediate cost 4e-5 relative on a
 // term; this order 1e-5).  Padding points get ny = 1e30 (term 0).
 __global__ __launch_bounds__(256) void kde4_operands_kernel(const float *__restrict__ xs, const float *__restrict__ ys,
-                                                            bf16x8 *__restrict__ aop, bf16x8 *__restrict__ bop, int N, int M, int Mp,
+                                                            bf16x8 *__restrict__ aop, bf16x8 *__restrict__ bop,
+                                                            unsigned long long *__restrict__ colacc, int N, int M, int Mp,
                                                             int NT, int MT, int Bt) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long na = (long)Bt * NT * 32, nb = (long)Bt * MT * 32;
+    // colacc (symmetric call): the column accumulators start at 0 -- the launch has na >= Bt * N threads, which saves a memset
+    if (colacc && idx < (long)Bt * N) colacc[idx] = 0ull;
     const __bf16 one = (__bf16)1.f, zero = (__bf16)0.f;
     if (idx < na) {
         const int bt = (int)(idx / ((long)NT * 32)), n = (int)(idx - (long)bt * NT * 32);
@@ -348,18 +351,36 @@ __global__ __launch_bounds__(256) void kde4_operands_kernel(const float *__restr
 // in one accumulator per point; to keep the result independent of the order in which waves arrive they are added as
 // 2^-40 fixed-point integers (integer addition is associative; densities < 2^23 fit 64 bits), and kde_combine_kernel
 // adds the two halves.  The diagonal block p == q holds both (i,j) and (j,i) and feeds row sums only.
+//
+// Dispatch order: in the symmetric kernel the wave of query block q visits p >= q only, so a workgroup's work falls from about twice
+// the mean at the first 256 queries of a row to nothing at the last.  A (x, ms, bt) grid is handed out x fastest and bt slowest:
+// the heaviest workgroups of the last rows start when the chip is already draining (2.5 rounds of workgroups at 32 x 20000) and
+// the launch ends on them.  The grid is therefore one-dimensional and kde_wg() maps the linear id with x OUTERMOST: every row's
+// heavy workgroups go out first, the nearly empty ones fill the tail.  (The hardware promises no order; the map is a bijection
+// and waves are independent, so only the time depends on it.)
+struct KdeWg { int x, ms, bt; };
+__device__ __forceinline__ KdeWg kde_wg(unsigned id, int MS, int Bt) {
+    const unsigned r = id / (unsigned)Bt;
+    // the divisions run on the vector unit; their (uniform) results belong in scalar registers: the kernel has no VGPR to spare
+    return KdeWg{__builtin_amdgcn_readfirstlane((int)(r / (unsigned)MS)), __builtin_amdgcn_readfirstlane((int)(r % (unsigned)MS)),
+                 __builtin_amdgcn_readfirstlane((int)(id % (unsigned)Bt))};
+}
+// Column sums (SYM): a block's column value leaves as one 64-bit atomic per lane at the end of the block, and the wait for the next
+// block's operands (vmcnt(0)) then also covers that atomic's round trip.  Parking the values in a per-wave LDS ring of 8 blocks
+// and issuing them back to back behind a later block's operand prefetch, so that they retire under its MFMAs and exponentials, was
+// built and measured level on top of the map (profiles/kde_dispatch.md); it is not kept.
 constexpr float kKdeFixScale = 1099511627776.f;  // 2^40
 template <bool SYM>
 __global__ __launch_bounds__(kKdeThreads, 4) void kde4_mfma_kernel(const float *__restrict__ xs, const bf16x8 *__restrict__ aop,
                                                                 const bf16x8 *__restrict__ bop, const float *__restrict__ box,
                                                                 float *__restrict__ part, unsigned long long *__restrict__ colacc,
-                                                                int N, int Mp, int NT, int MT) {
-    const int bt = blockIdx.z;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int q0 = blockIdx.x * kKdeThreads + wave * 64;
+                                                                int N, int Mp, int NT, int MT, int MS, int Bt) {
+    const KdeWg wg = kde_wg(blockIdx.x, MS, Bt);
+    const int bt = wg.bt, ms = wg.ms;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // scalar, and q0, qblk, b0 with it
+    const int q0 = wg.x * kKdeThreads + wave * 64;
     if (q0 >= N) return;
     const int n = q0 + lane;
-    const int MS = gridDim.y, ms = blockIdx.y;
     const int nblk = (Mp + 63) >> 6;
     const int per = (nblk + MS - 1) / MS;
     const int qblk = q0 >> 6;
@@ -649,21 +670,23 @@ GFN_EXPORT int gfn_kde_density_sorted(const float *x, const float *y, float *out
     float *opbase = part + (((int64_t)Bt * 32 * N + 3) & ~(int64_t)3);
     bf16x8 *aop = reinterpret_cast<bf16x8 *>(opbase), *bop = aop + (int64_t)Bt * NT * 128;
     const long npts = (long)Bt * 32 * (NT > MT ? NT : MT);
-    hipLaunchKernelGGL(kde4_operands_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, s, xs, ys, aop, bop, N, M, Mp, NT,
-                       MT, Bt);
+    // the symmetric kernel's fixed-point column sums; kde4_operands_kernel clears them
+    unsigned long long *colacc = sym ? reinterpret_cast<unsigned long long *>(bop + (int64_t)Bt * MT * 128) : nullptr;
+    hipLaunchKernelGGL(kde4_operands_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, s, xs, ys, aop, bop, colacc, N, M, Mp,
+                       NT, MT, Bt);
+    // one-dimensional grid, unpacked by kde_wg()
+    const long nwg = (long)((N + kKdeThreads - 1) / kKdeThreads) * MS * Bt;
+    if (nwg > 0x7fffffffL) return gfn::fail(GFN_ERR_INVALID_ARG, "kde_sorted: Bt * N too large for one launch");
     if (sym) {
-        unsigned long long *colacc = reinterpret_cast<unsigned long long *>(bop + (int64_t)Bt * MT * 128);
-        if (hipMemsetAsync(colacc, 0, sizeof(unsigned long long) * (size_t)Bt * N, s) != hipSuccess)
-            return gfn::fail(GFN_ERR_LAUNCH, "kde_sorted: memset failed");
-        hipLaunchKernelGGL(kde4_mfma_kernel<true>, dim3((N + kKdeThreads - 1) / kKdeThreads, MS, Bt), dim3(kKdeThreads), 0, s, xs, aop,
-                           bop, box32, part, colacc, N, Mp, NT, MT);
+        hipLaunchKernelGGL(kde4_mfma_kernel<true>, dim3((unsigned)nwg), dim3(kKdeThreads), 0, s, xs, aop, bop, box32, part, colacc, N, Mp,
+                           NT, MT, MS, Bt);
         if (int e = gfn::check_launch("kde4_mfma_kernel")) return e;
         const long total = (long)Bt * N;
         hipLaunchKernelGGL(kde_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, colacc, perm, out, N, MS, Bt);
         return gfn::check_launch("kde_combine_kernel");
     }
-    hipLaunchKernelGGL(kde4_mfma_kernel<false>, dim3((N + kKdeThreads - 1) / kKdeThreads, MS, Bt), dim3(kKdeThreads), 0, s, xs, aop, bop,
-                       box32, dst, nullptr, N, Mp, NT, MT);
+    hipLaunchKernelGGL(kde4_mfma_kernel<false>, dim3((unsigned)nwg), dim3(kKdeThreads), 0, s, xs, aop, bop, box32, dst, nullptr, N, Mp,
+                       NT, MT, MS, Bt);
     if (int e = gfn::check_launch("kde4_mfma_kernel")) return e;
     if (MS > 1 || perm) {
         const long total = (long)Bt * N;
