@@ -32,6 +32,11 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned n) {
     return start + local;
 }
 
+// a 32x32 MFMA accumulator (corr_common.h, pw_gemm_tile.h, kde.hip), and the row of it that register r of a lane in half-wave
+// h = lane >> 5 holds (its column is lane & 31)
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
 // counter-based random bits (sample.hip, homography.hip; restated in oracle/homography_oracle.c)
 __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ULL;

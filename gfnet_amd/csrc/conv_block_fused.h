@@ -1,20 +1,17 @@
 // conv_block_fused.h -- the fused conv block (depthwise 5x5 + BatchNorm + ReLU + 1x1 conv in one kernel) of csrc/conv_stack.hip
 // and csrc/conv_stack_half.hip (the same kernel on fp16 maps).  Opens its own anonymous namespace.
 #pragma once
-#include "common.h"
+#include "pw_gemm_tile.h"  // kKT, kBN, f32x16
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kKT = 16;    // channels per K tile
 constexpr int kNP = 8;     // channel pairs per K tile
-constexpr int kBN = 128;   // cells per workgroup tile: 4 waves x 32
 constexpr int kCP2 = 64;   // floats per channel PAIR in the packed depthwise parameters
 constexpr int kMM2 = 96;   // dwords per channel PAIR in the matrix-core depthwise parameters (see PackDims::mm_off)
 

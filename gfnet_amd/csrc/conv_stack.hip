@@ -18,10 +18,11 @@
 //
 // A two-pass variant (dw5x5 kernel -> t in HBM -> GEMM kernel) computes bit-identical results; it
 // serves grids whose side is not a multiple of 4 and is the ablation/parity partner of the fused one.
+// Its GEMM is the 1x1 tile of pw_gemm_tile.h, which the training kernels (conv_stack_train.hip) run too;
+// the depthwise arithmetic both variants share is dw_finish (conv_block_fused.h).
 #include "conv_block_fused.h"
 
 namespace {
-
 
 __global__ __launch_bounds__(256) void pack_block_kernel(const float *__restrict__ dw_w, const float *__restrict__ dw_b,
                                                          const float *__restrict__ alpha, const float *__restrict__ beta,
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(256) void dw5x5_kernel(const float *__restrict__ x,
     for (int q = 0; q < VEC; ++q) dst[q] = dw_finish(acc[q], wc[50], wc[52], wc[54]);
 }
 
-// y[b] = W . t[b] + bias on the matrix core; same operands, instruction and k order as the fused kernel.
+// y[b] = W . t[b] + bias on the tile of pw_gemm_tile.h; same operands, instruction and k order as the fused kernel.
 template <int MT, bool F16>
 __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(const float *__restrict__ packed, const float *__restrict__ t,
                                                          float *__restrict__ y, int M, int K, int N) {
@@ -138,33 +139,14 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(const float *__restrict
     const int b = blockIdx.z, m0 = blockIdx.y * BM, n0 = blockIdx.x * kBN;
     const float *tb = t + (size_t)b * K * N;
     const int col = lane & 31, kh = lane >> 5;
-    f32x16 acc[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    PwAcc<MT> acc;
+    acc.zero();
     for (int k0 = 0; k0 < Kp; k0 += kKT) {
         for (int e = tid; e < kKT * BM; e += 256) {
             const int k = e / BM, mm = e - k * BM;
             As[k][mm] = m0 + mm < Mp ? wt[pd.wt_index(k0 + k, m0 + mm)] : 0.f;
         }
-        for (int e = tid; e < kKT * (kBN / 4); e += 256) {
-            const int k = e / (kBN / 4), n4 = e - k * (kBN / 4);
-            const int kk = k0 + k, n = n0 + n4 * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (kk < K) {
-                const float *src = tb + (size_t)kk * N + n;
-                if ((N & 3) == 0) {
-                    if (n < N) v = *reinterpret_cast<const float4 *>(src);
-                } else {
-                    if (n < N) v.x = src[0];
-                    if (n + 1 < N) v.y = src[1];
-                    if (n + 2 < N) v.z = src[2];
-                    if (n + 3 < N) v.w = src[3];
-                }
-            }
-            *reinterpret_cast<float4 *>(&Bs[k][n4 * 4]) = v;
-        }
+        stage_cells(Bs, tb, k0, K, n0, N, tid, AsItIs());
         __syncthreads();
         if constexpr (F16) {
             const _Float16 *w16 = reinterpret_cast<const _Float16 *>(packed + pd.wt16_off());
@@ -177,31 +159,20 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(const float *__restrict
                 f16x8 av;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) av[j] = m < Mp ? w16[pd.wt16_index(k0 + 8 * kh + j, m)] : (_Float16)0.f;
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bv, acc[i], 0, 0, 0);
+                acc.a[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bv, acc.a[i], 0, 0, 0);
             }
         } else {
-#pragma unroll
-            for (int s = 0; s < kKT / 2; ++s) {
-                const float bv = Bs[2 * s + kh][wave * 32 + col];
-#pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    const float av = As[2 * s + kh][i * 32 + col];
-                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i], 0, 0, 0);
-                }
-            }
+            acc.products(As, Bs, wave, col, kh);
         }
         __syncthreads();
     }
     const int n = n0 + wave * 32 + col;
     if (n < N) {
         float *yb = y + (size_t)b * M * N + n;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                if (m < M) yb[(size_t)m * N] = acc[i][r] + bias[m];
-            }
+        acc.each(kh, [&](int row, float v) {
+            const int m = m0 + row;
+            if (m < M) yb[(size_t)m * N] = v + bias[m];
+        });
     }
 }
 
@@ -231,13 +202,6 @@ __global__ __launch_bounds__(256) void pw_small_kernel(const float *__restrict__
 inline unsigned grid_for(long total, int cap = 65536) {
     long g = (total + 255) / 256;
     return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-// output-channel slabs: as few workgroups along M as possible with <= 7 MFMA row tiles (112 accumulators)
-inline void slab_shape(int M, int *nblk, int *mt) {
-    const int tiles = (M + 31) / 32;
-    *nblk = (tiles + 6) / 7;
-    *mt = (tiles + *nblk - 1) / *nblk;
 }
 
 }  // namespace
@@ -288,21 +252,10 @@ GFN_EXPORT int gfn_conv_block_fwd(const float *x, const float *packed, float *y,
     }
     if (int rc = gfn::check_launch("dw5x5_kernel")) return rc;
     const dim3 grid((N + kBN - 1) / kBN, nblk, B), block(256);
-#define GFN_PW(MT)                                                                                                        \
-    if (f16)                                                                                                              \
-        hipLaunchKernelGGL((pw_gemm_kernel<MT, true>), grid, block, 0, s, packed, (const float *)t_scratch, y, M, C, N);  \
-    else                                                                                                                  \
-        hipLaunchKernelGGL((pw_gemm_kernel<MT, false>), grid, block, 0, s, packed, (const float *)t_scratch, y, M, C, N)
-    switch (mt) {
-        case 1: GFN_PW(1); break;
-        case 2: GFN_PW(2); break;
-        case 3: GFN_PW(3); break;
-        case 4: GFN_PW(4); break;
-        case 5: GFN_PW(5); break;
-        case 6: GFN_PW(6); break;
-        default: GFN_PW(7); break;
-    }
-#undef GFN_PW
+    with_row_tiles(mt, [&](auto MT) {
+        if (f16) hipLaunchKernelGGL((pw_gemm_kernel<decltype(MT)::value, true>), grid, block, 0, s, packed, (const float *)t_scratch, y, M, C, N);
+        else hipLaunchKernelGGL((pw_gemm_kernel<decltype(MT)::value, false>), grid, block, 0, s, packed, (const float *)t_scratch, y, M, C, N);
+    });
     return gfn::check_launch("pw_gemm_kernel");
 }
 

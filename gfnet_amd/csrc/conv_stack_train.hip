@@ -7,35 +7,33 @@
 // running buffers are updated, and the backward yields the input gradient and seven parameter gradients.
 //
 // Forward (3 launches)
-//   ct_dw_fwd_kernel       u = dw5x5(x) + b_dw on 32x32 tiles staged with their halo in LDS (25 fmas per cell in (dy, dx) order,
-//                          as dw5x5_kernel); u goes to HBM -- the backward needs it -- and every workgroup leaves its tile's
+//   ct_dw_fwd_kernel       u = dw5x5(x) + b_dw on 32x32 tiles staged with their halo in LDS (stage_halo; dw_taps: 25 fmas per cell in
+//                          (dy, dx) order); u goes to HBM -- the backward needs it -- and every workgroup leaves its tile's
 //                          (mean, M2 = sum (u - mean)^2): shifted sums, safe against cancellation
 //   ct_stats_kernel        per channel: Chan's merge of the tiles' (n, mean, M2) in double, in a fixed order; mean, invstd =
 //                          1/sqrt(var + eps) with the biased variance, and the running buffers (unbiased variance) as torch
-//   ct_pw_fwd_kernel       y = W_pw . relu(u*alpha + beta') + b_pw on the fp32 matrix core (v_mfma_f32_32x32x2_f32, as pw_gemm_kernel);
+//   ct_pw_fwd_kernel       y = W_pw . relu(u*alpha + beta') + b_pw on the fp32 matrix-core tile of pw_gemm_tile.h (pw_gemm_kernel's too);
 //                          alpha = gamma*invstd, beta' = beta - mean*alpha (bn_affine); t = relu(..) is formed while the B operand
 //                          tile is staged and never reaches HBM
 // Backward (up to 7 launches, each skipped when the `need` mask does not ask for what it makes)
-//   ct_pw_bwd_kernel       gt = W_pw^T . gy on the matrix core; gz = gt where u*alpha + beta' > 0 (the forward's own expression, so
+//   ct_pw_bwd_kernel       gt = W_pw^T . gy on the same tile; gz = gt where u*alpha + beta' > 0 (the forward's own expression, so
 //                          both masks agree bit for bit), written as a C map; per-workgroup partial sums of gz and gz*u_hat
 //   ct_bn_bwd_kernel       dbeta = sum gz, dgamma = sum gz*u_hat from the partials (double, fixed order)
-//   ct_pw_wgrad_kernel     dW_pw[m, c] = sum_p gy[m, p] t[c, p] on the matrix core, t recomputed from u; a column of ones appended
-//                          to t makes db_pw the (C+1)-th column.  Split over the cells; every split writes its own partial matrix
+//   ct_pw_wgrad_kernel     dW_pw[m, c] = sum_p gy[m, p] t[c, p] on the matrix core (PwAcc; K runs over the cells), t recomputed from u;
+//                          a column of ones appended to t makes db_pw the (C+1)-th column.  Split over the cells; every split writes
+//                          its own partial matrix
 //   ct_pw_wgrad_sum_kernel sums the partial matrices in a fixed order
 //   ct_dw_bwd_kernel       gu = alpha*(gz - dbeta/N - u_hat*dgamma/N) formed while the gz / u halo tile is staged; gx = dw5x5 of gu with
-//                          flipped taps; per-workgroup partials of dW_dw[c, k] = sum_p gu[p] x[p + off_k] and db_dw = sum gu
+//                          flipped taps (the forward's stage_halo and dw_taps); per-workgroup partials of dW_dw[c, k] =
+//                          sum_p gu[p] x[p + off_k] and db_dw = sum gu
 //   ct_dw_wgrad_kernel     sums those partials (double, fixed order)
 // No floating-point atomics anywhere: two identical calls give identical bits.
-#include "common.h"
+#include "pw_gemm_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kTile = 32;         // depthwise tile side in cells: 256 threads x 4 cells of a row
 constexpr int kHalo = kTile + 4;  // staged side (2 cells of halo all round)
-constexpr int kKT = 16;           // channels per K tile of the 1x1 GEMMs
-constexpr int kBN = 128;          // cells per workgroup of the 1x1 GEMMs: 4 waves x 32
 constexpr int kDwCols = 26;       // depthwise parameter gradients per channel: 25 taps + the bias
 constexpr int kWgCells = 32;      // cells per wave and K step of the 1x1 weight gradient
 
@@ -82,6 +80,34 @@ __device__ __forceinline__ TileId decode_tile(unsigned bid, int C, int tiles_x, 
     return t;
 }
 
+// the tile with its halo: Ts[cell] = f(the cell lies inside the map, its offset in the plane -- 0 outside)
+template <typename F>
+__device__ __forceinline__ void stage_halo(float *Ts, const TileId &t, int G, F f) {
+    for (int e = threadIdx.x; e < kHalo * kHalo; e += 256) {
+        const int hy = e / kHalo, hx = e - hy * kHalo;
+        const int gy = t.row0 - 2 + hy, gx = t.col0 - 2 + hx;
+        const bool ok = (unsigned)gy < (unsigned)G && (unsigned)gx < (unsigned)G;
+        Ts[e] = f(ok, ok ? gy * G + gx : 0);
+    }
+}
+
+// acc[q] = sum_k w[k] Ts[cell (r, c4 + q) + off_k], k = 5 dy + dx ascending: 25 fmas per cell; FLIP: w[24 - k], the transposed conv
+template <bool FLIP>
+__device__ __forceinline__ void dw_taps(const float *Ts, const float *wc, int r, int c4, float (&acc)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] = 0.f;
+#pragma unroll
+    for (int dy = 0; dy < 5; ++dy) {
+        const float4 a = *reinterpret_cast<const float4 *>(&Ts[(r + dy) * kHalo + c4]);
+        const float4 e = *reinterpret_cast<const float4 *>(&Ts[(r + dy) * kHalo + c4 + 4]);
+        const float v[8] = {a.x, a.y, a.z, a.w, e.x, e.y, e.z, e.w};
+#pragma unroll
+        for (int dx = 0; dx < 5; ++dx)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] = fmaf(wc[FLIP ? 24 - (dy * 5 + dx) : dy * 5 + dx], v[q + dx], acc[q]);
+    }
+}
+
 // ---- forward ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ct_dw_fwd_kernel(const float *__restrict__ x, const float *__restrict__ dw_w,
                                                         const float *__restrict__ dw_b, float *__restrict__ u, float *__restrict__ part,
@@ -91,27 +117,14 @@ __global__ __launch_bounds__(256) void ct_dw_fwd_kernel(const float *__restrict_
     const int tid = threadIdx.x;
     const TileId t = decode_tile(blockIdx.x, C, tiles_x, tiles);
     const float *xp = x + t.plane * (size_t)G * G;
-    for (int e = tid; e < kHalo * kHalo; e += 256) {
-        const int hy = e / kHalo, hx = e - hy * kHalo;
-        const int gy = t.row0 - 2 + hy, gx = t.col0 - 2 + hx;
-        const bool ok = (unsigned)gy < (unsigned)G && (unsigned)gx < (unsigned)G;
-        const float v = xp[ok ? gy * G + gx : 0];
-        Xs[e] = ok ? v : 0.f;
-    }
+    stage_halo(Xs, t, G, [&](bool ok, int off) {
+        const float v = xp[off];
+        return ok ? v : 0.f;
+    });
     __syncthreads();
     const int r = tid >> 3, c4 = (tid & 7) * 4;
-    const float *wc = dw_w + (size_t)t.c * 25;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dy = 0; dy < 5; ++dy) {
-        const float4 a = *reinterpret_cast<const float4 *>(&Xs[(r + dy) * kHalo + c4]);
-        const float4 e = *reinterpret_cast<const float4 *>(&Xs[(r + dy) * kHalo + c4 + 4]);
-        const float v[8] = {a.x, a.y, a.z, a.w, e.x, e.y, e.z, e.w};
-#pragma unroll
-        for (int dx = 0; dx < 5; ++dx)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] = fmaf(wc[dy * 5 + dx], v[q + dx], acc[q]);
-    }
+    float acc[4];
+    dw_taps<false>(Xs, dw_w + (size_t)t.c * 25, r, c4, acc);
     const float bias = dw_b ? dw_b[t.c] : 0.f;
     const int gy = t.row0 + r, gx0 = t.col0 + c4;
     float *up = u + t.plane * (size_t)G * G + (size_t)gy * G + gx0;
@@ -189,82 +202,44 @@ __global__ __launch_bounds__(64) void ct_stats_kernel(const float *__restrict__ 
     }
 }
 
-// four cells of a map row (any N: the tail cell by cell); cells past N read as zero
-__device__ __forceinline__ float4 load_cells(const float *src, int n, int N) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if ((N & 3) == 0) {
-        if (n < N) v = *reinterpret_cast<const float4 *>(src);
-    } else {
-        if (n < N) v.x = src[0];
-        if (n + 1 < N) v.y = src[1];
-        if (n + 2 < N) v.z = src[2];
-        if (n + 3 < N) v.w = src[3];
-    }
-    return v;
-}
-
-// y[b] = W . relu(u[b]*alpha + beta') + bias; W (M, K) row major.  Same instruction, operand roles and k order as pw_gemm_kernel.
+// y[b] = W . relu(u[b]*alpha + beta') + bias; W (M, K) row major, on the tile of pw_gemm_tile.h.
 template <int MT>
 __global__ __launch_bounds__(256, 2) void ct_pw_fwd_kernel(const float *__restrict__ u, const float *__restrict__ gamma,
                                                            const float *__restrict__ beta, const float *__restrict__ mean,
                                                            const float *__restrict__ invstd, const float *__restrict__ pw_w,
                                                            const float *__restrict__ pw_b, float *__restrict__ y, int M, int K, int N) {
     constexpr int BM = 32 * MT, AP = BM + 1;  // odd pitch: the transposing stores of the weight tile spread over the banks
-    __shared__ float As[kKT * AP];
+    __shared__ float As[kKT][AP];
     __shared__ __attribute__((aligned(16))) float Bs[kKT][kBN];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.z, m0 = blockIdx.y * BM, n0 = blockIdx.x * kBN;
     const float *ub = u + (size_t)b * K * N;
     const int col = lane & 31, kh = lane >> 5;
-    f32x16 acc[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    PwAcc<MT> acc;
+    acc.zero();
     for (int k0 = 0; k0 < K; k0 += kKT) {
         for (int e = tid; e < kKT * BM; e += 256) {
             const int mm = e / kKT, k = e - mm * kKT;
             const bool ok = m0 + mm < M && k0 + k < K;
             const float v = pw_w[ok ? (size_t)(m0 + mm) * K + k0 + k : 0];
-            As[k * AP + mm] = ok ? v : 0.f;
+            As[k][mm] = ok ? v : 0.f;
         }
-        for (int e = tid; e < kKT * (kBN / 4); e += 256) {
-            const int k = e / (kBN / 4), n4 = e - k * (kBN / 4);
-            const int kk = k0 + k, n = n0 + n4 * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (kk < K) {
-                float al, be;
-                bn_affine(gamma[kk], beta[kk], mean[kk], invstd[kk], al, be);
-                const float4 raw = load_cells(ub + (size_t)kk * N + n, n, N);
-                v.x = n < N ? fmaxf(bn_pre(raw.x, al, be), 0.f) : 0.f;
-                v.y = n + 1 < N ? fmaxf(bn_pre(raw.y, al, be), 0.f) : 0.f;
-                v.z = n + 2 < N ? fmaxf(bn_pre(raw.z, al, be), 0.f) : 0.f;
-                v.w = n + 3 < N ? fmaxf(bn_pre(raw.w, al, be), 0.f) : 0.f;
-            }
-            *reinterpret_cast<float4 *>(&Bs[k][n4 * 4]) = v;
-        }
+        stage_cells(Bs, ub, k0, K, n0, N, tid, [&](int kk) {
+            float al, be;
+            bn_affine(gamma[kk], beta[kk], mean[kk], invstd[kk], al, be);
+            return [=](float v) { return fmaxf(bn_pre(v, al, be), 0.f); };
+        });
         __syncthreads();
-#pragma unroll
-        for (int s = 0; s < kKT / 2; ++s) {
-            const float bv = Bs[2 * s + kh][wave * 32 + col];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const float av = As[(2 * s + kh) * AP + i * 32 + col];
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i], 0, 0, 0);
-            }
-        }
+        acc.products(As, Bs, wave, col, kh);
         __syncthreads();
     }
     const int n = n0 + wave * 32 + col;
     if (n < N) {
         float *yb = y + (size_t)b * M * N + n;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                if (m < M) yb[(size_t)m * N] = acc[i][r] + pw_b[m];
-            }
+        acc.each(kh, [&](int row, float v) {
+            const int m = m0 + row;
+            if (m < M) yb[(size_t)m * N] = v + pw_b[m];
+        });
     }
 }
 
@@ -295,11 +270,8 @@ __global__ __launch_bounds__(256, 2) void ct_pw_bwd_kernel(const float *__restri
         }
         Al[tid] = al, Be[tid] = be, Mn[tid] = mn, Is[tid] = is;
     }
-    f32x16 acc[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    PwAcc<MT> acc;
+    acc.zero();
     for (int k0 = 0; k0 < M; k0 += kKT) {
         for (int e = tid; e < kKT * BM; e += 256) {
             const int k = e / BM, cc = e - k * BM;
@@ -307,43 +279,25 @@ __global__ __launch_bounds__(256, 2) void ct_pw_bwd_kernel(const float *__restri
             const float v = pw_w[ok ? (size_t)(k0 + k) * C + c0 + cc : 0];
             As[k][cc] = ok ? v : 0.f;
         }
-        for (int e = tid; e < kKT * (kBN / 4); e += 256) {
-            const int k = e / (kBN / 4), n4 = e - k * (kBN / 4);
-            const int kk = k0 + k, n = n0 + n4 * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (kk < M) v = load_cells(gb + (size_t)kk * N + n, n, N);
-            *reinterpret_cast<float4 *>(&Bs[k][n4 * 4]) = v;
-        }
+        stage_cells(Bs, gb, k0, M, n0, N, tid, AsItIs());
         __syncthreads();
-#pragma unroll
-        for (int s = 0; s < kKT / 2; ++s) {
-            const float bv = Bs[2 * s + kh][wave * 32 + col];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const float av = As[2 * s + kh][i * 32 + col];
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i], 0, 0, 0);
-            }
-        }
+        acc.products(As, Bs, wave, col, kh);
         __syncthreads();
     }
     const int n = n0 + wave * 32 + col;
     const bool nok = n < N;
     const size_t base = (size_t)b * C * N + (nok ? n : 0);
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-            const int c = c0 + row;
-            const bool ok = nok && c < C;
-            const size_t at = base + (size_t)(ok ? c : 0) * N;
-            const float uu = u[at];
-            const float g = ok && bn_pre(uu, Al[row], Be[row]) > 0.f ? acc[i][r] : 0.f;
-            if (ok) gz[at] = g;
-            const float s1 = half_wave_sum(g);
-            const float s2 = half_wave_sum(ok ? g * ((uu - Mn[row]) * Is[row]) : 0.f);
-            if (col == 0) red[wave][row][0] = s1, red[wave][row][1] = s2;
-        }
+    acc.each(kh, [&](int row, float a) {
+        const int c = c0 + row;
+        const bool ok = nok && c < C;
+        const size_t at = base + (size_t)(ok ? c : 0) * N;
+        const float uu = u[at];
+        const float g = ok && bn_pre(uu, Al[row], Be[row]) > 0.f ? a : 0.f;
+        if (ok) gz[at] = g;
+        const float s1 = half_wave_sum(g);
+        const float s2 = half_wave_sum(ok ? g * ((uu - Mn[row]) * Is[row]) : 0.f);
+        if (col == 0) red[wave][row][0] = s1, red[wave][row][1] = s2;
+    });
     __syncthreads();
     if (tid < BM && c0 + tid < C) {
         float *p = part + ((size_t)(c0 + tid) * ((size_t)gridDim.z * gridDim.x) + (size_t)b * gridDim.x + blockIdx.x) * 2;
@@ -403,11 +357,8 @@ __global__ __launch_bounds__(256) void ct_pw_wgrad_kernel(const float *__restric
         Al[tid] = al, Be[tid] = be;
     }
     __syncthreads();
-    f32x16 acc[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    PwAcc<MT> acc;
+    acc.zero();
     for (int nb = n_begin; nb < n_end; nb += KTS) {
         for (int e = tid; e < BM * KTS; e += 256) {
             const int row = e / KTS, kk = e - row * KTS;
@@ -430,20 +381,16 @@ __global__ __launch_bounds__(256) void ct_pw_wgrad_kernel(const float *__restric
         for (int s = 0; s < kWgCells / 2; ++s) {
             const float bv = bp[2 * s];
 #pragma unroll
-            for (int i = 0; i < MT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[i * 32 * P + 2 * s], bv, acc[i], 0, 0, 0);
+            for (int i = 0; i < MT; ++i) acc.a[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[i * 32 * P + 2 * s], bv, acc.a[i], 0, 0, 0);
         }
         __syncthreads();
     }
     const int cidx = c0 + cw * 32 + col;
     if (cidx <= C) {
         float *pp = part + (size_t)(blockIdx.z * KS + ks) * M * (C + 1) + cidx;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                if (m < M) pp[(size_t)m * (C + 1)] = acc[i][r];
-            }
+        acc.each(kh, [&](int row, float v) {
+            if (m0 + row < M) pp[(size_t)(m0 + row) * (C + 1)] = v;
+        });
     }
 }
 
@@ -476,33 +423,20 @@ __global__ __launch_bounds__(256) void ct_dw_bwd_kernel(const float *__restrict_
     const float al = gamma[t.c] * is;  // bn_affine's alpha
     const float k1 = dgdb[C + t.c] * inv_n, k2 = dgdb[t.c] * inv_n;
     const bool want_x = need & 1, want_w = need & 2;
-    for (int e = tid; e < kHalo * kHalo; e += 256) {
-        const int hy = e / kHalo, hx = e - hy * kHalo;
-        const int yy = t.row0 - 2 + hy, xx = t.col0 - 2 + hx;
-        const bool ok = (unsigned)yy < (unsigned)G && (unsigned)xx < (unsigned)G;
-        const size_t at = pbase + (ok ? yy * G + xx : 0);
-        const float g = gz[at], uu = u[at];
-        Gs[e] = ok ? al * (g - k1 - ((uu - mn) * is) * k2) : 0.f;
-        if (want_w) {
-            const float xv = x[at];
-            Xs[e] = ok ? xv : 0.f;
-        }
-    }
+    stage_halo(Gs, t, G, [&](bool ok, int off) {
+        const float g = gz[pbase + off], uu = u[pbase + off];
+        return ok ? al * (g - k1 - ((uu - mn) * is) * k2) : 0.f;
+    });
+    if (want_w)
+        stage_halo(Xs, t, G, [&](bool ok, int off) {
+            const float xv = x[pbase + off];
+            return ok ? xv : 0.f;
+        });
     __syncthreads();
     const int r = tid >> 3, c4 = (tid & 7) * 4;
-    const float *wc = dw_w + (size_t)t.c * 25;
-    if (want_x) {  // gx[q] = sum_k w[k] gu[q - off_k]: the forward's loop with the taps flipped
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int dy = 0; dy < 5; ++dy) {
-            const float4 a = *reinterpret_cast<const float4 *>(&Gs[(r + dy) * kHalo + c4]);
-            const float4 e = *reinterpret_cast<const float4 *>(&Gs[(r + dy) * kHalo + c4 + 4]);
-            const float v[8] = {a.x, a.y, a.z, a.w, e.x, e.y, e.z, e.w};
-#pragma unroll
-            for (int dx = 0; dx < 5; ++dx)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = fmaf(wc[24 - (dy * 5 + dx)], v[q + dx], acc[q]);
-        }
+    if (want_x) {  // gx[q] = sum_k w[k] gu[q - off_k]: the forward's taps, flipped
+        float acc[4];
+        dw_taps<true>(Gs, dw_w + (size_t)t.c * 25, r, c4, acc);
         const int yy = t.row0 + r, xx0 = t.col0 + c4;
         float *gp = gx + pbase + (size_t)yy * G + xx0;
 #pragma unroll
@@ -559,13 +493,6 @@ __global__ __launch_bounds__(256) void ct_dw_wgrad_kernel(const float *__restric
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-// rows of a 1x1 GEMM's output: as few workgroups along them as possible with <= 7 MFMA row tiles each (conv_stack.hip)
-inline void slab_shape(int rows, int *nblk, int *mt) {
-    const int tiles = (rows + 31) / 32;
-    *nblk = (tiles + 6) / 7;
-    *mt = (tiles + *nblk - 1) / *nblk;
-}
-
 inline int64_t align4(int64_t floats) { return (floats + 3) / 4 * 4; }
 
 struct TrainPlan {
@@ -659,19 +586,10 @@ GFN_EXPORT int gfn_conv_block_train_fwd(const float *x, const float *dw_w, const
     int nblk, mt;
     slab_shape(M, &nblk, &mt);
     const dim3 grid((unsigned)p.ntn, (unsigned)nblk, (unsigned)B);
-#define GFN_CT(MT)                                                                                                                       \
-    hipLaunchKernelGGL((ct_pw_fwd_kernel<MT>), grid, dim3(256), 0, s, (const float *)u, bn_w, bn_b, (const float *)mean, (const float *)invstd, \
-                       pw_w, pw_b, y, M, C, N)
-    switch (mt) {
-        case 1: GFN_CT(1); break;
-        case 2: GFN_CT(2); break;
-        case 3: GFN_CT(3); break;
-        case 4: GFN_CT(4); break;
-        case 5: GFN_CT(5); break;
-        case 6: GFN_CT(6); break;
-        default: GFN_CT(7); break;
-    }
-#undef GFN_CT
+    with_row_tiles(mt, [&](auto MT) {
+        hipLaunchKernelGGL((ct_pw_fwd_kernel<decltype(MT)::value>), grid, dim3(256), 0, s, (const float *)u, bn_w, bn_b, (const float *)mean,
+                           (const float *)invstd, pw_w, pw_b, y, M, C, N);
+    });
     return gfn::check_launch("ct_pw_fwd_kernel");
 }
 
@@ -699,17 +617,10 @@ GFN_EXPORT int gfn_conv_block_train_bwd(const float *gy, const float *x, const f
         int nblk, mt;
         slab_shape(C, &nblk, &mt);
         const dim3 grid((unsigned)p.ntn, (unsigned)nblk, (unsigned)B);
-#define GFN_CT(MT) hipLaunchKernelGGL((ct_pw_bwd_kernel<MT>), grid, dim3(256), 0, s, gy, u, bn_w, bn_b, mean, invstd, pw_w, gz, part_bn, M, C, N)
-        switch (mt) {
-            case 1: GFN_CT(1); break;
-            case 2: GFN_CT(2); break;
-            case 3: GFN_CT(3); break;
-            case 4: GFN_CT(4); break;
-            case 5: GFN_CT(5); break;
-            case 6: GFN_CT(6); break;
-            default: GFN_CT(7); break;
-        }
-#undef GFN_CT
+        with_row_tiles(mt, [&](auto MT) {
+            hipLaunchKernelGGL((ct_pw_bwd_kernel<decltype(MT)::value>), grid, dim3(256), 0, s, gy, u, bn_w, bn_b, mean, invstd, pw_w, gz, part_bn, M,
+                               C, N);
+        });
         if (int rc = gfn::check_launch("ct_pw_bwd_kernel")) return rc;
         const bool bn = need & GFN_CBT_NEED_BN;
         hipLaunchKernelGGL(ct_bn_bwd_kernel, dim3((unsigned)C), dim3(64), 0, s, (const float *)part_bn, B * p.ntn, C, dgdb, bn ? d_bn_w : nullptr,

@@ -1,12 +1,11 @@
 // corr_common.h -- what the global-correlation kernels (corr_softargmax.hip, corr_softargmax_bwd.hip) say about a 32 x 32 tile, once:
-// the accumulator layout, the B-grid cell of a position, the fp32 tile product, the virtual symmetric direction and the host-side
-// argument checks.  split3 and the two vector types also serve kde.hip.
+// the B-grid cell of a position, the fp32 tile product, the virtual symmetric direction and the host-side argument checks (the
+// accumulator layout, f32x16 and acc_row, is common.h's: the 1x1 conv tile reads it too).  split3 and bf16x8 also serve kde.hip.
 #pragma once
 #include "common.h"
 
 namespace gfn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // x = h + m + l exactly (three round-to-nearest bf16 pieces of 8 significant bits each cover the 24 of an fp32 value)
@@ -16,9 +15,6 @@ __device__ __forceinline__ void split3(float v, __bf16 &h, __bf16 &m, __bf16 &l)
     m = (__bf16)r1;
     l = (__bf16)(r1 - (float)m);
 }
-
-// row of a 32x32 MFMA accumulator that register r of a lane in half-wave h = lane >> 5 holds (its column is lane & 31)
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // B-grid cell (jx, jy) of position j = jy W1 + jx, inv_w1 = 1.0f / W1.  The float quotient is off by one row for some j >= 2^22
 // (j + 0.5 and the product round); one integer step either way makes (jx, jy) exact for every j < 2^24 (tests/test_host_cpu.py

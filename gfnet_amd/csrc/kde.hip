@@ -12,7 +12,7 @@
 // matrix product); fp32 accumulation.  When N is too small to fill the chip the M range is split
 // over blockIdx.y and the partial sums are reduced by a second tiny kernel (deterministic, no
 // float atomics).
-#include "corr_common.h"  // split3, bf16x8, f32x16, acc_row
+#include "corr_common.h"  // split3, bf16x8; with it common.h: f32x16, acc_row
 #include <cstdlib>
 
 namespace {

@@ -8,6 +8,7 @@ is left out of any comparison."""
 import copy
 import functools
 
+import numpy as np
 import pytest
 import torch
 import torch.nn as nn
@@ -26,6 +27,7 @@ CASES = {
     "odd_c": (1, 73, 12, True, 1),
     "g_not_4k_batch3": (3, 37, 10, True, 2),
     "below_a_tile": (1, 7, 5, True, 1),
+    "five_row_tiles": (1, 150, 8, True, 1),
     "widest_k": (1, 417, 8, True, 1),
     "edge_tiles": (2, 16, 36, True, 3),
     "no_dw_bias": (2, 24, 16, False, 2),
@@ -120,6 +122,28 @@ def test_backward_matches_float64_autograd(name):
             continue
         assert got["grads"][k] is not None, f"{name}: no gradient for {k}"
         assert_grad_close(f"{name} d{k}", got["grads"][k], ref["grads"][k], 1e-4)
+
+
+@pytest.mark.parametrize("name", ["narrow", "odd_c", "g_not_4k_batch3", "five_row_tiles", "widest_k", "edge_tiles", "no_dw_bias"])
+def test_forward_is_the_eval_block_on_the_batch_statistics_bit_for_bit(name):
+    """The training forward and the eval-mode block (csrc/conv_stack.hip) share their depthwise arithmetic and their 1x1 tile
+    (csrc/pw_gemm_tile.h): with alpha = gamma * invstd and beta' = beta - mean * alpha formed as bn_affine forms them -- float32,
+    one rounding per operation -- and packed for the eval block, the two-pass kernels and, where G % 4 == 0, the fused kernel
+    give the training forward's y bit for bit."""
+    from gfnet_amd import ops
+
+    _, C, G, _, _ = CASES[name]
+    t = {k: (v.cuda() if v is not None else None) for k, v in make_inputs(*CASES[name]).items()}
+    y, _, mean, invstd = ops.conv_block_train_fwd(t["x"], t["dw_w"], t["dw_b"], t["bn_w"], t["bn_b"], t["rm"].clone(), t["rv"].clone(),
+                                                  MOMENTUM, EPS, t["pw_w"], t["pw_b"])
+    gamma, beta, mean, invstd = (v.cpu().numpy() for v in (t["bn_w"], t["bn_b"], mean, invstd))
+    assert all(v.dtype == np.float32 for v in (gamma, beta, mean, invstd))
+    alpha = gamma * invstd
+    betap = beta - mean * alpha
+    packed = ops.conv_block_pack(t["dw_w"], t["dw_b"], torch.from_numpy(alpha).cuda(), torch.from_numpy(betap).cuda(), t["pw_w"], t["pw_b"])
+    assert torch.equal(y, ops.conv_block(t["x"], packed, C, variant=1)), "two-pass eval block"
+    if G % 4 == 0:
+        assert torch.equal(y, ops.conv_block(t["x"], packed, C, variant=0)), "fused eval block"
 
 
 def cancellation_inputs():
