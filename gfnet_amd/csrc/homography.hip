@@ -26,8 +26,12 @@
 // fp64 throughout; compiled with -ffp-contract=off so hypotheses, inlier counts and the chosen
 // hypothesis are bit-identical to the oracle.
 #include "common.h"
+#include "ge_solve8.h"
 
 namespace {
+
+using gfn::ge_solve8;
+using gfn::lane_get;
 
 __device__ __forceinline__ uint32_t draw_index(uint64_t seed, uint32_t b, uint32_t t, uint32_t k, uint32_t a, uint32_t s, uint32_t N) {
     uint64_t h = gfn::splitmix64(seed ^ gfn::splitmix64(((uint64_t)b << 32) | t));
@@ -127,62 +131,6 @@ __device__ int ransac_update_iters(double conf, int good, int N, int niters) {
     denom = det_log(denom);
     if (denom >= 0 || -num >= (double)niters * (-denom)) return niters;
     return (int)floor(num / denom + 0.5);
-}
-
-// value of `v` in lane `srclane`.  UNIFORM: srclane is wave-uniform -> two v_readlane_b32 (a few
-// cycles); otherwise a general shuffle (ds_bpermute, LDS crossbar latency).
-template <bool UNIFORM>
-__device__ __forceinline__ double lane_get(double v, int srclane) {
-    if (UNIFORM) {
-        const int lo = __builtin_amdgcn_readlane(__double2loint(v), srclane);
-        const int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
-        return __hiloint2double(hi, lo);
-    }
-    return __shfl(v, srclane);
-}
-
-// Gaussian elimination with partial pivoting of an 8x8 system, one augmented row (9 doubles) per
-// lane: lanes base..base+7 of the wave hold rows 0..7.  Same operation order as solve_aug() in the
-// oracle.  Returns the solution component of this lane's row; ok is group-uniform.
-// UNIFORM = the wave holds a single system (base is wave-uniform).
-template <bool UNIFORM>
-__device__ double ge_solve8(double (&M)[9], int row, int base, bool &ok) {
-    ok = true;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        int piv = c;
-        double best = fabs(lane_get<UNIFORM>(M[c], base + c));
-#pragma unroll
-        for (int r = c + 1; r < 8; ++r) {
-            const double v = fabs(lane_get<UNIFORM>(M[c], base + r));
-            if (v > best) { best = v; piv = r; }
-        }
-        if (!(best > 1e-300)) ok = false;
-        if (UNIFORM) piv = __builtin_amdgcn_readfirstlane(piv);
-        // swap rows c and piv (every lane takes part in the exchange)
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const double from_piv = lane_get<UNIFORM>(M[k], base + piv), from_c = lane_get<UNIFORM>(M[k], base + c);
-            M[k] = (row == c) ? from_piv : ((row == piv) ? from_c : M[k]);
-        }
-        const double inv = 1.0 / lane_get<UNIFORM>(M[c], base + c);
-        const double f = M[c] * inv;
-#pragma unroll
-        for (int k = c; k < 9; ++k) {
-            const double prow = lane_get<UNIFORM>(M[k], base + c);
-            if (row > c) M[k] = M[k] - f * prow;
-        }
-    }
-    double s = M[8];
-    double x = 0.0;
-#pragma unroll
-    for (int k = 7; k >= 0; --k) {
-        // lane k finalises x_k = s / M[k][k]; every row above it (row < k) eliminates it
-        const double xk = lane_get<UNIFORM>(s / M[k], base + k);
-        if (row == k) x = xk;
-        if (row < k) s = s - M[k] * xk;
-    }
-    return x;
 }
 
 // Inlier test: squared reprojection error <= thr2, multiplied through by w^2 so that no division is needed, sums as

@@ -1020,3 +1020,155 @@ def robust_loss(scales, H, ext_a, ext_b, ce_weight, iteration_base, maps):
     loss = _RobustLossFn.apply(tuple(scales), (float(ext_a), float(ext_b), float(ce_weight), float(iteration_base)), f32c(H).detach(), stats,
                                *maps)
     return loss, stats
+
+
+# ---- training pairs (datasets/generate_random_H_large_size.py, csrc/pair_synth.hip) ---------------------------------------------------
+def get_perspective_transform(src, dst, return_ok=False):
+    """kornia's get_perspective_transform (generate_random_H_large_size.py:30, 71) for n four-point problems, solved in double on the
+    device: src, dst (n,4,2) or (4,2) -> H (n,3,3) float64 with H[2,2] = 1 and dst ~ H src.  return_ok: also the (n,) int32 flags,
+    0 where the source points are degenerate (H is then the identity)."""
+    dev = require_gpu(src, dst)
+    s, d = f32c(src).reshape(-1, 4, 2), f32c(dst).reshape(-1, 4, 2)
+    if s.shape != d.shape:
+        raise ValueError(f"get_perspective_transform: src {tuple(src.shape)} and dst {tuple(dst.shape)} differ")
+    n = s.shape[0]
+    H = torch.empty((n, 3, 3), device=dev, dtype=torch.float64)
+    ok = torch.empty((n,), device=dev, dtype=torch.int32)
+    _L().gfn_perspective_from_points(ptr(s), ptr(d), ptr(H), ptr(ok), n, stream_ptr(dev))
+    return (H, ok) if return_ok else H
+
+
+def _source_table(imgs, what):
+    """The per-sample source records of gfn_warp_perspective_fwd for a (B,C,H,W) tensor or a list of (C,H,W) tensors: returns
+    (device pointer array, device (B,3) int32 rows (H, W, channel stride), the tensors the pointers name, C).  A sample is read in
+    place when its rows are dense (stride W) -- any batch and channel stride, so views of larger buffers are not copied."""
+    samples = list(imgs.unbind(0)) if isinstance(imgs, torch.Tensor) and imgs.dim() == 4 else list(imgs)
+    if not samples:
+        raise ValueError(f"{what}: no images")
+    dev = require_gpu(*samples)
+    C, keep, rows = samples[0].shape[0], [], []
+    for t in samples:
+        if t.dim() != 3 or t.shape[0] != C or t.shape[1] < 1 or t.shape[2] < 1:
+            raise ValueError(f"{what}: every image must be (C,H,W) with C = {C}, got {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            t = t.float()
+        _, h, w = t.shape
+        if t.stride(2) != 1 or (h > 1 and t.stride(1) != w) or (C > 1 and t.stride(0) < h * w):
+            t = t.contiguous()
+        if h * w >= 2 ** 31:
+            raise ValueError(f"{what}: an image of {h} x {w} pixels is too large (pixel offsets are 32-bit)")
+        keep.append(t)
+        rows.append((h, w, t.stride(0) if C > 1 else h * w))
+    B = len(keep)
+    host = torch.empty(B + (3 * B + 1) // 2, dtype=torch.int64)  # B pointers, then the (B,3) int32 records: one upload
+    host[:B] = torch.tensor([t.data_ptr() for t in keep], dtype=torch.int64)
+    host[B:].view(torch.int32)[:3 * B] = torch.tensor(rows, dtype=torch.int32).reshape(-1)
+    table = host.to(dev)
+    return table[:B], table[B:].view(torch.int32), keep, C
+
+
+_norm_constants = {}
+
+
+def _mean_std(dev, mean, std, C):
+    """(mean, std) of a Normalize as device tensors of C floats, uploaded once per (device, values)"""
+    if (mean is None) != (std is None):
+        raise ValueError("warp_perspective: mean and std go together")
+    if mean is None:
+        return None, None
+    key = (dev.type, dev.index, tuple(float(v) for v in mean), tuple(float(v) for v in std))
+    if len(key[2]) != C or len(key[3]) != C:
+        raise ValueError(f"warp_perspective: mean and std need {C} values each")
+    if key not in _norm_constants:
+        _norm_constants[key] = (torch.tensor(key[2], dtype=torch.float32, device=dev), torch.tensor(key[3], dtype=torch.float32, device=dev))
+    return _norm_constants[key]
+
+
+def _warp(imgs, M, invert, dsize, mean=None, std=None, what="warp_perspective"):
+    """gfn_warp_perspective_fwd: output pixel -> source pixel through M (B,3,3) float64 on the device (inverted there first when
+    `invert`); imgs as _source_table takes them.  Returns (B,C,Ho,Wo) float32."""
+    planes, dims, keep, C = _source_table(imgs, what)
+    dev, B = planes.device, planes.shape[0]
+    if M.shape != (B, 3, 3) or M.dtype != torch.float64 or M.device != dev or not M.is_contiguous():
+        raise ValueError(f"{what}: M must be a contiguous ({B},3,3) float64 tensor on {dev}, got {tuple(M.shape)} {M.dtype} on {M.device}")
+    Ho, Wo = int(dsize[0]), int(dsize[1])
+    m, s = _mean_std(dev, mean, std, C)
+    out = torch.empty((B, C, Ho, Wo), device=dev, dtype=torch.float32)
+    _timed("warp_perspective", lambda: _L().gfn_warp_perspective_fwd(ptr(planes), ptr(dims), ptr(M), int(bool(invert)), ptr(out), C * Ho * Wo,
+                                                                     B, C, Ho, Wo, ptr(m), ptr(s), stream_ptr(dev)))
+    del keep  # (alive until after the launch; the allocator's reuse is ordered on this stream)
+    return out
+
+
+def warp_perspective(img, H, dsize, mean=None, std=None):
+    """kornia's warp_perspective(img, H, dsize, mode="bilinear", padding_mode="zeros", align_corners=True)
+    (generate_random_H_large_size.py:33, 83): H (B,3,3) maps source pixels to destination pixels and is inverted on the device in
+    double; pixel coordinates are evaluated in double, the blend is fp32.  img: (B,C,H,W) or a list of (C,H,W) tensors, which may
+    differ in size; dsize = (height, width).  mean / std (C values each): (v - mean[c]) / std[c] fused into the launch."""
+    require_gpu(H)
+    return _warp(img, H.to(torch.float64).reshape(-1, 3, 3).contiguous(), True, dsize, mean, std)
+
+
+def random_h_params(draws, crop_size, deform_area, final_size):
+    """gfn_random_h_params: draws (B,18) int32 on the device -> dict of H_s2t (B,3,3) float32, H_s2t64, M_A, M_B (B,3,3) float64 and
+    ok (B,) int32; M_A and M_B are views of one (2B,3,3) tensor "M"."""
+    dev = require_gpu(draws)
+    if draws.dim() != 2 or draws.shape[1] != 18 or draws.dtype != torch.int32:
+        raise ValueError(f"random_h_params: draws must be (B,18) int32, got {tuple(draws.shape)} {draws.dtype}")
+    d = draws.contiguous()
+    B = d.shape[0]
+    centre = int(crop_size) - 2 * (int(deform_area) // 2)
+    H32 = torch.empty((B, 3, 3), device=dev, dtype=torch.float32)
+    H64 = torch.empty((B, 3, 3), device=dev, dtype=torch.float64)
+    M = torch.empty((2 * B, 3, 3), device=dev, dtype=torch.float64)
+    ok = torch.empty((B,), device=dev, dtype=torch.int32)
+    _L().gfn_random_h_params(ptr(d), B, int(crop_size), int(deform_area), centre, centre, int(final_size[0]), int(final_size[1]), ptr(H32),
+                             ptr(H64), ptr(M[:B]), ptr(M[B:]), ptr(ok), stream_ptr(dev))
+    return {"H_s2t": H32, "H_s2t64": H64, "M": M, "M_A": M[:B], "M_B": M[B:], "ok": ok}
+
+
+def random_h_batch(imgs_a, imgs_b, draws, crop_size, input_size, deformation_ratio, bi, normalize=True, return_warped=False):
+    """randomH (generate_random_H_large_size.py:38-85) for a batch, after its pre-resize: imgs_a / imgs_b are B pairs of equally sized
+    (3,h,w) device images in [0,1] with h, w > crop_size (lists, or (B,3,h,w) tensors), draws the (B,18) int32 rows of
+    datasets.draw_random_h, input_size the final (h, w).  One parameter launch, then ONE warp launch for all 2B images: crop, warp and
+    centre crop are a single projective map per image (M_A, M_B), read straight from the sources.  Where the centre crop already has
+    input_size the ImageNet Normalize (normalize=True) is fused into that launch; otherwise the warp writes un-normalised centre
+    crops and resize_normalise (bicubic) makes the final images, H_s2t carrying the rescale of :77-79.
+    Returns a dict: im_A (the imgs_a image under H_1t), im_B (imgs_b under H_2t; the plain centre crop when not bi), both
+    (B,3,h,w) float32; H_s2t (B,3,3) float32, im_A pixels -> im_B pixels; H_s2t64, M_A, M_B (float64), ok (B,) int32; and with
+    return_warped, warped_img1: the un-normalised im_A warped by H_s2t (:83; two or three more launches)."""
+    a = list(imgs_a.unbind(0)) if isinstance(imgs_a, torch.Tensor) else list(imgs_a)
+    b = list(imgs_b.unbind(0)) if isinstance(imgs_b, torch.Tensor) else list(imgs_b)
+    if len(a) != len(b) or not a:
+        raise ValueError(f"random_h_batch: {len(a)} and {len(b)} images")
+    B = len(a)
+    for x, y in zip(a, b):
+        if x.shape != y.shape or x.dim() != 3 or x.shape[0] != 3:
+            raise ValueError(f"random_h_batch: a pair must be two (3,h,w) images of one size, got {tuple(x.shape)} and {tuple(y.shape)}")
+        if x.shape[1] <= crop_size or x.shape[2] <= crop_size:
+            raise ValueError(f"random_h_batch: a {x.shape[1]} x {x.shape[2]} image does not hold a {crop_size} crop (pre-resize it, :45-48)")
+    dev = require_gpu(*a, *b)
+    crop_size = int(crop_size)
+    deform_area = int(crop_size * deformation_ratio)  # :57
+    d2 = deform_area // 2
+    centre = crop_size - 2 * d2
+    out_h, out_w = int(input_size[0]), int(input_size[1])
+    draws = torch.as_tensor(draws).to(torch.int32).reshape(B, 18).clone()
+    if not bi:  # :27-28 -- image 2's source points are the target points: H_2t is the identity
+        draws[:, 10:18] = torch.tensor([d2, d2, crop_size - d2 - 1, d2, crop_size - d2 - 1, crop_size - d2 - 1, d2, crop_size - d2 - 1],
+                                       dtype=torch.int32, device=draws.device)
+    prm = random_h_params(draws.to(dev), crop_size, deform_area, (out_h, out_w))
+    fused = (centre, centre) == (out_h, out_w)
+    mean, std = (IMAGENET_MEAN, IMAGENET_STD) if normalize else ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+    norm_in_warp = fused and normalize
+    both = _warp(a + b, prm["M"], False, (centre, centre), mean if norm_in_warp else None, std if norm_in_warp else None, "random_h_batch")
+    final = both if fused else resize_normalise(both, (out_h, out_w), "bicubic", mean, std)
+    out = {"im_A": final[:B], "im_B": final[B:], "H_s2t": prm["H_s2t"], "H_s2t64": prm["H_s2t64"], "M_A": prm["M_A"], "M_B": prm["M_B"],
+           "ok": prm["ok"]}
+    if return_warped:
+        if not fused:
+            raw_a = resize_normalise(both[:B], (out_h, out_w), "bicubic", (0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+        else:
+            raw_a = _warp(a, prm["M_A"].contiguous(), False, (centre, centre), what="random_h_batch") if norm_in_warp else both[:B]
+        out["warped_img1"] = _warp(raw_a, prm["H_s2t64"], True, (out_h, out_w), what="random_h_batch")
+    return out

@@ -573,6 +573,46 @@ int gfn_train_step(const gfn_ts_tensor *tensor_table, int n_tensors, const gfn_t
                    double max_norm, double growth, double backoff, int growth_interval, int zero_grads, float *stats_out, void *ws,
                    int64_t ws_bytes, gfn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training pairs (the batch a training step consumes) -- datasets/generate_random_H_large_size.py:6-85 (random_four_points, randomH)
+ * as datasets/homography_dataset_large_size.py:148-228 calls it per sample on host workers, with kornia's get_perspective_transform,
+ * transform_points and warp_perspective; csrc/pair_synth.hip.  The crop, the 640 x 640 warp and the centre crop of an image are ONE
+ * projective map from output pixels to source pixels, so a batch is one parameter launch and one warp launch and the intermediates
+ * are never made.  The reference solves its 8 x 8 systems (entries up to 640^2) and inverts in fp32; here every solve, inverse and
+ * pixel coordinate is double.  3 x 3 matrices are inverted as adjugate / determinant: exact for the identity and integer translations.
+ *
+ * gfn_perspective_from_points: kornia.geometry.transform.get_perspective_transform (generate_random_H_large_size.py:30, 71) for n
+ *   four-point problems.  src, dst (n,4,2) float (x, y) -> H (n,3,3) double with H[8] = 1 and dst ~ H src.  The 8 x 8 system is
+ *   kornia's (rows [x y 1 0 0 0 -xu -yu | u], [0 0 0 x y 1 -xv -yv | v]), solved for H - identity -- the right-hand side is then
+ *   dst - src, which is exact, so src == dst gives the identity bit for bit -- by Gaussian elimination with partial pivoting, a row
+ *   per lane (csrc/ge_solve8.h).  ok (n): 1, or 0 with H = identity when three of the source points lie on a line (or coincide),
+ *   a pivot vanishes or a component is not finite.
+ * gfn_random_h_params: randomH's geometry for B samples from their random draws.  draws (B,18) int32: crop_x, crop_y (:50-51), then
+ *   the corner draws of image 1 and of image 2, each tl x,y; tr x,y; br x,y; bl x,y (:7-22; for bi = False the caller writes the
+ *   target points of :23 into image 2's eight).  crop_size = the side of the crop (:53-54), deform_area (:57); out_h, out_w = the
+ *   centre-cropped size crop_size - 2 * (deform_area / 2) (:34), checked; final_h, final_w = the size the images are resized to
+ *   afterwards (:73-74).  Per sample: H_1t, H_2t (:23-30), H_1t2t = H_2t H_1t^-1, the corner flow and H_s2t (:62-71) and, when
+ *   the final size differs from the output size, diag(final_h / out_h, final_h / out_h, 1) H_s2t diag(final_w / out_w, final_w /
+ *   out_w, 1)^-1 -- :77-79 as written, the height ratio on both axes on the left, the width ratio on both on the right.  Writes
+ *   H_s2t32 (B,3,3) float (what the reference hands to the loss), H_s2t64 (B,3,3) double, M_A and M_B (B,3,3) double: output pixel
+ *   -> source-image pixel of the two images, translate(crop_x, crop_y) H_it^-1 translate(deform_area / 2, deform_area / 2), and
+ *   ok (B): 1 when all three solves succeeded.  Any of the five outputs may be NULL.
+ * gfn_warp_perspective_fwd: kornia's warp_perspective(align_corners=True, mode="bilinear", padding_mode="zeros") (:33, :83;
+ *   homography_dataset_large_size.py:207) with the Normalize of :184-185 optionally fused.  out (B,C,Ho,Wo) float, batch stride
+ *   out_bs: pixel (u, v) of sample b reads its source at (x, y) = (X / Z, Y / Z), (X, Y, Z) = M_b (u, v, 1), evaluated in double
+ *   (invert != 0: M_b is first inverted, i.e. M holds kornia's source -> destination matrices); bilinear in PIXEL coordinates, a
+ *   neighbour outside the source counting as 0; floor and fractions from the double, the blend in fp32 in the order
+ *   (1-fy) * ((1-fx) * v00 + fx * v01) + fy * ((1-fx) * v10 + fx * v11); then (v - mean[c]) / std[c] when mean and std (C floats
+ *   each, DEVICE memory) are given (both or neither).  A non-finite coordinate reads 0.  Sources are given per sample, so a batch
+ *   may hold images of different sizes and views of larger buffers: src_planes, a DEVICE array of B pointers to channel 0 of each
+ *   sample, and src_dims, DEVICE (B,3) int32 rows (H, W, channel stride in floats); rows are W floats apart, H * W < 2^31.
+ *   No atomics: identical calls give identical bits.  B <= 65535; B, Ho or Wo = 0 is valid and launches nothing. */
+int gfn_perspective_from_points(const float *src, const float *dst, double *H, int *ok, int n, gfn_stream_t stream);
+int gfn_random_h_params(const int *draws, int B, int crop_size, int deform_area, int out_h, int out_w, int final_h, int final_w,
+                        float *H_s2t32, double *H_s2t64, double *M_A, double *M_B, int *ok, gfn_stream_t stream);
+int gfn_warp_perspective_fwd(const float *const *src_planes, const int *src_dims, const double *M, int invert, float *out,
+                             int64_t out_bs, int B, int C, int Ho, int Wo, const float *mean, const float *std, gfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
