@@ -1,7 +1,7 @@
 """The online pair synthesis of the reference's HomographyDataset (datasets/homography_dataset_large_size.py:148-228), batched on the
-device: `PairSynthesizer` is the train branch after `initial_transforms` (:168-185), `val_pair` the val branch's H rescale and
-warped image (:203-207).  File lists, image decoding, ColorJitter / blur (host, PIL), the offline `glunet` branch with its masks and
-uint8 sources are out of scope."""
+device: `PairSynthesizer` is the train branch (:168-185) -- after `initial_transforms`, or with a `PhotometricAugment`
+(datasets/photometric.py) from the decoded uint8 pixels on -- and `val_pair` the val branch's H rescale and warped image (:203-207).
+File lists, image decoding and the offline `glunet` branch's masks are out of scope."""
 import random
 
 import torch
@@ -18,10 +18,13 @@ class PairSynthesizer:
     input_resolution: int or (h, w); crop_size = int(input_resolution[0] / (1 - ratio)) (:175) and deform_area = int(crop_size *
     ratio) (generate_random_H_large_size.py:57), with one ratio drawn from deformation_ratio per call (the reference draws one per
     sample; its default list has one entry).  An image that does not hold the crop is first resized as :45-48 resize it.  The
-    random integers come from `generator` (None: torch's global generator) in the reference's order."""
+    random integers come from `generator` (None: torch's global generator) in the reference's order.
+
+    photometric: None, or a PhotometricAugment; the two lists then hold decoded (h,w,3) uint8 images, which it augments first, in
+    the order imgs0[0], imgs1[0], imgs0[1], ... in which __getitem__ (:168) passes them through `initial_transforms`."""
 
     def __init__(self, input_resolution, deformation_ratio=(0.3,), bi=True, normalize=True, generator=None, return_warped=False,
-                 device="cuda"):
+                 device="cuda", photometric=None):
         res = (int(input_resolution),) * 2 if isinstance(input_resolution, int) else tuple(int(v) for v in input_resolution)
         if len(res) != 2 or min(res) < 2:
             raise ValueError(f"PairSynthesizer: input_resolution must be an int or an (h, w) pair, got {input_resolution!r}")
@@ -29,11 +32,14 @@ class PairSynthesizer:
         if not self.deformation_ratio or not all(0.0 < r < 1.0 for r in self.deformation_ratio):
             raise ValueError(f"PairSynthesizer: deformation ratios must lie in (0, 1), got {deformation_ratio!r}")
         self.bi, self.normalize, self.generator, self.return_warped = bool(bi), bool(normalize), generator, bool(return_warped)
-        self.device = torch.device(device)
+        self.device, self.photometric = torch.device(device), photometric
 
     def __call__(self, imgs0, imgs1):
         if len(imgs0) != len(imgs1) or not len(imgs0):
             raise ValueError(f"PairSynthesizer: {len(imgs0)} and {len(imgs1)} images")
+        if self.photometric is not None:                                                            # :168
+            both = self.photometric([t for pair in zip(imgs0, imgs1) for t in pair])
+            imgs0, imgs1 = both[0::2], both[1::2]
         ratio = float(random.sample(self.deformation_ratio, 1)[0])                                  # :174
         crop_size = int(self.input_resolution[0] / (1 - ratio))                                     # :175
         a = [pre_resize(t.to(self.device, torch.float32), crop_size) for t in imgs0]

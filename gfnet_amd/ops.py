@@ -4,8 +4,10 @@ Each function cites the reference code it stands in for (paths relative to KN-Zh
 torch supplies device memory and the current HIP stream; every result comes from csrc/*.hip.
 There is no CPU implementation here: CPU tensors raise.
 """
+import functools
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1172,3 +1174,201 @@ def random_h_batch(imgs_a, imgs_b, draws, crop_size, input_size, deformation_rat
             raw_a = _warp(a, prm["M_A"].contiguous(), False, (centre, centre), what="random_h_batch") if norm_in_warp else both[:B]
         out["warped_img1"] = _warp(raw_a, prm["H_s2t64"], True, (out_h, out_w), what="random_h_batch")
     return out
+
+
+# ---- photometric augmentation (train.py:74-79, :88-93 initial_transforms; csrc/photometric.hip) -------------------------------------------
+PHOTO_OPS = ("brightness", "contrast", "saturation", "hue")  # GFN_PHOTO_* in this order: ColorJitter's fn_idx
+
+
+def resize_output_size(h, w, size):
+    """(h', w') of torchvision's Resize(size) with an int: the short side becomes `size`, the long side int(size * long / short);
+    unchanged when the short side already equals `size`."""
+    short, long = (w, h) if w <= h else (h, w)
+    if short == size:
+        return h, w
+    new_long = int(size * long / short)
+    return (new_long, size) if w <= h else (size, new_long)
+
+
+@functools.lru_cache(maxsize=256)
+def resize_axis_table(n_in, n_out):
+    """One axis of Image.resize(BILINEAR) as gfn_photo_resize_u8 reads it: (int32 array of n_out (min, count) pairs, then n_out rows of
+    `taps` weights; taps).  Resample.c's precompute_coeffs and normalize_coeffs_8bpc, in double, in its order of operations."""
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    taps = int(math.ceil(support)) * 2 + 1
+    centre = (np.arange(n_out) + 0.5) * scale
+    ss = 1.0 / fs
+    lo = np.maximum((centre - support + 0.5).astype(np.int64), 0)
+    count = np.minimum((centre + support + 0.5).astype(np.int64), n_in) - lo
+    k = np.arange(taps)
+    x = np.abs(((k[None, :] + lo[:, None]) - centre[:, None] + 0.5) * ss)
+    w = np.where((x < 1.0) & (k[None, :] < count[:, None]), 1.0 - x, 0.0)
+    total = np.zeros(n_out)
+    for j in range(taps):  # summed in tap order, as the C loop does
+        total = total + w[:, j]
+    w = np.where(total[:, None] != 0.0, w / np.where(total == 0.0, 1.0, total)[:, None], w)
+    fixed = (0.5 + w * (1 << 22)).astype(np.int64)
+    table = np.concatenate([np.stack([lo, count], 1).reshape(-1), fixed.reshape(-1)]).astype(np.int32)
+    table.setflags(write=False)
+    return table, taps
+
+
+def box_blur_radius(radius):
+    """The fractional box radius of ImageFilter.GaussianBlur(radius)'s three box passes (BoxBlur.c _gaussian_blur_radius), with its
+    float variables and double intermediates."""
+    f32 = np.float32
+    sigma2 = f32(f32(radius) * f32(radius) / f32(3))
+    L = f32(math.sqrt(12.0 * float(sigma2) + 1.0))
+    l = f32(math.floor((float(L) - 1.0) / 2.0))
+    a = f32(f32(f32(2) * l + f32(1)) * f32(f32(l * f32(l + f32(1))) - f32(f32(3) * sigma2)))
+    a = f32(a / f32(f32(6) * f32(sigma2 - f32(f32(l + f32(1)) * f32(l + f32(1))))))
+    return float(f32(l + a))
+
+
+def _photo_records(params, n):
+    """The (n, GFN_PHOTO_REC) int32 records of gfn_photo_jitter_blur from n dicts with the keys of datasets.draw_photometric."""
+    if len(params) != n:
+        raise ValueError(f"photo_augment: {len(params)} parameter records for {n} images")
+    rec = np.zeros((n, _lib.PHOTO_REC), dtype=np.int32)
+    flt = rec.view(np.float32)
+    for i, p in enumerate(params):
+        order = [int(v) for v in p.get("order", (0, 1, 2, 3))]
+        if sorted(order) != [0, 1, 2, 3]:
+            raise ValueError(f"photo_augment: order must be a permutation of 0..3, got {order}")
+        rec[i, :4] = order
+        mask = 0
+        for k, name in enumerate(PHOTO_OPS[:3]):
+            v = p.get(name)
+            if v is not None:
+                if not v >= 0.0:
+                    raise ValueError(f"photo_augment: {name} factor {v} is negative")
+                flt[i, 4 + k] = v
+                mask |= 1 << k
+        if p.get("hue") is not None:
+            if not -0.5 <= p["hue"] <= 0.5:
+                raise ValueError(f"photo_augment: hue factor {p['hue']} is not in [-0.5, 0.5]")
+            rec[i, 7] = int(p["hue"] * 255) & 255
+            mask |= 1 << _lib.PHOTO_HUE
+        rec[i, 8] = 1 if p.get("grayscale") else 0
+        if p.get("blur_radius"):
+            R = box_blur_radius(p["blur_radius"])
+            if not 0.0 <= R < 2.0:
+                raise ValueError(f"photo_augment: blur radius {p['blur_radius']} gives a box radius of {R}; the kernel's halo holds < 2")
+            flt[i, 9] = R
+        rec[i, 10] = mask
+    return rec
+
+
+def _photo_images(images, what):
+    samples = list(images.unbind(0)) if isinstance(images, torch.Tensor) and images.dim() == 4 else list(images)
+    dev = require_gpu(*samples)
+    keep = []
+    for t in samples:
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{what}: every image must be (h,w,3) uint8, got {tuple(t.shape)} {t.dtype}")
+        h, w, _ = t.shape
+        if h > 32768 or w > 32768:
+            raise ValueError(f"{what}: an image of {h} x {w} pixels is too large (32768 per side)")
+        if t.stride(2) != 1 or t.stride(1) != 3 or (h > 1 and t.stride(0) < 3 * w) or t.stride(0) >= 2 ** 31:
+            t = t.contiguous()
+        keep.append(t)
+    return keep, dev
+
+
+def _photo_run(images, size, params, out, what):
+    """Resize (size not None) and / or augment (params not None) a batch: ONE upload of every table, then at most three launches
+    (resize, stats when some image has contrast on, jitter + blur), whatever the number of images; no host synchronisation."""
+    if out not in ("float", "uint8"):
+        raise ValueError(f"{what}: out must be 'float' or 'uint8', got {out!r}")
+    keep, dev = _photo_images(images, what)
+    n = len(keep)
+    if n == 0:
+        return []
+    if n > 65535:
+        raise ValueError(f"{what}: {n} images in one batch (at most 65535)")
+    mid_hw = [resize_output_size(t.shape[0], t.shape[1], int(size)) if size is not None else (t.shape[0], t.shape[1]) for t in keep]
+    resized = [i for i, t in enumerate(keep) if mid_hw[i] != (t.shape[0], t.shape[1])]
+    mid = list(keep)
+    if resized:
+        buf = torch.empty(sum(3 * mid_hw[i][0] * mid_hw[i][1] for i in resized), device=dev, dtype=torch.uint8)
+        off = 0
+        for i in resized:
+            h, w = mid_hw[i]
+            mid[i] = buf[off:off + 3 * h * w].view(h, w, 3)
+            off += 3 * h * w
+    res = mid
+    if not resized and params is None:
+        return res  # nothing to resize: no table, no launch
+    if params is not None:
+        rec = _photo_records(params, n)
+        per = 3 if out == "uint8" else 12  # bytes per pixel: float planes start on 4-byte boundaries
+        buf = torch.empty(sum(per * h * w for h, w in mid_hw), device=dev, dtype=torch.uint8)
+        res, off = [], 0
+        for h, w in mid_hw:
+            piece = buf[off:off + per * h * w]
+            res.append(piece.view(h, w, 3) if out == "uint8" else piece.view(torch.float32).view(3, h, w))
+            off += per * h * w
+    # the tables, in one host array: n source, n intermediate and n output pointers and n zeroed sums (int64), then (int32) the
+    # source and intermediate (H, W, row stride) rows, the resize records, the chain records and the coefficient tables
+    RZ, PR = _lib.PHOTO_RESIZE_REC, _lib.PHOTO_REC
+    coef, coef_at, rz = [], {}, np.zeros((n, RZ), dtype=np.int32)
+    for i in resized:
+        (h, w, _), (ho, wo) = keep[i].shape, mid_hw[i]
+        at = []
+        for key in ((w, wo), (h, ho)):
+            if key not in coef_at:
+                table, taps = resize_axis_table(*key)
+                coef_at[key] = (sum(len(c) for c in coef), taps)
+                coef.append(table)
+            at.extend(coef_at[key])
+        rz[i] = (ho, wo, *at)
+
+    def dims(ts):  # (H, W, row stride in bytes): a view that was not resized keeps its own stride as the intermediate image too
+        return np.array([(t.shape[0], t.shape[1], t.stride(0) if t.shape[0] > 1 else 3 * t.shape[1]) for t in ts], dtype=np.int32).reshape(-1)
+
+    ints = [dims(keep), dims(mid), rz.reshape(-1),
+            rec.reshape(-1) if params is not None else np.zeros(n * PR, dtype=np.int32)] + coef
+    n_int = sum(len(a) for a in ints)
+    host = np.zeros(4 * n + (n_int + 1) // 2, dtype=np.int64)
+    host[:n] = [t.data_ptr() for t in keep]
+    host[n:2 * n] = [t.data_ptr() for t in mid]
+    host[2 * n:3 * n] = [t.data_ptr() for t in res]
+    host[4 * n:].view(np.int32)[:n_int] = np.concatenate(ints)
+    table = torch.from_numpy(host).to(dev)
+    tab32 = table[4 * n:].view(torch.int32)
+    src_dims, mid_dims, recs, prm, coefs = tab32[:3 * n], tab32[3 * n:6 * n], tab32[6 * n:6 * n + RZ * n], \
+        tab32[(6 + RZ) * n:(6 + RZ + PR) * n], tab32[(6 + RZ + PR) * n:]
+    stream = stream_ptr(dev)
+    if resized:
+        _timed("photo_resize", lambda: _L().gfn_photo_resize_u8(ptr(table[:n]), ptr(src_dims), ptr(table[n:2 * n]), ptr(recs), ptr(coefs), n,
+                                                                 max(mid_hw[i][0] for i in resized), max(mid_hw[i][1] for i in resized), stream))
+    if params is not None:
+        sums = table[3 * n:4 * n]
+        contrast = [mid_hw[i] for i in range(n) if (rec[i, 10] >> _lib.PHOTO_CONTRAST) & 1]
+        if contrast:
+            _timed("photo_stats", lambda: _L().gfn_photo_stats(ptr(table[n:2 * n]), ptr(mid_dims), ptr(prm), ptr(sums), n,
+                                                               max(h for h, _ in contrast), max(w for _, w in contrast), stream))
+        _timed("photo_jitter_blur", lambda: _L().gfn_photo_jitter_blur(ptr(table[n:2 * n]), ptr(mid_dims), ptr(prm), ptr(sums), ptr(table[2 * n:3 * n]),
+                                                                       int(out == "uint8"), n, max(h for h, _ in mid_hw),
+                                                                       max(w for _, w in mid_hw), stream))
+    del keep, mid  # (alive until after the launches; the allocator's reuse is ordered on this stream)
+    return res
+
+
+def photo_resize(images, size):
+    """torchvision's Resize(size) on PIL images (train.py:75), i.e. Pillow's Image.resize(BILINEAR), for a batch: images is a list of
+    (h,w,3) uint8 device tensors of any sizes, or one (N,h,w,3) tensor.  Returns a list of (h',w',3) uint8 tensors, bit for bit
+    Pillow's; an image whose short side already is `size` comes back as it is.  One upload and one launch."""
+    return _photo_run(images, int(size), None, "uint8", "photo_resize")
+
+
+def photo_augment(images, params, out="float", resize=None):
+    """ColorJitter, RandomGrayscale, RandomGaussianBlur and ToTensor (train.py:76-78, :89-92) with Pillow's arithmetic for a batch of
+    (h,w,3) uint8 device images (a list, or one (N,h,w,3) tensor).  params: one dict per image as datasets.draw_photometric makes
+    them -- "order" (a permutation of 0..3 = brightness, contrast, saturation, hue), "brightness" / "contrast" / "saturation" / "hue"
+    (a factor, or None = off), "grayscale" (bool), "blur_radius" (GaussianBlur's radius, or None).  out="float": a list of (3,h,w)
+    float32 tensors = u8 / 255 (ToTensor); "uint8": (h,w,3) uint8.  resize: first Resize(resize), in the same upload.  One upload
+    and at most two launches (three with resize), whatever the number of images."""
+    return _photo_run(images, resize, list(params), out, "photo_augment")

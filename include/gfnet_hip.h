@@ -613,6 +613,44 @@ int gfn_random_h_params(const int *draws, int B, int crop_size, int deform_area,
 int gfn_warp_perspective_fwd(const float *const *src_planes, const int *src_dims, const double *M, int invert, float *out,
                              int64_t out_bs, int B, int C, int Ho, int Wo, const float *mean, const float *std, gfn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Photometric augmentation (decoded uint8 pixels -> the float images the pair synthesis consumes) -- the `initial_transforms` of
+ * train.py:74-79 and :88-93: Resize(640), ColorJitter, RandomGrayscale, RandomGaussianBlur (datasets/homography_dataset_large_size.py:
+ * 17-28), ToTensor, which the reference runs per image on host workers on PIL images; csrc/photometric.hip.  What executes there is
+ * Pillow, and every stage here maps uint8 to uint8 with Pillow's arithmetic: pinned against Pillow 12.2.0, NOT against torchvision.
+ * A batch holds images of different sizes: `src` / `dst` are DEVICE arrays of N pointers, dims DEVICE (N,3) int32 rows (H, W, row
+ * stride in bytes) of (H,W,3) interleaved uint8 images.  max_h / max_w: the largest height and width in the batch (they size the
+ * grid).  N <= 65535; N = 0 or an empty largest image is valid and launches nothing.  Pointer tables and sums are 8-byte aligned,
+ * int tables 4-byte.  Identical calls give identical bits: the only atomics are the integer sums of gfn_photo_stats.
+ *
+ * gfn_photo_resize_u8: Image.resize(BILINEAR) (train.py:75 Resize(640), which antialiases on PIL images), both passes in one launch:
+ *   a pass is clip8((sum_k w_k x_k + 2^21) >> 22) over the taps [min, min + count) of an output index, horizontal first into uint8.
+ *   recs: DEVICE (N, GFN_PHOTO_RESIZE_REC) int32 rows (Hout, Wout, x offset, x taps, y offset, y taps); an axis table starts at
+ *   coef[offset] with Xout (min, count) pairs, then Xout rows of `taps` 22-bit fixed-point weights, computed by the host in double
+ *   as Resample.c does.  dst images are dense (Hout,Wout,3).  Hout = 0: the image is skipped.  max_out_h / max_out_w: largest output.
+ * gfn_photo_stats: sums[i] += sum of L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 over image i as it stands when contrast's turn
+ *   comes in its chain (ImageEnhance.Contrast's mean, torchvision's adjust_contrast), for every image whose record enables contrast;
+ *   sums (N) int64, zero on entry.
+ * gfn_photo_jitter_blur: per image its record's chain, then ToTensor.  params: DEVICE (N, GFN_PHOTO_REC) int32 rows: order[4] (the
+ *   GFN_PHOTO_* ops in ColorJitter's drawn order), the brightness, contrast and saturation factors (float bits), the hue byte
+ *   trunc(hue_factor * 255) & 255, the grey flag (RandomGrayscale), the box radius R of the blur (float bits; 0 = no blur, < 2), the
+ *   mask of enabled ops (bit GFN_PHOTO_*), one unused.  Brightness / contrast / saturation: ImageEnhance's blend a + f (b - a) in
+ *   float against black / the constant int(mean(L) + 0.5) from `sums` / L; hue: Pillow's RGB -> HSV -> RGB with H shifted; grey:
+ *   convert("L") into all channels; blur: ImageFilter.GaussianBlur's three box passes along rows, then three along columns, indices
+ *   clamped to the image.  dst: out_u8 != 0 (H,W,3) uint8, else planar (3,H,W) float = u8 / 255 (ToTensor), dense. */
+#define GFN_PHOTO_BRIGHTNESS 0
+#define GFN_PHOTO_CONTRAST 1
+#define GFN_PHOTO_SATURATION 2
+#define GFN_PHOTO_HUE 3
+#define GFN_PHOTO_REC 12
+#define GFN_PHOTO_RESIZE_REC 6
+int gfn_photo_resize_u8(const void *const *src, const int *src_dims, void *const *dst, const int *recs, const int *coef, int N,
+                        int max_out_h, int max_out_w, gfn_stream_t stream);
+int gfn_photo_stats(const void *const *src, const int *dims, const int *params, int64_t *sums, int N, int max_h, int max_w,
+                    gfn_stream_t stream);
+int gfn_photo_jitter_blur(const void *const *src, const int *dims, const int *params, const int64_t *sums, void *const *dst, int out_u8,
+                          int N, int max_h, int max_w, gfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
