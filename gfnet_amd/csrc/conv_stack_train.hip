@@ -28,85 +28,11 @@
 //                          sum_p gu[p] x[p + off_k] and db_dw = sum gu
 //   ct_dw_wgrad_kernel     sums those partials (double, fixed order)
 // No floating-point atomics anywhere: two identical calls give identical bits.
-#include "pw_gemm_tile.h"
+// The depthwise tile, bn_affine / bn_pre, the merge and three of the small reductions are conv_train_common.h's, shared with the fp16
+// autocast class of conv_stack_train_half.hip.
+#include "conv_train_common.h"
 
 namespace {
-
-constexpr int kTile = 32;         // depthwise tile side in cells: 256 threads x 4 cells of a row
-constexpr int kHalo = kTile + 4;  // staged side (2 cells of halo all round)
-constexpr int kDwCols = 26;       // depthwise parameter gradients per channel: 25 taps + the bias
-constexpr int kWgCells = 32;      // cells per wave and K step of the 1x1 weight gradient
-
-// BatchNorm as one multiply-add per value.  Forward and backward both come through here (and -ffp-contract=off keeps the
-// multiply and the add apart), so the backward's ReLU mask is the forward's, bit for bit.
-__device__ __forceinline__ void bn_affine(float gamma, float beta, float mean, float invstd, float &alpha, float &betap) {
-    alpha = gamma * invstd;
-    betap = beta - mean * alpha;
-}
-__device__ __forceinline__ float bn_pre(float u, float alpha, float betap) { return u * alpha + betap; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ float half_wave_sum(float v) {  // over the 32 lanes that share lane >> 5
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-// sum over the workgroup's 256 threads in a fixed order, returned to every thread; red: 4 floats of LDS
-__device__ __forceinline__ float block_sum(float v, float *red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-struct TileId {
-    int b, c, tile, row0, col0;
-    size_t plane;  // b * C + c
-};
-__device__ __forceinline__ TileId decode_tile(unsigned bid, int C, int tiles_x, int tiles) {
-    TileId t;
-    t.tile = (int)(bid % (unsigned)tiles);
-    const unsigned pl = bid / (unsigned)tiles;
-    t.c = (int)(pl % (unsigned)C);
-    t.b = (int)(pl / (unsigned)C);
-    t.plane = pl;
-    t.row0 = (t.tile / tiles_x) * kTile;
-    t.col0 = (t.tile % tiles_x) * kTile;
-    return t;
-}
-
-// the tile with its halo: Ts[cell] = f(the cell lies inside the map, its offset in the plane -- 0 outside)
-template <typename F>
-__device__ __forceinline__ void stage_halo(float *Ts, const TileId &t, int G, F f) {
-    for (int e = threadIdx.x; e < kHalo * kHalo; e += 256) {
-        const int hy = e / kHalo, hx = e - hy * kHalo;
-        const int gy = t.row0 - 2 + hy, gx = t.col0 - 2 + hx;
-        const bool ok = (unsigned)gy < (unsigned)G && (unsigned)gx < (unsigned)G;
-        Ts[e] = f(ok, ok ? gy * G + gx : 0);
-    }
-}
-
-// acc[q] = sum_k w[k] Ts[cell (r, c4 + q) + off_k], k = 5 dy + dx ascending: 25 fmas per cell; FLIP: w[24 - k], the transposed conv
-template <bool FLIP>
-__device__ __forceinline__ void dw_taps(const float *Ts, const float *wc, int r, int c4, float (&acc)[4]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = 0.f;
-#pragma unroll
-    for (int dy = 0; dy < 5; ++dy) {
-        const float4 a = *reinterpret_cast<const float4 *>(&Ts[(r + dy) * kHalo + c4]);
-        const float4 e = *reinterpret_cast<const float4 *>(&Ts[(r + dy) * kHalo + c4 + 4]);
-        const float v[8] = {a.x, a.y, a.z, a.w, e.x, e.y, e.z, e.w};
-#pragma unroll
-        for (int dx = 0; dx < 5; ++dx)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] = fmaf(wc[FLIP ? 24 - (dy * 5 + dx) : dy * 5 + dx], v[q + dx], acc[q]);
-    }
-}
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ct_dw_fwd_kernel(const float *__restrict__ x, const float *__restrict__ dw_w,
@@ -151,55 +77,10 @@ __global__ __launch_bounds__(256) void ct_dw_fwd_kernel(const float *__restrict_
     }
 }
 
-struct Moments {
-    double n, mean, m2;
-};
-// Chan, Golub, LeVeque: the moments of the union of two sets
-__device__ __forceinline__ void merge(Moments &a, const Moments &b) {
-    if (b.n == 0.0) return;
-    if (a.n == 0.0) {
-        a = b;
-        return;
-    }
-    const double n = a.n + b.n, d = b.mean - a.mean;
-    a.mean += d * (b.n / n);
-    a.m2 += b.m2 + d * d * (a.n * b.n / n);
-    a.n = n;
-}
-
-// one wave per channel
 __global__ __launch_bounds__(64) void ct_stats_kernel(const float *__restrict__ part, float *__restrict__ mean, float *__restrict__ invstd,
                                                       float *__restrict__ running_mean, float *__restrict__ running_var, int G, int tiles_x,
                                                       int tiles, int nparts, double momentum, double eps) {
-    __shared__ double sn[64], sm[64], s2[64];
-    const int c = blockIdx.x, lane = threadIdx.x;
-    Moments a = {0.0, 0.0, 0.0};
-    for (int i = lane; i < nparts; i += 64) {
-        const int tile = i % tiles;
-        const int rows = min(kTile, G - (tile / tiles_x) * kTile), cols = min(kTile, G - (tile % tiles_x) * kTile);
-        const float *p = part + ((size_t)c * nparts + i) * 2;
-        const Moments b = {(double)(rows * cols), (double)p[0], (double)p[1]};
-        merge(a, b);
-    }
-    sn[lane] = a.n, sm[lane] = a.mean, s2[lane] = a.m2;
-    __syncthreads();
-    for (int s = 32; s >= 1; s >>= 1) {
-        if (lane < s) {
-            Moments p = {sn[lane], sm[lane], s2[lane]};
-            const Moments q = {sn[lane + s], sm[lane + s], s2[lane + s]};
-            merge(p, q);
-            sn[lane] = p.n, sm[lane] = p.mean, s2[lane] = p.m2;
-        }
-        __syncthreads();
-    }
-    if (lane == 0) {
-        const double n = sn[0], mu = sm[0], var = s2[0] / n;  // biased: what normalises
-        mean[c] = (float)mu;
-        invstd[c] = (float)(1.0 / sqrt(var + eps));
-        // torch: running = (1 - momentum) * running + momentum * batch, the variance unbiased
-        running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mu);
-        running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * (s2[0] / (n - 1.0)));
-    }
+    stats_channel(part, mean, invstd, running_mean, running_var, G, tiles_x, tiles, nparts, momentum, eps);
 }
 
 // y[b] = W . relu(u[b]*alpha + beta') + bias; W (M, K) row major, on the tile of pw_gemm_tile.h.
@@ -306,28 +187,9 @@ __global__ __launch_bounds__(256, 2) void ct_pw_bwd_kernel(const float *__restri
     }
 }
 
-// dgamma[c] = sum gz*u_hat, dbeta[c] = sum gz: one wave per channel, double, fixed order.  dgdb: (2, C) = dgamma, dbeta
 __global__ __launch_bounds__(64) void ct_bn_bwd_kernel(const float *__restrict__ part, int nparts, int C, float *__restrict__ dgdb,
                                                        float *__restrict__ dgamma, float *__restrict__ dbeta) {
-    __shared__ double s1[64], s2[64];
-    const int c = blockIdx.x, lane = threadIdx.x;
-    double a1 = 0.0, a2 = 0.0;
-    for (int i = lane; i < nparts; i += 64) {
-        const float *p = part + ((size_t)c * nparts + i) * 2;
-        a1 += (double)p[0], a2 += (double)p[1];
-    }
-    s1[lane] = a1, s2[lane] = a2;
-    __syncthreads();
-    for (int s = 32; s >= 1; s >>= 1) {
-        if (lane < s) s1[lane] += s1[lane + s], s2[lane] += s2[lane + s];
-        __syncthreads();
-    }
-    if (lane == 0) {
-        const float db = (float)s1[0], dg = (float)s2[0];
-        dgdb[c] = dg, dgdb[C + c] = db;
-        if (dgamma) dgamma[c] = dg;
-        if (dbeta) dbeta[c] = db;
-    }
+    bn_bwd_channel(part, nparts, C, dgdb, dgamma, dbeta);
 }
 
 // One split of dW[m, c] = sum_p gy[m, p] t[c, p], c = C being a row of ones (db_pw).  Workgroup: 32*MT rows m x 32*CW columns c;
@@ -416,7 +278,7 @@ __global__ __launch_bounds__(256) void ct_dw_bwd_kernel(const float *__restrict_
     __shared__ __attribute__((aligned(16))) float Gs[kHalo * kHalo];
     __shared__ __attribute__((aligned(16))) float Xs[kHalo * kHalo];
     __shared__ float red[4][kDwCols];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const TileId t = decode_tile(blockIdx.x, C, tiles_x, tiles);
     const size_t pbase = t.plane * (size_t)G * G;
     const float mn = mean[t.c], is = invstd[t.c];
@@ -443,87 +305,22 @@ __global__ __launch_bounds__(256) void ct_dw_bwd_kernel(const float *__restrict_
         for (int q = 0; q < 4; ++q)
             if (yy < G && xx0 + q < G) gp[q] = acc[q];
     }
-    if (want_w) {  // gu is zero outside the map, so cells of the tile past the map's edge add nothing
-        float pw[kDwCols];
-        float gc[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gc[q] = Gs[(r + 2) * kHalo + c4 + 2 + q];
-        pw[25] = (gc[0] + gc[1]) + (gc[2] + gc[3]);
-#pragma unroll
-        for (int dy = 0; dy < 5; ++dy) {
-            const float4 a = *reinterpret_cast<const float4 *>(&Xs[(r + dy) * kHalo + c4]);
-            const float4 e = *reinterpret_cast<const float4 *>(&Xs[(r + dy) * kHalo + c4 + 4]);
-            const float v[8] = {a.x, a.y, a.z, a.w, e.x, e.y, e.z, e.w};
-#pragma unroll
-            for (int dx = 0; dx < 5; ++dx) {
-                float s = gc[0] * v[dx];
-#pragma unroll
-                for (int q = 1; q < 4; ++q) s = fmaf(gc[q], v[q + dx], s);
-                pw[dy * 5 + dx] = s;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kDwCols; ++j) {
-            const float s = wave_sum(pw[j]);
-            if (lane == 0) red[wave][j] = s;
-        }
-        __syncthreads();
-        if (tid < kDwCols)
-            part[((size_t)t.c * nparts + (size_t)t.b * tiles + t.tile) * kDwCols + tid] =
-                (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-    }
+    if (want_w) dw_param_partials(Gs, Xs, r, c4, red, part + ((size_t)t.c * nparts + (size_t)t.b * tiles + t.tile) * kDwCols);
 }
 
-// per channel: 8 groups of 32 lanes walk the partials, lane j < 26 owns column j; then the groups in a fixed order
 __global__ __launch_bounds__(256) void ct_dw_wgrad_kernel(const float *__restrict__ part, int nparts, float *__restrict__ d_dw_w,
                                                           float *__restrict__ d_dw_b) {
-    __shared__ double s[8][32];
-    const int c = blockIdx.x, g = threadIdx.x >> 5, j = threadIdx.x & 31;
-    double a = 0.0;
-    if (j < kDwCols)
-        for (int p = g; p < nparts; p += 8) a += (double)part[((size_t)c * nparts + p) * kDwCols + j];
-    s[g][j] = a;
-    __syncthreads();
-    if (threadIdx.x < kDwCols) {
-        double tot = 0.0;
-        for (int q = 0; q < 8; ++q) tot += s[q][j];
-        if (j < 25) d_dw_w[(size_t)c * 25 + j] = (float)tot;
-        else if (d_dw_b) d_dw_b[c] = (float)tot;
-    }
+    dw_wgrad_channel(part, nparts, d_dw_w, d_dw_b);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-inline int64_t align4(int64_t floats) { return (floats + 3) / 4 * 4; }
-
-struct TrainPlan {
-    int tiles_x, tiles;     // depthwise tiles per map
-    int ntn;                // 128-cell groups per map (1x1 GEMMs)
-    int wg_mt, wg_cw, wg_ks, wg_tm, wg_tc, wg_s, wg_chunk, wg_parts;  // 1x1 weight gradient
+// the tiling of TrainShape and where the partial sums and the gz map lie in the workspace, in floats
+struct TrainPlan : TrainShape {
     int64_t fwd_floats;
-    int64_t off_gz, off_bn, off_dgdb, off_dw, off_pw, bwd_floats;     // backward workspace, in floats
+    int64_t off_gz, off_bn, off_dgdb, off_dw, off_pw, bwd_floats;
 
-    TrainPlan(int B, int C, int M, int G) {
+    TrainPlan(int B, int C, int M, int G) : TrainShape(B, C, M, G) {
         const int64_t N = (int64_t)G * G;
-        tiles_x = (G + kTile - 1) / kTile;
-        tiles = tiles_x * tiles_x;
-        ntn = (int)((N + kBN - 1) / kBN);
-        wg_cw = C + 1 <= 32 ? 1 : C + 1 <= 64 ? 2 : 4;
-        wg_ks = 4 / wg_cw;
-        const int mtiles = (M + 31) / 32, mt_max = wg_cw == 1 ? 2 : 4;
-        wg_mt = mtiles >= mt_max ? mt_max : (mtiles == 3 ? 4 : mtiles);
-        if (wg_mt > mt_max) wg_mt = mt_max;
-        wg_tm = (M + 32 * wg_mt - 1) / (32 * wg_mt);
-        wg_tc = (C + 1 + 32 * wg_cw - 1) / (32 * wg_cw);
-        // enough workgroups to fill the chip (256 CUs), at least four K steps each
-        const int kts = kWgCells * wg_ks;
-        const int64_t per_image = (int64_t)wg_tm * wg_tc * (B > 0 ? B : 1);
-        int64_t s = (512 + per_image - 1) / per_image;
-        const int64_t s_max = (N + 4 * kts - 1) / (4 * kts);
-        if (s > s_max) s = s_max;
-        if (s < 1) s = 1;
-        wg_chunk = (int)(((N + s - 1) / s + kts - 1) / kts * kts);
-        wg_s = (int)((N + wg_chunk - 1) / wg_chunk);
-        wg_parts = B * wg_s * wg_ks;
         fwd_floats = align4((int64_t)C * B * tiles * 2);
         off_gz = 0;
         off_bn = off_gz + align4((int64_t)B * C * N);
@@ -533,23 +330,6 @@ struct TrainPlan {
         bwd_floats = off_pw + align4((int64_t)wg_parts * M * (C + 1));
     }
 };
-
-// what both directions refuse; 0 when the sizes are fine
-int check_sizes(const char *what, int B, int C, int M, int G) {
-    if (B < 0 || C <= 0 || M <= 0 || G <= 0) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: bad size (B=%d C=%d M=%d G=%d)", what, B, C, M, G);
-    if ((long)C * G * G > 0x1fffffffL || (long)M * G * G > 0x1fffffffL)
-        return gfn::fail(GFN_ERR_INVALID_ARG, "%s: a map (C*G*G floats) must stay below 2 GB", what);
-    if (B > 65535) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: batch > 65535", what);
-    if (B > 0) {
-        const TrainPlan p(B, C, M, G);
-        if ((int64_t)B * C * p.tiles > 0x7fffffffL || (int64_t)B * p.wg_s > 65535 || (int64_t)M * (C + 1) > 0x7fffffffL)
-            return gfn::fail(GFN_ERR_INVALID_ARG, "%s: too many tiles", what);
-        if ((int64_t)B * G * G < 2) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: batch statistics need more than one value per channel", what);
-    }
-    return GFN_OK;
-}
-
-bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 }  // namespace
 
@@ -566,7 +346,7 @@ GFN_EXPORT int gfn_conv_block_train_fwd(const float *x, const float *dw_w, const
     const char *what = "conv_block_train_fwd";
     if (!x || !dw_w || !bn_w || !bn_b || !running_mean || !running_var || !pw_w || !pw_b || !u || !mean || !invstd || !y)
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: null pointer", what);
-    if (int rc = check_sizes(what, B, C, M, G)) return rc;
+    if (int rc = check_train_sizes(what, B, C, M, G)) return rc;
     if (x == u || x == y || u == y) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: x, u and y must be three different maps", what);
     if (!(momentum >= 0.0 && momentum <= 1.0) || !(eps >= 0.0)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: momentum must lie in [0, 1] and eps be >= 0", what);
     if (B == 0) return GFN_OK;
@@ -599,7 +379,7 @@ GFN_EXPORT int gfn_conv_block_train_bwd(const float *gy, const float *x, const f
                                         int C, int M, int G, int need, void *ws, int64_t ws_bytes, gfn_stream_t stream) {
     const char *what = "conv_block_train_bwd";
     if (!gy || !x || !u || !mean || !invstd || !dw_w || !bn_w || !bn_b || !pw_w) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: null pointer", what);
-    if (int rc = check_sizes(what, B, C, M, G)) return rc;
+    if (int rc = check_train_sizes(what, B, C, M, G)) return rc;
     if (need < 0 || need > GFN_CBT_NEED_ALL) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: unknown need mask %d", what, need);
     if (((need & GFN_CBT_NEED_X) && !gx) || ((need & GFN_CBT_NEED_DW) && !d_dw_w) || ((need & GFN_CBT_NEED_BN) && (!d_bn_w || !d_bn_b)) ||
         ((need & GFN_CBT_NEED_PW) && (!d_pw_w || !d_pw_b)))

@@ -19,9 +19,11 @@ GFNet.extract_features (model/network.py:156-201), or feed pyramids directly to
 "fp32" exact fp32 products, "fp16" fp16 1x1 operands, "amp" the class the reference's amp=True refiners run in under
 torch.autocast -- fp16 maps between the blocks).  Training mode keeps the nn modules by default (BatchNorm uses batch statistics
 there); with `train_conv_impl = "hip"` on a refiner its nine blocks run on csrc/conv_stack_train.hip instead (ops.conv_block_train:
-batch-statistic forward, running-buffer update and backward in HIP) -- the fp32 class only; the autocast training class,
-GroupNorm or other norm types, non-depthwise blocks and symmetric batches beyond what the nn path does are out of scope and
-keep the modules.  Either way the refiner input is assembled with the same HIP launch as inference, which has a HIP backward
+batch-statistic forward, running-buffer update and backward in HIP) in the fp32 class, and with `train_conv_impl = "hip_amp"` on
+an amp=True refiner on csrc/conv_stack_train_half.hip (ops.conv_block_train_amp) in the class the reference trains in: fp16 maps
+between the blocks, fp16 operands on the matrix core, fp32 sums, parameters and parameter gradients, overflow to inf for the loss
+scaler.  GroupNorm or other norm types, non-depthwise blocks and symmetric batches beyond what the nn path does are out of scope
+and keep the modules.  Either way the refiner input is assembled with the same HIP launch as inference, which has a HIP backward
 (ops.refiner_input; csrc/refiner_input_bwd.hip).  Refiners with sample_mode "nearest" / "bicubic" train through differentiable
 torch ops instead.
 
@@ -52,7 +54,7 @@ class ConvRefiner(nn.Module):
     forward(num_grid, x, y, flow, scale_factor=1, logits=None) -> (delta_flow, delta_certainty,
     local_corr).  Input assembly (network.py:533-558) and, in eval mode, the conv stack
     (network.py:560-563) run in HIP; training mode keeps the nn modules unless `train_conv_impl`
-    is "hip" (fp32 class, csrc/conv_stack_train.hip).
+    is "hip" (fp32 class, csrc/conv_stack_train.hip) or "hip_amp" (fp16 autocast class, csrc/conv_stack_train_half.hip).
     """
 
     def __init__(self, in_dim=6, hidden_dim=16, out_dim=2, dw=False, kernel_size=5, hidden_blocks=3,
@@ -101,7 +103,8 @@ class ConvRefiner(nn.Module):
         # (operands rounded to fp16, fp32 accumulation: the autocast class the reference runs these refiners in on GPU)
         self.conv_precision = "fp32"
         # training mode: "torch" keeps the nn modules (the default); "hip" runs block1 + hidden_blocks through
-        # ops.conv_block_train where _hip_train_stack_supported() holds, the modules otherwise
+        # ops.conv_block_train where _hip_train_stack_supported() holds, "hip_amp" through ops.conv_block_train_amp (fp16 maps, the
+        # class of an amp=True refiner under autocast) where _hip_amp_train_stack_supported() holds; the modules otherwise
         self.train_conv_impl = "torch"
         self.fold_out_conv = True  # multiply out_conv into the last block's 1x1 conv (see folded_stack)
 
@@ -173,11 +176,9 @@ class ConvRefiner(nn.Module):
                 return False
         return True
 
-    def _hip_train_stack_supported(self, d):
-        """Training mode on csrc/conv_stack_train.hip: opt-in (`train_conv_impl = "hip"`), the fp32 class, depthwise blocks whose
-        norm is an affine BatchNorm2d that tracks running statistics with a float momentum; anything else keeps the modules."""
-        if not self.training or self.train_conv_impl != "hip" or self.conv_precision != "fp32":
-            return False
+    def _train_blocks_supported(self, d):
+        """What both HIP training stacks need of the input and the modules: an fp32 CUDA map on a square grid, depthwise blocks whose
+        norm is an affine BatchNorm2d that tracks running statistics with a float momentum, fp32 parameters."""
         if d.dim() != 4 or d.shape[-1] != d.shape[-2] or d.dtype != torch.float32 or not d.is_cuda:
             return False
         for blk in [self.block1] + list(self.hidden_blocks):
@@ -191,12 +192,29 @@ class ConvRefiner(nn.Module):
                 return False
         return True
 
-    def _train_stack_hip(self, d):
-        """hidden_blocks(block1(d)) in training mode, network.py:560-562, one ops.conv_block_train per block"""
+    def _hip_train_stack_supported(self, d):
+        """Training mode on csrc/conv_stack_train.hip: opt-in (`train_conv_impl = "hip"`), the fp32 class, depthwise blocks whose
+        norm is an affine BatchNorm2d that tracks running statistics with a float momentum; anything else keeps the modules."""
+        if not self.training or self.train_conv_impl != "hip" or self.conv_precision != "fp32":
+            return False
+        return self._train_blocks_supported(d)
+
+    def _hip_amp_train_stack_supported(self, d):
+        """Training mode on csrc/conv_stack_train_half.hip: opt-in (`train_conv_impl = "hip_amp"`) on a refiner that the modules would
+        run under fp16 autocast (amp set, amp_dtype float16), same structure as "hip"; conv_precision, an eval-mode setting, is not
+        consulted.  Anything else keeps the modules under autocast."""
+        if not self.training or self.train_conv_impl != "hip_amp" or not self.amp or self.amp_dtype is not torch.float16:
+            return False
+        return self._train_blocks_supported(d)
+
+    def _train_stack_hip(self, d, amp=False):
+        """hidden_blocks(block1(d)) in training mode, network.py:560-562, one ops.conv_block_train per block (amp: one
+        ops.conv_block_train_amp; the first reads the fp32 d, the others the fp16 map before them)"""
+        block = ops.conv_block_train_amp if amp else ops.conv_block_train
         h = d
         for conv, norm, _, pw in [self.block1] + list(self.hidden_blocks):
-            h = ops.conv_block_train(h, conv.weight, conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var,
-                                     norm.num_batches_tracked, norm.momentum, norm.eps, pw.weight, pw.bias)
+            h = block(h, conv.weight, conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var,
+                      norm.num_batches_tracked, norm.momentum, norm.eps, pw.weight, pw.bias)
         return h
 
     def folded_stack(self):
@@ -278,6 +296,9 @@ class ConvRefiner(nn.Module):
         if self._hip_train_stack_supported(d):
             # out_conv is not folded here: its parameters take their own gradients, and a 3-channel 1x1 needs no kernel
             return self.out_conv(self._train_stack_hip(d).float())
+        if self._hip_amp_train_stack_supported(d):
+            # fp16 maps between the nine blocks; the last y is fp16 and out_conv runs on fp32, as network.py:563 does
+            return self.out_conv(self._train_stack_hip(d, amp=True).float())
         with torch.autocast("cuda", enabled=bool(self.amp), dtype=self.amp_dtype):
             h = self.hidden_blocks(self.block1(d))
         return self.out_conv(h.float())

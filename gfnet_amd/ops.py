@@ -744,9 +744,9 @@ def pointwise_conv(t, w, bias, out=None):
     return out
 
 
-def _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b):
-    """Shape and dtype checks of conv_block_train; returns (B, C, M, G)."""
-    what = "conv_block_train"
+def _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b, amp=False):
+    """Shape and dtype checks of conv_block_train (amp: of conv_block_train_amp, whose x may be float16); returns (B, C, M, G)."""
+    what = "conv_block_train_amp" if amp else "conv_block_train"
     if x.dim() != 4 or x.shape[2] != x.shape[3]:
         raise ValueError(f"{what}: x must be (B,C,G,G) on a square grid, got {tuple(x.shape)}")
     B, C, G, _ = x.shape
@@ -759,11 +759,12 @@ def _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, runn
         if t is None:
             raise ValueError(f"{what}: {name} is missing")
         if t.dtype != torch.float32:
-            raise ValueError(f"{what}: {name} must be float32 (the fp32 training class), got {t.dtype}")
+            raise ValueError(f"{what}: {name} must be float32 ({'parameters stay fp32 in the autocast class' if amp else 'the fp32 training class'}), "
+                             f"got {t.dtype}")
         if t.numel() != n:
             raise ValueError(f"{what}: {name} has {t.numel()} elements, C={C} and M={M} need {n}")
-    if x.dtype != torch.float32:
-        raise ValueError(f"{what}: x must be float32, got {x.dtype}")
+    if x.dtype != torch.float32 and not (amp and x.dtype == torch.float16):
+        raise ValueError(f"{what}: x must be float32{' (a first block) or float16' if amp else ''}, got {x.dtype}")
     if B * G * G < 2:
         raise ValueError(f"{what}: batch statistics need more than one value per channel")
     return B, C, M, G
@@ -859,6 +860,111 @@ def conv_block_train(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_va
     require_gpu(x, dw_w, pw_w, running_mean, running_var)
     _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b)
     y = _ConvBlockTrainFn.apply(x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b, running_mean, running_var, float(momentum), float(eps))
+    # the kernels wrote the buffers through raw pointers: tell autograd's version counters
+    torch.autograd.graph.increment_version(running_mean)
+    torch.autograd.graph.increment_version(running_var)
+    if num_batches_tracked is not None:
+        num_batches_tracked.add_(1)
+    return y
+
+
+def _map_dtype(t):
+    return _lib.GFN_F16 if t.dtype == torch.float16 else _lib.GFN_F32
+
+
+def conv_block_train_amp_fwd(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, momentum, eps, pw_w, pw_b):
+    """The forward launches of conv_block_train_amp: returns (y, u, mean, invstd) -- y (B,M,G,G) and u (B,C,G,G) float16, mean and
+    invstd float32 -- and updates running_mean / running_var in place (csrc/conv_stack_train_half.hip).  x contiguous float32 or
+    float16, parameters contiguous float32."""
+    dev = require_gpu(x, dw_w, pw_w, running_mean, running_var)
+    B, C, M, G = _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b, amp=True)
+    if not (running_mean.is_contiguous() and running_var.is_contiguous()):
+        raise ValueError("conv_block_train_amp: the running statistics are updated in place and must be contiguous")
+    x, dw_w, pw_w = x.contiguous(), dw_w.contiguous(), pw_w.contiguous()
+    u = torch.empty((B, C, G, G), device=dev, dtype=torch.float16)
+    y = torch.empty((B, M, G, G), device=dev, dtype=torch.float16)
+    mean, invstd = torch.empty(C, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
+    nws = int(_L().gfn_conv_block_train_half_ws_bytes(B, C, M, G, 0))
+    ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
+    _timed("conv_block_train_amp_fwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_half_fwd(
+        ptr(x), _map_dtype(x), ptr(dw_w), ptr(dw_b.contiguous()) if dw_b is not None else None, ptr(bn_weight.contiguous()),
+        ptr(bn_bias.contiguous()), ptr(running_mean), ptr(running_var), ptr(pw_w), ptr(pw_b.contiguous()), ptr(u), ptr(mean), ptr(invstd),
+        ptr(y), B, C, M, G, float(momentum), float(eps), ptr(ws), nws, stream_ptr(dev)))
+    return y, u, mean, invstd
+
+
+def conv_block_train_amp_bwd(gy, x, u, mean, invstd, dw_w, bn_weight, bn_bias, pw_w, need=(True,) * 7, has_dw_bias=True):
+    """Gradients of conv_block_train_amp's y with respect to (x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b) given gy = dL/dy (rounded
+    to float16 if it is not) and what the forward saved; None where `need` says so.  gx has x's dtype -- float32, unrounded, for a
+    first block -- and the parameter gradients are float32; every result is reproducible bit for bit."""
+    dev = require_gpu(gy, x, u)
+    gy = gy.to(torch.float16).contiguous()
+    B, C, G, _ = x.shape
+    M = pw_w.shape[0]
+    if tuple(gy.shape) != (B, M, G, G):
+        raise ValueError(f"conv_block_train_amp_bwd: grad_y must be {(B, M, G, G)}, got {tuple(gy.shape)}")
+    if u.dtype != torch.float16 or tuple(u.shape) != (B, C, G, G) or not u.is_contiguous() or not x.is_contiguous():
+        raise ValueError("conv_block_train_amp_bwd: x and u are the contiguous maps of the forward, u float16")
+    n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb = need
+    n_dwb = n_dwb and has_dw_bias
+    mask = (_lib.CBT_NEED_X if n_x else 0) | (_lib.CBT_NEED_DW if (n_dww or n_dwb) else 0) | \
+        (_lib.CBT_NEED_BN if (n_g or n_b) else 0) | (_lib.CBT_NEED_PW if (n_pww or n_pwb) else 0)
+
+    def out(bit, *shape, dtype=torch.float32):
+        return torch.empty(shape, device=dev, dtype=dtype) if mask & bit else None
+
+    gx = out(_lib.CBT_NEED_X, B, C, G, G, dtype=x.dtype)
+    d_dww, d_dwb = out(_lib.CBT_NEED_DW, C, 25), (out(_lib.CBT_NEED_DW, C) if has_dw_bias else None)
+    d_g, d_b = out(_lib.CBT_NEED_BN, C), out(_lib.CBT_NEED_BN, C)
+    d_pww, d_pwb = out(_lib.CBT_NEED_PW, M, C), out(_lib.CBT_NEED_PW, M)
+    if mask:
+        nws = int(_L().gfn_conv_block_train_half_ws_bytes(B, C, M, G, 1))
+        ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
+        _timed("conv_block_train_amp_bwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_half_bwd(
+            ptr(gy), ptr(x), _map_dtype(x), ptr(u), ptr(mean), ptr(invstd), ptr(dw_w), ptr(bn_weight), ptr(bn_bias), ptr(pw_w), ptr(gx),
+            ptr(d_dww), ptr(d_dwb), ptr(d_g), ptr(d_b), ptr(d_pww), ptr(d_pwb), B, C, M, G, mask, ptr(ws), nws, stream_ptr(dev)))
+    grads = (gx, d_dww, d_dwb, d_g, d_b, d_pww, d_pwb)
+    return tuple(g if want else None for g, want in zip(grads, (n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb)))
+
+
+class _ConvBlockTrainAmpFn(torch.autograd.Function):
+    """conv_block_train_amp: saves x in its own dtype, u as float16, mean, invstd and the fp32 parameters the backward reads."""
+
+    @staticmethod
+    def forward(ctx, x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b, running_mean, running_var, momentum, eps):
+        C, M = x.shape[1], pw_w.shape[0]
+        xk, dww, pww = x.contiguous(), dw_w.reshape(C, 25).contiguous(), pw_w.reshape(M, C).contiguous()
+        bnw, bnb = bn_weight.contiguous(), bn_bias.contiguous()
+        y, u, mean, invstd = conv_block_train_amp_fwd(xk, dww, dw_b, bnw, bnb, running_mean, running_var, momentum, eps, pww, pw_b)
+        ctx.save_for_backward(xk, u, mean, invstd, dww, bnw, bnb, pww)
+        ctx.meta = (dw_w.shape, pw_w.shape, dw_b is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xk, u, mean, invstd, dww, bnw, bnb, pww = ctx.saved_tensors
+        dw_shape, pw_shape, has_bias = ctx.meta
+        g = list(conv_block_train_amp_bwd(gy, xk, u, mean, invstd, dww, bnw, bnb, pww, need=ctx.needs_input_grad[:7], has_dw_bias=has_bias))
+        if g[1] is not None:
+            g[1] = g[1].reshape(dw_shape)
+        if g[5] is not None:
+            g[5] = g[5].reshape(pw_shape)
+        return tuple(g) + (None,) * 4
+
+
+def conv_block_train_amp(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, pw_w, pw_b):
+    """conv_block_train in the class the reference trains its refiners in -- fp16 autocast around block1 + hidden_blocks
+    (model/network.py:90-152, 560-562; trainer/train.py:29-43) -- on csrc/conv_stack_train_half.hip.  x (B,C,G,G) float32 (a stack's
+    first block: rounded to fp16 on load) or float16 (the previous block's y); returns y (B,M,G,G) float16.  Parameters and their
+    gradients are float32 (autocast would round the gradients to fp16; this class does not); the gradient of x has x's dtype.  Maps
+    in HBM (u, y, the backward's intermediate and gx) are fp16, every sum fp32, the three 1x1 products fp16 operands on the matrix
+    core with fp32 accumulators; rounding overflows to inf, so a GradScaler (ops.FusedAdamWStep) sees a loss scale that is too large.
+    Running buffers, num_batches_tracked, momentum and eps as conv_block_train; identical calls give identical bits."""
+    if momentum is None:
+        raise ValueError("conv_block_train_amp: momentum must be a float (cumulative averaging, momentum=None, is not supported)")
+    require_gpu(x, dw_w, pw_w, running_mean, running_var)
+    _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b, amp=True)
+    y = _ConvBlockTrainAmpFn.apply(x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b, running_mean, running_var, float(momentum), float(eps))
     # the kernels wrote the buffers through raw pointers: tell autograd's version counters
     torch.autograd.graph.increment_version(running_mean)
     torch.autograd.graph.increment_version(running_var)

@@ -472,6 +472,29 @@ int gfn_conv_block_train_bwd(const float *gy, const float *x, const float *u, co
                              float *d_dw_b, float *d_bn_w, float *d_bn_b, float *d_pw_w, float *d_pw_b, int B, int C, int M, int G,
                              int need, void *ws, int64_t ws_bytes, gfn_stream_t stream);
 
+/* The same block in the reference's autocast training class (every ConvRefiner has amp=True, model/network.py:90-152, and
+ * trainer/train.py:29-43 scales the loss): fp16 maps in HBM; csrc/conv_stack_train_half.hip.  The entry points above are fp32
+ * throughout and unchanged.
+ *
+ * Maps -- x, u, y, gy, gx -- are plain contiguous (B,C,G,G) fp16 (torch.float16; NOT the half2 channel-pair layout of
+ *   gfn_conv_block_half_fwd), any C and any G.  x_dtype = GFN_F32 makes x the fp32 concat of a stack's first block: it is rounded
+ *   to fp16 on load, and gx is then fp32, unrounded.  Parameters, their gradients, mean and invstd are fp32; depthwise taps and 1x1
+ *   weights are rounded to fp16 where they are operands.  Every sum is fp32 (statistics merged in double); u is rounded once and
+ *   statistics, normalisation and backward read that rounded u; t = relu(bn(u)) is rounded as the 1x1 operand; the backward's gz
+ *   map is rounded before BatchNorm's backward reads it.  The three 1x1 products run on v_mfma_f32_32x32x16_f16.  Rounding is to
+ *   nearest even and overflows to inf (never clamps to 65504), so a loss scale that is too large shows in the gradients.
+ * Arguments, `need`, limits, the running-buffer update and bit-for-bit reproducibility are those of the fp32 entry points;
+ *   ws: gfn_conv_block_train_half_ws_bytes bytes, 16-byte aligned. */
+int64_t gfn_conv_block_train_half_ws_bytes(int B, int C, int M, int G, int backward);
+int gfn_conv_block_train_half_fwd(const void *x, int x_dtype, const float *dw_w, const float *dw_b, const float *bn_w,
+                                  const float *bn_b, float *running_mean, float *running_var, const float *pw_w, const float *pw_b,
+                                  void *u, float *mean, float *invstd, void *y, int B, int C, int M, int G, double momentum,
+                                  double eps, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+int gfn_conv_block_train_half_bwd(const void *gy, const void *x, int x_dtype, const void *u, const float *mean, const float *invstd,
+                                  const float *dw_w, const float *bn_w, const float *bn_b, const float *pw_w, void *gx,
+                                  float *d_dw_w, float *d_dw_b, float *d_bn_w, float *d_bn_b, float *d_pw_w, float *d_pw_b, int B,
+                                  int C, int M, int G, int need, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+
 /* The training objective on a homography ground truth (losses/robust_loss.py: get_gt_warp_homography :9-42,
  * RobustLosses.regression_loss :65-90 and the per-scale body of RobustLosses.forward :92-128); csrc/robust_loss.hip.  One call
  * is one scale with all of its iterations; fp32 contiguous maps on an h x w grid, batch B.

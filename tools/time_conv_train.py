@@ -1,11 +1,12 @@
 """Forward + backward time of one refiner's conv stack in train() (GPU): python tools/time_conv_train.py [--batch 8] [--reps 15] [--scales 16,8]
 
-Two paths on the same ConvRefiner weights, the same concat tensor d and the same output weighting, at the five GFNet widths on the
+Four paths on the same ConvRefiner weights, the same concat tensor d and the same output weighting, at the five GFNet widths on the
 grids bench.py's default 448 workload gives them (C, G = 417/32, 361/32, 177/64, 73/128, 24/256): `train_conv_impl = "hip"`
-(csrc/conv_stack_train.hip) and "torch" (the nn modules on MIOpen, fp32, amp off).  The runs alternate in one process; every
-timed step is bracketed by device synchronisation; the figure is the median of --reps steps after --warmup untimed ones, the
-spread their min .. max.  One JSON line per width, then a markdown table.  --scales picks widths, so that a job can give every
-width a process and a time limit of its own."""
+(csrc/conv_stack_train.hip, fp32) and "torch" (the nn modules on MIOpen, fp32, amp off), and in the reference's autocast class
+"hip_amp" (csrc/conv_stack_train_half.hip, fp16 maps) and "torch_amp" (the nn modules under torch.autocast, amp on).  The runs
+alternate in one process; every timed step is bracketed by device synchronisation; the figure is the median of --reps steps after
+--warmup untimed ones, the spread their min .. max.  One JSON line per width, then a markdown table.  --scales picks widths, so
+that a job can give every width a process and a time limit of its own; --paths picks paths."""
 import argparse
 import copy
 import json
@@ -39,48 +40,55 @@ def timed(ref, d, w):
     return (time.perf_counter() - t0) * 1e3
 
 
+# path -> (train_conv_impl, amp)
+PATHS = {"hip": ("hip", False), "modules": ("torch", False), "hip_amp": ("hip_amp", True), "torch_amp": ("torch", True)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scales", default=",".join(w[0] for w in WIDTHS), help="comma-separated subset of 16,8,4,2,1")
+    ap.add_argument("--paths", default=",".join(PATHS), help="comma-separated subset of " + ",".join(PATHS))
     args = ap.parse_args()
-    chosen = args.scales.split(",")
-    unknown = [s for s in chosen if s not in [w[0] for w in WIDTHS]]
+    chosen, paths = args.scales.split(","), args.paths.split(",")
+    unknown = [s for s in chosen if s not in [w[0] for w in WIDTHS]] + [p for p in paths if p not in PATHS]
     if unknown:
-        ap.error(f"unknown scales {unknown}")
+        ap.error(f"unknown scales or paths {unknown}")
     rows = []
     for scale, feat, disp, r, G in [w for w in WIDTHS if w[0] in chosen]:
         dim = 2 * feat + disp + ((2 * r + 1) ** 2 if r > 0 else 0)
         torch.manual_seed(0)
-        hip = ConvRefiner(dim, dim, 3, kernel_size=5, dw=True, hidden_blocks=8, displacement_emb="linear", displacement_emb_dim=disp,
-                          local_corr_num=r, corr_in_other=r > 0, amp=False, bn_momentum=0.01).cuda().train()
-        mio = copy.deepcopy(hip)
-        hip.train_conv_impl = "hip"
+        base = ConvRefiner(dim, dim, 3, kernel_size=5, dw=True, hidden_blocks=8, displacement_emb="linear", displacement_emb_dim=disp,
+                           local_corr_num=r, corr_in_other=r > 0, amp=False, bn_momentum=0.01).cuda().train()
         g = torch.Generator().manual_seed(1)
         d = torch.randn(args.batch, dim, G, G, generator=g).cuda().requires_grad_()
         w = torch.randn(args.batch, 3, G, G, generator=g).cuda()
-        assert hip._hip_train_stack_supported(d) and not mio._hip_train_stack_supported(d)
+        refs = {}
+        for name in paths:
+            refs[name] = copy.deepcopy(base)
+            refs[name].train_conv_impl, refs[name].amp = PATHS[name]
+            assert refs[name]._hip_train_stack_supported(d) == (name == "hip") and refs[name]._hip_amp_train_stack_supported(d) == (name == "hip_amp")
         for _ in range(args.warmup):
-            step(hip, d, w)
-            step(mio, d, w)
-        t_hip, t_mio = [], []
+            for ref in refs.values():
+                step(ref, d, w)
+        times = {name: [] for name in paths}
         for _ in range(args.reps):
-            t_hip.append(timed(hip, d, w))
-            t_mio.append(timed(mio, d, w))
-        row = {"scale": scale, "C": dim, "G": G, "batch": args.batch,
-               "hip_ms": statistics.median(t_hip), "hip_min": min(t_hip), "hip_max": max(t_hip),
-               "modules_ms": statistics.median(t_mio), "modules_min": min(t_mio), "modules_max": max(t_mio)}
+            for name, ref in refs.items():
+                times[name].append(timed(ref, d, w))
+        row = {"scale": scale, "C": dim, "G": G, "batch": args.batch}
+        for name, t in times.items():
+            row.update({name + "_ms": statistics.median(t), name + "_min": min(t), name + "_max": max(t)})
         rows.append(row)
         print(json.dumps(row), flush=True)
-        del hip, mio, d, w
+        del base, refs, d, w
         torch.cuda.empty_cache()
-    print("| C | G | batch | hip ms (min .. max) | nn modules ms (min .. max) | modules / hip |")
-    print("|---|---|---|---|---|---|")
+    print("| C | G | batch | " + " | ".join(f"{name} ms (min .. max)" for name in paths) + " |")
+    print("|---|---|---|" + "---|" * len(paths))
     for q in rows:
-        print(f"| {q['C']} | {q['G']} | {q['batch']} | {q['hip_ms']:.2f} ({q['hip_min']:.2f} .. {q['hip_max']:.2f}) | "
-              f"{q['modules_ms']:.2f} ({q['modules_min']:.2f} .. {q['modules_max']:.2f}) | {q['modules_ms'] / q['hip_ms']:.2f} |")
+        print(f"| {q['C']} | {q['G']} | {q['batch']} | " +
+              " | ".join(f"{q[n + '_ms']:.2f} ({q[n + '_min']:.2f} .. {q[n + '_max']:.2f})" for n in paths) + " |")
 
 
 if __name__ == "__main__":
