@@ -330,7 +330,9 @@ class GFNet(nn.Module):
             # of the user's checkout are assembled here, as the reference's constructor does (network.py:44-65)
             from ..reference_backbone import reference_backbone
 
-            backbone = reference_backbone(conf, amp=amp, amp_dtype=amp_dtype)
+            # GFNET_COMPAT_DECODER=hip: the native cross-view decoder (model/crossview_decoder.py) in place of the checkout's, whose
+            # shipped attention type needs flash_attn; unset: the checkout's class, as before
+            backbone = reference_backbone(conf, amp=amp, amp_dtype=amp_dtype, decoder=os.environ.get("GFNET_COMPAT_DECODER") or "checkout")
         self.backbone = backbone
         if conv_refiner is None:
             chs = conf["encoder_cfg"]["feat_chs"]  # coarse to fine: [64, 32, 16, 8]

@@ -120,6 +120,87 @@ class _CorrSoftargmaxFn(torch.autograd.Function):
         return (g0.to(ctx.dtypes[0]) if g0 is not None else None, g1.to(ctx.dtypes[1]) if g1 is not None else None, None)
 
 
+def reference_cross_attention(q, k, v, scale):
+    """The definition cross_attention computes, in plain torch on any device and in any floating dtype (float64 included), for
+    tests and for the decoder's attn_impl="torch": q (B,Nq,H,D), k, v (B,Nk,H,D) -> out (B,Nq,H,D) with, per batch and head,
+    out = softmax_j(scale * q . k_j) v_j.  Differentiable through torch autograd.
+
+    This restates the published definition of flash-attn's flash_attn_func(q, k, v, dropout_p=0, softmax_scale=scale, causal=False),
+    which the reference calls at model/transformer/layers/attention.py:252; it is NOT pinned against flash_attn itself, which is
+    absent here, as cv2 and kornia are for the stages that restate them."""
+    s = torch.einsum("bihd,bjhd->bhij", q, k) * scale
+    return torch.einsum("bhij,bjhd->bihd", torch.softmax(s, dim=-1), v)
+
+
+def _cross_attn_args(what, *tensors):
+    """The tensors as the kernels read them (contiguous, 16-byte aligned, one dtype: fp16 or fp32) and the dtype code."""
+    dev = require_gpu(*tensors)
+    dtypes = {t.dtype for t in tensors}
+    if len(dtypes) != 1 or tensors[0].dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"{what}: q, k and v must share one dtype, float16 or float32, got {sorted(str(d) for d in dtypes)}")
+    out = []
+    for t in tensors:
+        t = t.contiguous()
+        out.append(t.clone() if t.data_ptr() % 16 else t)
+    return dev, out, (_lib.GFN_F16 if tensors[0].dtype == torch.float16 else _lib.GFN_F32)
+
+
+def cross_attention_fwd(q, k, v, scale):
+    """The forward launch (gfn_cross_attn_fwd): returns (out, lse, q, k, v) with q, k, v as the kernel read them; lse (B,H,Nq) fp32."""
+    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2:] != k.shape[2:]:
+        raise ValueError(f"cross_attention: q (B,Nq,H,D) and k, v (B,Nk,H,D) expected, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    dev, (q, k, v), dt = _cross_attn_args("cross_attention", q, k, v)
+    B, Nq, H, D = q.shape
+    Nk = k.shape[1]
+    out = torch.empty_like(q)
+    lse = torch.empty((B, H, Nq), device=dev, dtype=torch.float32)
+    _timed("cross_attn_fwd", lambda: _L().gfn_cross_attn_fwd(ptr(q), ptr(k), ptr(v), dt, B, Nq, Nk, H, D, float(scale), ptr(out), ptr(lse),
+                                                             stream_ptr(dev)))
+    return out, lse, q, k, v
+
+
+def cross_attention_bwd(q, k, v, out, lse, dout, scale):
+    """(dq, dk, dv) of cross_attention given dout = dL/dout and the forward's out and lse (gfn_cross_attn_bwd): no atomics, so two
+    calls give the same bits; in fp16 the results are rounded once and overflow to inf."""
+    dev, (q, k, v, out, dout), dt = _cross_attn_args("cross_attention_bwd", q, k, v, out, dout)
+    B, Nq, H, D = q.shape
+    Nk = k.shape[1]
+    if dout.shape != q.shape or out.shape != q.shape or tuple(lse.shape) != (B, H, Nq):
+        raise ValueError("cross_attention_bwd: out and dout must have q's shape and lse must be (B,H,Nq) of the forward")
+    lse = f32c(lse)
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    _timed("cross_attn_bwd", lambda: _L().gfn_cross_attn_bwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), dt, B, Nq, Nk, H, D,
+                                                             float(scale), ptr(dq), ptr(dk), ptr(dv), stream_ptr(dev)))
+    return dq, dk, dv
+
+
+class _CrossAttentionFn(torch.autograd.Function):
+    """cross_attention with a backward; saves q, k, v, out and lse, never the Nq x Nk matrix."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        out, lse, q, k, v = cross_attention_fwd(q, k, v, scale)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = cross_attention_bwd(q, k, v, out, lse, dout.to(q.dtype), ctx.scale)
+        return dq, dk, dv, None
+
+
+def cross_attention(q, k, v, scale):
+    """The attention core of the reference's CrossFlashAttention2 (model/transformer/layers/attention.py:252, flash_attn_func with
+    dropout 0 and causal=False) at head dim 8: q (B,Nq,H,8), k, v (B,Nk,H,8), fp16 or fp32 -> out of q's shape and dtype =
+    softmax(scale * q k^T) v per batch and head.  Differentiable (gfn_cross_attn_bwd).  CPU tensors raise: reference_cross_attention
+    is the definition for every device, this is the product path."""
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        return _CrossAttentionFn.apply(q, k, v, float(scale))
+    return cross_attention_fwd(q, k, v, scale)[0]
+
+
 def corr_volume(feat0, feat1, with_flow=False):
     """GFNet.corr_volume (model/network.py:415-428): (B,H1,W1,H0,W0) = f0^T f1 / sqrt(C)."""
     dev = require_gpu(feat0, feat1)

@@ -23,12 +23,17 @@ import torch.nn.functional as F
 DINOV2_URL = "https://dl.fbaipublicfiles.com/dinov2/dinov2_vitl14/dinov2_vitl14_pretrain.pth"  # network.py:46
 
 
-def checkout_available():
-    """True when the reference's backbone modules can be found on sys.path (nothing is imported)."""
+DECODERS = ("checkout", "hip")
+
+
+def checkout_available(decoder="checkout"):
+    """True when the reference's backbone modules can be found on sys.path (nothing is imported).  decoder="hip" needs only
+    `model.FPN`: the cross-view decoder is then this package's."""
     import importlib.util
 
+    needed = ("model.FPN", "model.crossview_decoder_light") if decoder == "checkout" else ("model.FPN",)
     try:
-        return all(importlib.util.find_spec(m) is not None for m in ("model.FPN", "model.crossview_decoder_light"))
+        return all(importlib.util.find_spec(m) is not None for m in needed)
     except (ImportError, ValueError):
         return False
 
@@ -53,11 +58,16 @@ class ReferenceBackbone(nn.Module):
     """`backbone(images, upsample) -> (pyramid_A, pyramid_B)` from the checkout's DINOv2 + CrossVITDecoder_noself + FPN.
 
     vit: an already built ViT (anything with `forward_features(x)["x_norm_patchtokens"]`); None builds the checkout's `vit_large`
-    and loads `dino_weights` (a path, a state dict, $GFNET_DINOV2_WEIGHTS, or the reference's download URL in that order)."""
+    and loads `dino_weights` (a path, a state dict, $GFNET_DINOV2_WEIGHTS, or the reference's download URL in that order).
 
-    def __init__(self, conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None):
+    decoder: "checkout" (default) builds the checkout's CrossVITDecoder_noself, which with the shipped attention_type "FLASH2" raises
+    on its first forward where flash_attn is missing; "hip" builds gfnet_amd.model.crossview_decoder.CrossViewDecoder, the same
+    module under the same parameter names with its attention core in HIP, and does not import the checkout's decoder."""
+
+    def __init__(self, conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout"):
         super().__init__()
-        from model.crossview_decoder_light import CrossVITDecoder_noself
+        if decoder not in DECODERS:
+            raise ValueError(f"decoder must be one of {DECODERS}, got {decoder!r}")
         from model.FPN import FPNDecoder_concat, FPNEncoder, Swish
 
         self.amp, self.amp_dtype = amp, amp_dtype
@@ -67,7 +77,14 @@ class ReferenceBackbone(nn.Module):
             p.requires_grad = False
         self.dino = [vit]
         chs = list(conf["encoder_cfg"]["feat_chs"])  # coarse to fine
-        self.dino_decoder = CrossVITDecoder_noself(conf=conf, upsample=False)
+        if decoder == "hip":
+            from .model.crossview_decoder import CrossViewDecoder
+
+            self.dino_decoder = CrossViewDecoder(conf)
+        else:
+            from model.crossview_decoder_light import CrossVITDecoder_noself
+
+            self.dino_decoder = CrossVITDecoder_noself(conf=conf, upsample=False)
         self.encoder = FPNEncoder(feat_chs=chs[::-1])
         self.decoder = FPNDecoder_concat(feat_chs=chs[::-1])
         self.merge_layer = nn.Sequential(nn.Conv2d(2 * chs[0], chs[0], kernel_size=3, padding=1), nn.BatchNorm2d(chs[0]), Swish())
@@ -103,9 +120,15 @@ class ReferenceBackbone(nn.Module):
         return pyr_a, pyr_b
 
 
-def reference_backbone(conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None):
-    """Build the backbone from the checkout on sys.path; raises ImportError with the reason when there is none."""
-    if not checkout_available():
+def reference_backbone(conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout"):
+    """Build the backbone from the checkout on sys.path; raises ImportError with the reason when there is none.  decoder: see
+    ReferenceBackbone."""
+    if decoder not in DECODERS:
+        raise ValueError(f"decoder must be one of {DECODERS}, got {decoder!r}")
+    if not checkout_available(decoder):
+        if decoder == "hip":
+            raise ImportError("no KN-Zhang/GFNet checkout on sys.path: `model.FPN` cannot be found "
+                              "(put the checkout behind compat/ on PYTHONPATH, or run the script through compat/run.py)")
         raise ImportError("no KN-Zhang/GFNet checkout on sys.path: `model.FPN` / `model.crossview_decoder_light` cannot be found "
                           "(put the checkout behind compat/ on PYTHONPATH, or run the script through compat/run.py)")
-    return ReferenceBackbone(conf, amp=amp, amp_dtype=amp_dtype, vit=vit, dino_weights=dino_weights)
+    return ReferenceBackbone(conf, amp=amp, amp_dtype=amp_dtype, vit=vit, dino_weights=dino_weights, decoder=decoder)

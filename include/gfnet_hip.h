@@ -674,6 +674,31 @@ int gfn_photo_stats(const void *const *src, const int *dims, const int *params, 
 int gfn_photo_jitter_blur(const void *const *src, const int *dims, const int *params, const int64_t *sums, void *const *dst, int out_u8,
                           int N, int max_h, int max_w, gfn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Cross-attention core of the cross-view decoder -- model/transformer/layers/attention.py:227-258 (CrossFlashAttention2.forward:
+ * the flash_attn_func call at :252, which all shipped configs select with attention_type "FLASH2" and which raises at :230-231
+ * where flash_attn is absent); csrc/cross_attn.hip.  Per batch b and head h, with s[i][j] = scale * sum_d q[b,i,h,d] * k[b,j,h,d]:
+ *   out[b,i,h,:] = sum_j softmax_j(s[i][j]) * v[b,j,h,:]        lse[b,h,i] = max_j s[i][j] + log sum_j exp(s[i][j] - max)
+ * q, out, dout, dq (B,Nq,H,D) and k, v, dk, dv (B,Nk,H,D), contiguous (what q_proj(x).reshape(B,N,H,D) gives and flash_attn_func
+ * takes: no transposes), stored as dtype = GFN_F32 or GFN_F16, 16-byte aligned; lse (B,H,Nq) fp32.  D must be 8 (dim 64 over 8
+ * heads: the K of v_mfma_f32_32x32x8_f16); any other D returns GFN_ERR_INVALID_ARG.  H, Nq, Nk >= 1 are arbitrary (tails, Nk = 1),
+ * scale any finite value (0 gives the mean of v); B, H <= 65535.  No scratch, no allocation, the N x N matrix is never written.
+ * Arithmetic: the raw scores on the matrix core with fp32 accumulation (fp16 inputs: exact products; fp32 inputs: the fp32-input
+ * instruction, an fmaf chain bit for bit), online softmax and P V in fp32 (P is never rounded), fp16 results rounded to nearest
+ * once, overflow to inf.  A key past Nk in a tail tile weighs exactly zero.
+ * gfn_cross_attn_fwd writes out and lse. */
+int gfn_cross_attn_fwd(const void *q, const void *k, const void *v, int dtype, int B, int Nq, int Nk, int H, int D, float scale,
+                       void *out, float *lse, gfn_stream_t stream);
+/* Its backward (the reference differentiates attention.py:252 through flash-attn's autograd function): lse as the forward left it,
+ * dout = dL/dout -> dq, dk, dv, all OVERWRITTEN.  P is recomputed from lse.  Three launches: delta = sum_j P dP / sum_j P by query
+ * tile, dk and dv by key tile, dq by query tile.  delta is formed as that sum and not as sum_d dout * out: the saved out carries its
+ * own rounding, which for a row whose weight sits on one key of large norm would exceed the row's whole gradient; `out` is therefore
+ * checked like the other pointers but not read.  Between the launches delta lives in the first four bytes of each row of dq (the
+ * caller's buffer, overwritten by the last launch): no scratch.  No atomics, so identical calls give identical bits.  Sums are
+ * fp32, fp16 results are rounded once and overflow to inf (never clamped), so a loss scale that is too large shows. */
+int gfn_cross_attn_bwd(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *dout, int dtype,
+                       int B, int Nq, int Nk, int H, int D, float scale, void *dq, void *dk, void *dv, gfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
