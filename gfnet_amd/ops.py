@@ -4,6 +4,7 @@ Each function cites the reference code it stands in for (paths relative to KN-Zh
 torch supplies device memory and the current HIP stream; every result comes from csrc/*.hip.
 There is no CPU implementation here: CPU tensors raise.
 """
+import collections
 import functools
 import math
 
@@ -825,9 +826,19 @@ def pointwise_conv(t, w, bias, out=None):
     return out
 
 
-def _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b, amp=False):
-    """Shape and dtype checks of conv_block_train (amp: of conv_block_train_amp, whose x may be float16); returns (B, C, M, G)."""
-    what = "conv_block_train_amp" if amp else "conv_block_train"
+# The two classes of the training conv block: what differs between conv_block_train (fp32 maps, csrc/conv_stack_train.hip) and
+# conv_block_train_amp (fp16 maps, csrc/conv_stack_train_half.hip).  label: in messages and _timed names; ws_bytes / fwd / bwd: the
+# entry points; map_dtype: u, y, gy; x_dtype: x may also be float16 and the entry points are told its dtype
+_TrainClass = collections.namedtuple("_TrainClass", "label ws_bytes fwd bwd map_dtype x_dtype")
+_FP32 = _TrainClass("conv_block_train", "gfn_conv_block_train_ws_bytes", "gfn_conv_block_train_fwd", "gfn_conv_block_train_bwd",
+                    torch.float32, False)
+_AMP = _TrainClass("conv_block_train_amp", "gfn_conv_block_train_half_ws_bytes", "gfn_conv_block_train_half_fwd",
+                   "gfn_conv_block_train_half_bwd", torch.float16, True)
+
+
+def _conv_block_train_args(cls, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b):
+    """Shape and dtype checks of a training conv block of class cls; returns (B, C, M, G)."""
+    what, amp = cls.label, cls.x_dtype
     if x.dim() != 4 or x.shape[2] != x.shape[3]:
         raise ValueError(f"{what}: x must be (B,C,G,G) on a square grid, got {tuple(x.shape)}")
     B, C, G, _ = x.shape
@@ -851,81 +862,111 @@ def _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, runn
     return B, C, M, G
 
 
+def _x_dtype_arg(cls, x):
+    """The x_dtype argument of cls's entry points, where they take one."""
+    return (_lib.GFN_F16 if x.dtype == torch.float16 else _lib.GFN_F32,) if cls.x_dtype else ()
+
+
+def _conv_block_train_fwd(cls, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, momentum, eps, pw_w, pw_b):
+    dev = require_gpu(x, dw_w, pw_w, running_mean, running_var)
+    B, C, M, G = _conv_block_train_args(cls, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b)
+    if not (running_mean.is_contiguous() and running_var.is_contiguous()):
+        raise ValueError(f"{cls.label}: the running statistics are updated in place and must be contiguous")
+    x, dw_w, pw_w = x.contiguous(), dw_w.contiguous(), pw_w.contiguous()
+    u = torch.empty((B, C, G, G), device=dev, dtype=cls.map_dtype)
+    y = torch.empty((B, M, G, G), device=dev, dtype=cls.map_dtype)
+    mean, invstd = torch.empty(C, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
+    nws = int(getattr(_L(), cls.ws_bytes)(B, C, M, G, 0))
+    ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
+    _timed("%s_fwd_c%d_g%d" % (cls.label, C, G), lambda: getattr(_L(), cls.fwd)(
+        ptr(x), *_x_dtype_arg(cls, x), ptr(dw_w), ptr(dw_b.contiguous()) if dw_b is not None else None, ptr(bn_weight.contiguous()),
+        ptr(bn_bias.contiguous()), ptr(running_mean), ptr(running_var), ptr(pw_w), ptr(pw_b.contiguous()), ptr(u), ptr(mean), ptr(invstd),
+        ptr(y), B, C, M, G, float(momentum), float(eps), ptr(ws), nws, stream_ptr(dev)))
+    return y, u, mean, invstd
+
+
+def _conv_block_train_bwd(cls, gy, x, u, mean, invstd, dw_w, bn_weight, bn_bias, pw_w, need, has_dw_bias):
+    dev = require_gpu(gy, x, u)
+    gy = gy.to(cls.map_dtype).contiguous()
+    B, C, G, _ = x.shape
+    M = pw_w.shape[0]
+    if tuple(gy.shape) != (B, M, G, G):
+        raise ValueError(f"{cls.label}_bwd: grad_y must be {(B, M, G, G)}, got {tuple(gy.shape)}")
+    if cls is _AMP and (u.dtype != torch.float16 or tuple(u.shape) != (B, C, G, G) or not u.is_contiguous() or not x.is_contiguous()):
+        raise ValueError("conv_block_train_amp_bwd: x and u are the contiguous maps of the forward, u float16")
+    n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb = need
+    n_dwb = n_dwb and has_dw_bias
+    mask = (_lib.CBT_NEED_X if n_x else 0) | (_lib.CBT_NEED_DW if (n_dww or n_dwb) else 0) | \
+        (_lib.CBT_NEED_BN if (n_g or n_b) else 0) | (_lib.CBT_NEED_PW if (n_pww or n_pwb) else 0)
+
+    def out(bit, *shape, dtype=torch.float32):
+        return torch.empty(shape, device=dev, dtype=dtype) if mask & bit else None
+
+    gx = out(_lib.CBT_NEED_X, B, C, G, G, dtype=x.dtype if cls.x_dtype else torch.float32)
+    d_dww, d_dwb = out(_lib.CBT_NEED_DW, C, 25), (out(_lib.CBT_NEED_DW, C) if has_dw_bias else None)
+    d_g, d_b = out(_lib.CBT_NEED_BN, C), out(_lib.CBT_NEED_BN, C)
+    d_pww, d_pwb = out(_lib.CBT_NEED_PW, M, C), out(_lib.CBT_NEED_PW, M)
+    if mask:
+        nws = int(getattr(_L(), cls.ws_bytes)(B, C, M, G, 1))
+        ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
+        _timed("%s_bwd_c%d_g%d" % (cls.label, C, G), lambda: getattr(_L(), cls.bwd)(
+            ptr(gy), ptr(x), *_x_dtype_arg(cls, x), ptr(u), ptr(mean), ptr(invstd), ptr(dw_w), ptr(bn_weight), ptr(bn_bias), ptr(pw_w), ptr(gx),
+            ptr(d_dww), ptr(d_dwb), ptr(d_g), ptr(d_b), ptr(d_pww), ptr(d_pwb), B, C, M, G, mask, ptr(ws), nws, stream_ptr(dev)))
+    grads = (gx, d_dww, d_dwb, d_g, d_b, d_pww, d_pwb)
+    return tuple(g if want else None for g, want in zip(grads, (n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb)))
+
+
+class _ConvBlockTrainFn(torch.autograd.Function):
+    """A training conv block of class cls (the last argument): saves x in its own dtype, u, mean, invstd and the fp32 parameters the
+    backward reads -- not t = relu(bn(u)), which both directions recompute from u."""
+
+    @staticmethod
+    def forward(ctx, x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b, running_mean, running_var, momentum, eps, cls):
+        C, M = x.shape[1], pw_w.shape[0]
+        xk, dww, pww = x.contiguous(), dw_w.reshape(C, 25).contiguous(), pw_w.reshape(M, C).contiguous()
+        bnw, bnb = bn_weight.contiguous(), bn_bias.contiguous()
+        y, u, mean, invstd = _conv_block_train_fwd(cls, xk, dww, dw_b, bnw, bnb, running_mean, running_var, momentum, eps, pww, pw_b)
+        ctx.save_for_backward(xk, u, mean, invstd, dww, bnw, bnb, pww)
+        ctx.meta = (cls, dw_w.shape, pw_w.shape, dw_b is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xk, u, mean, invstd, dww, bnw, bnb, pww = ctx.saved_tensors
+        cls, dw_shape, pw_shape, has_bias = ctx.meta
+        g = list(_conv_block_train_bwd(cls, gy, xk, u, mean, invstd, dww, bnw, bnb, pww, ctx.needs_input_grad[:7], has_bias))
+        if g[1] is not None:
+            g[1] = g[1].reshape(dw_shape)
+        if g[5] is not None:
+            g[5] = g[5].reshape(pw_shape)
+        return tuple(g) + (None,) * 5
+
+
+def _conv_block_train(cls, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, pw_w, pw_b):
+    if momentum is None:
+        raise ValueError(f"{cls.label}: momentum must be a float (cumulative averaging, momentum=None, is not supported)")
+    require_gpu(x, dw_w, pw_w, running_mean, running_var)
+    _conv_block_train_args(cls, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b)
+    y = _ConvBlockTrainFn.apply(x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b, running_mean, running_var, float(momentum), float(eps), cls)
+    # the kernels wrote the buffers through raw pointers: tell autograd's version counters
+    torch.autograd.graph.increment_version(running_mean)
+    torch.autograd.graph.increment_version(running_var)
+    if num_batches_tracked is not None:
+        num_batches_tracked.add_(1)
+    return y
+
+
 def conv_block_train_fwd(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, momentum, eps, pw_w, pw_b):
     """The forward launches of conv_block_train: returns (y, u, mean, invstd) and updates running_mean / running_var in place
     (csrc/conv_stack_train.hip).  Tensors as the kernels read them: contiguous float32."""
-    dev = require_gpu(x, dw_w, pw_w, running_mean, running_var)
-    B, C, M, G = _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b)
-    if not (running_mean.is_contiguous() and running_var.is_contiguous()):
-        raise ValueError("conv_block_train: the running statistics are updated in place and must be contiguous")
-    x, dw_w, pw_w = x.contiguous(), dw_w.contiguous(), pw_w.contiguous()
-    u, y = torch.empty_like(x), torch.empty((B, M, G, G), device=dev, dtype=torch.float32)
-    mean, invstd = torch.empty(C, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
-    nws = int(_L().gfn_conv_block_train_ws_bytes(B, C, M, G, 0))
-    ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
-    _timed("conv_block_train_fwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_fwd(
-        ptr(x), ptr(dw_w), ptr(dw_b.contiguous()) if dw_b is not None else None, ptr(bn_weight.contiguous()), ptr(bn_bias.contiguous()),
-        ptr(running_mean), ptr(running_var), ptr(pw_w), ptr(pw_b.contiguous()), ptr(u), ptr(mean), ptr(invstd), ptr(y), B, C, M, G,
-        float(momentum), float(eps), ptr(ws), nws, stream_ptr(dev)))
-    return y, u, mean, invstd
+    return _conv_block_train_fwd(_FP32, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, momentum, eps, pw_w, pw_b)
 
 
 def conv_block_train_bwd(gy, x, u, mean, invstd, dw_w, bn_weight, bn_bias, pw_w, need=(True,) * 7, has_dw_bias=True):
     """Gradients of conv_block_train's y with respect to (x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b) given gy = dL/dy and what
     the forward saved; None where `need` says so.  Weight and bias of one layer come from the same launches (the C ABI's need
     mask has one bit per pair); every result is reproducible bit for bit."""
-    dev = require_gpu(gy, x, u)
-    gy = f32c(gy)
-    B, C, G, _ = x.shape
-    M = pw_w.shape[0]
-    if tuple(gy.shape) != (B, M, G, G):
-        raise ValueError(f"conv_block_train_bwd: grad_y must be {(B, M, G, G)}, got {tuple(gy.shape)}")
-    n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb = need
-    n_dwb = n_dwb and has_dw_bias
-    mask = (_lib.CBT_NEED_X if n_x else 0) | (_lib.CBT_NEED_DW if (n_dww or n_dwb) else 0) | \
-        (_lib.CBT_NEED_BN if (n_g or n_b) else 0) | (_lib.CBT_NEED_PW if (n_pww or n_pwb) else 0)
-
-    def out(bit, *shape):
-        return torch.empty(shape, device=dev, dtype=torch.float32) if mask & bit else None
-
-    gx = out(_lib.CBT_NEED_X, B, C, G, G)
-    d_dww, d_dwb = out(_lib.CBT_NEED_DW, C, 25), (out(_lib.CBT_NEED_DW, C) if has_dw_bias else None)
-    d_g, d_b = out(_lib.CBT_NEED_BN, C), out(_lib.CBT_NEED_BN, C)
-    d_pww, d_pwb = out(_lib.CBT_NEED_PW, M, C), out(_lib.CBT_NEED_PW, M)
-    if mask:
-        nws = int(_L().gfn_conv_block_train_ws_bytes(B, C, M, G, 1))
-        ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
-        _timed("conv_block_train_bwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_bwd(
-            ptr(gy), ptr(x), ptr(u), ptr(mean), ptr(invstd), ptr(dw_w), ptr(bn_weight), ptr(bn_bias), ptr(pw_w), ptr(gx), ptr(d_dww),
-            ptr(d_dwb), ptr(d_g), ptr(d_b), ptr(d_pww), ptr(d_pwb), B, C, M, G, mask, ptr(ws), nws, stream_ptr(dev)))
-    grads = (gx, d_dww, d_dwb, d_g, d_b, d_pww, d_pwb)
-    return tuple(g if want else None for g, want in zip(grads, (n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb)))
-
-
-class _ConvBlockTrainFn(torch.autograd.Function):
-    """conv_block_train: saves x, u, mean, invstd and the parameters the backward reads -- not t = relu(bn(u)), which both
-    directions recompute from u."""
-
-    @staticmethod
-    def forward(ctx, x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b, running_mean, running_var, momentum, eps):
-        C, M = x.shape[1], pw_w.shape[0]
-        xk, dww, pww = x.contiguous(), dw_w.reshape(C, 25).contiguous(), pw_w.reshape(M, C).contiguous()
-        bnw, bnb = bn_weight.contiguous(), bn_bias.contiguous()
-        y, u, mean, invstd = conv_block_train_fwd(xk, dww, dw_b, bnw, bnb, running_mean, running_var, momentum, eps, pww, pw_b)
-        ctx.save_for_backward(xk, u, mean, invstd, dww, bnw, bnb, pww)
-        ctx.meta = (dw_w.shape, pw_w.shape, dw_b is not None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        xk, u, mean, invstd, dww, bnw, bnb, pww = ctx.saved_tensors
-        dw_shape, pw_shape, has_bias = ctx.meta
-        g = list(conv_block_train_bwd(gy, xk, u, mean, invstd, dww, bnw, bnb, pww, need=ctx.needs_input_grad[:7], has_dw_bias=has_bias))
-        if g[1] is not None:
-            g[1] = g[1].reshape(dw_shape)
-        if g[5] is not None:
-            g[5] = g[5].reshape(pw_shape)
-        return tuple(g) + (None,) * 4
+    return _conv_block_train_bwd(_FP32, gy, x, u, mean, invstd, dw_w, bn_weight, bn_bias, pw_w, need, has_dw_bias)
 
 
 def conv_block_train(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, pw_w, pw_b):
@@ -936,101 +977,22 @@ def conv_block_train(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_va
     `momentum` (a float) as torch does (unbiased variance) and num_batches_tracked, when given, is incremented -- also without grad
     mode (train() under no_grad).  The buffers' version counters are bumped, so whatever caches on them (ConvRefiner.folded_stack)
     sees the change.  Gradients flow to x and the seven parameters; identical calls give identical bits."""
-    if momentum is None:
-        raise ValueError("conv_block_train: momentum must be a float (cumulative averaging, momentum=None, is not supported)")
-    require_gpu(x, dw_w, pw_w, running_mean, running_var)
-    _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b)
-    y = _ConvBlockTrainFn.apply(x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b, running_mean, running_var, float(momentum), float(eps))
-    # the kernels wrote the buffers through raw pointers: tell autograd's version counters
-    torch.autograd.graph.increment_version(running_mean)
-    torch.autograd.graph.increment_version(running_var)
-    if num_batches_tracked is not None:
-        num_batches_tracked.add_(1)
-    return y
-
-
-def _map_dtype(t):
-    return _lib.GFN_F16 if t.dtype == torch.float16 else _lib.GFN_F32
+    return _conv_block_train(_FP32, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, pw_w,
+                             pw_b)
 
 
 def conv_block_train_amp_fwd(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, momentum, eps, pw_w, pw_b):
     """The forward launches of conv_block_train_amp: returns (y, u, mean, invstd) -- y (B,M,G,G) and u (B,C,G,G) float16, mean and
     invstd float32 -- and updates running_mean / running_var in place (csrc/conv_stack_train_half.hip).  x contiguous float32 or
     float16, parameters contiguous float32."""
-    dev = require_gpu(x, dw_w, pw_w, running_mean, running_var)
-    B, C, M, G = _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b, amp=True)
-    if not (running_mean.is_contiguous() and running_var.is_contiguous()):
-        raise ValueError("conv_block_train_amp: the running statistics are updated in place and must be contiguous")
-    x, dw_w, pw_w = x.contiguous(), dw_w.contiguous(), pw_w.contiguous()
-    u = torch.empty((B, C, G, G), device=dev, dtype=torch.float16)
-    y = torch.empty((B, M, G, G), device=dev, dtype=torch.float16)
-    mean, invstd = torch.empty(C, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
-    nws = int(_L().gfn_conv_block_train_half_ws_bytes(B, C, M, G, 0))
-    ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
-    _timed("conv_block_train_amp_fwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_half_fwd(
-        ptr(x), _map_dtype(x), ptr(dw_w), ptr(dw_b.contiguous()) if dw_b is not None else None, ptr(bn_weight.contiguous()),
-        ptr(bn_bias.contiguous()), ptr(running_mean), ptr(running_var), ptr(pw_w), ptr(pw_b.contiguous()), ptr(u), ptr(mean), ptr(invstd),
-        ptr(y), B, C, M, G, float(momentum), float(eps), ptr(ws), nws, stream_ptr(dev)))
-    return y, u, mean, invstd
+    return _conv_block_train_fwd(_AMP, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, momentum, eps, pw_w, pw_b)
 
 
 def conv_block_train_amp_bwd(gy, x, u, mean, invstd, dw_w, bn_weight, bn_bias, pw_w, need=(True,) * 7, has_dw_bias=True):
     """Gradients of conv_block_train_amp's y with respect to (x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b) given gy = dL/dy (rounded
     to float16 if it is not) and what the forward saved; None where `need` says so.  gx has x's dtype -- float32, unrounded, for a
     first block -- and the parameter gradients are float32; every result is reproducible bit for bit."""
-    dev = require_gpu(gy, x, u)
-    gy = gy.to(torch.float16).contiguous()
-    B, C, G, _ = x.shape
-    M = pw_w.shape[0]
-    if tuple(gy.shape) != (B, M, G, G):
-        raise ValueError(f"conv_block_train_amp_bwd: grad_y must be {(B, M, G, G)}, got {tuple(gy.shape)}")
-    if u.dtype != torch.float16 or tuple(u.shape) != (B, C, G, G) or not u.is_contiguous() or not x.is_contiguous():
-        raise ValueError("conv_block_train_amp_bwd: x and u are the contiguous maps of the forward, u float16")
-    n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb = need
-    n_dwb = n_dwb and has_dw_bias
-    mask = (_lib.CBT_NEED_X if n_x else 0) | (_lib.CBT_NEED_DW if (n_dww or n_dwb) else 0) | \
-        (_lib.CBT_NEED_BN if (n_g or n_b) else 0) | (_lib.CBT_NEED_PW if (n_pww or n_pwb) else 0)
-
-    def out(bit, *shape, dtype=torch.float32):
-        return torch.empty(shape, device=dev, dtype=dtype) if mask & bit else None
-
-    gx = out(_lib.CBT_NEED_X, B, C, G, G, dtype=x.dtype)
-    d_dww, d_dwb = out(_lib.CBT_NEED_DW, C, 25), (out(_lib.CBT_NEED_DW, C) if has_dw_bias else None)
-    d_g, d_b = out(_lib.CBT_NEED_BN, C), out(_lib.CBT_NEED_BN, C)
-    d_pww, d_pwb = out(_lib.CBT_NEED_PW, M, C), out(_lib.CBT_NEED_PW, M)
-    if mask:
-        nws = int(_L().gfn_conv_block_train_half_ws_bytes(B, C, M, G, 1))
-        ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
-        _timed("conv_block_train_amp_bwd_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_train_half_bwd(
-            ptr(gy), ptr(x), _map_dtype(x), ptr(u), ptr(mean), ptr(invstd), ptr(dw_w), ptr(bn_weight), ptr(bn_bias), ptr(pw_w), ptr(gx),
-            ptr(d_dww), ptr(d_dwb), ptr(d_g), ptr(d_b), ptr(d_pww), ptr(d_pwb), B, C, M, G, mask, ptr(ws), nws, stream_ptr(dev)))
-    grads = (gx, d_dww, d_dwb, d_g, d_b, d_pww, d_pwb)
-    return tuple(g if want else None for g, want in zip(grads, (n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb)))
-
-
-class _ConvBlockTrainAmpFn(torch.autograd.Function):
-    """conv_block_train_amp: saves x in its own dtype, u as float16, mean, invstd and the fp32 parameters the backward reads."""
-
-    @staticmethod
-    def forward(ctx, x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b, running_mean, running_var, momentum, eps):
-        C, M = x.shape[1], pw_w.shape[0]
-        xk, dww, pww = x.contiguous(), dw_w.reshape(C, 25).contiguous(), pw_w.reshape(M, C).contiguous()
-        bnw, bnb = bn_weight.contiguous(), bn_bias.contiguous()
-        y, u, mean, invstd = conv_block_train_amp_fwd(xk, dww, dw_b, bnw, bnb, running_mean, running_var, momentum, eps, pww, pw_b)
-        ctx.save_for_backward(xk, u, mean, invstd, dww, bnw, bnb, pww)
-        ctx.meta = (dw_w.shape, pw_w.shape, dw_b is not None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        xk, u, mean, invstd, dww, bnw, bnb, pww = ctx.saved_tensors
-        dw_shape, pw_shape, has_bias = ctx.meta
-        g = list(conv_block_train_amp_bwd(gy, xk, u, mean, invstd, dww, bnw, bnb, pww, need=ctx.needs_input_grad[:7], has_dw_bias=has_bias))
-        if g[1] is not None:
-            g[1] = g[1].reshape(dw_shape)
-        if g[5] is not None:
-            g[5] = g[5].reshape(pw_shape)
-        return tuple(g) + (None,) * 4
+    return _conv_block_train_bwd(_AMP, gy, x, u, mean, invstd, dw_w, bn_weight, bn_bias, pw_w, need, has_dw_bias)
 
 
 def conv_block_train_amp(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, pw_w, pw_b):
@@ -1041,17 +1003,8 @@ def conv_block_train_amp(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, runnin
     in HBM (u, y, the backward's intermediate and gx) are fp16, every sum fp32, the three 1x1 products fp16 operands on the matrix
     core with fp32 accumulators; rounding overflows to inf, so a GradScaler (ops.FusedAdamWStep) sees a loss scale that is too large.
     Running buffers, num_batches_tracked, momentum and eps as conv_block_train; identical calls give identical bits."""
-    if momentum is None:
-        raise ValueError("conv_block_train_amp: momentum must be a float (cumulative averaging, momentum=None, is not supported)")
-    require_gpu(x, dw_w, pw_w, running_mean, running_var)
-    _conv_block_train_args(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b, amp=True)
-    y = _ConvBlockTrainAmpFn.apply(x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b, running_mean, running_var, float(momentum), float(eps))
-    # the kernels wrote the buffers through raw pointers: tell autograd's version counters
-    torch.autograd.graph.increment_version(running_mean)
-    torch.autograd.graph.increment_version(running_var)
-    if num_batches_tracked is not None:
-        num_batches_tracked.add_(1)
-    return y
+    return _conv_block_train(_AMP, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, pw_w,
+                             pw_b)
 
 
 # ---- the training loss (losses/robust_loss.py) -------------------------------------------------------------------------------------

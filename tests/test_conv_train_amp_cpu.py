@@ -10,15 +10,12 @@ reference's own class, fp16 at every module output, every module's grad-input an
 with the same ReLU mask.  The factor 2: both sides carry the same half-ulp roundings of y and gx, and the maximum over a few
 thousand of them moves by tens of percent between two correct implementations."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import ROOT
+from test_conv_train_cpu import assert_train_kernels_have_no_spills_and_no_scratch
 from test_conv_train_gpu import CASES, EPS, LEAVES, MOMENTUM, make_inputs
 
 PARAMS = LEAVES[1:]
@@ -180,22 +177,9 @@ def test_half_entry_points_refuse_bad_arguments_without_a_gpu():
 
 
 def test_half_kernels_have_no_spills_and_no_scratch():
-    obj = os.path.join(ROOT, "gfnet_amd", "csrc", "conv_stack_train_half.o")
-    if not os.path.exists(obj):
-        from gfnet_amd import build
-
-        build.build()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), obj, "cta_"], capture_output=True, text=True,
-                         check=True).stdout
-    rows = [ln for ln in out.splitlines() if "cta_" in ln]
     # 4 small reductions + the depthwise forward and backward for fp32 / fp16 x + the 1x1 forward and backward + 8 shapes of the
     # 1x1 weight gradient
-    assert len(rows) == 4 + 2 + 2 + 1 + 1 + 8, out
-    for ln in rows:
-        f = ln.split()
-        vals = {f[k]: f[k + 1] for k in range(len(f) - 1) if f[k] in ("spill", "sspill", "scratch")}
-        assert vals == {"spill": "0", "sspill": "0", "scratch": "0"}, ln
-        assert int(f[f.index("lds") + 1]) <= 64 * 1024, ln
+    assert_train_kernels_have_no_spills_and_no_scratch("conv_stack_train_half.o", 4 + 2 + 2 + 1 + 1 + 8)
 
 
 def test_hip_amp_is_accepted_and_leaves_the_other_predicates_alone():

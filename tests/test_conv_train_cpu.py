@@ -65,8 +65,10 @@ def test_conv_block_train_entry_points_refuse_bad_arguments_without_a_gpu():
     assert bwd(B=0) == 0 and bwd(need=0) == 0 and bwd(need=0, d_dw_b=None, gx=None) == 0
 
 
-def test_conv_block_train_kernels_have_no_spills_and_no_scratch():
-    obj = os.path.join(ROOT, "gfnet_amd", "csrc", "conv_stack_train.o")
+def assert_train_kernels_have_no_spills_and_no_scratch(obj_name, count):
+    """Every training kernel of csrc/<obj_name> -- both classes name theirs ct_... -- has no VGPR or SGPR spill, no scratch and at
+    most 64 KiB of LDS, and there are exactly `count` of them (tests/test_conv_train_amp_cpu.py checks the fp16 class's object)."""
+    obj = os.path.join(ROOT, "gfnet_amd", "csrc", obj_name)
     if not os.path.exists(obj):
         from gfnet_amd import build
 
@@ -74,14 +76,19 @@ def test_conv_block_train_kernels_have_no_spills_and_no_scratch():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), obj, "ct_"], capture_output=True, text=True,
                          check=True).stdout
     rows = [ln for ln in out.splitlines() if "ct_" in ln]
-    # 6 plain kernels + the 1x1 forward and backward for 1..7 row tiles + 8 shapes of the 1x1 weight gradient
-    assert len(rows) == 6 + 7 + 7 + 8, out
+    assert len(rows) == count, out
     for ln in rows:
         f = ln.split()
         vals = {f[k]: f[k + 1] for k in range(len(f) - 1) if f[k] in ("spill", "sspill", "scratch")}
         assert vals == {"spill": "0", "sspill": "0", "scratch": "0"}, ln
         lds = int(f[f.index("lds") + 1])
         assert lds <= 64 * 1024, ln
+
+
+def test_conv_block_train_kernels_have_no_spills_and_no_scratch():
+    # 6 plain kernels (the depthwise pair is one instantiation each) + the 1x1 forward and backward for 1..7 row tiles + 8 shapes of
+    # the 1x1 weight gradient
+    assert_train_kernels_have_no_spills_and_no_scratch("conv_stack_train.o", 6 + 7 + 7 + 8)
 
 
 def test_train_conv_impl_defaults_to_torch_and_leaves_the_eval_predicate_alone():
