@@ -135,13 +135,15 @@ __device__ int ransac_update_iters(double conf, int good, int N, int niters) {
 
 // Inlier test: squared reprojection error <= thr2, multiplied through by w^2 so that no division is needed, sums as
 // explicit v_fma_f64 (12 instead of 25 fp64 instructions per test under -ffp-contract=off) -- the same operation sequence as
-// is_inlier() in the oracle (bit-identical decisions).
+// is_inlier() in the oracle (bit-identical decisions).  w^2 must be positive AND finite: an infinite x or y makes both sides of
+// the comparison +inf (inf <= inf holds), and a row that is not finite is never an inlier.  One v_cmp_class_f64 tests both.
 __device__ __forceinline__ bool is_inlier(const double (&H)[9], double x, double y, double u, double v, double thr2) {
     const double w = fma(H[6], x, fma(H[7], y, H[8]));
     const double dx = fma(-u, w, fma(H[0], x, fma(H[1], y, H[2])));
     const double dy = fma(-v, w, fma(H[3], x, fma(H[4], y, H[5])));
     const double w2 = w * w;
-    return (fma(dx, dx, dy * dy) <= thr2 * w2) & (w2 > 0);
+    constexpr int kPosFinite = (1 << 7) | (1 << 8);  // +denormal | +normal
+    return (fma(dx, dx, dy * dy) <= thr2 * w2) & __builtin_amdgcn_class(w2, kPosFinite);
 }
 __device__ __forceinline__ bool is_inlier(const double (&H)[9], const float4 p, double thr2) {
     return is_inlier(H, (double)p.x, (double)p.y, (double)p.z, (double)p.w, thr2);
@@ -633,10 +635,18 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinParams P) {
         }
     }
 
-    // per-point weight (mask in ransac mode, certainty in dlt mode)
+    // Per-point weight (mask in ransac mode, certainty in dlt mode) and the point that goes with it.  THE RULE for every sum
+    // below (centroid, deviations, DLT rows, LM rows): in ransac mode a correspondence outside the inlier mask is left out BY
+    // SELECTION -- point_at() hands out the point (0,0,0,0) for it, so each of its terms is an exact zero of finite factors --
+    // and never by multiplying its coordinates with the weight 0: a rejected row may hold NaN or inf (a warp that went through
+    // fp16 maps), 0 * NaN is NaN, and the oracle skips such rows (`if (mask && !mask[n]) continue`).  For finite rows the sums
+    // are bit for bit what the multiplication gave.  In dlt mode the weight multiplies, as it does in the oracle.
     auto point_w = [&](int n, const double (&Hb)[9]) -> double {
         if (P.mode == 0) return is_inlier(Hb, pts[n], P.thr2) ? 1.0 : 0.0;
         return wgt ? (double)wgt[n] : 1.0;
+    };
+    auto point_at = [&](int n, double w) -> float4 {
+        return (P.mode == 0 && w == 0.0) ? make_float4(0.f, 0.f, 0.f, 0.f) : pts[n];
     };
     double Hb[9];
 #pragma unroll
@@ -647,7 +657,7 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinParams P) {
         double v[5] = {0, 0, 0, 0, 0};
         for (int n = tid; n < N; n += kFinThreads) {
             const double w = point_w(n, Hb);
-            const float4 p = pts[n];
+            const float4 p = point_at(n, w);
             v[0] += w; v[1] += w * p.x; v[2] += w * p.y; v[3] += w * p.z; v[4] += w * p.w;
         }
         block_sum<5>(sh, v, sh.stats);
@@ -660,7 +670,7 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinParams P) {
         double v[4] = {0, 0, 0, 0};
         for (int n = tid; n < N; n += kFinThreads) {
             const double w = point_w(n, Hb);
-            const float4 p = pts[n];
+            const float4 p = point_at(n, w);
             v[0] += w * fabs(p.x - cx); v[1] += w * fabs(p.y - cy); v[2] += w * fabs(p.z - cu); v[3] += w * fabs(p.w - cv);
         }
         block_sum<4>(sh, v, sh.stats + 5);
@@ -669,8 +679,8 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinParams P) {
     const double sx = sw / sh.stats[5], sy = sw / sh.stats[6], su = sw / sh.stats[7], sv = sw / sh.stats[8];
     if (dlt_ok) {
         gram_accumulate(sh, N, [&](int n, double (&a)[6], double (&bb)[6]) {
-            const double sw_ = sqrt(point_w(n, Hb));
-            const float4 p = pts[n];
+            const double w = point_w(n, Hb), sw_ = sqrt(w);
+            const float4 p = point_at(n, w);
             const double X = (p.x - cx) * sx * sw_, Y = (p.y - cy) * sy * sw_, x = (p.z - cu) * su, y = (p.w - cv) * sv;
             a[0] = X; a[1] = Y; a[2] = sw_; a[3] = -x * X; a[4] = -x * Y; a[5] = -x * sw_;
             bb[0] = X; bb[1] = Y; bb[2] = sw_; bb[3] = -y * X; bb[4] = -y * Y; bb[5] = -y * sw_;
@@ -723,7 +733,7 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinParams P) {
         for (int k = 0; k < 9; ++k) h[k] = hsrc[k];
         gram_accumulate(sh, N, [&](int n, double (&a)[6], double (&bb)[6]) {
             const double w = point_w(n, Hb);  // 0/1 here
-            const float4 p = pts[n];
+            const float4 p = point_at(n, w);
             const double X = p.x, Y = p.y, u = p.z, v = p.w;
             const double ww = w != 0.0 ? 1.0 / (h[6] * X + h[7] * Y + 1.0) : 0.0;  // masked points contribute exact zeros
             const double xi = (h[0] * X + h[1] * Y + h[2]) * ww, yi = (h[3] * X + h[4] * Y + h[5]) * ww;
