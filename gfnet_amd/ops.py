@@ -202,6 +202,47 @@ def cross_attention(q, k, v, scale):
     return cross_attention_fwd(q, k, v, scale)[0]
 
 
+CONV_ACTS = {None: 0, "none": 0, "leaky_relu": 1, "swish": 2}
+
+
+def conv2d_bn_act(x0, weight, scale, shift, x1=None, up0=False, residual=None, stride=1, act=None, slope=0.1):
+    """One FPN layer in inference as one launch (gfn_conv2d_bn_act_fwd; reference model/FPN.py:95-128 and :43-66):
+
+        out = act(conv(cat(x0', x1), weight) * scale[c] + shift[c]) + residual        zero padding K // 2
+
+    x0 (B, C0, H, W), or with up0 (B, C0, H/2, W/2) read through F.interpolate(scale_factor=2, mode="bilinear",
+    align_corners=False) without writing the doubled map; x1 (B, C1, H, W) or None; weight (Cout, C0 + C1, K, K), K in 1, 3, 5, 7;
+    scale, shift (Cout): BatchNorm and the conv bias folded; residual of the output's shape or None (it may be x0 or x1); stride 1
+    or 2; act None, "leaky_relu" (with slope) or "swish".  Contiguous fp32 CUDA tensors, the current stream, no autograd."""
+    if act not in CONV_ACTS:
+        raise ValueError(f"conv2d_bn_act: act must be one of {list(CONV_ACTS)}, got {act!r}")
+    tensors = {"x0": x0, "weight": weight, "scale": scale, "shift": shift, "x1": x1, "residual": residual}
+    dev = require_gpu(*tensors.values())
+    for name, t in tensors.items():
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError(f"conv2d_bn_act: {name} must be a contiguous float32 tensor, got {t.dtype}, contiguous={t.is_contiguous()}")
+    if x0.dim() != 4 or weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
+        raise ValueError(f"conv2d_bn_act: x0 (B,C0,H,W) and weight (Cout,Cin,K,K) expected, got {tuple(x0.shape)}, {tuple(weight.shape)}")
+    B, C0 = x0.shape[:2]
+    H, W = (2 * x0.shape[2], 2 * x0.shape[3]) if up0 else x0.shape[2:]
+    C1 = 0 if x1 is None else x1.shape[1]
+    Cout, Cin, K, _ = weight.shape
+    if x1 is not None and (x1.dim() != 4 or x1.shape[0] != B or tuple(x1.shape[2:]) != (H, W)):
+        raise ValueError(f"conv2d_bn_act: x1 must be ({B}, C1, {H}, {W}), got {tuple(x1.shape)}")
+    if Cin != C0 + C1 or tuple(scale.shape) != (Cout,) or tuple(shift.shape) != (Cout,):
+        raise ValueError(f"conv2d_bn_act: weight takes {Cin} channels but the inputs have {C0} + {C1}; scale and shift must be ({Cout},), "
+                         f"got {tuple(scale.shape)}, {tuple(shift.shape)}")
+    if stride not in (1, 2):
+        raise ValueError(f"conv2d_bn_act: stride must be 1 or 2, got {stride!r}")
+    out = torch.empty((B, Cout, (H + stride - 1) // stride, (W + stride - 1) // stride), device=dev, dtype=torch.float32)
+    if residual is not None and residual.shape != out.shape:
+        raise ValueError(f"conv2d_bn_act: residual must have the output's shape {tuple(out.shape)}, got {tuple(residual.shape)}")
+    _timed("conv2d_bn_act", lambda: _L().gfn_conv2d_bn_act_fwd(ptr(x0), C0, int(bool(up0)), ptr(x1), C1, ptr(weight), ptr(scale), ptr(shift),
+                                                               ptr(residual), ptr(out), B, H, W, Cout, K, stride, CONV_ACTS[act],
+                                                               float(slope), stream_ptr(dev)))
+    return out
+
+
 def corr_volume(feat0, feat1, with_flow=False):
     """GFNet.corr_volume (model/network.py:415-428): (B,H1,W1,H0,W0) = f0^T f1 / sqrt(C)."""
     dev = require_gpu(feat0, feat1)

@@ -1,7 +1,8 @@
 """The reference's feature extractor, built from the USER'S OWN GFNet checkout, as a `backbone=` for gfnet_amd's GFNet.
 
-BASELINE north_star: "host code stays PyTorch-ROCm for the FPN/transformer backbone".  Nothing of that backbone lives in this
-package; this module only *assembles* it from the checkout's classes when one is importable (`model.FPN`,
+BASELINE north_star: "host code stays PyTorch-ROCm for the FPN/transformer backbone".  By default nothing of that backbone is taken
+from this package (decoder="hip" and fpn="hip" opt into its own cross-view decoder and FPN, model/crossview_decoder.py and
+model/fpn.py); this module only *assembles* it from the checkout's classes when one is importable (`model.FPN`,
 `model.crossview_decoder_light`, `model.transformer` -- with compat/ on sys.path those still resolve to the checkout, see
 compat/model/__init__.py) and states the data flow of `GFNet.extract_features` (reference model/network.py:156-201) around them:
 
@@ -24,14 +25,27 @@ DINOV2_URL = "https://dl.fbaipublicfiles.com/dinov2/dinov2_vitl14/dinov2_vitl14_
 
 
 DECODERS = ("checkout", "hip")
+FPNS = ("checkout", "hip")
 
 
-def checkout_available(decoder="checkout"):
-    """True when the reference's backbone modules can be found on sys.path (nothing is imported).  decoder="hip" needs only
-    `model.FPN`: the cross-view decoder is then this package's."""
+def _needed(decoder, fpn):
+    return (("model.FPN",) if fpn == "checkout" else ()) + (("model.crossview_decoder_light",) if decoder == "checkout" else ())
+
+
+def _check_choices(decoder, fpn):
+    if decoder not in DECODERS:
+        raise ValueError(f"decoder must be one of {DECODERS}, got {decoder!r}")
+    if fpn not in FPNS:
+        raise ValueError(f"fpn must be one of {FPNS}, got {fpn!r}")
+
+
+def checkout_available(decoder="checkout", fpn="checkout"):
+    """True when the reference's backbone modules that this choice takes from the checkout can be found on sys.path (nothing is
+    imported).  decoder="hip" does without `model.crossview_decoder_light`, fpn="hip" without `model.FPN`: those are then this
+    package's; with both, nothing is needed (the ViT apart, which is built only where none is passed in)."""
     import importlib.util
 
-    needed = ("model.FPN", "model.crossview_decoder_light") if decoder == "checkout" else ("model.FPN",)
+    needed = _needed(decoder, fpn)
     try:
         return all(importlib.util.find_spec(m) is not None for m in needed)
     except (ImportError, ValueError):
@@ -62,13 +76,20 @@ class ReferenceBackbone(nn.Module):
 
     decoder: "checkout" (default) builds the checkout's CrossVITDecoder_noself, which with the shipped attention_type "FLASH2" raises
     on its first forward where flash_attn is missing; "hip" builds gfnet_amd.model.crossview_decoder.CrossViewDecoder, the same
-    module under the same parameter names with its attention core in HIP, and does not import the checkout's decoder."""
+    module under the same parameter names with its attention core in HIP, and does not import the checkout's decoder.
 
-    def __init__(self, conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout"):
+    fpn: "checkout" (default) builds the checkout's FPNEncoder, FPNDecoder_concat and merge layer; "hip" builds
+    gfnet_amd.model.fpn's, the same modules under the same parameter names with one fused HIP launch per layer in eval(), and does
+    not import `model.FPN`.  With decoder="hip", fpn="hip" and a `vit` passed in, nothing of a checkout is imported."""
+
+    def __init__(self, conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout"):
         super().__init__()
-        if decoder not in DECODERS:
-            raise ValueError(f"decoder must be one of {DECODERS}, got {decoder!r}")
-        from model.FPN import FPNDecoder_concat, FPNEncoder, Swish
+        _check_choices(decoder, fpn)
+        self.fpn = fpn
+        if fpn == "hip":
+            from .model.fpn import FPNDecoder_concat, FPNEncoder, merge_layer
+        else:
+            from model.FPN import FPNDecoder_concat, FPNEncoder, Swish
 
         self.amp, self.amp_dtype = amp, amp_dtype
         if vit is None:
@@ -87,7 +108,10 @@ class ReferenceBackbone(nn.Module):
             self.dino_decoder = CrossVITDecoder_noself(conf=conf, upsample=False)
         self.encoder = FPNEncoder(feat_chs=chs[::-1])
         self.decoder = FPNDecoder_concat(feat_chs=chs[::-1])
-        self.merge_layer = nn.Sequential(nn.Conv2d(2 * chs[0], chs[0], kernel_size=3, padding=1), nn.BatchNorm2d(chs[0]), Swish())
+        if fpn == "hip":
+            self.merge_layer = merge_layer(chs[0])
+        else:
+            self.merge_layer = nn.Sequential(nn.Conv2d(2 * chs[0], chs[0], kernel_size=3, padding=1), nn.BatchNorm2d(chs[0]), Swish())
 
     def _vit_tokens(self, x):
         vit = self.dino[0]
@@ -109,7 +133,8 @@ class ReferenceBackbone(nn.Module):
         c0, c1, c2, c3 = self.encoder(x)
         side = vit_feat if tuple(vit_feat.shape[2:]) == (H // 8, W // 8) else \
             F.interpolate(vit_feat, size=(H // 8, W // 8), mode="bilinear", align_corners=False)
-        c3 = c3 + self.merge_layer(torch.cat((c3, side), dim=1))
+        # (the native merge layer takes both maps and adds conv31 itself: one launch, no concatenation)
+        c3 = self.merge_layer(c3, side) if self.fpn == "hip" else c3 + self.merge_layer(torch.cat((c3, side), dim=1))
         levels = [vit_feat] + list(self.decoder(c0, c1, c2, c3))
         pyr_a, pyr_b = {}, {}
         for name, t in zip(("16", "8", "4", "2", "1"), levels):
@@ -120,15 +145,11 @@ class ReferenceBackbone(nn.Module):
         return pyr_a, pyr_b
 
 
-def reference_backbone(conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout"):
-    """Build the backbone from the checkout on sys.path; raises ImportError with the reason when there is none.  decoder: see
-    ReferenceBackbone."""
-    if decoder not in DECODERS:
-        raise ValueError(f"decoder must be one of {DECODERS}, got {decoder!r}")
-    if not checkout_available(decoder):
-        if decoder == "hip":
-            raise ImportError("no KN-Zhang/GFNet checkout on sys.path: `model.FPN` cannot be found "
-                              "(put the checkout behind compat/ on PYTHONPATH, or run the script through compat/run.py)")
-        raise ImportError("no KN-Zhang/GFNet checkout on sys.path: `model.FPN` / `model.crossview_decoder_light` cannot be found "
+def reference_backbone(conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout"):
+    """Build the backbone from the checkout on sys.path; raises ImportError with the reason when a module this choice needs from it
+    is missing.  decoder, fpn: see ReferenceBackbone."""
+    _check_choices(decoder, fpn)
+    if not checkout_available(decoder, fpn):
+        raise ImportError(f"no KN-Zhang/GFNet checkout on sys.path: {' / '.join(f'`{m}`' for m in _needed(decoder, fpn))} cannot be found "
                           "(put the checkout behind compat/ on PYTHONPATH, or run the script through compat/run.py)")
-    return ReferenceBackbone(conf, amp=amp, amp_dtype=amp_dtype, vit=vit, dino_weights=dino_weights, decoder=decoder)
+    return ReferenceBackbone(conf, amp=amp, amp_dtype=amp_dtype, vit=vit, dino_weights=dino_weights, decoder=decoder, fpn=fpn)

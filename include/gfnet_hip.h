@@ -699,6 +699,24 @@ int gfn_cross_attn_fwd(const void *q, const void *k, const void *v, int dtype, i
 int gfn_cross_attn_bwd(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *dout, int dtype,
                        int B, int Nq, int Nk, int H, int D, float scale, void *dq, void *dk, void *dv, gfn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * One layer of the FPN pyramid in inference -- model/FPN.py:95-128 (Conv2d: conv, BatchNorm, leaky ReLU), :43-52 (the decoder's
+ * Sequential(conv, BatchNorm, Swish) heads), :59-66 (cat(interpolate(intra), convN1) into innerN, plus convN1) and
+ * model/network.py:66, 182 (merge_layer and its residual); csrc/fpn_conv.hip.  fp32, NCHW, contiguous:
+ *   out = act(conv(cat(x0', x1), weight) * scale[c] + shift[c]) + residual          zero padding K/2, out (B, Cout, Ho, Wo) with
+ *   Ho = (H + stride - 1) / stride, Wo likewise.
+ * x0 (B, C0, H, W); with up0 != 0 x0 is (B, C0, H/2, W/2) and x0' its 2x bilinear upsample, exactly F.interpolate(scale_factor=2,
+ * mode="bilinear", align_corners=False) (H and W even), computed on the way in and never written.  x1 (B, C1, H, W) or NULL with
+ * C1 = 0.  weight (Cout, C0 + C1, K, K) as torch stores it; scale, shift (Cout): BatchNorm's running statistics, its affine and
+ * the conv bias, folded by the caller.  residual (B, Cout, Ho, Wo) or NULL; it may alias x0 or x1, out may alias nothing.
+ * K in {1, 3, 5, 7}, stride in {1, 2}, act 0 (none), 1 (leaky ReLU with `slope`) or 2 (x * sigmoid(x)); C0 >= 1, 1 <= Cout <= 256,
+ * any H, W >= 1, B <= 65535; every map of ONE image below 2^31 bytes (the batch may exceed 4 GB: batch offsets are 64-bit).
+ * Anything else returns GFN_ERR_INVALID_ARG before a launch; B = 0 returns GFN_OK.  fp32 operands and fmaf accumulation in a fixed
+ * order, no atomics: identical calls give identical bits.  Cout a multiple of 8 takes the LDS-tiled kernel, others a plain one. */
+int gfn_conv2d_bn_act_fwd(const float *x0, int C0, int up0, const float *x1, int C1, const float *weight, const float *scale,
+                          const float *shift, const float *residual, float *out, int B, int H, int W, int Cout, int K, int stride,
+                          int act, float slope, gfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
