@@ -202,6 +202,68 @@ def cross_attention(q, k, v, scale):
     return cross_attention_fwd(q, k, v, scale)[0]
 
 
+def reference_self_attention(qkv, scale):
+    """The definition self_attention computes, in plain torch on any device and in any floating dtype (float64 included), for tests:
+    qkv (B,N,3,H,D), the packed projection -> out (B,N,H,D) with, per batch and head, out_i = sum_j softmax_j(scale * q_i . k_j) v_j
+    for q = qkv[:, :, 0], k = qkv[:, :, 1], v = qkv[:, :, 2].  It is what the reference's Attention.forward computes with
+    F.scaled_dot_product_attention on the permuted tensors (model/transformer/layers/attention.py:79-97)."""
+    q, k, v = qkv.unbind(2)
+    return reference_cross_attention(q, k, v, scale)
+
+
+def self_attention(qkv, scale):
+    """The attention core of the reference's ViT (model/transformer/layers/attention.py:96, F.scaled_dot_product_attention) at head
+    dim 64 on the packed projection: qkv (B,N,3,H,64) fp16, as `self.qkv(x).reshape(B, N, 3, H, C // H)` gives it -> out
+    (B,N,H,64) fp16 = softmax(scale * q k^T) v per batch and head, so `out.reshape(B, N, C)` feeds proj (gfn_self_attn_fwd: one
+    launch, nothing N x N written).  Forward only, no autograd.  CPU tensors raise: reference_self_attention is the definition for
+    every device, this is the product path."""
+    dev = require_gpu(qkv)
+    if qkv.dim() != 5 or qkv.shape[2] != 3:
+        raise ValueError(f"self_attention: qkv (B,N,3,H,D) expected, got {tuple(qkv.shape)}")
+    if qkv.dtype != torch.float16:
+        raise TypeError(f"self_attention: qkv must be float16, got {qkv.dtype}")
+    qkv = qkv.contiguous()
+    if qkv.data_ptr() % 16:
+        qkv = qkv.clone()
+    B, N, _, H, D = qkv.shape
+    out = torch.empty((B, N, H, D), device=dev, dtype=torch.float16)
+    _timed("self_attn_fwd", lambda: _L().gfn_self_attn_fwd(ptr(qkv), _lib.GFN_F16, B, N, H, D, float(scale), ptr(out), stream_ptr(dev)))
+    return out
+
+
+def ls_add_layernorm(x, y, gamma, weight, bias, eps, inplace=False):
+    """The seam of a ViT block in one launch (gfn_ls_add_layernorm_fwd; reference model/transformer/layers/block.py:83-106):
+
+        x_out = x + gamma * y          h = LayerNorm(x_out) * weight + bias over the last dim, from x_out as stored
+
+    x, y (..., C) of one shape, gamma, weight, bias (C), all fp16 or all fp32, C a multiple of 8 up to 8192.  y None: the plain
+    LayerNorm of x (gamma is not read).  weight None: only the residual update (bias and eps are not read).  inplace=True writes
+    x_out into x (which must then be contiguous).  Returns (x_out, h): x itself where y is None, h None where weight is None.
+    Contiguous CUDA tensors, the current stream, no autograd."""
+    tensors = {"x": x, "y": y, "gamma": gamma if y is not None else None, "weight": weight, "bias": bias if weight is not None else None}
+    dev = require_gpu(*tensors.values())
+    if x.dtype not in (torch.float16, torch.float32) or any(t is not None and t.dtype != x.dtype for t in tensors.values()):
+        raise TypeError("ls_add_layernorm: every tensor must share one dtype, float16 or float32, got "
+                        f"{ {n: str(t.dtype) for n, t in tensors.items() if t is not None} }")
+    if y is None and weight is None:
+        raise ValueError("ls_add_layernorm: nothing to compute (y and weight are both None)")
+    C = x.shape[-1]
+    if y is not None and (y.shape != x.shape or gamma is None or tuple(gamma.shape) != (C,)):
+        raise ValueError(f"ls_add_layernorm: y must have x's shape {tuple(x.shape)} and gamma must be ({C},)")
+    if weight is not None and (bias is None or tuple(weight.shape) != (C,) or tuple(bias.shape) != (C,)):
+        raise ValueError(f"ls_add_layernorm: weight and bias must be ({C},)")
+    if inplace and y is not None and not x.is_contiguous():
+        raise ValueError("ls_add_layernorm: inplace=True needs a contiguous x")
+    x, y, gamma, weight, bias = (None if t is None else t.detach().contiguous() for t in (x, y, tensors["gamma"], weight, tensors["bias"]))
+    x_out = None if y is None else (x if inplace else torch.empty_like(x))
+    h = None if weight is None else torch.empty_like(x)
+    rows = x.numel() // C if C else 0
+    _timed("ls_add_layernorm", lambda: _L().gfn_ls_add_layernorm_fwd(ptr(x), ptr(y), ptr(gamma), ptr(weight), ptr(bias), float(eps),
+                                                                      _lib.GFN_F16 if x.dtype == torch.float16 else _lib.GFN_F32, rows, C,
+                                                                      ptr(x_out), ptr(h), stream_ptr(dev)))
+    return (x if y is None else x_out), h
+
+
 CONV_ACTS = {None: 0, "none": 0, "leaky_relu": 1, "swish": 2}
 
 

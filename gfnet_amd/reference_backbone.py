@@ -1,8 +1,9 @@
 """The reference's feature extractor, built from the USER'S OWN GFNet checkout, as a `backbone=` for gfnet_amd's GFNet.
 
 BASELINE north_star: "host code stays PyTorch-ROCm for the FPN/transformer backbone".  By default nothing of that backbone is taken
-from this package (decoder="hip" and fpn="hip" opt into its own cross-view decoder and FPN, model/crossview_decoder.py and
-model/fpn.py); this module only *assembles* it from the checkout's classes when one is importable (`model.FPN`,
+from this package (decoder="hip", fpn="hip" and dino="hip" opt into its own cross-view decoder, FPN and DINOv2 ViT,
+model/crossview_decoder.py, model/fpn.py and model/dinov2.py; with all three nothing of a checkout is imported); this module
+only *assembles* it from the checkout's classes when one is importable (`model.FPN`,
 `model.crossview_decoder_light`, `model.transformer` -- with compat/ on sys.path those still resolve to the checkout, see
 compat/model/__init__.py) and states the data flow of `GFNet.extract_features` (reference model/network.py:156-201) around them:
 
@@ -26,23 +27,27 @@ DINOV2_URL = "https://dl.fbaipublicfiles.com/dinov2/dinov2_vitl14/dinov2_vitl14_
 
 DECODERS = ("checkout", "hip")
 FPNS = ("checkout", "hip")
+DINOS = ("checkout", "hip")
 
 
 def _needed(decoder, fpn):
     return (("model.FPN",) if fpn == "checkout" else ()) + (("model.crossview_decoder_light",) if decoder == "checkout" else ())
 
 
-def _check_choices(decoder, fpn):
+def _check_choices(decoder, fpn, dino="checkout"):
     if decoder not in DECODERS:
         raise ValueError(f"decoder must be one of {DECODERS}, got {decoder!r}")
     if fpn not in FPNS:
         raise ValueError(f"fpn must be one of {FPNS}, got {fpn!r}")
+    if dino not in DINOS:
+        raise ValueError(f"dino must be one of {DINOS}, got {dino!r}")
 
 
 def checkout_available(decoder="checkout", fpn="checkout"):
     """True when the reference's backbone modules that this choice takes from the checkout can be found on sys.path (nothing is
     imported).  decoder="hip" does without `model.crossview_decoder_light`, fpn="hip" without `model.FPN`: those are then this
-    package's; with both, nothing is needed (the ViT apart, which is built only where none is passed in)."""
+    package's; with both, nothing is needed (the ViT apart, which is built only where none is passed in, and
+    with dino="hip" is this package's too)."""
     import importlib.util
 
     needed = _needed(decoder, fpn)
@@ -56,6 +61,17 @@ def _build_vit(dino_weights):
     from model.transformer import vit_large  # the checkout's DINOv2 (needs its own third-party imports, e.g. romatch)
 
     vit = vit_large(img_size=518, patch_size=14, init_values=1.0, ffn_layer="mlp", block_chunks=0).eval()  # network.py:48-54
+    return _load_dino_weights(vit, dino_weights)
+
+
+def _build_native_vit(dino_weights):
+    from .model.dinov2 import vit_large  # this package's DINOv2 under the same parameter names: nothing of a checkout
+
+    vit = vit_large(img_size=518, patch_size=14, init_values=1.0, ffn_layer="mlp", block_chunks=0).eval()
+    return _load_dino_weights(vit, dino_weights)
+
+
+def _load_dino_weights(vit, dino_weights):
     if dino_weights is None:
         dino_weights = os.environ.get("GFNET_DINOV2_WEIGHTS")
     if dino_weights is None:
@@ -80,11 +96,17 @@ class ReferenceBackbone(nn.Module):
 
     fpn: "checkout" (default) builds the checkout's FPNEncoder, FPNDecoder_concat and merge layer; "hip" builds
     gfnet_amd.model.fpn's, the same modules under the same parameter names with one fused HIP launch per layer in eval(), and does
-    not import `model.FPN`.  With decoder="hip", fpn="hip" and a `vit` passed in, nothing of a checkout is imported."""
+    not import `model.FPN`.
 
-    def __init__(self, conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout"):
+    dino: which ViT is built where none is passed in.  "checkout" (default) builds the checkout's `vit_large`, which imports
+    `model.transformer` and with it the checkout's third-party imports; "hip" builds gfnet_amd.model.dinov2.vit_large, the same model
+    under the same parameter names (`dino_weights` load strictly, exactly as above) with its attention and the seams of its blocks
+    in HIP in fp16 eval().  With decoder="hip", fpn="hip" and dino="hip" nothing of a checkout is imported."""
+
+    def __init__(self, conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout",
+                 dino="checkout"):
         super().__init__()
-        _check_choices(decoder, fpn)
+        _check_choices(decoder, fpn, dino)
         self.fpn = fpn
         if fpn == "hip":
             from .model.fpn import FPNDecoder_concat, FPNEncoder, merge_layer
@@ -93,7 +115,7 @@ class ReferenceBackbone(nn.Module):
 
         self.amp, self.amp_dtype = amp, amp_dtype
         if vit is None:
-            vit = _build_vit(dino_weights)
+            vit = _build_native_vit(dino_weights) if dino == "hip" else _build_vit(dino_weights)
         for p in vit.parameters():
             p.requires_grad = False
         self.dino = [vit]
@@ -145,11 +167,13 @@ class ReferenceBackbone(nn.Module):
         return pyr_a, pyr_b
 
 
-def reference_backbone(conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout"):
+def reference_backbone(conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout",
+                       dino="checkout"):
     """Build the backbone from the checkout on sys.path; raises ImportError with the reason when a module this choice needs from it
-    is missing.  decoder, fpn: see ReferenceBackbone."""
-    _check_choices(decoder, fpn)
+    is missing.  decoder, fpn, dino: see ReferenceBackbone."""
+    _check_choices(decoder, fpn, dino)
     if not checkout_available(decoder, fpn):
         raise ImportError(f"no KN-Zhang/GFNet checkout on sys.path: {' / '.join(f'`{m}`' for m in _needed(decoder, fpn))} cannot be found "
                           "(put the checkout behind compat/ on PYTHONPATH, or run the script through compat/run.py)")
-    return ReferenceBackbone(conf, amp=amp, amp_dtype=amp_dtype, vit=vit, dino_weights=dino_weights, decoder=decoder, fpn=fpn)
+    return ReferenceBackbone(conf, amp=amp, amp_dtype=amp_dtype, vit=vit, dino_weights=dino_weights, decoder=decoder, fpn=fpn,
+                             dino=dino)

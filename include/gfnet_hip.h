@@ -717,6 +717,35 @@ int gfn_conv2d_bn_act_fwd(const float *x0, int C0, int up0, const float *x1, int
                           const float *shift, const float *residual, float *out, int B, int H, int W, int Cout, int K, int stride,
                           int act, float slope, gfn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Self-attention forward of the DINOv2 ViT at head dim 64 -- model/transformer/layers/attention.py:77-101 (Attention.forward:
+ * the F.scaled_dot_product_attention call at :96, which MemEffAttention falls back to without xformers, :106-110);
+ * csrc/self_attn.hip.  Per batch b and head h, with s[i][j] = scale * sum_d q[b,i,h,d] * k[b,j,h,d]:
+ *   out[b,i,h,:] = sum_j softmax_j(s[i][j]) * v[b,j,h,:]
+ * qkv is the PACKED projection (B,N,3,H,D) contiguous -- what self.qkv(x).reshape(B,N,3,H,C/H) gives: q = qkv[:,:,0], k = [:,:,1],
+ * v = [:,:,2], no permutes and no copies -- and out (B,N,H,D) contiguous, so out.reshape(B,N,C) feeds proj; both 16-byte aligned.
+ * dtype must be GFN_F16 and D must be 64; N, H >= 1 are arbitrary (tails on both axes), scale any finite value (0 gives the mean of
+ * v); B * H * ceil(N / 128) is the grid, at most 2^31 - 1.  Anything else returns GFN_ERR_INVALID_ARG before a launch; B = 0 returns
+ * GFN_OK.  No scratch, no allocation, nothing N x N is written.  Forward only: the reference freezes the ViT.
+ * Arithmetic: the raw scores on the matrix core (exact products, fp32 accumulation), online softmax in fp32 from a running maximum
+ * that starts at -inf, a key past N in a tail tile weighs exactly zero (selected by its index); the weights are rounded to fp16
+ * once for P V on the matrix core (fp32 accumulation; the row sum takes the unrounded weights), results rounded to fp16 once,
+ * overflow to inf.  No atomics: identical calls give identical bits. */
+int gfn_self_attn_fwd(const void *qkv, int dtype, int B, int N, int H, int D, float scale, void *out, gfn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The seam of a ViT block in one pass -- model/transformer/layers/block.py:83-106 with layer_scale.py (x + ls(f(norm(x))) and the
+ * norm that follows); csrc/layernorm.hip.  x, y, x_out, h_out (rows, C) contiguous, gamma, weight, bias (C), all stored as dtype =
+ * GFN_F32 or GFN_F16 and 16-byte aligned:
+ *   x_out = x + gamma * y          h_out = (x_out - mean) / sqrt(var + eps) * weight + bias     (mean, biased var over a row)
+ * y == NULL: plain LayerNorm of x (gamma and x_out may then be NULL and are not touched).  h_out == NULL: only the residual
+ * update (weight and bias may then be NULL).  Both NULL is an error.  x_out may alias x; h_out may alias nothing.  C a multiple of
+ * 8 from 8 to 8192 (the row is held in registers), rows >= 0 arbitrary; anything else returns GFN_ERR_INVALID_ARG before a launch.
+ * Arithmetic: fp32; x_out = fma(gamma, y, x) rounded to the storage type once; mean and variance two-pass (sum of squared
+ * distances from the mean) over x_out AS STORED, i.e. after that rounding, which is what a following norm reads in the reference. */
+int gfn_ls_add_layernorm_fwd(const void *x, const void *y, const void *gamma, const void *weight, const void *bias, float eps,
+                             int dtype, int64_t rows, int C, void *x_out, void *h_out, gfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
