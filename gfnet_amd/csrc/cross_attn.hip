@@ -11,26 +11,20 @@
 // registers (rows acc_row(r, lane >> 5)): running maximum, running sum and the 8-wide fp32 results are per-lane registers, and
 // the two lane halves of a row are merged once at the end.  What multiplies P or dS (V; K; dO and Q) is read from LDS as fp32
 // rows: every lane of a half wants the same row, so the read is a broadcast.  P and dS are never rounded.
-#include <hip/hip_fp16.h>
-
-#include <cmath>
 #include <initializer_list>
 
-#include "common.h"
+#include "attn_common.h"
 
 namespace {
 
 using gfn::acc_row;
 using gfn::f32x16;
+using namespace gfn::attn;
 
 constexpr int kThreads = 256;           // 4 waves: 4 own tiles of 32 rows per workgroup
 constexpr int kOwn = 128;               // own rows per workgroup
 constexpr int kChunk = 128;             // streamed rows staged per step (4 tiles); threads 0..127 stage one tensor, 128..255 another
 constexpr int kRowImg = kChunk * 8 + kChunk;  // floats of a row image: 8 per row + 4 after every 4th row (see row_at)
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 // one 8-value row as stored
 template <typename T>
@@ -142,10 +136,6 @@ __device__ __forceinline__ void get_row(const float *img, int row, float out[8])
     out[0] = a.x, out[1] = a.y, out[2] = a.z, out[3] = a.w, out[4] = b.x, out[5] = b.y, out[6] = b.z, out[7] = b.w;
 }
 
-__device__ __forceinline__ float hw_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ float other_half(float x) { return __shfl_xor(x, 32, 64); }
-
 // lane half h stores values 4h..4h+3 of its row's 8 results (both halves hold all 8 after the merge); fp16: rounded to nearest
 // even once, overflow to inf
 __device__ __forceinline__ void store_half_row(_Float16 *p, const float v[8], int h) {
@@ -160,6 +150,58 @@ __device__ __forceinline__ void store_half_row(float *p, const float v[8], int h
 
 __device__ __forceinline__ int64_t row_offset(int b, int N, int n, int H, int hd) { return (((int64_t)b * N + n) * H + hd) * 8; }
 
+// where query i's lse sits, (B, H, Nq); the grid is (tiles of own rows, H, B) in every kernel
+__device__ __forceinline__ int64_t lse_index(int Nq, int H, int i) { return ((int64_t)blockIdx.z * H + blockIdx.y) * Nq + i; }
+
+// A lane's own row of the N its kernel keeps results for: lane half h, index i, whether it exists, and its offset (row 0's where it
+// does not, so that the address is always one of the tensor's)
+struct OwnRow {
+    int lane, h, i;
+    bool ok;
+    int64_t off;
+};
+__device__ __forceinline__ OwnRow own_row(int N, int H) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = (blockIdx.x * 4 + wave) * 32 + (lane & 31);
+    return {lane, lane >> 5, i, i < N, row_offset(blockIdx.z, N, i < N ? i : 0, H, blockIdx.y)};
+}
+
+// The loop every kernel runs over the N rows of the side that streams past, kChunk at a time: stage(first_half, row, n, offset, ok)
+// once per thread puts row n of the tensors (slot `row` of the chunk; threads 0..127 are first_half and stage one tensor, 128..255
+// the other; !ok: n is past the end, offset is row 0's and zeros are staged) into the kernel's own LDS images, then tile(t, left)
+// runs for each 32-row tile t that has a row below left = the rows remaining from the chunk's start.  The tile loop stays rolled.
+// (The kernels' tile lambdas take lane and h by value: captured by reference, every kernel's tile loop comes out a few address
+// instructions longer, which measured 1 % at N = 1600.)
+template <typename Stage, typename Tile>
+__device__ __forceinline__ void stream_rows(int N, int H, Stage stage, Tile tile) {
+    const int tid = threadIdx.x, hd = blockIdx.y, b = blockIdx.z;
+    for (int n0 = 0; n0 < N; n0 += kChunk) {
+        __syncthreads();  // the previous chunk has been consumed
+        {
+            const int row = tid & (kChunk - 1), n = n0 + row;
+            const bool ok = n < N;
+            if (tid < kChunk)  // (one call per half, each forming its offset: see the note at the forward's store)
+                stage(true, row, n, row_offset(b, N, ok ? n : 0, H, hd), ok);
+            else
+                stage(false, row, n, row_offset(b, N, ok ? n : 0, H, hd), ok);
+        }
+        __syncthreads();
+        const int left = N - n0, ntile = left >= kChunk ? kChunk / 32 : (left + 31) / 32;
+#pragma unroll 1
+        for (int t = 0; t < ntile; ++t) tile(t, left);
+    }
+}
+
+// The backward's weight of one score, recomputed from the forward's lse.  The order is the forward's: the scaled score is rounded
+// once, fl(s * scale), exactly as the forward rounded it before taking the maximum, and lse is in those units, so where one key
+// holds a row's weight the difference is exactly 0 and P exactly 1; log2e multiplies afterwards (folding it into scale and lse is
+// three roundings at the score's magnitude instead of a cancelling one: 2.4x the fp32 bound on dV).  A row past the end weighs
+// exactly zero, and the exponential is evaluated for every row and then selected: `in_range ? exp2(..) : 0` is compiled as a branch
+// per row, which cost 256 VGPRs and all but one wave per SIMD.
+__device__ __forceinline__ float prob(float s, float scale, float lse, bool in_range) {
+    const float e = hw_exp2((s * scale - lse) * kLog2e);
+    return in_range ? e : 0.f;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // forward: own = queries, streamed = keys (K as the A operand: S^T = K Q^T; V as fp32 rows)
 template <typename T>
@@ -168,33 +210,26 @@ __global__ __launch_bounds__(kThreads) void cross_attn_fwd_kernel(const T *__res
                                                                   float scale) {
     __shared__ OpImg<T> kop;
     __shared__ alignas(16) float vrow[kRowImg];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
-    const int hd = blockIdx.y, b = blockIdx.z;
-    const int qi = (blockIdx.x * 4 + wave) * 32 + (lane & 31);
-    const bool qok = qi < Nq;
-    const Frag<T> qf = frag_of(load_row(q + row_offset(b, Nq, qok ? qi : 0, H, hd), qok), h);
+    const OwnRow own = own_row(Nq, H);
+    const int lane = own.lane, h = own.h;
+    const Frag<T> qf = frag_of(load_row(q + own.off, own.ok), h);
 
     float m = -INFINITY, l = 0.f, o[8];
 #pragma unroll
     for (int d = 0; d < 8; ++d) o[d] = 0.f;
 
-    for (int k0 = 0; k0 < Nk; k0 += kChunk) {
-        __syncthreads();  // the previous chunk has been consumed
-        {
-            const int row = tid & (kChunk - 1), key = k0 + row;
-            const bool ok = key < Nk;
-            if (tid < kChunk)
-                kop.put(row, load_row(k + row_offset(b, Nk, ok ? key : 0, H, hd), ok));
+    stream_rows(
+        Nk, H,
+        [&](bool first, int row, int, int64_t off, bool ok) {
+            if (first)
+                kop.put(row, load_row(k + off, ok));
             else
-                put_row(vrow, row, load_row(v + row_offset(b, Nk, ok ? key : 0, H, hd), ok));
-        }
-        __syncthreads();
-        const int left = Nk - k0, ntile = left >= kChunk ? kChunk / 32 : (left + 31) / 32;
-#pragma unroll 1
-        for (int t = 0; t < ntile; ++t) {
+                put_row(vrow, row, load_row(v + off, ok));
+        },
+        [&, lane, h](int t, int left) {
             const f32x16 s = dot8(kop.get(t, lane), qf);
             // scaled scores are rounded once, as the definition's `s * scale` is, and maximum and lse are kept in those units: the
-            // backward forms the same rounded score, so where one key holds a row's weight score - lse is exactly 0 and P exactly 1
+            // backward forms the same rounded score (prob), so where one key holds a row's weight score - lse is exactly 0 and P exactly 1
             float tv[16], mx = m;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -209,8 +244,9 @@ __global__ __launch_bounds__(kThreads) void cross_attn_fwd_kernel(const T *__res
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = t * 32 + acc_row(r, h);
-                // a key past the end weighs exactly zero: selected, not pushed below a sentinel
-                const float e = hw_exp2((tv[r] - mx) * kLog2e);  // (evaluated for every row and selected: `ok ? exp2(..) : 0` is a branch per row)
+                // a key past the end weighs exactly zero: selected, not pushed below a sentinel, and evaluated for every row first (see
+                // prob, the backward's form of this weight)
+                const float e = hw_exp2((tv[r] - mx) * kLog2e);
                 const float p = row < left ? e : 0.f;
                 float vr[8];
                 get_row(vrow, row, vr);
@@ -219,8 +255,7 @@ __global__ __launch_bounds__(kThreads) void cross_attn_fwd_kernel(const T *__res
                 for (int d = 0; d < 8; ++d) o[d] = fmaf(p, vr[d], o[d]);
             }
             m = mx;
-        }
-    }
+        });
     // merge the two lane halves of a query
     const float M = fmaxf(m, other_half(m));
     const float a = (m == -INFINITY) ? 0.f : hw_exp2((m - M) * kLog2e);
@@ -232,9 +267,11 @@ __global__ __launch_bounds__(kThreads) void cross_attn_fwd_kernel(const T *__res
         o[d] += other_half(o[d]);
         o[d] = o[d] / l;
     }
-    if (qok) {
-        store_half_row(out + row_offset(b, Nq, qi, H, hd), o, h);
-        if (h == 0) lse[((int64_t)b * H + hd) * Nq + qi] = fmaf(log2f(l), kLn2, M);
+    if (own.ok) {
+        // The offset is formed again here, and stream_rows forms the staged row's once per thread half: with own.off held across the
+        // loop, or with one offset shared by the two halves, the fp32 instantiation takes 114 to 125 VGPRs and loses a wave per SIMD.
+        store_half_row(out + row_offset(blockIdx.z, Nq, own.i, H, blockIdx.y), o, h);
+        if (h == 0) lse[lse_index(Nq, H, own.i)] = fmaf(log2f(l), kLn2, M);
     }
 }
 
@@ -257,44 +294,33 @@ __global__ __launch_bounds__(kThreads) void cross_attn_bwd_delta_kernel(const T 
                                                                         const T *__restrict__ dout, T *__restrict__ dq, int Nq, int Nk,
                                                                         int H, float scale) {
     __shared__ OpImg<T> kop, vop;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
-    const int hd = blockIdx.y, b = blockIdx.z;
-    const int qi = (blockIdx.x * 4 + wave) * 32 + (lane & 31);
-    const bool qok = qi < Nq;
-    const int64_t qoff = row_offset(b, Nq, qok ? qi : 0, H, hd);
-    const Frag<T> qf = frag_of(load_row(q + qoff, qok), h);
-    const Frag<T> dof = frag_of(load_row(dout + qoff, qok), h);
-    const float lse_q = qok ? lse[((int64_t)b * H + hd) * Nq + qi] : 0.f;
+    const OwnRow own = own_row(Nq, H);
+    const int lane = own.lane, h = own.h;
+    const Frag<T> qf = frag_of(load_row(q + own.off, own.ok), h);
+    const Frag<T> dof = frag_of(load_row(dout + own.off, own.ok), h);
+    const float lse_q = own.ok ? lse[lse_index(Nq, H, own.i)] : 0.f;
     float acc = 0.f, psum = 0.f;
-    for (int k0 = 0; k0 < Nk; k0 += kChunk) {
-        __syncthreads();
-        {
-            const int row = tid & (kChunk - 1), key = k0 + row;
-            const bool ok = key < Nk;
-            const int64_t off = row_offset(b, Nk, ok ? key : 0, H, hd);
-            if (tid < kChunk)
+    stream_rows(
+        Nk, H,
+        [&](bool first, int row, int, int64_t off, bool ok) {
+            if (first)
                 kop.put(row, load_row(k + off, ok));
             else
                 vop.put(row, load_row(v + off, ok));
-        }
-        __syncthreads();
-        const int left = Nk - k0, ntile = left >= kChunk ? kChunk / 32 : (left + 31) / 32;
-#pragma unroll 1
-        for (int t = 0; t < ntile; ++t) {
+        },
+        [&, lane, h](int t, int left) {
             const f32x16 s = dot8(kop.get(t, lane), qf);
             const f32x16 dp = dot8(vop.get(t, lane), dof);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float e = hw_exp2((s[r] * scale - lse_q) * kLog2e);
-                const float p = t * 32 + acc_row(r, h) < left ? e : 0.f;
+                const float p = prob(s[r], scale, lse_q, t * 32 + acc_row(r, h) < left);
                 psum += p;
                 acc = fmaf(p, dp[r], acc);
             }
-        }
-    }
+        });
     acc += other_half(acc);
     psum += other_half(psum);
-    if (qok && h == 0) *delta_slot(dq + qoff) = acc / psum;
+    if (own.ok && h == 0) *delta_slot(dq + own.off) = acc / psum;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -306,58 +332,47 @@ __global__ __launch_bounds__(kThreads) void cross_attn_bwd_dq_kernel(const T *__
                                                                      const T *__restrict__ dout, T *dq, int Nq, int Nk, int H, float scale) {
     __shared__ OpImg<T> kop, vop;
     __shared__ alignas(16) float krow[kRowImg];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
-    const int hd = blockIdx.y, b = blockIdx.z;
-    const int qi = (blockIdx.x * 4 + wave) * 32 + (lane & 31);
-    const bool qok = qi < Nq;
-    const int64_t qoff = row_offset(b, Nq, qok ? qi : 0, H, hd);
-    const Frag<T> qf = frag_of(load_row(q + qoff, qok), h);
-    const Frag<T> dof = frag_of(load_row(dout + qoff, qok), h);
-    const float delta = qok ? *delta_slot(dq + qoff) : 0.f;  // both lane halves of the row read it; the row is stored after the loop
-    const float lse_q = qok ? lse[((int64_t)b * H + hd) * Nq + qi] : 0.f;
+    const OwnRow own = own_row(Nq, H);
+    const int lane = own.lane, h = own.h;
+    const Frag<T> qf = frag_of(load_row(q + own.off, own.ok), h);
+    const Frag<T> dof = frag_of(load_row(dout + own.off, own.ok), h);
+    const float delta = own.ok ? *delta_slot(dq + own.off) : 0.f;  // both lane halves of the row read it; the row is stored after the loop
+    const float lse_q = own.ok ? lse[lse_index(Nq, H, own.i)] : 0.f;
 
     float g[8];
 #pragma unroll
     for (int d = 0; d < 8; ++d) g[d] = 0.f;
 
-    for (int k0 = 0; k0 < Nk; k0 += kChunk) {
-        __syncthreads();
-        {
-            const int row = tid & (kChunk - 1), key = k0 + row;
-            const bool ok = key < Nk;
-            if (tid < kChunk) {
-                const Row<T> kr = load_row(k + row_offset(b, Nk, ok ? key : 0, H, hd), ok);
+    stream_rows(
+        Nk, H,
+        [&](bool first, int row, int, int64_t off, bool ok) {
+            if (first) {
+                const Row<T> kr = load_row(k + off, ok);
                 kop.put(row, kr);
                 put_row(krow, row, kr);
             } else {
-                vop.put(row, load_row(v + row_offset(b, Nk, ok ? key : 0, H, hd), ok));
+                vop.put(row, load_row(v + off, ok));
             }
-        }
-        __syncthreads();
-        const int left = Nk - k0, ntile = left >= kChunk ? kChunk / 32 : (left + 31) / 32;
-#pragma unroll 1
-        for (int t = 0; t < ntile; ++t) {
+        },
+        [&, lane, h](int t, int left) {
             const f32x16 s = dot8(kop.get(t, lane), qf);
             const f32x16 dp = dot8(vop.get(t, lane), dof);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = t * 32 + acc_row(r, h);
-                const float e = hw_exp2((s[r] * scale - lse_q) * kLog2e);  // (evaluated for every row and selected: `ok ? exp2(..) : 0` is a branch per row)
-                const float p = row < left ? e : 0.f;
-                const float ds = p * (dp[r] - delta);
+                const float ds = prob(s[r], scale, lse_q, row < left) * (dp[r] - delta);
                 float kr[8];
                 get_row(krow, row, kr);
 #pragma unroll
                 for (int d = 0; d < 8; ++d) g[d] = fmaf(ds, kr[d], g[d]);
             }
-        }
-    }
+        });
 #pragma unroll
     for (int d = 0; d < 8; ++d) {
         g[d] += other_half(g[d]);
         g[d] *= scale;
     }
-    if (qok) store_half_row(dq + qoff, g, h);
+    if (own.ok) store_half_row(dq + own.off, g, h);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -373,49 +388,38 @@ __global__ __launch_bounds__(kThreads) void cross_attn_bwd_dkv_kernel(const T *_
     __shared__ alignas(16) float qrow[kRowImg];
     __shared__ alignas(16) float dorow[kRowImg];
     __shared__ float lses[kChunk], deltas[kChunk];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
-    const int hd = blockIdx.y, b = blockIdx.z;
-    const int ki = (blockIdx.x * 4 + wave) * 32 + (lane & 31);
-    const bool kok = ki < Nk;
-    const int64_t koff = row_offset(b, Nk, kok ? ki : 0, H, hd);
-    const Frag<T> kf = frag_of(load_row(k + koff, kok), h);
-    const Frag<T> vf = frag_of(load_row(v + koff, kok), h);
+    const OwnRow own = own_row(Nk, H);
+    const int lane = own.lane, h = own.h;
+    const Frag<T> kf = frag_of(load_row(k + own.off, own.ok), h);
+    const Frag<T> vf = frag_of(load_row(v + own.off, own.ok), h);
 
     float gk[8], gv[8];
 #pragma unroll
     for (int d = 0; d < 8; ++d) gk[d] = gv[d] = 0.f;
 
-    for (int q0 = 0; q0 < Nq; q0 += kChunk) {
-        __syncthreads();
-        {
-            const int row = tid & (kChunk - 1), qi = q0 + row;
-            const bool ok = qi < Nq;
-            const int64_t off = row_offset(b, Nq, ok ? qi : 0, H, hd);
-            if (tid < kChunk) {
+    stream_rows(
+        Nq, H,
+        [&](bool first, int row, int qi, int64_t off, bool ok) {
+            if (first) {
                 const Row<T> qr = load_row(q + off, ok);
                 qop.put(row, qr);
                 put_row(qrow, row, qr);
-                lses[row] = ok ? lse[((int64_t)b * H + hd) * Nq + qi] : 0.f;
+                lses[row] = ok ? lse[lse_index(Nq, H, qi)] : 0.f;
             } else {
                 const Row<T> dor = load_row(dout + off, ok);
                 doop.put(row, dor);
                 put_row(dorow, row, dor);
                 deltas[row] = ok ? *reinterpret_cast<const float *>(dq + off) : 0.f;
             }
-        }
-        __syncthreads();
-        const int left = Nq - q0, ntile = left >= kChunk ? kChunk / 32 : (left + 31) / 32;
-#pragma unroll 1
-        for (int t = 0; t < ntile; ++t) {
+        },
+        [&, lane, h](int t, int left) {
             const f32x16 s = dot8(qop.get(t, lane), kf);
             const f32x16 dp = dot8(doop.get(t, lane), vf);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = t * 32 + acc_row(r, h);
-                const float lq = lses[row], dl = deltas[row];
-                const float e = hw_exp2((s[r] * scale - lq) * kLog2e);
-                const float p = row < left ? e : 0.f;
-                const float ds = p * (dp[r] - dl);
+                const float p = prob(s[r], scale, lses[row], row < left);
+                const float ds = p * (dp[r] - deltas[row]);
                 float qr[8], dr[8];
                 get_row(qrow, row, qr);
                 get_row(dorow, row, dr);
@@ -425,17 +429,16 @@ __global__ __launch_bounds__(kThreads) void cross_attn_bwd_dkv_kernel(const T *_
                     gk[d] = fmaf(ds, qr[d], gk[d]);
                 }
             }
-        }
-    }
+        });
 #pragma unroll
     for (int d = 0; d < 8; ++d) {
         gv[d] += other_half(gv[d]);
         gk[d] += other_half(gk[d]);
         gk[d] *= scale;
     }
-    if (kok) {
-        store_half_row(dk + koff, gk, h);
-        store_half_row(dv + koff, gv, h);
+    if (own.ok) {
+        store_half_row(dk + own.off, gk, h);
+        store_half_row(dv + own.off, gv, h);
     }
 }
 
@@ -451,6 +454,13 @@ int check_args(const char *what, int dtype, int B, int Nq, int Nk, int H, int D,
         if ((uintptr_t)p & 15) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: tensors must be 16-byte aligned (rows are read as one vector)", what);
     }
     return GFN_OK;
+}
+
+template <typename T>
+int launch_fwd(const void *q, const void *k, const void *v, void *out, float *lse, int B, int Nq, int Nk, int H, float scale, hipStream_t s) {
+    hipLaunchKernelGGL(cross_attn_fwd_kernel<T>, dim3((Nq + kOwn - 1) / kOwn, H, B), dim3(kThreads), 0, s, (const T *)q, (const T *)k,
+                       (const T *)v, (T *)out, lse, Nq, Nk, H, scale);
+    return gfn::check_launch("cross_attn_fwd_kernel");
 }
 
 // delta pass -> dK, dV pass -> dQ pass, in that order: delta travels in dq (see cross_attn_bwd_delta_kernel)
@@ -478,14 +488,8 @@ GFN_EXPORT int gfn_cross_attn_fwd(const void *q, const void *k, const void *v, i
     if (B == 0 || Nq == 0) return GFN_OK;
     if (!lse || ((uintptr_t)lse & 3)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: lse missing or not 4-byte aligned", what);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((Nq + kOwn - 1) / kOwn, H, B);
-    if (dtype == GFN_F16)
-        hipLaunchKernelGGL(cross_attn_fwd_kernel<_Float16>, grid, dim3(kThreads), 0, s, (const _Float16 *)q, (const _Float16 *)k,
-                           (const _Float16 *)v, (_Float16 *)out, lse, Nq, Nk, H, scale);
-    else
-        hipLaunchKernelGGL(cross_attn_fwd_kernel<float>, grid, dim3(kThreads), 0, s, (const float *)q, (const float *)k, (const float *)v,
-                           (float *)out, lse, Nq, Nk, H, scale);
-    return gfn::check_launch("cross_attn_fwd_kernel");
+    return dtype == GFN_F16 ? launch_fwd<_Float16>(q, k, v, out, lse, B, Nq, Nk, H, scale, s)
+                            : launch_fwd<float>(q, k, v, out, lse, B, Nq, Nk, H, scale, s);
 }
 
 GFN_EXPORT int gfn_cross_attn_bwd(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *dout, int dtype,

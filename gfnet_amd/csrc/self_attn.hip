@@ -9,17 +9,15 @@
 // rounded to fp16, are the fragment of k-step s, with no trip through LDS.  Inside such a step the k order is permuted -- element j
 // of lane half h is key 16s + 8(j >> 2) + 4h + (j & 3) of the tile -- so the V^T fragment is gathered in that same order
 // (vt_frag); tests/test_self_attn_gpu.py::test_layout_exact fails for any other order.
-#include <hip/hip_fp16.h>
-
 #include <climits>
-#include <cmath>
 
-#include "common.h"
+#include "attn_common.h"
 
 namespace {
 
 using gfn::acc_row;
 using gfn::f32x16;
+using namespace gfn::attn;
 
 constexpr int kD = 64;         // head dim: four k-steps of v_mfma_f32_32x32x16_f16 per score tile
 constexpr int kThreads = 256;  // 4 waves, 32 queries each
@@ -29,13 +27,6 @@ constexpr int kChunk = 64;     // keys staged per step (2 tiles)
 // bytes moves consecutive keys 36 banks on, so 16 lanes' reads cover all 64 banks once.  V^T rows (read as 8 bytes at
 // [d][key 16s + 4h] and + 8): 136 bytes moves consecutive d 34 banks on, 32 lanes' reads cover 64 banks once.
 constexpr int kKPitch = 72, kVPitch = 68;
-constexpr float kLog2e = 1.4426950408889634f;
-
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float hw_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float other_half(float x) { return __shfl_xor(x, 32, 64); }
 
 // the 16-byte piece of a staged chunk that piece index p (0..511) names: key p >> 3 of the chunk, values 8 (p & 7) ...
 __device__ __forceinline__ h8 load_piece(const _Float16 *__restrict__ base, int64_t token_stride, int key0, int N, int p) {

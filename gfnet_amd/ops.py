@@ -133,12 +133,18 @@ def reference_cross_attention(q, k, v, scale):
     return torch.einsum("bhij,bjhd->bihd", torch.softmax(s, dim=-1), v)
 
 
-def _cross_attn_args(what, *tensors):
-    """The tensors as the kernels read them (contiguous, 16-byte aligned, one dtype: fp16 or fp32) and the dtype code."""
+_F16_F32 = (torch.float16, torch.float32)
+
+
+def _attn_args(what, names, allowed, *tensors):
+    """The tensors as the attention kernels read them (contiguous, 16-byte aligned, one dtype out of `allowed`) and the dtype code."""
     dev = require_gpu(*tensors)
-    dtypes = {t.dtype for t in tensors}
-    if len(dtypes) != 1 or tensors[0].dtype not in (torch.float16, torch.float32):
-        raise TypeError(f"{what}: q, k and v must share one dtype, float16 or float32, got {sorted(str(d) for d in dtypes)}")
+    dtypes = sorted({str(t.dtype) for t in tensors})
+    if len(dtypes) != 1 or tensors[0].dtype not in allowed:
+        want = " or ".join(str(d).replace("torch.", "") for d in allowed)
+        if len(tensors) == 1:
+            raise TypeError(f"{what}: {names} must be {want}, got {dtypes[0]}")
+        raise TypeError(f"{what}: {names} must share one dtype, {want}, got {dtypes}")
     out = []
     for t in tensors:
         t = t.contiguous()
@@ -150,7 +156,7 @@ def cross_attention_fwd(q, k, v, scale):
     """The forward launch (gfn_cross_attn_fwd): returns (out, lse, q, k, v) with q, k, v as the kernel read them; lse (B,H,Nq) fp32."""
     if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2:] != k.shape[2:]:
         raise ValueError(f"cross_attention: q (B,Nq,H,D) and k, v (B,Nk,H,D) expected, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
-    dev, (q, k, v), dt = _cross_attn_args("cross_attention", q, k, v)
+    dev, (q, k, v), dt = _attn_args("cross_attention", "q, k and v", _F16_F32, q, k, v)
     B, Nq, H, D = q.shape
     Nk = k.shape[1]
     out = torch.empty_like(q)
@@ -163,7 +169,7 @@ def cross_attention_fwd(q, k, v, scale):
 def cross_attention_bwd(q, k, v, out, lse, dout, scale):
     """(dq, dk, dv) of cross_attention given dout = dL/dout and the forward's out and lse (gfn_cross_attn_bwd): no atomics, so two
     calls give the same bits; in fp16 the results are rounded once and overflow to inf."""
-    dev, (q, k, v, out, dout), dt = _cross_attn_args("cross_attention_bwd", q, k, v, out, dout)
+    dev, (q, k, v, out, dout), dt = _attn_args("cross_attention_bwd", "q, k and v", _F16_F32, q, k, v, out, dout)
     B, Nq, H, D = q.shape
     Nk = k.shape[1]
     if dout.shape != q.shape or out.shape != q.shape or tuple(lse.shape) != (B, H, Nq):
@@ -217,17 +223,12 @@ def self_attention(qkv, scale):
     (B,N,H,64) fp16 = softmax(scale * q k^T) v per batch and head, so `out.reshape(B, N, C)` feeds proj (gfn_self_attn_fwd: one
     launch, nothing N x N written).  Forward only, no autograd.  CPU tensors raise: reference_self_attention is the definition for
     every device, this is the product path."""
-    dev = require_gpu(qkv)
     if qkv.dim() != 5 or qkv.shape[2] != 3:
         raise ValueError(f"self_attention: qkv (B,N,3,H,D) expected, got {tuple(qkv.shape)}")
-    if qkv.dtype != torch.float16:
-        raise TypeError(f"self_attention: qkv must be float16, got {qkv.dtype}")
-    qkv = qkv.contiguous()
-    if qkv.data_ptr() % 16:
-        qkv = qkv.clone()
+    dev, (qkv,), dt = _attn_args("self_attention", "qkv", (torch.float16,), qkv)
     B, N, _, H, D = qkv.shape
     out = torch.empty((B, N, H, D), device=dev, dtype=torch.float16)
-    _timed("self_attn_fwd", lambda: _L().gfn_self_attn_fwd(ptr(qkv), _lib.GFN_F16, B, N, H, D, float(scale), ptr(out), stream_ptr(dev)))
+    _timed("self_attn_fwd", lambda: _L().gfn_self_attn_fwd(ptr(qkv), dt, B, N, H, D, float(scale), ptr(out), stream_ptr(dev)))
     return out
 
 

@@ -48,8 +48,9 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "g14_crossview_decoder.npz")
 DEV = "cuda"
 
 # (B, Nq, Nk, H) at D = 8: one exact tile; tails on both axes with an odd head count; one query and one key past a boundary;
-# smaller than a tile (the golden's grid); one key (out = v); and the 560 pass: 50 key tiles of rescaling
-SMALL = [(1, 32, 32, 1), (2, 40, 77, 3), (1, 129, 33, 8), (2, 30, 30, 8), (1, 5, 1, 2)]
+# smaller than a tile (the golden's grid); one key (out = v); keys over two staged chunks, the second with two tiles of which the last
+# holds one key (lane half 1 meets nothing there) and queries one tile plus one row; and the 560 pass: 50 key tiles of rescaling
+SMALL = [(1, 32, 32, 1), (2, 40, 77, 3), (1, 129, 33, 8), (2, 30, 30, 8), (1, 5, 1, 2), (1, 33, 161, 2)]
 BIG = (1, 1600, 1600, 8)
 FAMILIES = ("normal", "spread60", "max_last", "max_first", "dominant", "scale0")
 NAMES = ("out", "lse", "dq", "dk", "dv")
