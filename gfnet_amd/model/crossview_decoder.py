@@ -13,9 +13,15 @@ dropout 0.  Parameter names are the reference's, so the `dino_decoder.*` entries
 
 The reference's attention calls flash_attn_func, which is absent on this platform (attention.py:230-231 then raises);
 here it is ops.cross_attention (csrc/cross_attn.hip), and both directions of a block -- x attending to y and y to x, with the same
-weights (crossview_decoder_light.py:53-54) -- are ONE launch on the concatenated batch.  Linear layers, LayerNorm and the MLP stay
-torch.  attn_impl="torch" routes the core through ops.reference_cross_attention instead: the same module on any device and dtype,
-which is how the tests run it in float64 on the CPU.
+weights (crossview_decoder_light.py:53-54) -- are ONE launch on the concatenated batch.  attn_impl="torch" routes the core through
+ops.reference_cross_attention instead: the same module on any device and dtype, which is how the tests run it in float64 on the CPU.
+
+block_impl="torch" (the default) leaves the linear layers, LayerNorm and the MLP of a block to torch.  block_impl="hip" runs a block
+in inference under fp16 autocast as three launches on the concatenated residual stream: ops.decoder_qkv (norm1 and the q, k, v
+projections, csrc/decoder_block.hip), ops.cross_attention, ops.decoder_post (output projection, both LayerScales and residual adds,
+norm2 and the MLP); the entry projection and the position encoding stay torch.  Whatever that path is not built for -- train(),
+tensors off the GPU, no fp16 autocast, parameters that are not fp32, attn_impl="torch", anything that requires grad -- runs the
+torch blocks, exactly as block_impl="torch" does.
 """
 import math
 
@@ -25,6 +31,7 @@ import torch.nn as nn
 from .. import ops
 
 ATTN_IMPLS = ("hip", "torch")
+BLOCK_IMPLS = ("torch", "hip")
 MAX_SHAPE = (128, 128)  # crossview_decoder_light.py:37: the extent the position encoding normalises to
 
 
@@ -104,6 +111,19 @@ class CrossBlock(nn.Module):
         x = x + self.ls1(self.attn(self.norm1(x), kv))
         return x + self.ls2(self.mlp(self.norm2(x)))
 
+    def forward_fused(self, X):
+        """The block on the residual stream X = cat(x, y), (2B, N, dim) fp32, updated in place: both directions in three launches,
+        in the fp16 autocast class (CrossViewDecoder._fused says when)."""
+        attn, N = self.attn, X.shape[1]
+        q, k, v = ops.decoder_qkv(X, self.norm1.weight, self.norm1.bias, self.norm1.eps, attn.q_proj.weight, attn.k_proj.weight,
+                                  attn.v_proj.weight)
+        scale = attn.scale if attn.softmax_scale is None else attn.scale * math.log(N, attn.train_avg_length)
+        # (init_values None: no LayerScale, a gamma of 1)
+        gamma1, gamma2 = (ls.gamma if isinstance(ls, LayerScale) else torch.ones_like(self.norm1.weight) for ls in (self.ls1, self.ls2))
+        return ops.decoder_post(X, ops.cross_attention(q, k, v, scale), attn.proj.weight, attn.proj.bias, gamma1, self.norm2.weight,
+                                self.norm2.bias, self.norm2.eps, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight,
+                                self.mlp.fc2.bias, gamma2, inplace=True)
+
 
 def _check_cfg(cfg):
     """Raise, naming the key, for every setting of decoder_cfg whose reference behaviour is not built here."""
@@ -122,14 +142,16 @@ class CrossViewDecoder(nn.Module):
     """`decoder(x, y, vit_shape=(B, _, H, W)) -> (map_x, map_y)`: ViT patch tokens (B, H*W, d_model) of the two views -> their
     stride-16 feature maps (B, out_dim, H, W), out_dim = conf["encoder_cfg"]["feat_chs"][0] (64: 8 heads of dim 8)."""
 
-    def __init__(self, conf, attn_impl="hip"):
+    def __init__(self, conf, attn_impl="hip", block_impl="torch"):
         super().__init__()
         if attn_impl not in ATTN_IMPLS:
             raise ValueError(f"attn_impl must be one of {ATTN_IMPLS}, got {attn_impl!r}")
+        if block_impl not in BLOCK_IMPLS:
+            raise ValueError(f"block_impl must be one of {BLOCK_IMPLS}, got {block_impl!r}")
         cfg = conf["dino_cfg"]["decoder_cfg"]
         _check_cfg(cfg)
         dim = conf["encoder_cfg"]["feat_chs"][0]
-        self.dim, self.attn_impl = dim, attn_impl
+        self.dim, self.attn_impl, self.block_impl = dim, attn_impl, block_impl
         self.cross_attn_blocks = nn.ModuleList(
             CrossBlock(dim, cfg["nhead"], cfg.get("init_values"), cfg.get("softmax_scale"), cfg.get("train_avg_length"), attn_impl)
             for _ in range(cfg["num_cross_attn"]))
@@ -142,13 +164,33 @@ class CrossViewDecoder(nn.Module):
             self._pe[key] = sine_position_encoding(self.dim, H, W).flatten(2).transpose(1, 2).contiguous().to(device)
         return self._pe[key]
 
+    def _fused(self, x, y):
+        """Whether this call takes the fused blocks: block_impl="hip" with the HIP attention, inference (eval() and nothing that
+        requires grad) on CUDA tensors under fp16 autocast with fp32 parameters -- the class decoder_block.hip is written in."""
+        if self.block_impl != "hip" or self.attn_impl != "hip" or self.training or not (x.is_cuda and y.is_cuda):
+            return False
+        if self.dim != ops.DECODER_DIM or any(b.attn.num_heads * 8 != self.dim for b in self.cross_attn_blocks):  # (the one width it is built for)
+            return False
+        if not torch.is_autocast_enabled("cuda") or torch.get_autocast_dtype("cuda") != torch.float16:
+            return False
+        if any(p.dtype != torch.float32 or not p.is_cuda for p in self.parameters()):
+            return False
+        return not (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad or any(p.requires_grad for p in self.parameters())))
+
     def forward(self, x, y, vit_shape=None):
         B, _, H, W = vit_shape
         pe = self.position_encoding(H, W, x.device)
         if x.dtype == torch.float64:
             pe = pe.double()
+        fused = self._fused(x, y)
         x, y = self.proj(x) + pe, self.proj(y) + pe
-        for blk in self.cross_attn_blocks:
-            # x against y and y against x with the same weights (crossview_decoder_light.py:53-54), as one batch of 2B
-            x, y = blk(torch.cat((x, y)), torch.cat((y, x))).chunk(2)
+        if fused and x.dtype == torch.float32:  # (fp16 projection + fp32 encoding: the residual stream is fp32 under autocast)
+            X = torch.cat((x, y))  # the one concatenation: k and v change sides inside decoder_qkv
+            for blk in self.cross_attn_blocks:
+                blk.forward_fused(X)
+            x, y = X.chunk(2)
+        else:
+            for blk in self.cross_attn_blocks:
+                # x against y and y against x with the same weights (crossview_decoder_light.py:53-54), as one batch of 2B
+                x, y = blk(torch.cat((x, y)), torch.cat((y, x))).chunk(2)
         return (x.reshape(B, H, W, -1).permute(0, 3, 1, 2), y.reshape(B, H, W, -1).permute(0, 3, 1, 2))

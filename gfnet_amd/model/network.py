@@ -331,7 +331,8 @@ class GFNet(nn.Module):
             from ..reference_backbone import reference_backbone
 
             # GFNET_COMPAT_DECODER=hip: the native cross-view decoder (model/crossview_decoder.py) in place of the checkout's, whose
-            # shipped attention type needs flash_attn; unset: the checkout's class, as before
+            # shipped attention type needs flash_attn (hip_fused: the same with its blocks fused around the attention in fp16 eval());
+            # unset: the checkout's class, as before
             # GFNET_COMPAT_FPN=hip: the native FPN encoder, merge layer and decoder (model/fpn.py) in place of the checkout's
             # `model.FPN`, one fused launch per layer in eval(); unset: the checkout's classes, as before
             # GFNET_COMPAT_DINO=hip: the native DINOv2 ViT (model/dinov2.py) in place of the checkout's `model.transformer`, attention

@@ -265,6 +265,85 @@ def ls_add_layernorm(x, y, gamma, weight, bias, eps, inplace=False):
     return (x if y is None else x_out), h
 
 
+DECODER_DIM, DECODER_HIDDEN = 64, 256  # the width and hidden width decoder_qkv and decoder_post are built for (8 heads of 8)
+
+
+def _decoder_args(what, tensors, shapes):
+    """The named tensors as the decoder-block kernels read them: CUDA, contiguous, the dtype and shape listed in `shapes`
+    (name -> (dtype, shape)), 16-byte aligned (a misaligned parameter view is copied); no autograd."""
+    dev = require_gpu(*tensors.values())
+    out = {}
+    for name, t in tensors.items():
+        dtype, shape = shapes[name]
+        if t.dtype != dtype:
+            raise TypeError(f"{what}: {name} must be {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what}: {name} must be {tuple(shape)}, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if torch.is_grad_enabled() and t.requires_grad:
+            raise RuntimeError(f"{what}: {name} requires grad, and this op is forward only (inference; call it under torch.no_grad())")
+        t = t.detach()
+        out[name] = t.clone() if t.data_ptr() % 16 else t
+    return dev, out
+
+
+def decoder_qkv(X, norm_weight, norm_bias, eps, wq, wk, wv):
+    """What a cross-view decoder block does before its attention, in one launch (gfn_decoder_qkv_fwd; reference
+    model/transformer/layers/block.py:327 and attention.py:236-238) in the fp16 autocast class:
+
+        q = wq . fp16(LayerNorm(X))        k = wk . fp16(X)        v = wv . fp16(X)        each rounded to fp16 once
+
+    X (2B, N, 64) fp32, the residual stream cat(x, y) of both views; norm_weight, norm_bias (64) and wq, wk, wv (64, 64) fp32 as the
+    module stores them.  Returns q, k, v (2B, N, 8, 8) fp16 for ops.cross_attention, with k and v of batch entry b written at
+    (b + B) mod 2B: every view's queries meet the OTHER view's keys, without the concatenated copy.  Contiguous CUDA tensors, the
+    current stream, forward only: raises if grad mode is on and an input requires grad."""
+    what, C = "decoder_qkv", DECODER_DIM
+    if X.dim() != 3 or X.shape[0] % 2 or X.shape[1] < 1:
+        raise ValueError(f"{what}: X must be (2B, N, {C}) with an even batch and N >= 1, got {tuple(X.shape)}")
+    f32 = torch.float32
+    dev, t = _decoder_args(what, {"X": X, "norm_weight": norm_weight, "norm_bias": norm_bias, "wq": wq, "wk": wk, "wv": wv},
+                           {"X": (f32, (X.shape[0], X.shape[1], C)), "norm_weight": (f32, (C,)), "norm_bias": (f32, (C,)),
+                            "wq": (f32, (C, C)), "wk": (f32, (C, C)), "wv": (f32, (C, C))})
+    B2, N = X.shape[:2]
+    q, k, v = (torch.empty((B2, N, 8, C // 8), device=dev, dtype=torch.float16) for _ in range(3))
+    _timed("decoder_qkv", lambda: _L().gfn_decoder_qkv_fwd(ptr(t["X"]), ptr(t["norm_weight"]), ptr(t["norm_bias"]), float(eps), ptr(t["wq"]),
+                                                           ptr(t["wk"]), ptr(t["wv"]), B2, N, C, ptr(q), ptr(k), ptr(v), stream_ptr(dev)))
+    return q, k, v
+
+
+def decoder_post(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, inplace=False):
+    """What a cross-view decoder block does after its attention, in one launch (gfn_decoder_post_fwd; reference
+    model/transformer/layers/attention.py:255, block.py:327-328, mlp.py, layer_scale.py) in the fp16 autocast class:
+
+        x1    = X  + gamma1 * (wproj . attn + bproj)
+        X_out = x1 + gamma2 * (w2 . fp16(GELU(w1 . fp16(LayerNorm(x1)) + b1)) + b2)          GELU in its exact erf form
+
+    X (..., 64) fp32, attn of as many rows of 64 in fp16 (ops.cross_attention's (2B, N, 8, 8) output as it is); wproj (64, 64),
+    w1 (256, 64), w2 (64, 256), bproj, gamma1, norm_weight, norm_bias, b2, gamma2 (64) and b1 (256) fp32 as the module stores them.
+    Returns X_out, fp32 of X's shape; inplace=True writes it over X.  Contiguous CUDA tensors, the current stream, forward only:
+    raises if grad mode is on and an input requires grad."""
+    what, C, Hd = "decoder_post", DECODER_DIM, DECODER_HIDDEN
+    if X.dim() < 1 or X.shape[-1] != C:
+        raise ValueError(f"{what}: X must be (..., {C}), got {tuple(X.shape)}")
+    if attn.numel() != X.numel():
+        raise ValueError(f"{what}: attn must hold X's {X.numel() // C} rows of {C}, got {tuple(attn.shape)}")
+    f32 = torch.float32
+    vec = (f32, (C,))
+    dev, t = _decoder_args(what, {"X": X, "attn": attn, "wproj": wproj, "bproj": bproj, "gamma1": gamma1, "norm_weight": norm_weight,
+                                  "norm_bias": norm_bias, "w1": w1, "b1": b1, "w2": w2, "b2": b2, "gamma2": gamma2},
+                           {"X": (f32, X.shape), "attn": (torch.float16, attn.shape), "wproj": (f32, (C, C)), "bproj": vec, "gamma1": vec,
+                            "norm_weight": vec, "norm_bias": vec, "w1": (f32, (Hd, C)), "b1": (f32, (Hd,)), "w2": (f32, (C, Hd)), "b2": vec,
+                            "gamma2": vec})
+    out = t["X"] if inplace else torch.empty_like(t["X"])
+    _timed("decoder_post", lambda: _L().gfn_decoder_post_fwd(
+        ptr(t["X"]), ptr(t["attn"]), ptr(t["wproj"]), ptr(t["bproj"]), ptr(t["gamma1"]), ptr(t["norm_weight"]), ptr(t["norm_bias"]), float(eps),
+        ptr(t["w1"]), ptr(t["b1"]), ptr(t["w2"]), ptr(t["b2"]), ptr(t["gamma2"]), X.numel() // C, C, Hd, ptr(out), stream_ptr(dev)))
+    if inplace and out.data_ptr() != X.data_ptr():  # (a misaligned X was copied for the kernel)
+        X.copy_(out)
+    return X if inplace else out
+
+
 CONV_ACTS = {None: 0, "none": 0, "leaky_relu": 1, "swish": 2}
 
 

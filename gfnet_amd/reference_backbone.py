@@ -25,7 +25,7 @@ import torch.nn.functional as F
 DINOV2_URL = "https://dl.fbaipublicfiles.com/dinov2/dinov2_vitl14/dinov2_vitl14_pretrain.pth"  # network.py:46
 
 
-DECODERS = ("checkout", "hip")
+DECODERS = ("checkout", "hip", "hip_fused")
 FPNS = ("checkout", "hip")
 DINOS = ("checkout", "hip")
 
@@ -92,7 +92,9 @@ class ReferenceBackbone(nn.Module):
 
     decoder: "checkout" (default) builds the checkout's CrossVITDecoder_noself, which with the shipped attention_type "FLASH2" raises
     on its first forward where flash_attn is missing; "hip" builds gfnet_amd.model.crossview_decoder.CrossViewDecoder, the same
-    module under the same parameter names with its attention core in HIP, and does not import the checkout's decoder.
+    module under the same parameter names with its attention core in HIP, and does not import the checkout's decoder;
+    "hip_fused" builds the same module with block_impl="hip": in inference under fp16 autocast each block is three HIP launches
+    (csrc/decoder_block.hip around the attention), every other call is "hip" exactly.
 
     fpn: "checkout" (default) builds the checkout's FPNEncoder, FPNDecoder_concat and merge layer; "hip" builds
     gfnet_amd.model.fpn's, the same modules under the same parameter names with one fused HIP launch per layer in eval(), and does
@@ -120,10 +122,10 @@ class ReferenceBackbone(nn.Module):
             p.requires_grad = False
         self.dino = [vit]
         chs = list(conf["encoder_cfg"]["feat_chs"])  # coarse to fine
-        if decoder == "hip":
+        if decoder in ("hip", "hip_fused"):
             from .model.crossview_decoder import CrossViewDecoder
 
-            self.dino_decoder = CrossViewDecoder(conf)
+            self.dino_decoder = CrossViewDecoder(conf, block_impl="hip" if decoder == "hip_fused" else "torch")
         else:
             from model.crossview_decoder_light import CrossVITDecoder_noself
 

@@ -746,6 +746,37 @@ int gfn_self_attn_fwd(const void *qkv, int dtype, int B, int N, int H, int D, fl
 int gfn_ls_add_layernorm_fwd(const void *x, const void *y, const void *gamma, const void *weight, const void *bias, float eps,
                              int dtype, int64_t rows, int C, void *x_out, void *h_out, gfn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A block of the cross-view decoder around its attention core, inference in the fp16 autocast class; csrc/decoder_block.hip.
+ * Width C = 64 (8 heads of 8) and hidden width 256 only.  X is the residual stream of both views, cat(x, y): (2B, N, 64) fp32
+ * contiguous.  Parameters are passed as the module stores them (fp32, a Linear weight (out, in)) and rounded to fp16 once while a
+ * workgroup stages them; every pointer 16-byte aligned.  Every product runs on the matrix core (v_mfma_f32_32x32x8_f16: exact
+ * products, fp32 accumulation); LayerNorm is fp32, two-pass (mean, then the squared distances from it) over the row as read, biased
+ * variance.  Persistent workgroups over 32-token tiles; no scratch, no allocation, no atomics: identical calls give identical bits,
+ * and a row's result depends on that row alone (a non-finite row stays in its row).  Forward only.
+ *
+ * gfn_decoder_qkv_fwd -- what precedes gfn_cross_attn_fwd: model/transformer/layers/block.py:327 (norm1; the other view's tokens
+ * are not normalised, pre_norm_query) and attention.py:236-238 (the three bias-free projections), with the torch.cat((y, x)) of
+ * crossview_decoder_light.py:53-54 folded into where k and v are written.  For batch entry b and token n:
+ *   q[b,n]              = fp16(wq . fp16(LayerNorm(X[b,n]) * norm_weight + norm_bias))
+ *   k[(b + B) mod 2B,n] = fp16(wk . fp16(X[b,n]))          v likewise with wv
+ * q, k, v (2B, N, 8, 8) fp16 contiguous, as gfn_cross_attn_fwd takes them; results rounded once, overflow to inf.  B2 = 2B must be
+ * even, N >= 1, B2 * N < 2^31 - 32; anything else returns GFN_ERR_INVALID_ARG before a launch.  B2 = 0 returns GFN_OK. */
+int gfn_decoder_qkv_fwd(const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq, const float *wk,
+                        const float *wv, int B2, int N, int C, void *q, void *k, void *v, gfn_stream_t stream);
+/* gfn_decoder_post_fwd -- what follows it: attention.py:255 (the output projection), the rest of block.py:327-328 with
+ * layer_scale.py (both LayerScales and residual adds, norm2) and mlp.py (fc1, the exact erf GELU, fc2).  Per row, with a the
+ * attention output (rows, 64) fp16:
+ *   x1    = x  + gamma1 * (wproj . a + bproj)
+ *   x_out = x1 + gamma2 * (w2 . fp16(GELU(w1 . fp16(LayerNorm(x1) * norm_weight + norm_bias) + b1)) + b2)
+ * x, x_out (rows, 64) fp32; x_out may be x.  w1 (hidden, C), w2 (C, hidden).  Operands are rounded to fp16 where the reference's
+ * autocast rounds the input of a Linear; the proj, fc1 and fc2 results, which the reference rounds to fp16, stay fp32 in registers.
+ * C must be 64, hidden 256, 0 <= rows < 2^31 - 32; anything else returns GFN_ERR_INVALID_ARG before a launch.  rows = 0 returns
+ * GFN_OK. */
+int gfn_decoder_post_fwd(const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,
+                         const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1, const float *w2,
+                         const float *b2, const float *gamma2, int64_t rows, int C, int hidden, float *x_out, gfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
