@@ -12,29 +12,17 @@
 // order (input channel, kernel column, output-channel octet, kernel row): the result depends on the arguments alone.  The layers
 // with 32 and 64 output channels run here too, four to eight channel groups per tile: not yet on the matrix core.
 // conv_general_kernel: one thread per output value straight from global memory, for Cout that is no multiple of 8.
-#include <cmath>
-
-#include "common.h"
+#include "fpn_conv_launch.h"
 
 namespace {
+
+using gfn::activate;  // (ConvArgs and the activation: fpn_conv_launch.h, shared with the training path)
+using gfn::ConvArgs;
 
 constexpr int kThreads = 256;
 constexpr int kTW = 32;                     // tile columns: the lanes of a half-wave
 constexpr int kStrips = kThreads / kTW;     // row strips of a tile, R rows each
 constexpr int kSplitAbove = 32;             // input channels above which the sum is split by stage (conv_tile_kernel, SPLIT)
-
-struct ConvArgs {
-    const float *x0, *x1, *weight, *scale, *shift, *residual;
-    float *out;
-    int C0, C1, up0, H, W, Cout, Ho, Wo, act;
-    float slope;
-};
-
-__device__ __forceinline__ float activate(float v, int act, float slope) {
-    if (act == 1) return v > 0.f ? v : v * slope;
-    if (act == 2) return v * (1.f / (1.f + expf(-v)));
-    return v;
-}
 
 // F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) of the (h2, w2) plane p at (y, x) of the doubled grid: the
 // source coordinate 0.5 (dst + 0.5) - 0.5 clamped at 0, the far neighbour clamped to the plane, weights and sum in ATen's order
@@ -251,6 +239,21 @@ int launch_tile_stride(const ConvArgs &a, int S, int B, hipStream_t s) {
 
 }  // namespace
 
+int gfn::fpn_conv_launch(const ConvArgs &a, int B, int K, int stride, hipStream_t s) {
+    if (a.Cout % 8 == 0) {
+        switch (K) {
+            case 1: return launch_tile_stride<1>(a, stride, B, s);
+            case 3: return launch_tile_stride<3>(a, stride, B, s);
+            case 5: return launch_tile_stride<5>(a, stride, B, s);
+            default: return launch_tile_stride<7>(a, stride, B, s);
+        }
+    }
+    const int64_t per_image = (int64_t)a.Cout * a.Ho * a.Wo;
+    hipLaunchKernelGGL(conv_general_kernel, dim3((unsigned)((per_image + kThreads - 1) / kThreads), (unsigned)B), dim3(kThreads), 0, s, a,
+                       K, stride, per_image);
+    return gfn::check_launch("conv_general_kernel");
+}
+
 GFN_EXPORT int gfn_conv2d_bn_act_fwd(const float *x0, int C0, int up0, const float *x1, int C1, const float *weight, const float *scale,
                                      const float *shift, const float *residual, float *out, int B, int H, int W, int Cout, int K,
                                      int stride, int act, float slope, gfn_stream_t stream) {
@@ -274,17 +277,5 @@ GFN_EXPORT int gfn_conv2d_bn_act_fwd(const float *x0, int C0, int up0, const flo
     if (!x0 || !weight || !scale || !shift || !out || (C1 > 0 && !x1)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: null pointer", what);
 
     const ConvArgs a{x0, x1, weight, scale, shift, residual, out, C0, C1, up0 ? 1 : 0, H, W, Cout, Ho, Wo, act, slope};
-    hipStream_t s = (hipStream_t)stream;
-    if (Cout % 8 == 0) {
-        switch (K) {
-            case 1: return launch_tile_stride<1>(a, stride, B, s);
-            case 3: return launch_tile_stride<3>(a, stride, B, s);
-            case 5: return launch_tile_stride<5>(a, stride, B, s);
-            default: return launch_tile_stride<7>(a, stride, B, s);
-        }
-    }
-    const int64_t per_image = outb / 4;
-    hipLaunchKernelGGL(conv_general_kernel, dim3((unsigned)((per_image + kThreads - 1) / kThreads), (unsigned)B), dim3(kThreads), 0, s, a,
-                       K, stride, per_image);
-    return gfn::check_launch("conv_general_kernel");
+    return gfn::fpn_conv_launch(a, B, K, stride, (hipStream_t)stream);
 }

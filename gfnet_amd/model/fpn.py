@@ -10,15 +10,25 @@ configuration GFNet builds: norm_type "BN".  Submodule and parameter names are t
     decoder   out0 inner1 out1 inner2 out2 inner3 out3, each with .0.{weight,bias} (conv)  .1.* (BatchNorm)
     merge     0.{weight,bias}  1.*
 
-Two paths over the same parameters:
+Three paths over the same parameters:
 
   * in eval() on CUDA fp32 input with conv_impl "hip" (the default) every layer is ONE ops.conv2d_bn_act launch
     (csrc/fpn_conv.hip): BatchNorm's running statistics, its affine and the conv bias are folded into a per-channel scale and shift
     on the device at every forward (a few tiny torch ops, no host sync, nothing cached that load_state_dict could leave stale); the
     decoder's cat(interpolate(intra), convN1) and its `convN1 +` residual ride in the innerN launch, conv31 + merge(cat(conv31,
     side)) likewise, so neither the doubled map nor the concatenation is ever written.  No autograd on this path.
-  * in train(), on CPU tensors, in other dtypes or with conv_impl "torch": F.conv2d, BatchNorm, the activation, F.interpolate and
-    torch.cat, as the reference writes them; differentiable, and the BatchNorm buffers move as in the reference.
+  * in train() on CUDA fp32 input with train_conv_impl "hip" (NOT the default) every layer is one ops.conv2d_bn_act_train call
+    (csrc/fpn_conv_train.hip): convolution, the batch's own statistics, BatchNorm, activation and residual in HIP with a HIP backward.
+    Autograd keeps the layer's inputs and ONE map per layer, the raw convolution output; the normalised map, the activation's mask
+    or sigmoid and the concatenation are recomputed or never written.  The 2x upsample in front of innerN stays F.interpolate
+    (which differentiates it) and its result is passed as x0.  The BatchNorm buffers move as in the reference.  A conv bias in front
+    of a batch-statistics BatchNorm (the decoder's and the merge layer's) gets EXACT zeros as its gradient: it cancels in u - mean,
+    the true gradient is zero, and torch's autograd returns rounding noise around 1e-7 there.
+  * everything else -- train() with train_conv_impl "torch" (the default), CPU tensors, other dtypes, conv_impl "torch" in eval():
+    F.conv2d, BatchNorm, the activation, F.interpolate and torch.cat, as the reference writes them; differentiable, and the
+    BatchNorm buffers move as in the reference.
+
+The top-level module's conv_impl and train_conv_impl govern its children (run(x, hip, train_hip)).
 """
 import torch
 import torch.nn as nn
@@ -36,9 +46,20 @@ def _check_impl(conv_impl):
     return conv_impl
 
 
+def _check_train_impl(train_conv_impl):
+    if train_conv_impl not in CONV_IMPLS:
+        raise ValueError(f"train_conv_impl must be one of {CONV_IMPLS}, got {train_conv_impl!r}")
+    return train_conv_impl
+
+
 def _use_hip(module, x):
     _check_impl(module.conv_impl)
     return module.conv_impl == "hip" and not module.training and x.is_cuda and x.dtype == torch.float32
+
+
+def _use_train_hip(module, x):
+    _check_train_impl(module.train_conv_impl)
+    return module.train_conv_impl == "hip" and module.training and x.is_cuda and x.dtype == torch.float32
 
 
 def _fold(conv, bn):
@@ -58,12 +79,28 @@ def _fold(conv, bn):
         return scale.contiguous(), shift.contiguous()
 
 
-def _hip_layer(conv, bn, act, x0, x1=None, up0=False, residual=None):
+def _check_conv(conv, switch):
     k = conv.kernel_size[0]
     if (conv.kernel_size != (k, k) or k not in (1, 3, 5, 7) or conv.padding != (k // 2, k // 2) or conv.stride not in ((1, 1), (2, 2))
             or conv.dilation != (1, 1) or conv.groups != 1 or conv.padding_mode != "zeros"):
-        raise NotImplementedError(f"conv_impl='hip' runs square kernels of 1, 3, 5 or 7 with padding k // 2, stride 1 or 2, no dilation "
-                                  f"and no groups; got {conv}: construct with conv_impl='torch'")
+        raise NotImplementedError(f"{switch}='hip' runs square kernels of 1, 3, 5 or 7 with padding k // 2, stride 1 or 2, no dilation "
+                                  f"and no groups; got {conv}: construct with {switch}='torch'")
+
+
+def _hip_train_layer(conv, bn, act, x0, x1=None, residual=None):
+    """One layer on the batch's own statistics through ops.conv2d_bn_act_train; x0 is the doubled map where the layer upsamples."""
+    _check_conv(conv, "train_conv_impl")
+    if bn is None or not bn.affine or not bn.track_running_stats:
+        raise NotImplementedError("train_conv_impl='hip' needs an affine BatchNorm2d that tracks its running statistics after every "
+                                  "convolution: construct with train_conv_impl='torch'")
+    x0, x1, residual = (None if t is None else t.contiguous() for t in (x0, x1, residual))
+    return ops.conv2d_bn_act_train(x0, conv.weight.contiguous(), conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                   bn.num_batches_tracked, bn.momentum, bn.eps, x1=x1, residual=residual, stride=conv.stride[0], act=act,
+                                   slope=LEAKY_SLOPE)
+
+
+def _hip_layer(conv, bn, act, x0, x1=None, up0=False, residual=None):
+    _check_conv(conv, "conv_impl")
     scale, shift = _fold(conv, bn)
     x0, x1, residual = (None if t is None else t.contiguous() for t in (x0, x1, residual))
     return ops.conv2d_bn_act(x0, conv.weight.detach().contiguous(), scale, shift, x1=x1, up0=up0, residual=residual, stride=conv.stride[0],
@@ -85,62 +122,67 @@ class Conv2d(nn.Module):
     reference's "IN" (InstanceNorm, which GFNet never builds) raises NotImplementedError."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, relu=True, bn=True, bn_momentum=0.1, norm_type="BN",
-                 conv_impl="hip", **kwargs):
+                 conv_impl="hip", train_conv_impl="torch", **kwargs):
         super().__init__()
         if norm_type != "BN":
             raise NotImplementedError(f"Conv2d: norm_type = {norm_type!r} is not supported, only 'BN' (what GFNet builds)")
         self.conv_impl = _check_impl(conv_impl)
+        self.train_conv_impl = _check_train_impl(train_conv_impl)
         self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride=stride, bias=(not bn), **kwargs)
         self.kernel_size = kernel_size
         self.stride = stride
         self.bn = nn.BatchNorm2d(out_channels, momentum=bn_momentum) if bn else None
         self.relu = relu
 
-    def run(self, x, hip):
+    def run(self, x, hip, train_hip=False):
         if hip:
             return _hip_layer(self.conv, self.bn, "leaky_relu" if self.relu else None, x)
+        if train_hip:
+            return _hip_train_layer(self.conv, self.bn, "leaky_relu" if self.relu else None, x)
         y = self.conv(x)
         if self.bn is not None:
             y = self.bn(y)
         return F.leaky_relu(y, LEAKY_SLOPE, inplace=True) if self.relu else y
 
     def forward(self, x):
-        return self.run(x, _use_hip(self, x))
+        return self.run(x, _use_hip(self, x), _use_train_hip(self, x))
 
 
 class FPNEncoder(nn.Module):
     """FPN.py:5-36: images (B, 3, H, W) -> [conv01, conv11, conv21, conv31] at strides 1, 2, 4, 8 with feat_chs channels (fine to
     coarse).  H and W must be multiples of 8 (the reference fails later, inside the decoder's torch.cat)."""
 
-    def __init__(self, feat_chs, norm_type="BN", conv_impl="hip"):
+    def __init__(self, feat_chs, norm_type="BN", conv_impl="hip", train_conv_impl="torch"):
         super().__init__()
         if norm_type != "BN":
             raise NotImplementedError(f"FPNEncoder: norm_type = {norm_type!r} is not supported, only 'BN' (what GFNet builds)")
         self.conv_impl = _check_impl(conv_impl)
+        self.train_conv_impl = _check_train_impl(train_conv_impl)
         c = feat_chs
-        self.conv00 = Conv2d(3, c[0], 7, 1, padding=3, norm_type=norm_type, conv_impl=conv_impl)
-        self.conv01 = Conv2d(c[0], c[0], 5, 1, padding=2, norm_type=norm_type, conv_impl=conv_impl)
+        kw = {"norm_type": norm_type, "conv_impl": conv_impl, "train_conv_impl": train_conv_impl}
+        self.conv00 = Conv2d(3, c[0], 7, 1, padding=3, **kw)
+        self.conv01 = Conv2d(c[0], c[0], 5, 1, padding=2, **kw)
 
-        self.downsample1 = Conv2d(c[0], c[1], 5, stride=2, padding=2, norm_type=norm_type, conv_impl=conv_impl)
-        self.conv10 = Conv2d(c[1], c[1], 3, 1, padding=1, norm_type=norm_type, conv_impl=conv_impl)
-        self.conv11 = Conv2d(c[1], c[1], 3, 1, padding=1, norm_type=norm_type, conv_impl=conv_impl)
+        self.downsample1 = Conv2d(c[0], c[1], 5, stride=2, padding=2, **kw)
+        self.conv10 = Conv2d(c[1], c[1], 3, 1, padding=1, **kw)
+        self.conv11 = Conv2d(c[1], c[1], 3, 1, padding=1, **kw)
 
-        self.downsample2 = Conv2d(c[1], c[2], 5, stride=2, padding=2, norm_type=norm_type, conv_impl=conv_impl)
-        self.conv20 = Conv2d(c[2], c[2], 3, 1, padding=1, norm_type=norm_type, conv_impl=conv_impl)
-        self.conv21 = Conv2d(c[2], c[2], 3, 1, padding=1, norm_type=norm_type, conv_impl=conv_impl)
+        self.downsample2 = Conv2d(c[1], c[2], 5, stride=2, padding=2, **kw)
+        self.conv20 = Conv2d(c[2], c[2], 3, 1, padding=1, **kw)
+        self.conv21 = Conv2d(c[2], c[2], 3, 1, padding=1, **kw)
 
-        self.downsample3 = Conv2d(c[2], c[3], 3, stride=2, padding=1, norm_type=norm_type, conv_impl=conv_impl)
-        self.conv30 = Conv2d(c[3], c[3], 3, 1, padding=1, norm_type=norm_type, conv_impl=conv_impl)
-        self.conv31 = Conv2d(c[3], c[3], 3, 1, padding=1, norm_type=norm_type, conv_impl=conv_impl)
+        self.downsample3 = Conv2d(c[2], c[3], 3, stride=2, padding=1, **kw)
+        self.conv30 = Conv2d(c[3], c[3], 3, 1, padding=1, **kw)
+        self.conv31 = Conv2d(c[3], c[3], 3, 1, padding=1, **kw)
 
     def forward(self, x):
         if x.dim() != 4 or x.shape[2] % 8 or x.shape[3] % 8:
             raise ValueError(f"FPNEncoder: height and width must be multiples of 8, got an input of shape {tuple(x.shape)}")
-        hip = _use_hip(self, x)
-        conv01 = self.conv01.run(self.conv00.run(x, hip), hip)
-        conv11 = self.conv11.run(self.conv10.run(self.downsample1.run(conv01, hip), hip), hip)
-        conv21 = self.conv21.run(self.conv20.run(self.downsample2.run(conv11, hip), hip), hip)
-        conv31 = self.conv31.run(self.conv30.run(self.downsample3.run(conv21, hip), hip), hip)
+        hip, th = _use_hip(self, x), _use_train_hip(self, x)
+        conv01 = self.conv01.run(self.conv00.run(x, hip, th), hip, th)
+        conv11 = self.conv11.run(self.conv10.run(self.downsample1.run(conv01, hip, th), hip, th), hip, th)
+        conv21 = self.conv21.run(self.conv20.run(self.downsample2.run(conv11, hip, th), hip, th), hip, th)
+        conv31 = self.conv31.run(self.conv30.run(self.downsample3.run(conv21, hip, th), hip, th), hip, th)
         return [conv01, conv11, conv21, conv31]
 
 
@@ -152,24 +194,28 @@ class merge_layer(nn.Sequential):
     """network.py:66, 182: `conv31 + Sequential(conv3x3(2 ch -> ch), BatchNorm, Swish)(cat(conv31, side))`, the addition included:
     forward(conv31, side) -> the merged stride-8 map."""
 
-    def __init__(self, ch, conv_impl="hip"):
+    def __init__(self, ch, conv_impl="hip", train_conv_impl="torch"):
         super().__init__(nn.Conv2d(2 * ch, ch, kernel_size=3, padding=1), nn.BatchNorm2d(ch), Swish())
         self.conv_impl = _check_impl(conv_impl)
+        self.train_conv_impl = _check_train_impl(train_conv_impl)
 
     def forward(self, conv31, side):
         if conv31.shape != side.shape:
             raise ValueError(f"merge_layer: conv31 {tuple(conv31.shape)} and the side map {tuple(side.shape)} must have one shape")
         if _use_hip(self, conv31) and side.is_cuda and side.dtype == torch.float32:
             return _hip_layer(*_head(self), conv31, x1=side, residual=conv31)
+        if _use_train_hip(self, conv31) and side.is_cuda and side.dtype == torch.float32:
+            return _hip_train_layer(*_head(self), conv31, x1=side, residual=conv31)
         return conv31 + nn.Sequential.forward(self, torch.cat((conv31, side), dim=1))
 
 
 class FPNDecoder_concat(nn.Module):
     """FPN.py:39-69: (conv01, conv11, conv21, conv31) -> [out0, out1, out2, out3] at strides 8, 4, 2, 1."""
 
-    def __init__(self, feat_chs, conv_impl="hip"):
+    def __init__(self, feat_chs, conv_impl="hip", train_conv_impl="torch"):
         super().__init__()
         self.conv_impl = _check_impl(conv_impl)
+        self.train_conv_impl = _check_train_impl(train_conv_impl)
         c = feat_chs
 
         def block(cin, cout, k):
@@ -193,6 +239,7 @@ class FPNDecoder_concat(nn.Module):
                 raise ValueError(f"FPNDecoder_concat: every level must double the one below it, got {[tuple(m.shape) for m in maps]} "
                                  "(image heights and widths must be multiples of 8)")
         hip = _use_hip(self, conv31) and all(m.is_cuda and m.dtype == torch.float32 for m in maps)
+        th = _use_train_hip(self, conv31) and all(m.is_cuda and m.dtype == torch.float32 for m in maps)
         intra = conv31
         outs = []
         for inner, out, skip in ((None, self.out0, None), (self.inner1, self.out1, conv21), (self.inner2, self.out2, conv11),
@@ -200,7 +247,9 @@ class FPNDecoder_concat(nn.Module):
             if inner is not None:  # FPN.py:59: skip + inner(cat(interpolate(intra), skip))
                 if hip:
                     intra = _hip_layer(*_head(inner), intra, x1=skip, up0=True, residual=skip)
+                elif th:  # the doubled map from torch, which differentiates the upsample; still no concatenation
+                    intra = _hip_train_layer(*_head(inner), _up2(intra), x1=skip, residual=skip)
                 else:
                     intra = skip + inner(torch.cat((_up2(intra), skip), dim=1))
-            outs.append(_hip_layer(*_head(out), intra) if hip else out(intra))
+            outs.append(_hip_layer(*_head(out), intra) if hip else _hip_train_layer(*_head(out), intra) if th else out(intra))
         return outs

@@ -43,6 +43,13 @@ def _check_choices(decoder, fpn, dino="checkout"):
         raise ValueError(f"dino must be one of {DINOS}, got {dino!r}")
 
 
+def _check_fpn_train_impl(fpn, fpn_train_impl):
+    if fpn_train_impl not in ("torch", "hip"):
+        raise ValueError(f"fpn_train_impl must be 'torch' or 'hip', got {fpn_train_impl!r}")
+    if fpn_train_impl != "torch" and fpn != "hip":
+        raise ValueError(f"fpn_train_impl={fpn_train_impl!r} needs fpn='hip': the checkout's FPN modules train through torch only")
+
+
 def checkout_available(decoder="checkout", fpn="checkout"):
     """True when the reference's backbone modules that this choice takes from the checkout can be found on sys.path (nothing is
     imported).  decoder="hip" does without `model.crossview_decoder_light`, fpn="hip" without `model.FPN`: those are then this
@@ -103,12 +110,16 @@ class ReferenceBackbone(nn.Module):
     dino: which ViT is built where none is passed in.  "checkout" (default) builds the checkout's `vit_large`, which imports
     `model.transformer` and with it the checkout's third-party imports; "hip" builds gfnet_amd.model.dinov2.vit_large, the same model
     under the same parameter names (`dino_weights` load strictly, exactly as above) with its attention and the seams of its blocks
-    in HIP in fp16 eval().  With decoder="hip", fpn="hip" and dino="hip" nothing of a checkout is imported."""
+    in HIP in fp16 eval().  With decoder="hip", fpn="hip" and dino="hip" nothing of a checkout is imported.
+
+    fpn_train_impl: "torch" (default) or "hip", the train_conv_impl of the three native FPN modules: what they run under train() (see
+    gfnet_amd/model/fpn.py).  The checkout's modules have no such switch: anything but "torch" with fpn="checkout" raises ValueError."""
 
     def __init__(self, conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout",
-                 dino="checkout"):
+                 dino="checkout", fpn_train_impl="torch"):
         super().__init__()
         _check_choices(decoder, fpn, dino)
+        _check_fpn_train_impl(fpn, fpn_train_impl)
         self.fpn = fpn
         if fpn == "hip":
             from .model.fpn import FPNDecoder_concat, FPNEncoder, merge_layer
@@ -130,10 +141,11 @@ class ReferenceBackbone(nn.Module):
             from model.crossview_decoder_light import CrossVITDecoder_noself
 
             self.dino_decoder = CrossVITDecoder_noself(conf=conf, upsample=False)
-        self.encoder = FPNEncoder(feat_chs=chs[::-1])
-        self.decoder = FPNDecoder_concat(feat_chs=chs[::-1])
+        native = {"train_conv_impl": fpn_train_impl} if fpn == "hip" else {}
+        self.encoder = FPNEncoder(feat_chs=chs[::-1], **native)
+        self.decoder = FPNDecoder_concat(feat_chs=chs[::-1], **native)
         if fpn == "hip":
-            self.merge_layer = merge_layer(chs[0])
+            self.merge_layer = merge_layer(chs[0], **native)
         else:
             self.merge_layer = nn.Sequential(nn.Conv2d(2 * chs[0], chs[0], kernel_size=3, padding=1), nn.BatchNorm2d(chs[0]), Swish())
 
@@ -170,12 +182,13 @@ class ReferenceBackbone(nn.Module):
 
 
 def reference_backbone(conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout",
-                       dino="checkout"):
+                       dino="checkout", fpn_train_impl="torch"):
     """Build the backbone from the checkout on sys.path; raises ImportError with the reason when a module this choice needs from it
-    is missing.  decoder, fpn, dino: see ReferenceBackbone."""
+    is missing.  decoder, fpn, dino, fpn_train_impl: see ReferenceBackbone."""
     _check_choices(decoder, fpn, dino)
+    _check_fpn_train_impl(fpn, fpn_train_impl)
     if not checkout_available(decoder, fpn):
         raise ImportError(f"no KN-Zhang/GFNet checkout on sys.path: {' / '.join(f'`{m}`' for m in _needed(decoder, fpn))} cannot be found "
                           "(put the checkout behind compat/ on PYTHONPATH, or run the script through compat/run.py)")
     return ReferenceBackbone(conf, amp=amp, amp_dtype=amp_dtype, vit=vit, dino_weights=dino_weights, decoder=decoder, fpn=fpn,
-                             dino=dino)
+                             dino=dino, fpn_train_impl=fpn_train_impl)

@@ -717,6 +717,44 @@ int gfn_conv2d_bn_act_fwd(const float *x0, int C0, int up0, const float *x1, int
                           const float *shift, const float *residual, float *out, int B, int H, int W, int Cout, int K, int stride,
                           int act, float slope, gfn_stream_t stream);
 
+/* The same layer in TRAINING mode (model.train(): the reference trains the whole FPN, trainer/train.py:108, through torch autograd);
+ * csrc/fpn_conv_train.hip.  fp32, NCHW, contiguous, x = cat(x0, x1) with x0 (B, C0, H, W) and x1 (B, C1, H, W) or NULL with C1 = 0 (no
+ * up0 here: the caller passes the doubled map as x0, F.interpolate differentiates the upsample):
+ *   u    = conv(x, weight)                      zero padding K/2; the conv bias is NOT in u
+ *   mean, invstd (Cout) of u over B*Ho*Wo       biased variance, eps inside the root
+ *   out  = act(bn_w * (u - mean) * invstd + bn_b) + residual             (evaluated as u * alpha + beta', alpha = bn_w * invstd)
+ *   running_mean <- (1 - m) running_mean + m (mean + conv_bias)          running_var <- (1 - m) running_var + m var * n / (n - 1)
+ * gfn_conv2d_bn_act_train_fwd writes u (B, Cout, Ho, Wo; the ONE map kept for the backward), mean, invstd and out, and updates the
+ *   running buffers in place.  conv_bias (Cout) may be NULL; residual (B, Cout, Ho, Wo) may be NULL and may alias x0 or x1; u and out
+ *   alias nothing.  The gradient of residual is gy itself and is left to the caller.  The gradient of a conv bias in front of
+ *   batch statistics is analytically zero (the bias cancels in u - mean): there is no pointer for it, the caller returns exact zeros
+ *   (torch returns rounding noise around 1e-7 there).
+ * gfn_conv2d_bn_act_train_bwd: gy = dL/dout and x0, x1, weight, bn_w, bn_b, u, mean, invstd as the forward had them -> gx0 (B, C0, H,
+ *   W), gx1 (B, C1, H, W), d_weight (Cout, C0 + C1, K, K), d_bn_w, d_bn_b (Cout), all OVERWRITTEN.  `need` is a sum of GFN_CBT_NEED_X
+ *   (gx0 and gx1), GFN_CBT_NEED_W (d_weight) and GFN_CBT_NEED_BN (d_bn_w, d_bn_b): only what it names is computed and only those
+ *   pointers are touched; need = 0 launches nothing.  The activation's derivative is recomputed from u, mean and invstd with the
+ *   forward's expression.
+ * Limits: those of gfn_conv2d_bn_act_fwd, and C0 + C1 <= 65535 and B*Ho*Wo >= 2 (one value per channel has no variance; torch
+ *   refuses it too).  Anything else returns GFN_ERR_INVALID_ARG before a launch; B = 0 returns GFN_OK.
+ * Arithmetic: operands and products fp32.  Every reduction is two-stage in a fixed order -- the statistics (per 4096 values of a
+ *   plane the mean and the squares about it, merged with Chan's formula in double), d_bn_w / d_bn_b (fp32 partials, summed in
+ *   double) and the weight gradient (fp32 runs of 32 products, P partial gradients summed in double) -- and there are no
+ *   floating-point atomics: identical calls give identical bits.
+ * ws: gfn_conv2d_bn_act_train_ws_bytes(...) bytes of 16-byte aligned device memory, contents undefined before and after.  In floats,
+ *   each term rounded up to 4:  forward  2 Cout B ceil(Ho Wo / 4096) + 2 max(Cout, C0, C1);  backward  that + 2 Cout + B Cout Ho Wo (the
+ *   gu map) + Cout Cin K K (the repacked weight) + P Cout Cin K K with P = min(512, 2^22 / (Cout Cin K K), B ceil(Ho / 8)
+ *   ceil(Wo / 32)), at least 1: the partial weight gradients never take more than 16 MiB. */
+#define GFN_CBT_NEED_W 2 /* d_weight of gfn_conv2d_bn_act_train_bwd */
+int64_t gfn_conv2d_bn_act_train_ws_bytes(int C0, int C1, int B, int H, int W, int Cout, int K, int stride, int backward);
+int gfn_conv2d_bn_act_train_fwd(const float *x0, int C0, const float *x1, int C1, const float *weight, const float *conv_bias,
+                                const float *bn_w, const float *bn_b, float *running_mean, float *running_var, const float *residual,
+                                float *u, float *mean, float *invstd, float *out, int B, int H, int W, int Cout, int K, int stride,
+                                int act, float slope, double momentum, double eps, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+int gfn_conv2d_bn_act_train_bwd(const float *gy, const float *x0, int C0, const float *x1, int C1, const float *weight, const float *bn_w,
+                                const float *bn_b, const float *u, const float *mean, const float *invstd, float *gx0, float *gx1,
+                                float *d_weight, float *d_bn_w, float *d_bn_b, int B, int H, int W, int Cout, int K, int stride, int act,
+                                float slope, int need, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Self-attention forward of the DINOv2 ViT at head dim 64 -- model/transformer/layers/attention.py:77-101 (Attention.forward:
  * the F.scaled_dot_product_attention call at :96, which MemEffAttention falls back to without xformers, :106-110);

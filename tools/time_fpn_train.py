@@ -1,0 +1,176 @@
+#!/usr/bin/env python3
+"""Time the native FPN in TRAINING mode (gfnet_amd/model/fpn.py under train()): forward + backward with train_conv_impl "hip"
+(csrc/fpn_conv_train.hip: one op per layer, one saved map per layer) against the module's own torch path on the same commit
+(F.conv2d, BatchNorm2d on batch statistics, the activation, F.interpolate, torch.cat and autograd), same parameters and inputs.
+
+    python tools/time_fpn_train.py [--images 16] [--sizes 448] [--rounds 7] [--reps 3] [--out fpn_train_timing.json]
+
+Per size: every layer forward + backward on its real input (the maps of one torch-path forward) with a fixed output gradient, then
+the three modules forward + backward, and for those the peak of torch.cuda.max_memory_allocated above what is allocated before the
+step.  The two paths ALTERNATE round by round; a round is `reps` back-to-back calls between two device events; reported per path
+are the median round and the spread (min .. max) over the rounds, in ms per call.  Every shape is warmed up on both paths first.
+Needs a GPU; nothing here falls back."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from gfnet_amd.model import fpn  # noqa: E402
+
+FEAT_CHS = [8, 16, 32, 64]
+ENCODER = ("conv00", "conv01", "downsample1", "conv10", "conv11", "downsample2", "conv20", "conv21", "downsample3", "conv30", "conv31")
+
+
+def build(device):
+    torch.manual_seed(0)
+    mods = {"encoder": fpn.FPNEncoder(FEAT_CHS), "decoder": fpn.FPNDecoder_concat(FEAT_CHS), "merge_layer": fpn.merge_layer(FEAT_CHS[-1])}
+    for m in mods.values():
+        m.to(device).train(True)
+    return mods
+
+
+def layer_calls(mods):
+    """[(name, input keys, call(hip, *inputs) -> map, parameters, key under which the map goes into ctx)] in forward order."""
+    enc, dec, merge = mods["encoder"], mods["decoder"], mods["merge_layer"]
+    calls, prev = [], "image"
+    for name in ENCODER:
+        layer = getattr(enc, name)
+        calls.append((name, (prev,), (lambda layer: lambda hip, x: layer.run(x, False, hip))(layer), list(layer.parameters()), name))
+        prev = name
+
+    def run_merge(hip, c3, side):
+        if hip:
+            return fpn._hip_train_layer(*fpn._head(merge), c3, x1=side, residual=c3)
+        return c3 + torch.nn.Sequential.forward(merge, torch.cat((c3, side), dim=1))
+
+    def head(seq):
+        return lambda hip, x: fpn._hip_train_layer(*fpn._head(seq), x) if hip else seq(x)
+
+    def inner(seq):
+        def run(hip, intra, skip):
+            if hip:
+                return fpn._hip_train_layer(*fpn._head(seq), fpn._up2(intra), x1=skip, residual=skip)
+            return skip + seq(torch.cat((fpn._up2(intra), skip), dim=1))
+        return run
+
+    calls.append(("merge_layer", ("conv31", "side"), run_merge, list(merge.parameters()), "merged"))
+    calls.append(("out0", ("merged",), head(dec.out0), list(dec.out0.parameters()), "out0"))
+    calls.append(("inner1", ("merged", "conv21"), inner(dec.inner1), list(dec.inner1.parameters()), "intra1"))
+    calls.append(("out1", ("intra1",), head(dec.out1), list(dec.out1.parameters()), "out1"))
+    calls.append(("inner2", ("intra1", "conv11"), inner(dec.inner2), list(dec.inner2.parameters()), "intra2"))
+    calls.append(("out2", ("intra2",), head(dec.out2), list(dec.out2.parameters()), "out2"))
+    calls.append(("inner3", ("intra2", "conv01"), inner(dec.inner3), list(dec.inner3.parameters()), "intra3"))
+    calls.append(("out3", ("intra3",), head(dec.out3), list(dec.out3.parameters()), "out3"))
+    return calls
+
+
+def pyramid_step(mods, hip, image, side, gys):
+    """The three modules forward and backward: gradients of sum_k (out_k * gy_k).sum() for every parameter and the side map."""
+    for m in mods.values():
+        m.train_conv_impl = "hip" if hip else "torch"
+    c0, c1, c2, c3 = mods["encoder"](image)
+    outs = mods["decoder"](c0, c1, c2, mods["merge_layer"](c3, side))
+    params = [p for m in mods.values() for p in m.parameters()]
+    return torch.autograd.grad(outs, [side] + params, gys)
+
+
+def time_pair(fn, rounds, reps):
+    """fn(hip) timed on both paths, alternating: {"hip": [ms per call, one per round], "torch": [...]}."""
+    out = {"hip": [], "torch": []}
+    for hip in (True, False, True, False):  # warm-up: code objects, algorithm choice, allocator
+        fn(hip)
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for path in ("hip", "torch"):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                fn(path == "hip")
+            e1.record()
+            e1.synchronize()
+            out[path].append(e0.elapsed_time(e1) / reps)
+    return out
+
+
+def peak_bytes(fn):
+    """The peak of allocated device memory during fn() above what is allocated before it."""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - base
+
+
+def summary(ms):
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms)}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--images", type=int, default=16, help="images per call (an 8-pair batch is 16)")
+    ap.add_argument("--sizes", type=int, nargs="+", default=[448])
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None, help="write the numbers as JSON here")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("time_fpn_train.py needs a GPU")
+    dev = torch.device("cuda")
+    mods = build(dev)
+    calls = layer_calls(mods)
+    result = {"device": torch.cuda.get_device_name(0), "images": args.images, "rounds": args.rounds, "reps": args.reps, "sizes": {}}
+    for size in args.sizes:
+        g = torch.Generator(device=dev).manual_seed(size)
+        ctx = {"image": torch.rand((args.images, 3, size, size), device=dev, generator=g) * 2 - 1,
+               "side": (torch.randn((args.images, FEAT_CHS[-1], size // 8, size // 8), device=dev, generator=g) * 0.5).requires_grad_()}
+        rows, worst = {}, 0.0
+        for name, keys, call, params, key in calls:
+            inputs = tuple(ctx[k] for k in keys)
+            with torch.no_grad():
+                ref = call(False, *inputs)
+                diff = float((call(True, *inputs) - ref).abs().max())
+            ctx[key] = ref.detach().requires_grad_()
+            worst = max(worst, diff)
+            gy = torch.randn(ref.shape, device=dev, generator=g)
+            wanted = [t for t in inputs if t.requires_grad] + params
+
+            def step(hip, call=call, inputs=inputs, gy=gy, wanted=wanted):
+                return torch.autograd.grad(call(hip, *inputs), wanted, gy)
+
+            t = time_pair(step, args.rounds, args.reps)
+            rows[name] = {"hip": summary(t["hip"]), "torch": summary(t["torch"]), "max_abs_diff": diff, "shape": list(ref.shape)}
+            del ref, gy
+        side = ctx["side"]
+        image = ctx["image"]
+        shapes = [ctx[k].shape for k in ("out0", "out1", "out2", "out3")]
+        del ctx
+        gys = [torch.randn(s, device=dev, generator=g) for s in shapes]
+        t = time_pair(lambda hip: pyramid_step(mods, hip, image, side, gys), args.rounds, args.reps)
+        total = {"hip": summary(t["hip"]), "torch": summary(t["torch"])}
+        memory = {path: peak_bytes(lambda: pyramid_step(mods, path == "hip", image, side, gys)) for path in ("hip", "torch")}
+        result["sizes"][str(size)] = {"layers": rows, "total": total, "peak_bytes": memory, "max_abs_diff": worst}
+        print(f"\n{args.images} images of {size} x {size} on {result['device']}, forward + backward: ms per call, median (min .. max) of "
+              f"{args.rounds} rounds of {args.reps}")
+        print("| layer | output | HIP | torch | torch / HIP |\n|---|---|---|---|---|")
+        for name, r in list(rows.items()) + [("three modules", dict(total, shape=[]))]:
+            h, c = r["hip"], r["torch"]
+            print(f"| {name} | {'x'.join(str(v) for v in r['shape'][1:])} | {h['median_ms']:.3f} ({h['min_ms']:.3f} .. {h['max_ms']:.3f}) | "
+                  f"{c['median_ms']:.3f} ({c['min_ms']:.3f} .. {c['max_ms']:.3f}) | {c['median_ms'] / h['median_ms']:.2f} |")
+        print(f"peak memory of one step above the resident tensors: HIP {memory['hip'] / 2 ** 20:.0f} MiB, torch {memory['torch'] / 2 ** 20:.0f} MiB")
+        print(f"largest difference between the two paths' layer outputs: {worst:.3e}")
+        del gys, image, side
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
