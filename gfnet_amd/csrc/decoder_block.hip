@@ -10,7 +10,8 @@
 // without moving between lanes, a LayerNorm is per-lane sums and one cross-half shuffle per statistic, and fc1 -> GELU -> fc2 never
 // leaves the registers.  Workgroups are persistent: the weights are converted to fp16 into LDS once and the waves loop over
 // 32-token tiles with no barrier in the loop.  No scratch, no atomics: identical calls give identical bits, and a token's result
-// does not depend on where it sits in a tile or which tile it is in.
+// does not depend on where it sits in a tile or which tile it is in.  The second half of the file is the backward of both launches,
+// for training in the same class (the forward kernels are the training forward as they are).
 #include <climits>
 #include <initializer_list>
 
@@ -326,4 +327,648 @@ GFN_EXPORT int gfn_decoder_post_fwd(const float *x, const void *attn, const floa
     hipLaunchKernelGGL(decoder_post_kernel, dim3(grid), dim3(kPostThreads), 0, (hipStream_t)stream, x, (const _Float16 *)attn, wproj, bproj,
                        gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, x_out, rows, ntiles);
     return gfn::check_launch("decoder_post_kernel");
+}
+
+// =================================================================================================================================
+// Training: the backward of the two launches above, differentiating the forward as those kernels compute it with every fp16
+// rounding taken as the identity (what autocast's backward does).  Tokens stay on lane & 31; a W^T g product takes the weight's
+// other orientation, staged transposed, as its A operand.  A parameter gradient is a sum over tokens of g (x) operand, so there the
+// tokens are the K dimension: both factors go through a wave-private [channel][token] fp16 tile in LDS and come back as 8-byte
+// operand reads.  No atomics: every workgroup leaves fp32 partial sums in the caller's workspace and a later launch adds them in
+// a fixed order, so identical calls give identical bits.  Nothing (rows, 256) leaves the chip.
+namespace {
+
+constexpr int kBwdThreads = 256, kBwdWaves = kBwdThreads / 64;  // one wave per SIMD: the accumulators take the register file
+constexpr int kMaxGroups = 256;   // the persistent grids never exceed this, whatever the device: the workspace size is a function of rows alone
+constexpr int kPitchT = 32 + 4;   // halves per row of a [channel][token] tile: 18 dwords, so 32 rows' 8-byte reads cover all 64 banks once
+constexpr int kPartNorm = 4 * kC;                                                   // post, first launch: norm2 weight | bias | s2 = sum g | s1 = sum g1
+constexpr int kOffW1 = kC * kHidden, kOffRp = 2 * kC * kHidden, kOffB1 = kOffRp + kC * kC;
+constexpr int kPartPost = kOffB1 + kHidden;                                         // post, second launch: R2 | gW1 | Rp | gb1
+constexpr int kPartQkv = 3 * kC * kC + 2 * kC;                                      // qkv: gWq | gWk | gWv | norm1 weight | bias
+
+// W (rows, cols) fp32 as stored -> W^T, cols rows of `pitch` halves in LDS
+__device__ __forceinline__ void stage_weight_t(_Float16 *dst, const float *__restrict__ src, int rows, int cols, int pitch) {
+    for (int i = threadIdx.x; i < rows * cols; i += blockDim.x) dst[(i % cols) * pitch + i / cols] = (_Float16)src[i];
+}
+
+// LDS accesses of one wave complete in order; this keeps the compiler from moving a tile's reads across its writes
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// the first half of layernorm(): (row - mean) * rstd and rstd, the same sums in the same order
+struct Normed {
+    Tok xhat;
+    float rstd;
+};
+__device__ __forceinline__ Normed normalise(const Tok &t, float eps) {
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) sum += t.v[i];
+    const float mean = (sum + other_half(sum)) / (float)kC;
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const float d = t.v[i] - mean;
+        sq = fmaf(d, d, sq);
+    }
+    Normed r;
+    r.rstd = 1.0f / sqrtf((sq + other_half(sq)) / (float)kC + eps);
+#pragma unroll
+    for (int i = 0; i < 32; ++i) r.xhat.v[i] = (t.v[i] - mean) * r.rstd;
+    return r;
+}
+// its second half as the B operands: fp16(xhat * weight + bias), layernorm()'s bits
+__device__ __forceinline__ void affine_operand(const Tok &xhat, const float *weight, const float *bias, int h, h4 b[8]) {
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+        const float4 w = chan4(weight, g, h), c = chan4(bias, g, h);
+        b[g][0] = (_Float16)fmaf(xhat.v[4 * g], w.x, c.x);
+        b[g][1] = (_Float16)fmaf(xhat.v[4 * g + 1], w.y, c.y);
+        b[g][2] = (_Float16)fmaf(xhat.v[4 * g + 2], w.z, c.z);
+        b[g][3] = (_Float16)fmaf(xhat.v[4 * g + 3], w.w, c.w);
+    }
+}
+// gradient of the row given gn = dL/d(xhat * weight + bias): rstd * (gh - mean(gh) - xhat * mean(gh * xhat)), gh = gn * weight
+__device__ __forceinline__ Tok layernorm_bwd(const Tok &gn, const Normed &n, const float *weight, int h) {
+    Tok gh;
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+        const float4 w = chan4(weight, g, h);
+        gh.v[4 * g] = gn.v[4 * g] * w.x, gh.v[4 * g + 1] = gn.v[4 * g + 1] * w.y;
+        gh.v[4 * g + 2] = gn.v[4 * g + 2] * w.z, gh.v[4 * g + 3] = gn.v[4 * g + 3] * w.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        s1 += gh.v[i];
+        s2 = fmaf(gh.v[i], n.xhat.v[i], s2);
+    }
+    const float m1 = (s1 + other_half(s1)) / (float)kC, m2 = (s2 + other_half(s2)) / (float)kC;
+    Tok r;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) r.v[i] = n.rstd * (gh.v[i] - m1 - n.xhat.v[i] * m2);
+    return r;
+}
+
+// two accumulators of a 64-row product (rows 0..31 and 32..63) as the token's row
+__device__ __forceinline__ Tok as_tok(const f32x16 &lo, const f32x16 &hi) {
+    Tok t;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t.v[i] = lo[i], t.v[16 + i] = hi[i];
+    return t;
+}
+
+__device__ __forceinline__ void load_operand(const _Float16 *p, int h, bool ok, h4 b[8]) {
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+        const h4 zero = {};
+        b[g] = ok ? *reinterpret_cast<const h4 *>(p + 8 * g + 4 * h) : zero;
+    }
+}
+
+// x += g1 * (Wproj a + bproj), as decoder_post_kernel forms x1
+__device__ __forceinline__ void add_proj(Tok &x, const h4 ab[8], const _Float16 *wp, const float *bp, const float *g1, int lane, int h) {
+#pragma unroll
+    for (int m0 = 0; m0 < kC; m0 += 32) {
+        const f32x16 z = {};
+        const f32x16 p = matmul<8>(wp, kPitchC, m0, 0, ab, z, lane);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int G = m0 / 8 + g;
+            const float4 b = chan4(bp, G, h), s = chan4(g1, G, h);
+            x.v[4 * G] = fmaf(s.x, p[4 * g] + b.x, x.v[4 * G]);
+            x.v[4 * G + 1] = fmaf(s.y, p[4 * g + 1] + b.y, x.v[4 * G + 1]);
+            x.v[4 * G + 2] = fmaf(s.z, p[4 * g + 2] + b.z, x.v[4 * G + 2]);
+            x.v[4 * G + 3] = fmaf(s.w, p[4 * g + 3] + b.w, x.v[4 * G + 3]);
+        }
+    }
+}
+
+// the exact erf GELU and its derivative from one erf: GELU(x) = x Phi(x) (gelu()'s bits: a factor 1/2 is exact wherever it is
+// applied), GELU'(x) = Phi(x) + x phi(x)
+__device__ __forceinline__ float gelu_cdf(float x) { return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)); }
+__device__ __forceinline__ float gelu_grad(float x, float cdf) { return cdf + x * (0.39894228040143267794f * expf(-0.5f * x * x)); }
+
+// G groups of 4 operand values (local channel 8g + 4h + j) of the lane's token into column lane & 31 of a [channel][token] tile;
+// a lane past the last row writes zeros, so that it adds nothing to a sum over tokens whatever it computed
+template <int G>
+__device__ __forceinline__ void put_columns(_Float16 *T, int pitch, int token, const h4 *b, bool ok, int h) {
+    _Float16 *col = T + 4 * h * pitch + token;
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) col[(8 * g + j) * pitch] = ok ? b[g][j] : (_Float16)0.f;
+}
+// rows n0 .. n0 + 31 of a tile as the B operands of the KSTEPS k-steps over its 8 * KSTEPS tokens
+template <int KSTEPS>
+__device__ __forceinline__ void tile_operand(const _Float16 *T, int pitch, int n0, int lane, h4 *b) {
+    const _Float16 *row = T + (n0 + (lane & 31)) * pitch + 4 * (lane >> 5);
+#pragma unroll
+    for (int s = 0; s < KSTEPS; ++s) b[s] = *reinterpret_cast<const h4 *>(row + 8 * s);
+}
+// sum over the 32 tokens of a lane half; both partners of every exchange form the same sum, so all 32 lanes end with the same bits
+__device__ __forceinline__ float sum_tokens(float v) {
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+// acc[r] is element (m0 + acc_row(r, h), n0 + lane & 31) of a row-major matrix with `ld` columns
+__device__ __forceinline__ void store_block(float *M, int ld, int m0, int n0, const f32x16 &acc, int lane) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) M[(m0 + acc_row(r, lane >> 5)) * ld + n0 + (lane & 31)] = acc[r];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// post backward, first launch: gX, g_attn and the partial sums of everything 64-wide: norm2's gradients, s2 = sum g and s1 = sum g1.  Per token, g = gX_out:
+//   gy = gamma2 g;  per hidden chunk: u = W1 n + b1 (recomputed), gu = (W2^T gy) GELU'(u), gn += W1^T gu;
+//   g1 = g + LN2^T(gn);  gX = g1;  g_attn = fp16(Wproj^T (gamma1 g1))
+__global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_data_kernel(
+    const float *__restrict__ X, const _Float16 *__restrict__ attn, const float *__restrict__ wproj, const float *__restrict__ bproj,
+    const float *__restrict__ gamma1, const float *__restrict__ norm_w, const float *__restrict__ norm_b, float eps,
+    const float *__restrict__ w1, const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ gamma2,
+    const float *__restrict__ gX_out, float *__restrict__ gX, _Float16 *__restrict__ g_attn, float *__restrict__ part, int64_t rows,
+    int ntiles) {
+    __shared__ alignas(16) _Float16 wp[kC * kPitchC], wpt[kC * kPitchC];
+    __shared__ alignas(16) _Float16 wf1[kHidden * kPitchC], w1t[kC * kPitchH];
+    __shared__ alignas(16) _Float16 w2t[kHidden * kPitchC];
+    __shared__ alignas(16) float bp[kC], g1[kC], nw[kC], nb[kC], g2[kC], bf1[kHidden];
+    __shared__ float red[kBwdWaves][kPartNorm];
+    stage_weight(wp, wproj, kC, kC, kPitchC);
+    stage_weight_t(wpt, wproj, kC, kC, kPitchC);
+    stage_weight(wf1, w1, kHidden, kC, kPitchC);
+    stage_weight_t(w1t, w1, kHidden, kC, kPitchH);
+    stage_weight_t(w2t, w2, kC, kHidden, kPitchC);
+    stage_vector(bp, bproj, kC);
+    stage_vector(g1, gamma1, kC);
+    stage_vector(nw, norm_w, kC);
+    stage_vector(nb, norm_b, kC);
+    stage_vector(g2, gamma2, kC);
+    stage_vector(bf1, b1, kHidden);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, h = lane >> 5, wave = threadIdx.x >> 6;
+    Tok acc_w = {}, acc_b = {}, s2 = {}, s1 = {};  // this lane's tokens' share of norm2's weight and bias gradients, of sum g and of sum g1
+    for (int tile = blockIdx.x * kBwdWaves + wave; tile < ntiles; tile += gridDim.x * kBwdWaves) {  // (no barrier in the loop)
+        asm volatile("" ::: "memory");  // (the weights are read again for every tile, as in the forward)
+        const int64_t row = (int64_t)tile * 32 + (lane & 31);
+        const bool ok = row < rows;
+        const int64_t off = (ok ? row : 0) * kC;
+        Tok x = load_tok(X + off, h, ok);
+        const Tok g = load_tok(gX_out + off, h, ok);
+        h4 ab[8], nx[8], gyb[8];
+        load_operand(attn + off, h, ok, ab);
+        add_proj(x, ab, wp, bp, g1, lane, h);
+        const Normed n = normalise(x, eps);
+        affine_operand(n.xhat, nw, nb, h, nx);
+#pragma unroll
+        for (int G = 0; G < 8; ++G) {
+            const float4 s = chan4(g2, G, h);
+            gyb[G][0] = (_Float16)(s.x * g.v[4 * G]), gyb[G][1] = (_Float16)(s.y * g.v[4 * G + 1]);
+            gyb[G][2] = (_Float16)(s.z * g.v[4 * G + 2]), gyb[G][3] = (_Float16)(s.w * g.v[4 * G + 3]);
+        }
+        f32x16 gn0 = {}, gn1 = {};  // W1^T gu, rows 0..31 and 32..63
+#pragma unroll 1
+        for (int c0 = 0; c0 < kHidden; c0 += 32) {
+            const f32x16 z = {};
+            const f32x16 u = matmul<8>(wf1, kPitchC, c0, 0, nx, z, lane);
+            const f32x16 ga = matmul<8>(w2t, kPitchC, c0, 0, gyb, z, lane);
+            h4 gub[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 b = *reinterpret_cast<const float4 *>(bf1 + c0 + 8 * q + 4 * h);
+                const float bj[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float uu = u[4 * q + j] + bj[j];
+                    gub[q][j] = (_Float16)(ga[4 * q + j] * gelu_grad(uu, gelu_cdf(uu)));
+                }
+            }
+            gn0 = matmul<4>(w1t, kPitchH, 0, c0, gub, gn0, lane);
+            gn1 = matmul<4>(w1t, kPitchH, 32, c0, gub, gn1, lane);
+        }
+        const Tok gn = as_tok(gn0, gn1);
+        if (ok) {
+#pragma unroll
+            for (int i = 0; i < 32; ++i) {
+                acc_w.v[i] = fmaf(gn.v[i], n.xhat.v[i], acc_w.v[i]);
+                acc_b.v[i] += gn.v[i];
+            }
+        }
+        Tok gx = layernorm_bwd(gn, n, nw, h);
+        h4 gpb[8];
+#pragma unroll
+        for (int G = 0; G < 8; ++G) {
+            const float4 s = chan4(g1, G, h);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) gx.v[4 * G + j] += g.v[4 * G + j];
+            gpb[G][0] = (_Float16)(s.x * gx.v[4 * G]), gpb[G][1] = (_Float16)(s.y * gx.v[4 * G + 1]);
+            gpb[G][2] = (_Float16)(s.z * gx.v[4 * G + 2]), gpb[G][3] = (_Float16)(s.w * gx.v[4 * G + 3]);
+        }
+        if (ok) {
+            store_tok(gX + off, h, gx);
+#pragma unroll
+            for (int i = 0; i < 32; ++i) s2.v[i] += g.v[i], s1.v[i] += gx.v[i];
+        }
+#pragma unroll
+        for (int m0 = 0; m0 < kC; m0 += 32) {
+            const f32x16 z = {};
+            const f32x16 ga = matmul<8>(wpt, kPitchC, m0, 0, gpb, z, lane);
+            if (ok) store_proj(g_attn + off, m0, h, ga);
+        }
+    }
+    // this workgroup's partial: tokens of a wave first, then the waves in order
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const float sw = sum_tokens(acc_w.v[i]), sb = sum_tokens(acc_b.v[i]), t2 = sum_tokens(s2.v[i]), t1 = sum_tokens(s1.v[i]);
+        if ((lane & 31) == 0) {
+            const int c = 8 * (i >> 2) + 4 * h + (i & 3);
+            red[wave][c] = sw, red[wave][kC + c] = sb, red[wave][2 * kC + c] = t2, red[wave][3 * kC + c] = t1;
+        }
+    }
+    __syncthreads();
+    static_assert(kPartNorm <= kBwdThreads, "one thread per sum");
+    if (threadIdx.x < kPartNorm) {
+        float s = red[0][threadIdx.x];
+        for (int w = 1; w < kBwdWaves; ++w) s += red[w][threadIdx.x];
+        part[(int64_t)blockIdx.x * kPartNorm + threadIdx.x] = s;
+    }
+}
+
+// post backward, second launch: the sums over tokens behind the parameter gradients, with x1, n, u recomputed and g1 = gX read back:
+//   R2 = g (x) act, gW1 = gu (x) n, gb1 = sum gu, Rp = g1 (x) a
+// A workgroup takes one 32-token tile at a time; its wave w owns hidden units 64w .. 64w + 63 (those columns of R2, rows of gW1) and
+// one 32 x 32 block of Rp, so each sum has one owner and no wave waits for another.
+__global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_weight_kernel(
+    const float *__restrict__ X, const _Float16 *__restrict__ attn, const float *__restrict__ wproj, const float *__restrict__ bproj,
+    const float *__restrict__ gamma1, const float *__restrict__ norm_w, const float *__restrict__ norm_b, float eps,
+    const float *__restrict__ w1, const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ gamma2,
+    const float *__restrict__ gX_out, const float *__restrict__ gX, float *__restrict__ part, int64_t rows, int ntiles) {
+    __shared__ alignas(16) _Float16 wp[kC * kPitchC];
+    __shared__ alignas(16) _Float16 wf1[kHidden * kPitchC];
+    __shared__ alignas(16) _Float16 w2t[kHidden * kPitchC];
+    __shared__ alignas(16) float bp[kC], g1[kC], nw[kC], nb[kC], g2[kC], bf1[kHidden];
+    __shared__ alignas(16) _Float16 tiles[kBwdWaves][(kC + kC + 32 + 32) * kPitchT];
+    stage_weight(wp, wproj, kC, kC, kPitchC);
+    stage_weight(wf1, w1, kHidden, kC, kPitchC);
+    stage_weight_t(w2t, w2, kC, kHidden, kPitchC);
+    stage_vector(bp, bproj, kC);
+    stage_vector(g1, gamma1, kC);
+    stage_vector(nw, norm_w, kC);
+    stage_vector(nb, norm_b, kC);
+    stage_vector(g2, gamma2, kC);
+    stage_vector(bf1, b1, kHidden);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, h = lane >> 5, wave = threadIdx.x >> 6;
+    _Float16 *Tg = tiles[wave], *Tn = Tg + kC * kPitchT, *Ta = Tn + kC * kPitchT, *Tu = Ta + 32 * kPitchT;
+    f32x16 r2[2][2] = {}, gw1[2][2] = {}, rp = {};  // [hidden chunk of the wave][32-channel block]
+    float gb1[2][16] = {};
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // (no workgroup barrier in the loop)
+        asm volatile("" ::: "memory");
+        const int64_t row = (int64_t)tile * 32 + (lane & 31);
+        const bool ok = row < rows;
+        const int64_t off = (ok ? row : 0) * kC;
+        Tok x = load_tok(X + off, h, ok);
+        const Tok g = load_tok(gX_out + off, h, ok), gx = load_tok(gX + off, h, ok);
+        h4 ab[8], nx[8], gyb[8], gb[8], g1b[8];
+        load_operand(attn + off, h, ok, ab);
+        add_proj(x, ab, wp, bp, g1, lane, h);
+        const Normed n = normalise(x, eps);
+        affine_operand(n.xhat, nw, nb, h, nx);
+#pragma unroll
+        for (int G = 0; G < 8; ++G) {
+            const float4 s = chan4(g2, G, h);
+            gyb[G][0] = (_Float16)(s.x * g.v[4 * G]), gyb[G][1] = (_Float16)(s.y * g.v[4 * G + 1]);
+            gyb[G][2] = (_Float16)(s.z * g.v[4 * G + 2]), gyb[G][3] = (_Float16)(s.w * g.v[4 * G + 3]);
+        }
+        to_operand(g, gb);
+        to_operand(gx, g1b);
+        wave_sync();  // the previous tile's reads are done
+        put_columns<8>(Tg, kPitchT, lane & 31, gb, ok, h);
+        put_columns<8>(Tn, kPitchT, lane & 31, nx, ok, h);
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+            const int c0 = 64 * wave + 32 * cc;
+            const f32x16 z = {};
+            const f32x16 u = matmul<8>(wf1, kPitchC, c0, 0, nx, z, lane);
+            const f32x16 ga = matmul<8>(w2t, kPitchC, c0, 0, gyb, z, lane);
+            h4 actb[4], gub[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 b = *reinterpret_cast<const float4 *>(bf1 + c0 + 8 * q + 4 * h);
+                const float bj[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float uu = u[4 * q + j] + bj[j];
+                    const float cdf = gelu_cdf(uu);
+                    const float gu = ok ? ga[4 * q + j] * gelu_grad(uu, cdf) : 0.f;
+                    actb[q][j] = (_Float16)(uu * cdf);
+                    gub[q][j] = (_Float16)gu;
+                    gb1[cc][4 * q + j] += gu;
+                }
+            }
+            wave_sync();  // the previous chunk's reads of Ta and Tu are done
+            put_columns<4>(Ta, kPitchT, lane & 31, actb, ok, h);
+            put_columns<4>(Tu, kPitchT, lane & 31, gub, ok, h);
+            wave_sync();
+            h4 b[4];
+            tile_operand<4>(Ta, kPitchT, 0, lane, b);
+            r2[cc][0] = matmul<4>(Tg, kPitchT, 0, 0, b, r2[cc][0], lane);
+            r2[cc][1] = matmul<4>(Tg, kPitchT, 32, 0, b, r2[cc][1], lane);
+            tile_operand<4>(Tn, kPitchT, 0, lane, b);
+            gw1[cc][0] = matmul<4>(Tu, kPitchT, 0, 0, b, gw1[cc][0], lane);
+            tile_operand<4>(Tn, kPitchT, 32, lane, b);
+            gw1[cc][1] = matmul<4>(Tu, kPitchT, 0, 0, b, gw1[cc][1], lane);
+        }
+        // Rp's block (wave >> 1, wave & 1): rows from g1, columns from a
+        wave_sync();
+        if (wave >> 1) put_columns<4>(Ta, kPitchT, lane & 31, g1b + 4, ok, h);
+        else put_columns<4>(Ta, kPitchT, lane & 31, g1b, ok, h);
+        if (wave & 1) put_columns<4>(Tu, kPitchT, lane & 31, ab + 4, ok, h);
+        else put_columns<4>(Tu, kPitchT, lane & 31, ab, ok, h);
+        wave_sync();
+        h4 b[4];
+        tile_operand<4>(Tu, kPitchT, 0, lane, b);
+        rp = matmul<4>(Ta, kPitchT, 0, 0, b, rp, lane);
+    }
+    float *P = part + (int64_t)blockIdx.x * kPartPost;
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc) {
+        const int c0 = 64 * wave + 32 * cc;
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            store_block(P, kHidden, 32 * m, c0, r2[cc][m], lane);       // R2[c][hidden]
+            store_block(P + kOffW1, kC, c0, 32 * m, gw1[cc][m], lane);  // gW1[hidden][c]
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float s = sum_tokens(gb1[cc][i]);
+            if ((lane & 31) == 0) P[kOffB1 + c0 + 8 * (i >> 2) + 4 * h + (i & 3)] = s;
+        }
+    }
+    store_block(P + kOffRp, kC, 32 * (wave >> 1), 32 * (wave & 1), rp, lane);
+}
+
+// the second stage of both backwards: sums[i] = sum over the workgroups g of part[g][i], for two sets of partials in one launch (a of
+// na values from ga workgroups, then b).  A block takes 32 values; its 8 groups of 32 threads each add every 8th workgroup's partial
+// in order, and the 8 sums meet in a fixed tree: the result depends on the number of workgroups, which depends on rows alone.
+constexpr int kSumThreads = 256;
+__global__ __launch_bounds__(kSumThreads) void decoder_bwd_sum_partials_kernel(const float *__restrict__ a, int ga, int na,
+                                                                               const float *__restrict__ b, int gb, int nb,
+                                                                               float *__restrict__ sums) {
+    __shared__ float red[8][32];
+    const int blocks_a = na / 32, e = threadIdx.x & 31, part = threadIdx.x >> 5;
+    const bool first = (int)blockIdx.x < blocks_a;
+    const float *p = first ? a : b;
+    const int groups = first ? ga : gb, n = first ? na : nb, i = (first ? blockIdx.x : blockIdx.x - blocks_a) * 32 + e;
+    float s = 0.f;
+    for (int g = part; g < groups; g += 8) s += p[(int64_t)g * n + i];
+    red[part][e] = s;
+    __syncthreads();
+    if (part == 0)
+        sums[(first ? 0 : na) + i] = ((red[0][e] + red[1][e]) + (red[2][e] + red[3][e])) + ((red[4][e] + red[5][e]) + (red[6][e] + red[7][e]));
+}
+
+// post backward, last launch: the LayerScales taken out of the sums (pn and pw are now the totals of the first and second launch):
+//   gW2 = gamma2_c R2, gb2 = gamma2_c s2, ggamma2_c = sum_h W2[c][h] R2[c][h] + b2_c s2_c, and the same for gamma1 with Wproj, bproj
+// blocks 0..63: channel c of everything 64-wide; 64..127: gW1; 128: gb1
+__global__ __launch_bounds__(256) void decoder_post_bwd_finish_kernel(const float *__restrict__ pn, const float *__restrict__ pw,
+                                                                      const float *__restrict__ wproj, const float *__restrict__ bproj,
+                                                                      const float *__restrict__ gamma1, const float *__restrict__ w2,
+                                                                      const float *__restrict__ b2, const float *__restrict__ gamma2,
+                                                                      float *__restrict__ g_wproj, float *__restrict__ g_bproj,
+                                                                      float *__restrict__ g_gamma1, float *__restrict__ g_norm_w,
+                                                                      float *__restrict__ g_norm_b, float *__restrict__ g_w1,
+                                                                      float *__restrict__ g_b1, float *__restrict__ g_w2,
+                                                                      float *__restrict__ g_b2, float *__restrict__ g_gamma2) {
+    __shared__ float red[256];
+    const int t = threadIdx.x, b = blockIdx.x;
+    auto block_sum = [&](float v) {  // a fixed tree over the 256 threads
+        red[t] = v;
+        __syncthreads();
+        for (int s = 128; s >= 1; s >>= 1) {
+            if (t < s) red[t] += red[t + s];
+            __syncthreads();
+        }
+        const float r = red[0];
+        __syncthreads();
+        return r;
+    };
+    if (b < kC) {
+        const int c = b;
+        const float r = pw[c * kHidden + t];
+        g_w2[c * kHidden + t] = gamma2[c] * r;
+        const float dot2 = block_sum(w2[c * kHidden + t] * r);
+        float dp = 0.f;
+        if (t < kC) {
+            const float q = pw[kOffRp + c * kC + t];
+            g_wproj[c * kC + t] = gamma1[c] * q;
+            dp = wproj[c * kC + t] * q;
+        }
+        const float dot1 = block_sum(dp);
+        if (t == 0) {
+            const float s2 = pn[2 * kC + c], s1 = pn[3 * kC + c];
+            g_b2[c] = gamma2[c] * s2;
+            g_gamma2[c] = dot2 + b2[c] * s2;
+            g_bproj[c] = gamma1[c] * s1;
+            g_gamma1[c] = dot1 + bproj[c] * s1;
+            g_norm_w[c] = pn[c];
+            g_norm_b[c] = pn[kC + c];
+        }
+    } else if (b < 2 * kC) {
+        const int i = (b - kC) * 256 + t;
+        g_w1[i] = pw[kOffW1 + i];
+    } else {
+        g_b1[t] = pw[kOffB1 + t];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// qkv backward: gX = LN1^T(Wq^T gq) + Wk^T gk' + Wv^T gv', with gk', gv' read where the forward wrote the row's k and v (the other
+// view's batch entry), and the partial sums of gWq = gq (x) n, gWk = gk' (x) x, gWv = gv' (x) x and norm1's gradients.  A workgroup
+// takes four tiles at a time: wave w computes gX of tile w and leaves its five operands in the shared [channel][128 tokens] images,
+// then owns block (w >> 1, w & 1) of each of the three weight gradients over all 128 tokens.
+constexpr int kPitchQ = 32 * kBwdWaves + 4;  // 66 dwords a row: 32 rows' 8-byte reads cover all 64 banks once
+__global__ __launch_bounds__(kBwdThreads) void decoder_qkv_bwd_kernel(const float *__restrict__ X, const float *__restrict__ norm_w,
+                                                                      const float *__restrict__ norm_b, float eps,
+                                                                      const float *__restrict__ wq, const float *__restrict__ wk,
+                                                                      const float *__restrict__ wv, const _Float16 *__restrict__ gq,
+                                                                      const _Float16 *__restrict__ gk, const _Float16 *__restrict__ gv,
+                                                                      float *__restrict__ gX, float *__restrict__ part, int64_t rows,
+                                                                      int ntiles) {
+    __shared__ alignas(16) _Float16 wt[3][kC * kPitchC];
+    __shared__ alignas(16) float nw[kC], nb[kC];
+    __shared__ alignas(16) _Float16 T[5][kC * kPitchQ];  // gq | gk' | gv' | n | x
+    __shared__ float red[kBwdWaves][2 * kC];
+    stage_weight_t(wt[0], wq, kC, kC, kPitchC);
+    stage_weight_t(wt[1], wk, kC, kC, kPitchC);
+    stage_weight_t(wt[2], wv, kC, kC, kPitchC);
+    stage_vector(nw, norm_w, kC);
+    stage_vector(nb, norm_b, kC);
+    const int lane = threadIdx.x & 63, h = lane >> 5, wave = threadIdx.x >> 6;
+    const int m0 = 32 * (wave >> 1), n0 = 32 * (wave & 1);
+    f32x16 gw[3] = {};  // this wave's block of gWq, gWk, gWv
+    Tok acc_w = {}, acc_b = {};
+    for (int first = blockIdx.x * kBwdWaves; first < ntiles; first += gridDim.x * kBwdWaves) {  // (every wave makes every trip)
+        const int64_t row = (int64_t)(first + wave) * 32 + (lane & 31);
+        const bool ok = row < rows;
+        const int64_t off = (ok ? row : 0) * kC;
+        const int64_t other = (ok ? (row + rows / 2 < rows ? row + rows / 2 : row - rows / 2) : 0) * kC;
+        const Tok x = load_tok(X + off, h, ok);
+        h4 xb[8], nx[8], gb[3][8];
+        load_operand(gq + off, h, ok, gb[0]);
+        load_operand(gk + other, h, ok, gb[1]);
+        load_operand(gv + other, h, ok, gb[2]);
+        to_operand(x, xb);
+        const Normed n = normalise(x, eps);
+        affine_operand(n.xhat, nw, nb, h, nx);
+        __syncthreads();  // the weights are staged; the previous trip's reads of T are done
+#pragma unroll
+        for (int p = 0; p < 3; ++p) put_columns<8>(T[p], kPitchQ, 32 * wave + (lane & 31), gb[p], ok, h);
+        put_columns<8>(T[3], kPitchQ, 32 * wave + (lane & 31), nx, ok, h);
+        put_columns<8>(T[4], kPitchQ, 32 * wave + (lane & 31), xb, ok, h);
+        const f32x16 z = {};
+        const Tok gn = as_tok(matmul<8>(wt[0], kPitchC, 0, 0, gb[0], z, lane), matmul<8>(wt[0], kPitchC, 32, 0, gb[0], z, lane));
+        if (ok) {
+#pragma unroll
+            for (int i = 0; i < 32; ++i) {
+                acc_w.v[i] = fmaf(gn.v[i], n.xhat.v[i], acc_w.v[i]);
+                acc_b.v[i] += gn.v[i];
+            }
+        }
+        Tok gx = layernorm_bwd(gn, n, nw, h);
+        const Tok gkv = as_tok(matmul<8>(wt[2], kPitchC, 0, 0, gb[2], matmul<8>(wt[1], kPitchC, 0, 0, gb[1], z, lane), lane),
+                               matmul<8>(wt[2], kPitchC, 32, 0, gb[2], matmul<8>(wt[1], kPitchC, 32, 0, gb[1], z, lane), lane));
+#pragma unroll
+        for (int i = 0; i < 32; ++i) gx.v[i] += gkv.v[i];
+        if (ok) store_tok(gX + off, h, gx);
+        __syncthreads();  // all four tiles' operands are in T
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            h4 b[4 * kBwdWaves];
+            tile_operand<4 * kBwdWaves>(T[p == 0 ? 3 : 4], kPitchQ, n0, lane, b);
+            gw[p] = matmul<4 * kBwdWaves>(T[p], kPitchQ, m0, 0, b, gw[p], lane);
+        }
+    }
+    float *P = part + (int64_t)blockIdx.x * kPartQkv;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) store_block(P + p * kC * kC, kC, m0, n0, gw[p], lane);
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const float sw = sum_tokens(acc_w.v[i]), sb = sum_tokens(acc_b.v[i]);
+        if ((lane & 31) == 0) {
+            const int c = 8 * (i >> 2) + 4 * h + (i & 3);
+            red[wave][c] = sw, red[wave][kC + c] = sb;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * kC) {
+        float s = red[0][threadIdx.x];
+        for (int w = 1; w < kBwdWaves; ++w) s += red[w][threadIdx.x];  // wave order
+        P[3 * kC * kC + threadIdx.x] = s;
+    }
+}
+
+// qkv backward, last launch: the totals to where they belong
+__global__ __launch_bounds__(256) void decoder_qkv_bwd_finish_kernel(const float *__restrict__ sums, float *__restrict__ g_wq,
+                                                                     float *__restrict__ g_wk, float *__restrict__ g_wv,
+                                                                     float *__restrict__ g_norm_w, float *__restrict__ g_norm_b) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= kPartQkv) return;
+    const float s = sums[i];
+    const int m = i / (kC * kC);
+    if (m == 0) g_wq[i] = s;
+    else if (m == 1) g_wk[i - kC * kC] = s;
+    else if (m == 2) g_wv[i - 2 * kC * kC] = s;
+    else if (i < 3 * kC * kC + kC) g_norm_w[i - 3 * kC * kC] = s;
+    else g_norm_b[i - 3 * kC * kC - kC] = s;
+}
+
+// workgroups of a persistent backward grid: one per `per_group` tiles, kMaxGroups at most
+int bwd_groups(int64_t rows, int per_group) {
+    const int64_t groups = ((rows + 31) / 32 + per_group - 1) / per_group;
+    return (int)(groups < kMaxGroups ? groups : kMaxGroups);
+}
+constexpr int kDataTiles = kBwdWaves, kWeightTiles = 4;  // tiles per workgroup before a grid stops growing
+static_assert(kPartNorm % 32 == 0 && kPartPost % 32 == 0 && kPartQkv % 32 == 0, "decoder_bwd_sum_partials_kernel takes 32 values a block");
+// the workgroups' partials, then their totals
+int64_t bwd_ws_floats(int64_t rows) {
+    const int64_t post = (int64_t)(bwd_groups(rows, kDataTiles) + 1) * kPartNorm + (int64_t)(bwd_groups(rows, kWeightTiles) + 1) * kPartPost;
+    const int64_t qkv = (int64_t)(bwd_groups(rows, kDataTiles) + 1) * kPartQkv;
+    return post > qkv ? post : qkv;
+}
+int check_ws(const char *what, int64_t rows, int64_t ws_bytes) {
+    const int64_t need = bwd_ws_floats(rows) * (int64_t)sizeof(float);
+    if (ws_bytes < need)
+        return gfn::fail(GFN_ERR_INVALID_ARG, "%s: ws_bytes = %lld is too small, gfn_decoder_bwd_ws_bytes(%lld) = %lld", what, (long long)ws_bytes,
+                         (long long)rows, (long long)need);
+    return GFN_OK;
+}
+
+}  // namespace
+
+GFN_EXPORT int64_t gfn_decoder_bwd_ws_bytes(int64_t rows) {
+    if (rows <= 0 || rows > (int64_t)INT_MAX - 31) return 0;
+    return bwd_ws_floats(rows) * (int64_t)sizeof(float);
+}
+
+GFN_EXPORT int gfn_decoder_qkv_bwd(const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq,
+                                   const float *wk, const float *wv, const void *gq, const void *gk, const void *gv, int B2, int N, int C,
+                                   float *gx, float *g_wq, float *g_wk, float *g_wv, float *g_norm_weight, float *g_norm_bias, void *ws,
+                                   int64_t ws_bytes, gfn_stream_t stream) {
+    const char *what = "gfn_decoder_qkv_bwd";
+    if (B2 < 0 || N < 1) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: bad size (batch %d, N %d)", what, B2, N);
+    if (B2 & 1) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: the batch holds both views and must be even, got %d", what, B2);
+    const int64_t rows = (int64_t)B2 * N;
+    if (int rc = check_args(what, rows, C, kHidden, eps,
+                            {{x, "x"}, {norm_weight, "norm_weight"}, {norm_bias, "norm_bias"}, {wq, "wq"}, {wk, "wk"}, {wv, "wv"},
+                             {gq, "gq"}, {gk, "gk"}, {gv, "gv"}, {gx, "gx"}, {g_wq, "g_wq"}, {g_wk, "g_wk"}, {g_wv, "g_wv"},
+                             {g_norm_weight, "g_norm_weight"}, {g_norm_bias, "g_norm_bias"}, {ws, "ws"}}))
+        return rc;
+    if (rows == 0) return GFN_OK;
+    if (int rc = check_ws(what, rows, ws_bytes)) return rc;
+    const int ntiles = (int)((rows + 31) / 32), groups = bwd_groups(rows, kDataTiles);
+    hipLaunchKernelGGL(decoder_qkv_bwd_kernel, dim3(groups), dim3(kBwdThreads), 0, (hipStream_t)stream, x, norm_weight, norm_bias, eps, wq, wk,
+                       wv, (const _Float16 *)gq, (const _Float16 *)gk, (const _Float16 *)gv, gx, (float *)ws, rows, ntiles);
+    if (int rc = gfn::check_launch("decoder_qkv_bwd_kernel")) return rc;
+    float *sums = (float *)ws + (int64_t)groups * kPartQkv;
+    hipLaunchKernelGGL(decoder_bwd_sum_partials_kernel, dim3(kPartQkv / 32), dim3(kSumThreads), 0, (hipStream_t)stream, (const float *)ws, groups,
+                       kPartQkv, (const float *)nullptr, 0, 0, sums);
+    if (int rc = gfn::check_launch("decoder_bwd_sum_partials_kernel")) return rc;
+    hipLaunchKernelGGL(decoder_qkv_bwd_finish_kernel, dim3((kPartQkv + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float *)sums, g_wq,
+                       g_wk, g_wv, g_norm_weight, g_norm_bias);
+    return gfn::check_launch("decoder_qkv_bwd_finish_kernel");
+}
+
+GFN_EXPORT int gfn_decoder_post_bwd(const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,
+                                    const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1,
+                                    const float *w2, const float *b2, const float *gamma2, const float *gx_out, int64_t rows, int C,
+                                    int hidden, float *gx, void *g_attn, float *g_wproj, float *g_bproj, float *g_gamma1,
+                                    float *g_norm_weight, float *g_norm_bias, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
+                                    float *g_gamma2, void *ws, int64_t ws_bytes, gfn_stream_t stream) {
+    const char *what = "gfn_decoder_post_bwd";
+    if (int rc = check_args(what, rows, C, hidden, eps,
+                            {{x, "x"}, {attn, "attn"}, {wproj, "wproj"}, {bproj, "bproj"}, {gamma1, "gamma1"}, {norm_weight, "norm_weight"},
+                             {norm_bias, "norm_bias"}, {w1, "w1"}, {b1, "b1"}, {w2, "w2"}, {b2, "b2"}, {gamma2, "gamma2"}, {gx_out, "gx_out"},
+                             {gx, "gx"}, {g_attn, "g_attn"}, {g_wproj, "g_wproj"}, {g_bproj, "g_bproj"}, {g_gamma1, "g_gamma1"},
+                             {g_norm_weight, "g_norm_weight"}, {g_norm_bias, "g_norm_bias"}, {g_w1, "g_w1"}, {g_b1, "g_b1"}, {g_w2, "g_w2"},
+                             {g_b2, "g_b2"}, {g_gamma2, "g_gamma2"}, {ws, "ws"}}))
+        return rc;
+    if (rows == 0) return GFN_OK;
+    if (int rc = check_ws(what, rows, ws_bytes)) return rc;
+    const int ntiles = (int)((rows + 31) / 32), groups_n = bwd_groups(rows, kDataTiles), groups_w = bwd_groups(rows, kWeightTiles);
+    float *pn = (float *)ws, *pw = pn + (int64_t)groups_n * kPartNorm, *sums = pw + (int64_t)groups_w * kPartPost;
+    hipLaunchKernelGGL(decoder_post_bwd_data_kernel, dim3(groups_n), dim3(kBwdThreads), 0, (hipStream_t)stream, x, (const _Float16 *)attn, wproj,
+                       bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, gamma2, gx_out, gx, (_Float16 *)g_attn, pn, rows, ntiles);
+    if (int rc = gfn::check_launch("decoder_post_bwd_data_kernel")) return rc;
+    hipLaunchKernelGGL(decoder_post_bwd_weight_kernel, dim3(groups_w), dim3(kBwdThreads), 0, (hipStream_t)stream, x, (const _Float16 *)attn,
+                       wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, gamma2, gx_out, (const float *)gx, pw, rows, ntiles);
+    if (int rc = gfn::check_launch("decoder_post_bwd_weight_kernel")) return rc;
+    hipLaunchKernelGGL(decoder_bwd_sum_partials_kernel, dim3((kPartNorm + kPartPost) / 32), dim3(kSumThreads), 0, (hipStream_t)stream,
+                       (const float *)pn, groups_n, kPartNorm, (const float *)pw, groups_w, kPartPost, sums);
+    if (int rc = gfn::check_launch("decoder_bwd_sum_partials_kernel")) return rc;
+    hipLaunchKernelGGL(decoder_post_bwd_finish_kernel, dim3(2 * kC + 1), dim3(256), 0, (hipStream_t)stream, (const float *)sums,
+                       (const float *)(sums + kPartNorm), wproj, bproj, gamma1, w2, b2, gamma2, g_wproj, g_bproj, g_gamma1, g_norm_weight,
+                       g_norm_bias, g_w1, g_b1, g_w2, g_b2, g_gamma2);
+    return gfn::check_launch("decoder_post_bwd_finish_kernel");
 }

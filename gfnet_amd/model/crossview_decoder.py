@@ -22,6 +22,13 @@ projections, csrc/decoder_block.hip), ops.cross_attention, ops.decoder_post (out
 norm2 and the MLP); the entry projection and the position encoding stay torch.  Whatever that path is not built for -- train(),
 tensors off the GPU, no fp16 autocast, parameters that are not fp32, attn_impl="torch", anything that requires grad -- runs the
 torch blocks, exactly as block_impl="torch" does.
+
+train_block_impl="torch" (the default) leaves train() to those torch blocks and autograd.  train_block_impl="hip" trains the blocks
+in HIP: in train() with grad mode on, on CUDA tensors under fp16 autocast (the reference's training class, model/network.py:171)
+with fp32 parameters and the HIP attention, a block is ops.decoder_qkv_train -> ops.cross_attention -> ops.decoder_post_train on
+cat(x, y), the same three forward launches (not in place) with the backward kernels of csrc/decoder_block.hip behind them; what
+autograd keeps per block is X, q, k, v, the attention output and its log-sum-exp.  The entry projection, the position encoding and
+the concatenation stay torch, so autograd carries the gradient on to proj.weight and the tokens.  Every other call is unchanged.
 """
 import math
 
@@ -32,6 +39,7 @@ from .. import ops
 
 ATTN_IMPLS = ("hip", "torch")
 BLOCK_IMPLS = ("torch", "hip")
+TRAIN_BLOCK_IMPLS = ("torch", "hip")
 MAX_SHAPE = (128, 128)  # crossview_decoder_light.py:37: the extent the position encoding normalises to
 
 
@@ -124,6 +132,19 @@ class CrossBlock(nn.Module):
                                 self.norm2.bias, self.norm2.eps, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight,
                                 self.mlp.fc2.bias, gamma2, inplace=True)
 
+    def forward_train(self, X):
+        """The block on X = cat(x, y), (2B, N, dim) fp32, differentiable and not in place: the same three launches with the HIP
+        backward behind each (CrossViewDecoder._train_fused says when).  Returns the new residual stream."""
+        attn, N = self.attn, X.shape[1]
+        q, k, v = ops.decoder_qkv_train(X, self.norm1.weight, self.norm1.bias, self.norm1.eps, attn.q_proj.weight, attn.k_proj.weight,
+                                        attn.v_proj.weight)
+        scale = attn.scale if attn.softmax_scale is None else attn.scale * math.log(N, attn.train_avg_length)
+        # (init_values None: no LayerScale, a constant gamma of 1 that takes no gradient)
+        gamma1, gamma2 = (ls.gamma if isinstance(ls, LayerScale) else torch.ones_like(self.norm1.weight) for ls in (self.ls1, self.ls2))
+        return ops.decoder_post_train(X, ops.cross_attention(q, k, v, scale), attn.proj.weight, attn.proj.bias, gamma1, self.norm2.weight,
+                                      self.norm2.bias, self.norm2.eps, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight,
+                                      self.mlp.fc2.bias, gamma2)
+
 
 def _check_cfg(cfg):
     """Raise, naming the key, for every setting of decoder_cfg whose reference behaviour is not built here."""
@@ -142,16 +163,18 @@ class CrossViewDecoder(nn.Module):
     """`decoder(x, y, vit_shape=(B, _, H, W)) -> (map_x, map_y)`: ViT patch tokens (B, H*W, d_model) of the two views -> their
     stride-16 feature maps (B, out_dim, H, W), out_dim = conf["encoder_cfg"]["feat_chs"][0] (64: 8 heads of dim 8)."""
 
-    def __init__(self, conf, attn_impl="hip", block_impl="torch"):
+    def __init__(self, conf, attn_impl="hip", block_impl="torch", train_block_impl="torch"):
         super().__init__()
         if attn_impl not in ATTN_IMPLS:
             raise ValueError(f"attn_impl must be one of {ATTN_IMPLS}, got {attn_impl!r}")
         if block_impl not in BLOCK_IMPLS:
             raise ValueError(f"block_impl must be one of {BLOCK_IMPLS}, got {block_impl!r}")
+        if train_block_impl not in TRAIN_BLOCK_IMPLS:
+            raise ValueError(f"train_block_impl must be one of {TRAIN_BLOCK_IMPLS}, got {train_block_impl!r}")
         cfg = conf["dino_cfg"]["decoder_cfg"]
         _check_cfg(cfg)
         dim = conf["encoder_cfg"]["feat_chs"][0]
-        self.dim, self.attn_impl, self.block_impl = dim, attn_impl, block_impl
+        self.dim, self.attn_impl, self.block_impl, self.train_block_impl = dim, attn_impl, block_impl, train_block_impl
         self.cross_attn_blocks = nn.ModuleList(
             CrossBlock(dim, cfg["nhead"], cfg.get("init_values"), cfg.get("softmax_scale"), cfg.get("train_avg_length"), attn_impl)
             for _ in range(cfg["num_cross_attn"]))
@@ -164,10 +187,23 @@ class CrossViewDecoder(nn.Module):
             self._pe[key] = sine_position_encoding(self.dim, H, W).flatten(2).transpose(1, 2).contiguous().to(device)
         return self._pe[key]
 
+    def _train_fused(self, x, y):
+        """Whether this call trains the blocks in HIP: train_block_impl="hip" with the HIP attention, train() with grad mode on,
+        CUDA tensors under fp16 autocast, fp32 parameters."""
+        if self.train_block_impl != "hip" or not self.training or not torch.is_grad_enabled():
+            return False
+        return self._kernel_class(x, y)
+
     def _fused(self, x, y):
         """Whether this call takes the fused blocks: block_impl="hip" with the HIP attention, inference (eval() and nothing that
         requires grad) on CUDA tensors under fp16 autocast with fp32 parameters -- the class decoder_block.hip is written in."""
-        if self.block_impl != "hip" or self.attn_impl != "hip" or self.training or not (x.is_cuda and y.is_cuda):
+        if self.block_impl != "hip" or self.training or not self._kernel_class(x, y):
+            return False
+        return not (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad or any(p.requires_grad for p in self.parameters())))
+
+    def _kernel_class(self, x, y):
+        """The class decoder_block.hip is written in: the HIP attention, width 64, CUDA tensors under fp16 autocast, fp32 parameters."""
+        if self.attn_impl != "hip" or not (x.is_cuda and y.is_cuda):
             return False
         if self.dim != ops.DECODER_DIM or any(b.attn.num_heads * 8 != self.dim for b in self.cross_attn_blocks):  # (the one width it is built for)
             return False
@@ -175,16 +211,21 @@ class CrossViewDecoder(nn.Module):
             return False
         if any(p.dtype != torch.float32 or not p.is_cuda for p in self.parameters()):
             return False
-        return not (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad or any(p.requires_grad for p in self.parameters())))
+        return True
 
     def forward(self, x, y, vit_shape=None):
         B, _, H, W = vit_shape
         pe = self.position_encoding(H, W, x.device)
         if x.dtype == torch.float64:
             pe = pe.double()
-        fused = self._fused(x, y)
+        fused, train_fused = self._fused(x, y), self._train_fused(x, y)
         x, y = self.proj(x) + pe, self.proj(y) + pe
-        if fused and x.dtype == torch.float32:  # (fp16 projection + fp32 encoding: the residual stream is fp32 under autocast)
+        if train_fused and x.dtype == torch.float32:
+            X = torch.cat((x, y))
+            for blk in self.cross_attn_blocks:
+                X = blk.forward_train(X)
+            x, y = X.chunk(2)
+        elif fused and x.dtype == torch.float32:  # (fp16 projection + fp32 encoding: the residual stream is fp32 under autocast)
             X = torch.cat((x, y))  # the one concatenation: k and v change sides inside decoder_qkv
             for blk in self.cross_attn_blocks:
                 blk.forward_fused(X)

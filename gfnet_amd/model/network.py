@@ -333,13 +333,16 @@ class GFNet(nn.Module):
             # GFNET_COMPAT_DECODER=hip: the native cross-view decoder (model/crossview_decoder.py) in place of the checkout's, whose
             # shipped attention type needs flash_attn (hip_fused: the same with its blocks fused around the attention in fp16 eval());
             # unset: the checkout's class, as before
+            # GFNET_COMPAT_DECODER_TRAIN=hip: the native decoder trains its blocks through the backward kernels of
+            # csrc/decoder_block.hip (train_block_impl="hip"); unset: torch autograd, as before
             # GFNET_COMPAT_FPN=hip: the native FPN encoder, merge layer and decoder (model/fpn.py) in place of the checkout's
             # `model.FPN`, one fused launch per layer in eval(); unset: the checkout's classes, as before
             # GFNET_COMPAT_DINO=hip: the native DINOv2 ViT (model/dinov2.py) in place of the checkout's `model.transformer`, attention
             # and block seams in HIP in fp16 eval(); unset: the checkout's class, as before
             backbone = reference_backbone(conf, amp=amp, amp_dtype=amp_dtype, decoder=os.environ.get("GFNET_COMPAT_DECODER") or "checkout",
                                           fpn=os.environ.get("GFNET_COMPAT_FPN") or "checkout",
-                                          dino=os.environ.get("GFNET_COMPAT_DINO") or "checkout")
+                                          dino=os.environ.get("GFNET_COMPAT_DINO") or "checkout",
+                                          decoder_train_impl=os.environ.get("GFNET_COMPAT_DECODER_TRAIN") or "torch")
         self.backbone = backbone
         if conv_refiner is None:
             chs = conf["encoder_cfg"]["feat_chs"]  # coarse to fine: [64, 32, 16, 8]

@@ -268,9 +268,10 @@ def ls_add_layernorm(x, y, gamma, weight, bias, eps, inplace=False):
 DECODER_DIM, DECODER_HIDDEN = 64, 256  # the width and hidden width decoder_qkv and decoder_post are built for (8 heads of 8)
 
 
-def _decoder_args(what, tensors, shapes):
+def _decoder_args(what, tensors, shapes, forward_only=True):
     """The named tensors as the decoder-block kernels read them: CUDA, contiguous, the dtype and shape listed in `shapes`
-    (name -> (dtype, shape)), 16-byte aligned (a misaligned parameter view is copied); no autograd."""
+    (name -> (dtype, shape)), 16-byte aligned (a misaligned parameter view is copied); no autograd.  forward_only=False (the
+    backward ops, which are what autograd calls) leaves out the refusal of tensors that require grad."""
     dev = require_gpu(*tensors.values())
     out = {}
     for name, t in tensors.items():
@@ -281,7 +282,7 @@ def _decoder_args(what, tensors, shapes):
             raise ValueError(f"{what}: {name} must be {tuple(shape)}, got {tuple(t.shape)}")
         if not t.is_contiguous():
             raise ValueError(f"{what}: {name} must be contiguous")
-        if torch.is_grad_enabled() and t.requires_grad:
+        if forward_only and torch.is_grad_enabled() and t.requires_grad:
             raise RuntimeError(f"{what}: {name} requires grad, and this op is forward only (inference; call it under torch.no_grad())")
         t = t.detach()
         out[name] = t.clone() if t.data_ptr() % 16 else t
@@ -342,6 +343,111 @@ def decoder_post(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1,
     if inplace and out.data_ptr() != X.data_ptr():  # (a misaligned X was copied for the kernel)
         X.copy_(out)
     return X if inplace else out
+
+
+def _decoder_bwd_ws(dev, rows):
+    nws = int(_L().gfn_decoder_bwd_ws_bytes(rows))
+    return torch.empty(max(nws, 16), device=dev, dtype=torch.uint8), nws
+
+
+def decoder_qkv_bwd(X, norm_weight, norm_bias, eps, wq, wk, wv, gq, gk, gv):
+    """The backward of decoder_qkv (gfn_decoder_qkv_bwd), differentiating the forward as the kernel computes it with every fp16
+    rounding taken as the identity: X and the parameters as decoder_qkv took them, gq, gk, gv (2B, N, 8, 8) fp16 as
+    cross_attention_bwd returns them (gk and gv of a row are read where its k and v were written, at the other view's batch entry).
+    Returns (gX, g_wq, g_wk, g_wv, g_norm_weight, g_norm_bias), all fp32.  No atomics: two calls give the same bits."""
+    what, C = "decoder_qkv_bwd", DECODER_DIM
+    if X.dim() != 3 or X.shape[0] % 2 or X.shape[1] < 1:
+        raise ValueError(f"{what}: X must be (2B, N, {C}) with an even batch and N >= 1, got {tuple(X.shape)}")
+    f32, B2, N = torch.float32, X.shape[0], X.shape[1]
+    grad = (torch.float16, (B2, N, 8, C // 8))
+    dev, t = _decoder_args(what, {"X": X, "norm_weight": norm_weight, "norm_bias": norm_bias, "wq": wq, "wk": wk, "wv": wv, "gq": gq, "gk": gk,
+                                  "gv": gv},
+                           {"X": (f32, (B2, N, C)), "norm_weight": (f32, (C,)), "norm_bias": (f32, (C,)), "wq": (f32, (C, C)),
+                            "wk": (f32, (C, C)), "wv": (f32, (C, C)), "gq": grad, "gk": grad, "gv": grad}, forward_only=False)
+    gX = torch.empty((B2, N, C), device=dev, dtype=f32)
+    g_wq, g_wk, g_wv = (torch.empty((C, C), device=dev, dtype=f32) for _ in range(3))
+    g_nw, g_nb = (torch.empty((C,), device=dev, dtype=f32) for _ in range(2))
+    ws, nws = _decoder_bwd_ws(dev, B2 * N)
+    _timed("decoder_qkv_bwd", lambda: _L().gfn_decoder_qkv_bwd(
+        ptr(t["X"]), ptr(t["norm_weight"]), ptr(t["norm_bias"]), float(eps), ptr(t["wq"]), ptr(t["wk"]), ptr(t["wv"]), ptr(t["gq"]), ptr(t["gk"]),
+        ptr(t["gv"]), B2, N, C, ptr(gX), ptr(g_wq), ptr(g_wk), ptr(g_wv), ptr(g_nw), ptr(g_nb), ptr(ws), nws, stream_ptr(dev)))
+    return gX, g_wq, g_wk, g_wv, g_nw, g_nb
+
+
+def decoder_post_bwd(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, gX_out):
+    """The backward of decoder_post (gfn_decoder_post_bwd): X, attn and the parameters as decoder_post took them (x1, norm2, fc1 and
+    the GELU are recomputed from them, nothing of the forward is saved), gX_out fp32 of X's shape.  Returns (gX, g_attn, g_wproj,
+    g_bproj, g_gamma1, g_norm_weight, g_norm_bias, g_w1, g_b1, g_w2, g_b2, g_gamma2): gX fp32 of X's shape, g_attn fp16 of attn's
+    shape (rounded once, overflow to inf: the dout of cross_attention_bwd), the rest fp32 of the parameters' shapes.  No atomics:
+    two calls give the same bits."""
+    what, C, Hd = "decoder_post_bwd", DECODER_DIM, DECODER_HIDDEN
+    if X.dim() < 1 or X.shape[-1] != C:
+        raise ValueError(f"{what}: X must be (..., {C}), got {tuple(X.shape)}")
+    if attn.numel() != X.numel():
+        raise ValueError(f"{what}: attn must hold X's {X.numel() // C} rows of {C}, got {tuple(attn.shape)}")
+    f32 = torch.float32
+    vec = (f32, (C,))
+    dev, t = _decoder_args(what, {"X": X, "attn": attn, "wproj": wproj, "bproj": bproj, "gamma1": gamma1, "norm_weight": norm_weight,
+                                  "norm_bias": norm_bias, "w1": w1, "b1": b1, "w2": w2, "b2": b2, "gamma2": gamma2, "gX_out": gX_out},
+                           {"X": (f32, X.shape), "attn": (torch.float16, attn.shape), "wproj": (f32, (C, C)), "bproj": vec, "gamma1": vec,
+                            "norm_weight": vec, "norm_bias": vec, "w1": (f32, (Hd, C)), "b1": (f32, (Hd,)), "w2": (f32, (C, Hd)), "b2": vec,
+                            "gamma2": vec, "gX_out": (f32, X.shape)}, forward_only=False)
+    rows = X.numel() // C
+    gX, g_attn = torch.empty_like(t["X"]), torch.empty_like(t["attn"])
+    names = ("wproj", "bproj", "gamma1", "norm_weight", "norm_bias", "w1", "b1", "w2", "b2", "gamma2")
+    grads = [torch.empty_like(t[n]) for n in names]
+    ws, nws = _decoder_bwd_ws(dev, rows)
+    _timed("decoder_post_bwd", lambda: _L().gfn_decoder_post_bwd(
+        ptr(t["X"]), ptr(t["attn"]), ptr(t["wproj"]), ptr(t["bproj"]), ptr(t["gamma1"]), ptr(t["norm_weight"]), ptr(t["norm_bias"]), float(eps),
+        ptr(t["w1"]), ptr(t["b1"]), ptr(t["w2"]), ptr(t["b2"]), ptr(t["gamma2"]), ptr(t["gX_out"]), rows, C, Hd, ptr(gX), ptr(g_attn),
+        *(ptr(g) for g in grads), ptr(ws), nws, stream_ptr(dev)))
+    return (gX, g_attn, *grads)
+
+
+class _DecoderQkvFn(torch.autograd.Function):
+    """decoder_qkv with a backward: the same launch forward (same bits), decoder_qkv_bwd backward; saves its inputs only."""
+
+    @staticmethod
+    def forward(ctx, X, norm_weight, norm_bias, eps, wq, wk, wv):
+        ctx.save_for_backward(X, norm_weight, norm_bias, wq, wk, wv)
+        ctx.eps = eps
+        return decoder_qkv(X, norm_weight, norm_bias, eps, wq, wk, wv)  # (grad mode is off in here)
+
+    @staticmethod
+    def backward(ctx, gq, gk, gv):
+        X, norm_weight, norm_bias, wq, wk, wv = ctx.saved_tensors
+        gq, gk, gv = (g.to(torch.float16).contiguous() for g in (gq, gk, gv))
+        gX, g_wq, g_wk, g_wv, g_nw, g_nb = decoder_qkv_bwd(X, norm_weight, norm_bias, ctx.eps, wq, wk, wv, gq, gk, gv)
+        return gX, g_nw, g_nb, None, g_wq, g_wk, g_wv
+
+
+class _DecoderPostFn(torch.autograd.Function):
+    """decoder_post (not in place) with a backward: saves X, attn and the parameters; everything between them is recomputed."""
+
+    @staticmethod
+    def forward(ctx, X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2):
+        ctx.save_for_backward(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, w1, b1, w2, b2, gamma2)
+        ctx.eps = eps
+        return decoder_post(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, inplace=False)
+
+    @staticmethod
+    def backward(ctx, gX_out):
+        X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, w1, b1, w2, b2, gamma2 = ctx.saved_tensors
+        g = decoder_post_bwd(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, ctx.eps, w1, b1, w2, b2, gamma2,
+                             gX_out.to(torch.float32).contiguous())
+        return (*g[:7], None, *g[7:])
+
+
+def decoder_qkv_train(X, norm_weight, norm_bias, eps, wq, wk, wv):
+    """decoder_qkv, differentiable with respect to X and the five parameters (gfn_decoder_qkv_bwd): the training forward is the
+    same launch, in the reference's fp16 autocast class (model/network.py:171).  Saves its inputs, nothing else."""
+    return _DecoderQkvFn.apply(X, norm_weight, norm_bias, float(eps), wq, wk, wv)
+
+
+def decoder_post_train(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2):
+    """decoder_post(..., inplace=False), differentiable with respect to X, attn and the ten parameters (gfn_decoder_post_bwd).
+    Saves its inputs, nothing else: x1, norm2, the 256-wide fc1 and GELU outputs are recomputed in the backward."""
+    return _DecoderPostFn.apply(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, float(eps), w1, b1, w2, b2, gamma2)
 
 
 CONV_ACTS = {None: 0, "none": 0, "leaky_relu": 1, "swish": 2}

@@ -50,6 +50,14 @@ def _check_fpn_train_impl(fpn, fpn_train_impl):
         raise ValueError(f"fpn_train_impl={fpn_train_impl!r} needs fpn='hip': the checkout's FPN modules train through torch only")
 
 
+def _check_decoder_train_impl(decoder, decoder_train_impl):
+    if decoder_train_impl not in ("torch", "hip"):
+        raise ValueError(f"decoder_train_impl must be 'torch' or 'hip', got {decoder_train_impl!r}")
+    if decoder_train_impl != "torch" and decoder == "checkout":
+        raise ValueError(f"decoder_train_impl={decoder_train_impl!r} needs decoder='hip' or 'hip_fused': the checkout's decoder trains "
+                         "through torch only")
+
+
 def checkout_available(decoder="checkout", fpn="checkout"):
     """True when the reference's backbone modules that this choice takes from the checkout can be found on sys.path (nothing is
     imported).  decoder="hip" does without `model.crossview_decoder_light`, fpn="hip" without `model.FPN`: those are then this
@@ -113,13 +121,18 @@ class ReferenceBackbone(nn.Module):
     in HIP in fp16 eval().  With decoder="hip", fpn="hip" and dino="hip" nothing of a checkout is imported.
 
     fpn_train_impl: "torch" (default) or "hip", the train_conv_impl of the three native FPN modules: what they run under train() (see
-    gfnet_amd/model/fpn.py).  The checkout's modules have no such switch: anything but "torch" with fpn="checkout" raises ValueError."""
+    gfnet_amd/model/fpn.py).  The checkout's modules have no such switch: anything but "torch" with fpn="checkout" raises ValueError.
+
+    decoder_train_impl: "torch" (default) or "hip", the train_block_impl of the native cross-view decoder: "hip" trains its blocks
+    through the backward kernels of csrc/decoder_block.hip under fp16 autocast (see gfnet_amd/model/crossview_decoder.py).  Anything
+    but "torch" with decoder="checkout" raises ValueError."""
 
     def __init__(self, conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout",
-                 dino="checkout", fpn_train_impl="torch"):
+                 dino="checkout", fpn_train_impl="torch", decoder_train_impl="torch"):
         super().__init__()
         _check_choices(decoder, fpn, dino)
         _check_fpn_train_impl(fpn, fpn_train_impl)
+        _check_decoder_train_impl(decoder, decoder_train_impl)
         self.fpn = fpn
         if fpn == "hip":
             from .model.fpn import FPNDecoder_concat, FPNEncoder, merge_layer
@@ -136,7 +149,8 @@ class ReferenceBackbone(nn.Module):
         if decoder in ("hip", "hip_fused"):
             from .model.crossview_decoder import CrossViewDecoder
 
-            self.dino_decoder = CrossViewDecoder(conf, block_impl="hip" if decoder == "hip_fused" else "torch")
+            self.dino_decoder = CrossViewDecoder(conf, block_impl="hip" if decoder == "hip_fused" else "torch",
+                                                 train_block_impl=decoder_train_impl)
         else:
             from model.crossview_decoder_light import CrossVITDecoder_noself
 
@@ -182,13 +196,14 @@ class ReferenceBackbone(nn.Module):
 
 
 def reference_backbone(conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout",
-                       dino="checkout", fpn_train_impl="torch"):
+                       dino="checkout", fpn_train_impl="torch", decoder_train_impl="torch"):
     """Build the backbone from the checkout on sys.path; raises ImportError with the reason when a module this choice needs from it
-    is missing.  decoder, fpn, dino, fpn_train_impl: see ReferenceBackbone."""
+    is missing.  decoder, fpn, dino, fpn_train_impl, decoder_train_impl: see ReferenceBackbone."""
     _check_choices(decoder, fpn, dino)
     _check_fpn_train_impl(fpn, fpn_train_impl)
+    _check_decoder_train_impl(decoder, decoder_train_impl)
     if not checkout_available(decoder, fpn):
         raise ImportError(f"no KN-Zhang/GFNet checkout on sys.path: {' / '.join(f'`{m}`' for m in _needed(decoder, fpn))} cannot be found "
                           "(put the checkout behind compat/ on PYTHONPATH, or run the script through compat/run.py)")
     return ReferenceBackbone(conf, amp=amp, amp_dtype=amp_dtype, vit=vit, dino_weights=dino_weights, decoder=decoder, fpn=fpn,
-                             dino=dino, fpn_train_impl=fpn_train_impl)
+                             dino=dino, fpn_train_impl=fpn_train_impl, decoder_train_impl=decoder_train_impl)

@@ -815,6 +815,40 @@ int gfn_decoder_post_fwd(const float *x, const void *attn, const float *wproj, c
                          const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1, const float *w2,
                          const float *b2, const float *gamma2, int64_t rows, int C, int hidden, float *x_out, gfn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training of those blocks: the backward of the two launches above, which are themselves the training forward (the fp16 autocast
+ * class is the reference's training class, model/network.py:171).  Both differentiate the forward AS THE KERNELS COMPUTE IT, every
+ * fp16 rounding taken as the identity (autocast's backward).  Products run on v_mfma_f32_32x32x8_f16 with operands rounded to fp16
+ * once; a parameter gradient is a sum over tokens of an outer product, taken on the matrix core with the tokens as its K dimension.
+ * No atomics: every workgroup leaves fp32 partial sums in ws and a later launch adds them in a fixed order, so identical calls
+ * give identical bits in every output; the grids depend on rows alone, not on the device.  Nothing (rows, hidden) is written.
+ * gX and g_attn of a row depend on that row alone: a non-finite row of the incoming gradient stays in its row there (and reaches
+ * the parameter gradients).  Same sizes as the forward entries, refused the same way.
+ * ws: gfn_decoder_bwd_ws_bytes(rows) bytes (one size serves both entries), 16-byte aligned, contents undefined before and after. */
+int64_t gfn_decoder_bwd_ws_bytes(int64_t rows);
+/* gfn_decoder_qkv_bwd -- backward of gfn_decoder_qkv_fwd (block.py:327, attention.py:236-238, crossview_decoder_light.py:53-54).
+ * gq, gk, gv (2B, N, 8, 8) fp16 as gfn_cross_attn_bwd writes them; row r's k and v were written at row (r + rows / 2) mod rows, so
+ * its gk and gv are read from there (gk', gv').  With n = fp16(LayerNorm(X) * norm_weight + norm_bias):
+ *   gx = LayerNorm^T(wq^T gq) + wk^T gk' + wv^T gv'       (2B, N, 64) fp32
+ *   g_wq = sum gq (x) n   g_wk = sum gk' (x) fp16(X)   g_wv = sum gv' (x) fp16(X)   g_norm_weight, g_norm_bias: norm1's   all fp32 */
+int gfn_decoder_qkv_bwd(const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq, const float *wk,
+                        const float *wv, const void *gq, const void *gk, const void *gv, int B2, int N, int C, float *gx, float *g_wq,
+                        float *g_wk, float *g_wv, float *g_norm_weight, float *g_norm_bias, void *ws, int64_t ws_bytes,
+                        gfn_stream_t stream);
+/* gfn_decoder_post_bwd -- backward of gfn_decoder_post_fwd (attention.py:255, block.py:327-328, layer_scale.py, mlp.py).  x and attn
+ * are the forward's inputs: x1, norm2's output n, u = w1 n + b1 and GELU(u) are recomputed, not saved.  Per row, with g = gx_out:
+ *   gu = (w2^T (gamma2 g)) GELU'(u)      g1 = g + LayerNorm^T(w1^T gu)      gx = g1      g_attn = fp16(wproj^T (gamma1 g1))
+ * g_attn (rows, 64) fp16, rounded once, overflow to inf: the dout of gfn_cross_attn_bwd.  The parameter gradients, fp32, of the
+ * parameters' shapes: g_w2 = gamma2_c sum g (x) fp16(GELU(u)), g_b2 = gamma2_c sum g, g_gamma2 = sum g (w2 fp16(GELU(u)) + b2)
+ * (formed from the same sums, without dividing by gamma2), g_w1 = sum gu (x) n, g_b1 = sum gu, g_norm_weight and g_norm_bias
+ * (norm2's), and g_wproj, g_bproj, g_gamma1 from g1 and attn as the fc2 three are from g and GELU(u). */
+int gfn_decoder_post_bwd(const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,
+                         const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1, const float *w2,
+                         const float *b2, const float *gamma2, const float *gx_out, int64_t rows, int C, int hidden, float *gx,
+                         void *g_attn, float *g_wproj, float *g_bproj, float *g_gamma1, float *g_norm_weight, float *g_norm_bias,
+                         float *g_w1, float *g_b1, float *g_w2, float *g_b2, float *g_gamma2, void *ws, int64_t ws_bytes,
+                         gfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
