@@ -24,16 +24,7 @@ constexpr int kTW = 32;                     // tile columns: the lanes of a half
 constexpr int kStrips = kThreads / kTW;     // row strips of a tile, R rows each
 constexpr int kSplitAbove = 32;             // input channels above which the sum is split by stage (conv_tile_kernel, SPLIT)
 
-// F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) of the (h2, w2) plane p at (y, x) of the doubled grid: the
-// source coordinate 0.5 (dst + 0.5) - 0.5 clamped at 0, the far neighbour clamped to the plane, weights and sum in ATen's order
-__device__ __forceinline__ float up2_at(const float *__restrict__ p, int h2, int w2, int y, int x) {
-    const float sy = fmaxf(0.5f * ((float)y + 0.5f) - 0.5f, 0.f), sx = fmaxf(0.5f * ((float)x + 0.5f) - 0.5f, 0.f);
-    const int y0 = (int)sy, x0 = (int)sx;
-    const int y1 = min(y0 + 1, h2 - 1), x1 = min(x0 + 1, w2 - 1);
-    const float ly = sy - (float)y0, lx = sx - (float)x0;
-    const float hy = 1.f - ly, hx = 1.f - lx;
-    return hy * (hx * p[y0 * w2 + x0] + lx * p[y0 * w2 + x1]) + ly * (hx * p[y1 * w2 + x0] + lx * p[y1 * w2 + x1]);
-}
+using gfn::up2_at;  // (the 2x bilinear upsample as every reader of the doubled map evaluates it: fpn_conv_launch.h)
 
 // channel ci of cat(x0', x1) of one image at (y, x), zero outside the map
 __device__ __forceinline__ float input_at(const ConvArgs &a, const float *__restrict__ x0b, const float *__restrict__ x1b, int ci,

@@ -23,6 +23,37 @@ __device__ __forceinline__ float activate(float v, int act, float slope) {
     return v;
 }
 
+// F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) of the (h2, w2) plane p at (y, x) of the doubled grid: the
+// source coordinate 0.5 (dst + 0.5) - 0.5 clamped at 0, the far neighbour clamped to the plane, weights and sum in ATen's order
+__device__ __forceinline__ float up2_at(const float *__restrict__ p, int h2, int w2, int y, int x) {
+    const float sy = fmaxf(0.5f * ((float)y + 0.5f) - 0.5f, 0.f), sx = fmaxf(0.5f * ((float)x + 0.5f) - 0.5f, 0.f);
+    const int y0 = (int)sy, x0 = (int)sx;
+    const int y1 = min(y0 + 1, h2 - 1), x1 = min(x0 + 1, w2 - 1);
+    const float ly = sy - (float)y0, lx = sx - (float)x0;
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    return hy * (hx * p[y0 * w2 + x0] + lx * p[y0 * w2 + x1]) + ly * (hx * p[y1 * w2 + x0] + lx * p[y1 * w2 + x1]);
+}
+
+// up2_at in two halves, for a reader whose four values lie elsewhere than in the plane itself (the weight gradient's LDS copy of a
+// tile's coarse footprint): the same operations on the same operands in the same order, and the library is built without FMA
+// contraction, so both directions of the training path see the same x0' bit for bit.
+struct Up2Taps {
+    int y0, y1, x0, x1;
+    float ly, lx;
+};
+__device__ __forceinline__ Up2Taps up2_taps(int h2, int w2, int y, int x) {
+    const float sy = fmaxf(0.5f * ((float)y + 0.5f) - 0.5f, 0.f), sx = fmaxf(0.5f * ((float)x + 0.5f) - 0.5f, 0.f);
+    Up2Taps t;
+    t.y0 = (int)sy, t.x0 = (int)sx;
+    t.y1 = min(t.y0 + 1, h2 - 1), t.x1 = min(t.x0 + 1, w2 - 1);
+    t.ly = sy - (float)t.y0, t.lx = sx - (float)t.x0;
+    return t;
+}
+__device__ __forceinline__ float up2_blend(const Up2Taps &t, float v00, float v01, float v10, float v11) {
+    const float hy = 1.f - t.ly, hx = 1.f - t.lx;
+    return hy * (hx * v00 + t.lx * v01) + t.ly * (hx * v10 + t.lx * v11);
+}
+
 // the kernel for (K, stride, a.Cout) on stream s; the caller has checked the sizes (gfn_conv2d_bn_act_fwd's limits)
 int fpn_conv_launch(const ConvArgs &a, int B, int K, int stride, hipStream_t s);
 

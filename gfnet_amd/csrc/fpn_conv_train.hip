@@ -4,6 +4,8 @@
 //     u = conv(cat(x0, x1), weight)      mean, invstd of u over the batch      out = act(bn_w (u - mean) invstd + bn_b) + residual
 //
 // Only u is kept for the backward; the activation's derivative is recomputed from u, mean and invstd with the forward's expression.
+// With up0 (the gfn_conv2d_up_bn_act_train_* entry points; stride 1) x0 is (B, C0, H/2, W/2) and stands for its 2x bilinear upsample
+// x0' in both directions: the doubled map is never written, and gx0 comes back at the coarse size.
 //
 // Forward (5 launches): ones / zeros for the shared convolution kernels; u by fpn_conv.hip's kernels (fpn_conv_launch.h) with
 // scale 1 and shift 0; ft_moments_kernel, a workgroup per 4096 values of one channel plane: (mean, M2) about its own mean;
@@ -13,12 +15,16 @@
 //   ft_bn_bwd_part_kernel   per 4096 values of a plane: sum ga and sum ga x_hat with ga = gy act'(.)     -> ct_bn_bwd_kernel (double)
 //   ft_gu_kernel            gu = bn_w invstd (ga - S1/n - x_hat S2/n), written once into the workspace
 //   input gradient          stride 1: the forward convolution kernels on gu with the weights transposed and flipped on the device
-//                           (ft_repack_kernel), one launch per input (gx0, gx1: the concatenation is never written);
+//                           (ft_repack_kernel), one launch per input (gx0, gx1: the concatenation is never written); with up0 the
+//                           launch for x0 writes the gradient of x0' into the workspace and ft_up2_adjoint_kernel gathers gx0 from
+//                           it: the transposed upsample, 16 taps per coarse value in a fixed order;
 //                           stride 2: ft_gather_s2_kernel, a workgroup per output parity class, so the taps it visits are uniform
 //   weight gradient         ft_wgrad_kernel: a workgroup stages the halo tile of up to CIG input channels and the 8 x 32 tile of gu
 //                           of 8 output channels in LDS; a thread owns one (ci, ky, kx) and 8 output channels, sums runs of 32
 //                           positions in fp32 and adds the runs up; a workgroup walks every P-th tile and leaves one partial
-//                           (Cout, Cin, K, K); ft_wsum_kernel adds the P partials in double, in order.
+//                           (Cout, Cin, K, K); ft_wsum_kernel adds the P partials in double, in order.  With up0 the coarse
+//                           footprint of the tile goes into LDS first and the halo tile of an x0 channel is interpolated from it
+//                           with up2_at's operations (fpn_conv_launch.h), so that it holds what the forward's staging held.
 // Every sum has a fixed order and there are no floating-point atomics: identical calls give identical bits.
 #include <algorithm>
 
@@ -218,6 +224,40 @@ __global__ __launch_bounds__(256) void ft_repack_kernel(const float *__restrict_
     wt[((int64_t)ci * Cout + co) * KK + (KK - 1 - k)] = w[e];
 }
 
+// The transposed 2x upsample along one axis: coarse index c of n gets the doubled grid's entries 2c - 1 .. 2c + 2 with the weights
+// 1/4, 3/4, 3/4, 1/4 (up2_taps: entry 2m + 1 reads m and m + 1 with 3/4 and 1/4, entry 2m reads m - 1 and m with 1/4 and 3/4).  The
+// two clamps fold the border onto the first and last index: entry 0 reads index 0 alone, entry 2n - 1 reads index n - 1 twice.  An
+// entry outside the grid gets weight 0 and an index inside it.
+__device__ __forceinline__ void up2_adjoint_taps(int c, int n, int idx[4], float wt[4]) {
+    idx[0] = max(2 * c - 1, 0), wt[0] = c > 0 ? 0.25f : 0.f;
+    idx[1] = 2 * c, wt[1] = c > 0 ? 0.75f : 1.f;
+    idx[2] = 2 * c + 1, wt[2] = c < n - 1 ? 0.75f : 1.f;
+    idx[3] = min(2 * c + 2, 2 * n - 1), wt[3] = c < n - 1 ? 0.25f : 0.f;
+}
+
+// gx (planes of h2 x w2) = the transposed upsample of gf (planes of 2 h2 x 2 w2): a thread per coarse value gathers its 4 x 4 taps,
+// columns within a row, then the rows, always in that order.  The weights and their products are exact in fp32.
+__global__ __launch_bounds__(256) void ft_up2_adjoint_kernel(const float *__restrict__ gf, float *__restrict__ gx, int64_t total, int h2, int w2) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int cx = (int)(e % w2), cy = (int)(e / w2 % h2);
+    const float *__restrict__ p = gf + (e / ((int64_t)w2 * h2)) * (4 * (int64_t)h2 * w2);
+    int iy[4], ix[4];
+    float wy[4], wx[4];
+    up2_adjoint_taps(cy, h2, iy, wy);
+    up2_adjoint_taps(cx, w2, ix, wx);
+    float acc = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float *__restrict__ row = p + (int64_t)iy[r] * (2 * w2);
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s = fmaf(wx[k], row[ix[k]], s);
+        acc = fmaf(wy[r], s, acc);
+    }
+    gx[e] = acc;
+}
+
 // Stride 2: gx[ci][y][x] = sum_co sum over the taps (ky, kx) with the parity of (y + pad, x + pad) of gu[co][(y + pad - ky) / 2][..]
 // w[co][ci][ky][kx].  A workgroup serves 256 positions of ONE parity class (y & 1, x & 1) of one input plane, so its taps and with
 // them its weight addresses are uniform.  Four output channels to a partial sum where there are more than 32 (fpn_conv.hip: SPLIT).
@@ -264,12 +304,13 @@ __global__ __launch_bounds__(256) void ft_gather_s2_kernel(const float *__restri
 
 // how the weight gradient is cut up
 struct WgradShape {
-    int IH, IW, PITCH, cig, nci, nco, tiles_x, tiles_y, parts;
+    int IH, IW, PITCH, coarse, cig, nci, nco, tiles_x, tiles_y, parts;
     int64_t ntiles, wn;
 
-    WgradShape(int B, int Cin, int Cout, int Ho, int Wo, int K, int S) {
+    WgradShape(int B, int Cin, int Cout, int Ho, int Wo, int K, int S, int up0) {
         IH = (kWgTH - 1) * S + K, IW = (kWgTW - 1) * S + K, PITCH = IW | 1;
-        int cap = std::min(256 / (K * K), kWgXFloats / (IH * PITCH));
+        coarse = up0 ? (IH / 2 + 2) * (IW / 2 + 2) : 0;  // per channel: the coarse rows and columns that an IH x IW tile of x0' reads
+        int cap = std::min(256 / (K * K), kWgXFloats / (IH * PITCH + coarse));
         if (cap < 1) cap = 1;
         nci = (Cin + cap - 1) / cap;
         cig = (Cin + nci - 1) / nci;
@@ -282,15 +323,25 @@ struct WgradShape {
         if (p > ntiles) p = ntiles;
         parts = (int)(p < 1 ? 1 : p);
     }
-    int lds_floats() const { return cig * IH * PITCH + kWgPos * kWgCo; }
+    int lds_floats() const { return cig * (IH * PITCH + coarse) + kWgPos * kWgCo; }
 };
 
 // grid (parts, nci, nco).  Workgroup (slot, ci group, co group) walks tiles slot, slot + parts, ...: a tile is 8 x 32 outputs of one
 // image.  Thread tid: item = tid / PG = (ci, ky, kx) of the group, pg = tid % PG takes positions pg, pg + PG, ... of the tile
 // (PG = 256 / items).  Runs of 32 products in fp32, the runs added up in fp32, the PG threads of an item in order, the partial stored.
+// UP (stride 1): x0 is (B, C0, H/2, W/2).  Behind gs lie CH x CW coarse values per x0 channel of the group, rows cy0 .. and columns
+// cx0 .. clamped into the plane: every tap that up2_taps names for a position of the halo tile that lies inside the map.  KT: the
+// kernel size at compile time, 0 to take it and what follows from it from the arguments; the UP instantiations fix it, which keeps
+// the second staging pass's state within the scalar registers.
+template <bool UP, int KT>
 __global__ __launch_bounds__(256) void ft_wgrad_kernel(const float *__restrict__ x0, const float *__restrict__ x1, const float *__restrict__ gu,
-                                                       float *__restrict__ part, int C0, int C1, int H, int W, int Cout, int Ho, int Wo, int K,
-                                                       int S, int IH, int IW, int PITCH, int cig, int tiles_x, int tiles_y, int64_t ntiles) {
+                                                       float *__restrict__ part, int C0, int C1, int H, int W, int Cout, int Ho_, int Wo_, int K_,
+                                                       int S_, int IH_, int IW_, int PITCH_, int cig, int tiles_x, int tiles_y,
+                                                       int64_t ntiles) {
+    static_assert(UP == (KT != 0), "the kernel size is fixed exactly where x0 is upsampled");
+    const int K = KT ? KT : K_, S = UP ? 1 : S_, IH = KT ? kWgTH - 1 + KT : IH_, IW = KT ? kWgTW - 1 + KT : IW_;
+    const int Ho = UP ? H : Ho_, Wo = UP ? W : Wo_;  // (stride 1)
+    const int PITCH = KT ? ((kWgTW - 1 + KT) | 1) : PITCH_;
     extern __shared__ float lds[];
     float *xs = lds, *gs = lds + cig * IH * PITCH;  // gs[j * 256 + p]; afterwards the threads' totals
     const int tid = threadIdx.x, Cin = C0 + C1, KK = K * K, pad = K / 2;
@@ -301,6 +352,9 @@ __global__ __launch_bounds__(256) void ft_wgrad_kernel(const float *__restrict__
     const int ci_l = active ? item / KK : 0, k = active ? item % KK : 0;
     const float *xrow = xs + (ci_l * IH + k / K) * PITCH + k % K;
     const int niter = (kWgPos - pg + PG - 1) / PG;
+    const int h2 = H >> 1, w2 = W >> 1, CH = IH / 2 + 2, CW = IW / 2 + 2;  // (UP only)
+    float *cs = gs + kWgPos * kWgCo;
+    const int nc0 = min(max(C0 - ci0, 0), cig);  // the group's x0 channels
 
     float total[kWgCo];
 #pragma unroll
@@ -310,13 +364,29 @@ __global__ __launch_bounds__(256) void ft_wgrad_kernel(const float *__restrict__
         const int tx = (int)(t % tiles_x), ty = (int)(t / tiles_x % tiles_y), b = (int)(t / ((int64_t)tiles_x * tiles_y));
         const int iy0 = ty * kWgTH * S - pad, ix0 = tx * kWgTW * S - pad;
         __syncthreads();  // the previous tile has been consumed
+        const int cy0 = (iy0 - 1) >> 1, cx0 = (ix0 - 1) >> 1;  // (UP only) the first coarse row and column the tile can name
+        if (UP) {
+            for (int e = tid; e < nc0 * CH * CW; e += 256) {
+                const int c = e / (CH * CW), rem = e - c * (CH * CW), r = rem / CW, xx = rem - r * CW;
+                const int yy = min(max(cy0 + r, 0), h2 - 1), xc = min(max(cx0 + xx, 0), w2 - 1);
+                cs[e] = x0[((int64_t)b * C0 + ci0 + c) * h2 * w2 + (int64_t)yy * w2 + xc];
+            }
+            __syncthreads();
+        }
         for (int e = tid; e < cig * IH * IW; e += 256) {
             const int c = e / (IH * IW), rem = e - c * (IH * IW), r = rem / IW, xx = rem - r * IW;
             const int ci = ci0 + c, gy = iy0 + r, gx = ix0 + xx;
             float v = 0.f;
-            if (ci < Cin && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)
-                v = ci < C0 ? x0[((int64_t)b * C0 + ci) * H * W + (int64_t)gy * W + gx]
-                            : x1[((int64_t)b * C1 + (ci - C0)) * H * W + (int64_t)gy * W + gx];
+            if (ci < Cin && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) {
+                if (UP && ci < C0) {
+                    const gfn::Up2Taps t = gfn::up2_taps(h2, w2, gy, gx);
+                    const float *r0 = cs + (c * CH + (t.y0 - cy0)) * CW - cx0, *r1 = cs + (c * CH + (t.y1 - cy0)) * CW - cx0;
+                    v = gfn::up2_blend(t, r0[t.x0], r0[t.x1], r1[t.x0], r1[t.x1]);
+                } else {
+                    v = ci < C0 ? x0[((int64_t)b * C0 + ci) * H * W + (int64_t)gy * W + gx]
+                                : x1[((int64_t)b * C1 + (ci - C0)) * H * W + (int64_t)gy * W + gx];
+                }
+            }
             xs[(c * IH + r) * PITCH + xx] = v;
         }
         for (int e = tid; e < kWgPos * kWgCo; e += 256) {
@@ -370,30 +440,37 @@ __global__ __launch_bounds__(256) void ft_wsum_kernel(const float *__restrict__ 
 struct Plan {
     int Cin, Ho, Wo, HW, red_chunks, nparts, ew_chunks, nident;
     WgradShape wg;
-    int64_t off_ident, fwd_floats;                                  // forward: part, ident
-    int64_t off_dgdb, off_gu, off_wt, off_wpart, bwd_floats;        // backward: part, ident, dgdb, gu, wt, wpart
+    int64_t off_ident, fwd_floats;                                        // forward: part, ident
+    int64_t off_dgdb, off_gu, off_wt, off_wpart, off_gx0f, bwd_floats;    // backward: part, ident, dgdb, gu, wt, wpart; up0: the gradient of x0'
 
-    Plan(int C0, int C1, int B, int H, int W, int Cout, int K, int S)
+    Plan(int C0, int C1, int B, int H, int W, int Cout, int K, int S, int up0)
         : Cin(C0 + C1), Ho((H + S - 1) / S), Wo((W + S - 1) / S), HW(Ho * Wo), red_chunks((HW + kRed - 1) / kRed), nparts(B * red_chunks),
-          ew_chunks((HW + kEw - 1) / kEw), nident(std::max(Cout, std::max(C0, C1))), wg(B, C0 + C1, Cout, Ho, Wo, K, S) {
+          ew_chunks((HW + kEw - 1) / kEw), nident(std::max(Cout, std::max(C0, C1))), wg(B, C0 + C1, Cout, Ho, Wo, K, S, up0) {
         off_ident = align4((int64_t)Cout * nparts * 2);
         fwd_floats = off_ident + align4(2 * (int64_t)nident);
         off_dgdb = fwd_floats;
         off_gu = off_dgdb + align4(2 * (int64_t)Cout);
         off_wt = off_gu + align4((int64_t)B * Cout * HW);
         off_wpart = off_wt + align4(wg.wn);
-        bwd_floats = off_wpart + align4((int64_t)wg.parts * wg.wn);
+        off_gx0f = off_wpart + align4((int64_t)wg.parts * wg.wn);
+        bwd_floats = off_gx0f + (up0 ? align4((int64_t)B * C0 * H * W) : 0);
     }
 };
 
-// gfn_conv2d_bn_act_fwd's limits and batch statistics' own; 0 when fine
-int check_sizes(const char *what, int C0, int C1, int B, int H, int W, int Cout, int K, int stride, int act) {
+// up0 reads x0 as its doubled image: what that needs of the sizes
+bool up0_fits(int up0, int H, int W, int stride) { return !up0 || (stride == 1 && !((H | W) & 1)); }
+
+// gfn_conv2d_bn_act_fwd's limits and batch statistics' own; 0 when fine.  With up0 the x0 bound is that of its doubled image, which
+// the backward writes too (into the workspace)
+int check_sizes(const char *what, int C0, int C1, int B, int H, int W, int Cout, int K, int stride, int act, int up0) {
     if (K != 1 && K != 3 && K != 5 && K != 7) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: kernel size %d is not supported, only 1, 3, 5, 7", what, K);
     if (stride != 1 && stride != 2) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: stride %d is not supported, only 1 and 2", what, stride);
     if (act < 0 || act > 2) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: act %d is not one of 0 (none), 1 (leaky ReLU), 2 (swish)", what, act);
     if (B < 0 || H < 1 || W < 1 || C0 < 1 || C1 < 0 || Cout < 1 || Cout > 256 || B > 65535)
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: bad size (B=%d H=%d W=%d C0=%d C1=%d Cout=%d; C0 >= 1, Cout <= 256, B <= 65535)", what, B,
                          H, W, C0, C1, Cout);
+    if (up0 && stride != 1) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: up0 needs stride 1, got stride %d", what, stride);
+    if (up0 && ((H | W) & 1)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: up0 doubles x0, so H and W must be even (H=%d W=%d)", what, H, W);
     if (C0 + (int64_t)C1 > 65535) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: more than 65535 input channels (C0=%d C1=%d)", what, C0, C1);
     const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
     const int64_t limit = (int64_t)1 << 31;
@@ -412,21 +489,18 @@ int check_sizes(const char *what, int C0, int C1, int B, int H, int W, int Cout,
     return GFN_OK;
 }
 
-}  // namespace
-
-GFN_EXPORT int64_t gfn_conv2d_bn_act_train_ws_bytes(int C0, int C1, int B, int H, int W, int Cout, int K, int stride, int backward) {
+int64_t train_ws_bytes(int C0, int C1, int B, int H, int W, int Cout, int K, int stride, int backward, int up0) {
     if (C0 < 1 || C1 < 0 || B < 1 || H < 1 || W < 1 || Cout < 1 || (K != 1 && K != 3 && K != 5 && K != 7) || (stride != 1 && stride != 2)) return 0;
-    const Plan p(C0, C1, B, H, W, Cout, K, stride);
+    if (!up0_fits(up0, H, W, stride)) return 0;
+    const Plan p(C0, C1, B, H, W, Cout, K, stride, up0);
     return (backward ? p.bwd_floats : p.fwd_floats) * (int64_t)sizeof(float);
 }
 
-GFN_EXPORT int gfn_conv2d_bn_act_train_fwd(const float *x0, int C0, const float *x1, int C1, const float *weight, const float *conv_bias,
-                                           const float *bn_w, const float *bn_b, float *running_mean, float *running_var,
-                                           const float *residual, float *u, float *mean, float *invstd, float *out, int B, int H, int W,
-                                           int Cout, int K, int stride, int act, float slope, double momentum, double eps, void *ws,
-                                           int64_t ws_bytes, gfn_stream_t stream) {
-    const char *what = "gfn_conv2d_bn_act_train_fwd";
-    if (int rc = check_sizes(what, C0, C1, B, H, W, Cout, K, stride, act)) return rc;
+int train_fwd(const char *what, const float *x0, int C0, int up0, const float *x1, int C1, const float *weight, const float *conv_bias,
+              const float *bn_w, const float *bn_b, float *running_mean, float *running_var, const float *residual, float *u, float *mean,
+              float *invstd, float *out, int B, int H, int W, int Cout, int K, int stride, int act, float slope, double momentum, double eps,
+              void *ws, int64_t ws_bytes, gfn_stream_t stream) {
+    if (int rc = check_sizes(what, C0, C1, B, H, W, Cout, K, stride, act, up0)) return rc;
     if (!(momentum >= 0.0 && momentum <= 1.0) || !(eps >= 0.0))
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: momentum must lie in [0, 1] and eps be >= 0", what);
     if (B == 0) return GFN_OK;
@@ -434,14 +508,14 @@ GFN_EXPORT int gfn_conv2d_bn_act_train_fwd(const float *x0, int C0, const float 
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: null pointer", what);
     if (u == out || u == x0 || u == x1 || out == x0 || out == x1)
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: u and out must be maps of their own", what);
-    const Plan p(C0, C1, B, H, W, Cout, K, stride);
+    const Plan p(C0, C1, B, H, W, Cout, K, stride, up0);
     if (int rc = check_workspace(what, ws, ws_bytes, p.fwd_floats)) return rc;
     hipStream_t s = (hipStream_t)stream;
     float *part = static_cast<float *>(ws), *ident = part + p.off_ident;
 
     hipLaunchKernelGGL(ft_identity_kernel, dim3(1), dim3(64), 0, s, ident, p.nident);
     if (int rc = gfn::check_launch("ft_identity_kernel")) return rc;
-    const ConvArgs a{x0, x1, weight, ident, ident + p.nident, nullptr, u, C0, C1, 0, H, W, Cout, p.Ho, p.Wo, 0, 0.f};
+    const ConvArgs a{x0, x1, weight, ident, ident + p.nident, nullptr, u, C0, C1, up0, H, W, Cout, p.Ho, p.Wo, 0, 0.f};
     if (int rc = gfn::fpn_conv_launch(a, B, K, stride, s)) return rc;
     hipLaunchKernelGGL(ft_moments_kernel, dim3((unsigned)(Cout * p.nparts)), dim3(256), 0, s, (const float *)u, part, Cout, p.HW, p.red_chunks,
                        p.nparts);
@@ -460,13 +534,11 @@ GFN_EXPORT int gfn_conv2d_bn_act_train_fwd(const float *x0, int C0, const float 
     return gfn::check_launch("ft_apply_kernel");
 }
 
-GFN_EXPORT int gfn_conv2d_bn_act_train_bwd(const float *gy, const float *x0, int C0, const float *x1, int C1, const float *weight,
-                                           const float *bn_w, const float *bn_b, const float *u, const float *mean, const float *invstd,
-                                           float *gx0, float *gx1, float *d_weight, float *d_bn_w, float *d_bn_b, int B, int H, int W,
-                                           int Cout, int K, int stride, int act, float slope, int need, void *ws, int64_t ws_bytes,
-                                           gfn_stream_t stream) {
-    const char *what = "gfn_conv2d_bn_act_train_bwd";
-    if (int rc = check_sizes(what, C0, C1, B, H, W, Cout, K, stride, act)) return rc;
+int train_bwd(const char *what, const float *gy, const float *x0, int C0, int up0, const float *x1, int C1, const float *weight,
+              const float *bn_w, const float *bn_b, const float *u, const float *mean, const float *invstd, float *gx0, float *gx1,
+              float *d_weight, float *d_bn_w, float *d_bn_b, int B, int H, int W, int Cout, int K, int stride, int act, float slope, int need,
+              void *ws, int64_t ws_bytes, gfn_stream_t stream) {
+    if (int rc = check_sizes(what, C0, C1, B, H, W, Cout, K, stride, act, up0)) return rc;
     const int all = GFN_CBT_NEED_X | GFN_CBT_NEED_W | GFN_CBT_NEED_BN;
     if (need < 0 || (need & ~all)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: unknown need mask %d", what, need);
     if (B == 0 || need == 0) return GFN_OK;
@@ -475,7 +547,7 @@ GFN_EXPORT int gfn_conv2d_bn_act_train_bwd(const float *gy, const float *x0, int
     if (((need & GFN_CBT_NEED_X) && (!gx0 || (C1 > 0 && !gx1))) || ((need & GFN_CBT_NEED_W) && !d_weight) ||
         ((need & GFN_CBT_NEED_BN) && (!d_bn_w || !d_bn_b)))
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: the need mask asks for a gradient whose pointer is null", what);
-    const Plan p(C0, C1, B, H, W, Cout, K, stride);
+    const Plan p(C0, C1, B, H, W, Cout, K, stride, up0);
     if (int rc = check_workspace(what, ws, ws_bytes, p.bwd_floats)) return rc;
     hipStream_t s = (hipStream_t)stream;
     float *w = static_cast<float *>(ws);
@@ -500,8 +572,15 @@ GFN_EXPORT int gfn_conv2d_bn_act_train_bwd(const float *gy, const float *x0, int
             if (int rc = gfn::check_launch("ft_identity_kernel")) return rc;
             hipLaunchKernelGGL(ft_repack_kernel, dim3((unsigned)((p.wg.wn + 255) / 256)), dim3(256), 0, s, weight, wt, Cout, p.Cin, K * K);
             if (int rc = gfn::check_launch("ft_repack_kernel")) return rc;
-            const ConvArgs a0{gu, nullptr, wt, ident, ident + p.nident, nullptr, gx0, Cout, 0, 0, H, W, C0, H, W, 0, 0.f};
+            float *gx0f = up0 ? w + p.off_gx0f : gx0;  // the gradient of what the convolution read: x0, or with up0 its doubled image
+            const ConvArgs a0{gu, nullptr, wt, ident, ident + p.nident, nullptr, gx0f, Cout, 0, 0, H, W, C0, H, W, 0, 0.f};
             if (int rc = gfn::fpn_conv_launch(a0, B, K, 1, s)) return rc;
+            if (up0) {
+                const int64_t total = (int64_t)B * C0 * (H / 2) * (W / 2);
+                hipLaunchKernelGGL(ft_up2_adjoint_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float *)gx0f, gx0, total,
+                                   H / 2, W / 2);
+                if (int rc = gfn::check_launch("ft_up2_adjoint_kernel")) return rc;
+            }
             if (C1 > 0) {
                 const ConvArgs a1{gu, nullptr, wt + (int64_t)C0 * Cout * K * K, ident, ident + p.nident, nullptr, gx1, Cout, 0, 0, H, W, C1, H, W, 0, 0.f};
                 if (int rc = gfn::fpn_conv_launch(a1, B, K, 1, s)) return rc;
@@ -515,12 +594,63 @@ GFN_EXPORT int gfn_conv2d_bn_act_train_bwd(const float *gy, const float *x0, int
     }
     if (need & GFN_CBT_NEED_W) {
         const WgradShape &g = p.wg;
-        hipLaunchKernelGGL(ft_wgrad_kernel, dim3((unsigned)g.parts, (unsigned)g.nci, (unsigned)g.nco), dim3(256),
-                           (size_t)g.lds_floats() * sizeof(float), s, x0, x1, (const float *)gu, wpart, C0, C1, H, W, Cout, p.Ho, p.Wo, K, stride,
-                           g.IH, g.IW, g.PITCH, g.cig, g.tiles_x, g.tiles_y, g.ntiles);
+        const dim3 grid((unsigned)g.parts, (unsigned)g.nci, (unsigned)g.nco);
+        const size_t lds = (size_t)g.lds_floats() * sizeof(float);
+        auto kernel = ft_wgrad_kernel<false, 0>;
+        if (up0) kernel = K == 1 ? ft_wgrad_kernel<true, 1> : K == 3 ? ft_wgrad_kernel<true, 3> : K == 5 ? ft_wgrad_kernel<true, 5> : ft_wgrad_kernel<true, 7>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, x0, x1, (const float *)gu, wpart, C0, C1, H, W, Cout, p.Ho, p.Wo, K, stride, g.IH,
+                           g.IW, g.PITCH, g.cig, g.tiles_x, g.tiles_y, g.ntiles);
         if (int rc = gfn::check_launch("ft_wgrad_kernel")) return rc;
         hipLaunchKernelGGL(ft_wsum_kernel, dim3((unsigned)((g.wn + 255) / 256)), dim3(256), 0, s, (const float *)wpart, g.parts, g.wn, d_weight);
         if (int rc = gfn::check_launch("ft_wsum_kernel")) return rc;
     }
     return GFN_OK;
 }
+
+}  // namespace
+
+GFN_EXPORT int64_t gfn_conv2d_bn_act_train_ws_bytes(int C0, int C1, int B, int H, int W, int Cout, int K, int stride, int backward) {
+    return train_ws_bytes(C0, C1, B, H, W, Cout, K, stride, backward, 0);
+}
+
+GFN_EXPORT int64_t gfn_conv2d_up_bn_act_train_ws_bytes(int C0, int up0, int C1, int B, int H, int W, int Cout, int K, int stride,
+                                                       int backward) {
+    return train_ws_bytes(C0, C1, B, H, W, Cout, K, stride, backward, up0 ? 1 : 0);
+}
+
+GFN_EXPORT int gfn_conv2d_bn_act_train_fwd(const float *x0, int C0, const float *x1, int C1, const float *weight, const float *conv_bias,
+                                           const float *bn_w, const float *bn_b, float *running_mean, float *running_var,
+                                           const float *residual, float *u, float *mean, float *invstd, float *out, int B, int H, int W,
+                                           int Cout, int K, int stride, int act, float slope, double momentum, double eps, void *ws,
+                                           int64_t ws_bytes, gfn_stream_t stream) {
+    return train_fwd("gfn_conv2d_bn_act_train_fwd", x0, C0, 0, x1, C1, weight, conv_bias, bn_w, bn_b, running_mean, running_var, residual, u,
+                     mean, invstd, out, B, H, W, Cout, K, stride, act, slope, momentum, eps, ws, ws_bytes, stream);
+}
+
+GFN_EXPORT int gfn_conv2d_up_bn_act_train_fwd(const float *x0, int C0, int up0, const float *x1, int C1, const float *weight,
+                                              const float *conv_bias, const float *bn_w, const float *bn_b, float *running_mean,
+                                              float *running_var, const float *residual, float *u, float *mean, float *invstd, float *out,
+                                              int B, int H, int W, int Cout, int K, int stride, int act, float slope, double momentum,
+                                              double eps, void *ws, int64_t ws_bytes, gfn_stream_t stream) {
+    return train_fwd("gfn_conv2d_up_bn_act_train_fwd", x0, C0, up0 ? 1 : 0, x1, C1, weight, conv_bias, bn_w, bn_b, running_mean, running_var,
+                     residual, u, mean, invstd, out, B, H, W, Cout, K, stride, act, slope, momentum, eps, ws, ws_bytes, stream);
+}
+
+GFN_EXPORT int gfn_conv2d_bn_act_train_bwd(const float *gy, const float *x0, int C0, const float *x1, int C1, const float *weight,
+                                           const float *bn_w, const float *bn_b, const float *u, const float *mean, const float *invstd,
+                                           float *gx0, float *gx1, float *d_weight, float *d_bn_w, float *d_bn_b, int B, int H, int W,
+                                           int Cout, int K, int stride, int act, float slope, int need, void *ws, int64_t ws_bytes,
+                                           gfn_stream_t stream) {
+    return train_bwd("gfn_conv2d_bn_act_train_bwd", gy, x0, C0, 0, x1, C1, weight, bn_w, bn_b, u, mean, invstd, gx0, gx1, d_weight, d_bn_w,
+                     d_bn_b, B, H, W, Cout, K, stride, act, slope, need, ws, ws_bytes, stream);
+}
+
+GFN_EXPORT int gfn_conv2d_up_bn_act_train_bwd(const float *gy, const float *x0, int C0, int up0, const float *x1, int C1, const float *weight,
+                                              const float *bn_w, const float *bn_b, const float *u, const float *mean, const float *invstd,
+                                              float *gx0, float *gx1, float *d_weight, float *d_bn_w, float *d_bn_b, int B, int H, int W,
+                                              int Cout, int K, int stride, int act, float slope, int need, void *ws, int64_t ws_bytes,
+                                              gfn_stream_t stream) {
+    return train_bwd("gfn_conv2d_up_bn_act_train_bwd", gy, x0, C0, up0 ? 1 : 0, x1, C1, weight, bn_w, bn_b, u, mean, invstd, gx0, gx1,
+                     d_weight, d_bn_w, d_bn_b, B, H, W, Cout, K, stride, act, slope, need, ws, ws_bytes, stream);
+}
+

@@ -20,10 +20,14 @@ Three paths over the same parameters:
   * in train() on CUDA fp32 input with train_conv_impl "hip" (NOT the default) every layer is one ops.conv2d_bn_act_train call
     (csrc/fpn_conv_train.hip): convolution, the batch's own statistics, BatchNorm, activation and residual in HIP with a HIP backward.
     Autograd keeps the layer's inputs and ONE map per layer, the raw convolution output; the normalised map, the activation's mask
-    or sigmoid and the concatenation are recomputed or never written.  The 2x upsample in front of innerN stays F.interpolate
+    or sigmoid and the concatenation are recomputed or never written.  The 2x upsample in front of innerN is F.interpolate
     (which differentiates it) and its result is passed as x0.  The BatchNorm buffers move as in the reference.  A conv bias in front
     of a batch-statistics BatchNorm (the decoder's and the merge layer's) gets EXACT zeros as its gradient: it cancels in u - mean,
     the true gradient is zero, and torch's autograd returns rounding noise around 1e-7 there.
+  * train_conv_impl "hip_fused" (opt-in like "hip") is "hip" for every layer but the decoder's inner1..3: those pass the coarse
+    map with up0=True, and the op interpolates it on the way in, in the forward and in the weight gradient, and gathers the coarse
+    input gradient with the transposed upsample (ft_up2_adjoint_kernel).  The doubled map is then neither written, nor kept by
+    autograd, nor differentiated by torch; still 19 calls of the op per forward.
   * everything else -- train() with train_conv_impl "torch" (the default), CPU tensors, other dtypes, conv_impl "torch" in eval():
     F.conv2d, BatchNorm, the activation, F.interpolate and torch.cat, as the reference writes them; differentiable, and the
     BatchNorm buffers move as in the reference.
@@ -37,6 +41,7 @@ import torch.nn.functional as F
 from .. import ops
 
 CONV_IMPLS = ("hip", "torch")
+TRAIN_CONV_IMPLS = ("hip", "hip_fused", "torch")  # "hip_fused": "hip" with the decoder's 2x upsample inside the innerN op
 LEAKY_SLOPE = 0.1  # FPN.py:127
 
 
@@ -47,8 +52,8 @@ def _check_impl(conv_impl):
 
 
 def _check_train_impl(train_conv_impl):
-    if train_conv_impl not in CONV_IMPLS:
-        raise ValueError(f"train_conv_impl must be one of {CONV_IMPLS}, got {train_conv_impl!r}")
+    if train_conv_impl not in TRAIN_CONV_IMPLS:
+        raise ValueError(f"train_conv_impl must be one of {TRAIN_CONV_IMPLS}, got {train_conv_impl!r}")
     return train_conv_impl
 
 
@@ -59,7 +64,7 @@ def _use_hip(module, x):
 
 def _use_train_hip(module, x):
     _check_train_impl(module.train_conv_impl)
-    return module.train_conv_impl == "hip" and module.training and x.is_cuda and x.dtype == torch.float32
+    return module.train_conv_impl in ("hip", "hip_fused") and module.training and x.is_cuda and x.dtype == torch.float32
 
 
 def _fold(conv, bn):
@@ -87,8 +92,9 @@ def _check_conv(conv, switch):
                                   f"and no groups; got {conv}: construct with {switch}='torch'")
 
 
-def _hip_train_layer(conv, bn, act, x0, x1=None, residual=None):
-    """One layer on the batch's own statistics through ops.conv2d_bn_act_train; x0 is the doubled map where the layer upsamples."""
+def _hip_train_layer(conv, bn, act, x0, x1=None, residual=None, up0=False):
+    """One layer on the batch's own statistics through ops.conv2d_bn_act_train; where the layer upsamples x0 is the doubled map, or
+    with up0 the coarse one."""
     _check_conv(conv, "train_conv_impl")
     if bn is None or not bn.affine or not bn.track_running_stats:
         raise NotImplementedError("train_conv_impl='hip' needs an affine BatchNorm2d that tracks its running statistics after every "
@@ -96,7 +102,7 @@ def _hip_train_layer(conv, bn, act, x0, x1=None, residual=None):
     x0, x1, residual = (None if t is None else t.contiguous() for t in (x0, x1, residual))
     return ops.conv2d_bn_act_train(x0, conv.weight.contiguous(), conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                    bn.num_batches_tracked, bn.momentum, bn.eps, x1=x1, residual=residual, stride=conv.stride[0], act=act,
-                                   slope=LEAKY_SLOPE)
+                                   slope=LEAKY_SLOPE, up0=up0)
 
 
 def _hip_layer(conv, bn, act, x0, x1=None, up0=False, residual=None):
@@ -247,6 +253,8 @@ class FPNDecoder_concat(nn.Module):
             if inner is not None:  # FPN.py:59: skip + inner(cat(interpolate(intra), skip))
                 if hip:
                     intra = _hip_layer(*_head(inner), intra, x1=skip, up0=True, residual=skip)
+                elif th and self.train_conv_impl == "hip_fused":  # the upsample inside the op, in both directions
+                    intra = _hip_train_layer(*_head(inner), intra, x1=skip, residual=skip, up0=True)
                 elif th:  # the doubled map from torch, which differentiates the upsample; still no concatenation
                     intra = _hip_train_layer(*_head(inner), _up2(intra), x1=skip, residual=skip)
                 else:

@@ -491,9 +491,9 @@ def conv2d_bn_act(x0, weight, scale, shift, x1=None, up0=False, residual=None, s
     return out
 
 
-def _conv2d_train_args(what, x0, x1, weight, residual, vectors, stride, act):
+def _conv2d_train_args(what, x0, x1, weight, residual, vectors, stride, act, up0=False):
     """The refusals of conv2d_bn_act, for the training entry points; vectors: name -> (Cout,) tensor or None.  Returns
-    (dev, B, C0, C1, H, W, Cout, K, Ho, Wo)."""
+    (dev, B, C0, C1, H, W, Cout, K, Ho, Wo); with up0 x0 is the coarse map and H, W are twice its height and width."""
     if act not in CONV_ACTS:
         raise ValueError(f"{what}: act must be one of {list(CONV_ACTS)}, got {act!r}")
     tensors = {"x0": x0, "weight": weight, "x1": x1, "residual": residual, **vectors}
@@ -503,13 +503,16 @@ def _conv2d_train_args(what, x0, x1, weight, residual, vectors, stride, act):
             raise TypeError(f"{what}: {name} must be a contiguous float32 tensor, got {t.dtype}, contiguous={t.is_contiguous()}")
     if x0.dim() != 4 or weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
         raise ValueError(f"{what}: x0 (B,C0,H,W) and weight (Cout,Cin,K,K) expected, got {tuple(x0.shape)}, {tuple(weight.shape)}")
-    B, C0, H, W = x0.shape
+    B, C0 = x0.shape[:2]
+    H, W = (2 * x0.shape[2], 2 * x0.shape[3]) if up0 else x0.shape[2:]
     C1 = 0 if x1 is None else x1.shape[1]
     Cout, Cin, K, _ = weight.shape
     if x1 is not None and (x1.dim() != 4 or x1.shape[0] != B or tuple(x1.shape[2:]) != (H, W)):
         raise ValueError(f"{what}: x1 must be ({B}, C1, {H}, {W}), got {tuple(x1.shape)}")
     if Cin != C0 + C1:
         raise ValueError(f"{what}: weight takes {Cin} channels but the inputs have {C0} + {C1}")
+    if up0 and stride != 1:
+        raise ValueError(f"{what}: up0 needs stride 1, got {stride!r}")
     for name, t in vectors.items():
         if t is not None and tuple(t.shape) != (Cout,):
             raise ValueError(f"{what}: {name} must be ({Cout},), got {tuple(t.shape)}")
@@ -522,35 +525,40 @@ def _conv2d_train_args(what, x0, x1, weight, residual, vectors, stride, act):
 
 
 def conv2d_bn_act_train_fwd(x0, weight, conv_bias, bn_weight, bn_bias, running_mean, running_var, momentum, eps, x1=None, residual=None,
-                            stride=1, act=None, slope=0.1):
-    """The forward launches of conv2d_bn_act_train (gfn_conv2d_bn_act_train_fwd): returns (out, u, mean, invstd) -- u the raw
-    convolution output without the conv bias -- and updates running_mean / running_var in place.  Contiguous float32 CUDA tensors."""
+                            stride=1, act=None, slope=0.1, up0=False):
+    """The forward launches of conv2d_bn_act_train (gfn_conv2d_bn_act_train_fwd; with up0 gfn_conv2d_up_bn_act_train_fwd, x0 the
+    coarse map): returns (out, u, mean, invstd) -- u the raw convolution output without the conv bias -- and updates running_mean /
+    running_var in place.  Contiguous float32 CUDA tensors."""
     what = "conv2d_bn_act_train"
     if bn_weight is None or bn_bias is None or running_mean is None or running_var is None:
         raise ValueError(f"{what}: BatchNorm's weight, bias and running statistics are needed (affine, track_running_stats)")
     dev, B, C0, C1, H, W, Cout, K, Ho, Wo = _conv2d_train_args(
         what, x0, x1, weight, residual, {"conv_bias": conv_bias, "bn_weight": bn_weight, "bn_bias": bn_bias, "running_mean": running_mean,
-                                         "running_var": running_var}, stride, act)
+                                         "running_var": running_var}, stride, act, up0)
     out, u = (torch.empty((B, Cout, Ho, Wo), device=dev, dtype=torch.float32) for _ in range(2))
     mean, invstd = torch.empty(Cout, device=dev, dtype=torch.float32), torch.empty(Cout, device=dev, dtype=torch.float32)
-    nws = int(_L().gfn_conv2d_bn_act_train_ws_bytes(C0, C1, B, H, W, Cout, K, stride, 0))
+    # the entry points with the upsample inside only when asked: every other call keeps its launches
+    size, entry, c0 = ((_L().gfn_conv2d_up_bn_act_train_ws_bytes, _L().gfn_conv2d_up_bn_act_train_fwd, (C0, 1)) if up0 else
+                       (_L().gfn_conv2d_bn_act_train_ws_bytes, _L().gfn_conv2d_bn_act_train_fwd, (C0,)))
+    nws = int(size(*c0, C1, B, H, W, Cout, K, stride, 0))
     ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
-    _timed("conv2d_bn_act_train_fwd", lambda: _L().gfn_conv2d_bn_act_train_fwd(
-        ptr(x0), C0, ptr(x1), C1, ptr(weight), ptr(conv_bias), ptr(bn_weight), ptr(bn_bias), ptr(running_mean), ptr(running_var), ptr(residual),
+    _timed("conv2d_bn_act_train_fwd", lambda: entry(
+        ptr(x0), *c0, ptr(x1), C1, ptr(weight), ptr(conv_bias), ptr(bn_weight), ptr(bn_bias), ptr(running_mean), ptr(running_var), ptr(residual),
         ptr(u), ptr(mean), ptr(invstd), ptr(out), B, H, W, Cout, K, stride, CONV_ACTS[act], float(slope), float(momentum), float(eps), ptr(ws),
         nws, stream_ptr(dev)))
     return out, u, mean, invstd
 
 
 def conv2d_bn_act_train_bwd(gy, x0, weight, bn_weight, bn_bias, u, mean, invstd, x1=None, stride=1, act=None, slope=0.1,
-                            need=(True, True, True), buffers=None):
-    """Gradients of conv2d_bn_act_train's out given gy = dL/dout and what the forward saved (gfn_conv2d_bn_act_train_bwd): returns
-    (gx0, gx1, d_weight, d_bn_weight, d_bn_bias), None where `need` = (inputs, weight, BatchNorm) says so or x1 is None.  buffers: a
+                            need=(True, True, True), buffers=None, up0=False):
+    """Gradients of conv2d_bn_act_train's out given gy = dL/dout and what the forward saved (gfn_conv2d_bn_act_train_bwd; with up0
+    gfn_conv2d_up_bn_act_train_bwd, x0 the coarse map and gx0 of its shape): returns (gx0, gx1, d_weight, d_bn_weight, d_bn_bias),
+    None where `need` = (inputs, weight, BatchNorm) says so or x1 is None.  buffers: a
     dict under those five names of tensors to write into instead of fresh ones; one that `need` does not ask for is handed to the
     library all the same and comes back untouched.  Every result is reproducible bit for bit."""
     what = "conv2d_bn_act_train_bwd"
     dev, B, C0, C1, H, W, Cout, K, Ho, Wo = _conv2d_train_args(
-        what, x0, x1, weight, None, {"bn_weight": bn_weight, "bn_bias": bn_bias, "mean": mean, "invstd": invstd}, stride, act)
+        what, x0, x1, weight, None, {"bn_weight": bn_weight, "bn_bias": bn_bias, "mean": mean, "invstd": invstd}, stride, act, up0)
     for name, t in (("gy", gy), ("u", u)):
         if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, Cout, Ho, Wo):
             raise ValueError(f"{what}: {name} must be a contiguous float32 {(B, Cout, Ho, Wo)}, got {t.dtype} {tuple(t.shape)}")
@@ -558,7 +566,7 @@ def conv2d_bn_act_train_bwd(gy, x0, weight, bn_weight, bn_bias, u, mean, invstd,
     n_x, n_w, n_bn = (bool(n) for n in need)
     mask = (_lib.CBT_NEED_X if n_x else 0) | (_lib.CBT_NEED_W if n_w else 0) | (_lib.CBT_NEED_BN if n_bn else 0)
     buffers = dict(buffers or {})
-    shapes = {"gx0": (n_x, (B, C0, H, W)), "gx1": (n_x and C1 > 0, (B, C1, H, W)), "d_weight": (n_w, tuple(weight.shape)),
+    shapes = {"gx0": (n_x, tuple(x0.shape)), "gx1": (n_x and C1 > 0, (B, C1, H, W)), "d_weight": (n_w, tuple(weight.shape)),
               "d_bn_weight": (n_bn, (Cout,)), "d_bn_bias": (n_bn, (Cout,))}
     for name, (wanted, shape) in shapes.items():
         t = buffers.get(name)
@@ -567,10 +575,12 @@ def conv2d_bn_act_train_bwd(gy, x0, weight, bn_weight, bn_bias, u, mean, invstd,
         elif t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape or not t.is_cuda:
             raise ValueError(f"{what}: buffer {name} must be a contiguous float32 CUDA tensor of shape {shape}")
     if mask:
-        nws = int(_L().gfn_conv2d_bn_act_train_ws_bytes(C0, C1, B, H, W, Cout, K, stride, 1))
+        size, entry, c0 = ((_L().gfn_conv2d_up_bn_act_train_ws_bytes, _L().gfn_conv2d_up_bn_act_train_bwd, (C0, 1)) if up0 else
+                           (_L().gfn_conv2d_bn_act_train_ws_bytes, _L().gfn_conv2d_bn_act_train_bwd, (C0,)))
+        nws = int(size(*c0, C1, B, H, W, Cout, K, stride, 1))
         ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
-        _timed("conv2d_bn_act_train_bwd", lambda: _L().gfn_conv2d_bn_act_train_bwd(
-            ptr(gy), ptr(x0), C0, ptr(x1), C1, ptr(weight), ptr(bn_weight), ptr(bn_bias), ptr(u), ptr(mean), ptr(invstd), ptr(buffers["gx0"]),
+        _timed("conv2d_bn_act_train_bwd", lambda: entry(
+            ptr(gy), ptr(x0), *c0, ptr(x1), C1, ptr(weight), ptr(bn_weight), ptr(bn_bias), ptr(u), ptr(mean), ptr(invstd), ptr(buffers["gx0"]),
             ptr(buffers["gx1"]), ptr(buffers["d_weight"]), ptr(buffers["d_bn_weight"]), ptr(buffers["d_bn_bias"]), B, H, W, Cout, K, stride,
             CONV_ACTS[act], float(slope), mask, ptr(ws), nws, stream_ptr(dev)))
     return tuple(buffers[name] if wanted else None for name, (wanted, _) in shapes.items())
@@ -578,42 +588,46 @@ def conv2d_bn_act_train_bwd(gy, x0, weight, bn_weight, bn_bias, u, mean, invstd,
 
 class _Conv2dBnActTrainFn(torch.autograd.Function):
     """One FPN layer in training mode: saves x0, x1, u, mean, invstd and the parameters -- not the normalised map, the activation's
-    mask or sigmoid, or the concatenation, which the backward recomputes from u or never needs."""
+    mask or sigmoid, or the concatenation, which the backward recomputes from u or never needs.  With up0 the saved x0 is the coarse
+    map and so is the gx0 that comes back: the doubled map exists in neither direction."""
 
     @staticmethod
-    def forward(ctx, x0, x1, weight, conv_bias, bn_weight, bn_bias, residual, running_mean, running_var, momentum, eps, stride, act, slope):
+    def forward(ctx, x0, x1, weight, conv_bias, bn_weight, bn_bias, residual, running_mean, running_var, momentum, eps, stride, act, slope,
+                up0):
         out, u, mean, invstd = conv2d_bn_act_train_fwd(x0, weight, conv_bias, bn_weight, bn_bias, running_mean, running_var, momentum, eps,
-                                                       x1=x1, residual=residual, stride=stride, act=act, slope=slope)
+                                                       x1=x1, residual=residual, stride=stride, act=act, slope=slope, up0=up0)
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(x0, x1, weight, bn_weight, bn_bias, u, mean, invstd)
-            ctx.meta = (stride, act, slope, None if conv_bias is None else conv_bias.shape)
+            ctx.meta = (stride, act, slope, None if conv_bias is None else conv_bias.shape, up0)
         return out
 
     @staticmethod
     def backward(ctx, gy):
         x0, x1, weight, bn_weight, bn_bias, u, mean, invstd = ctx.saved_tensors
-        stride, act, slope, bias_shape = ctx.meta
+        stride, act, slope, bias_shape, up0 = ctx.meta
         n = ctx.needs_input_grad
         gy = gy.contiguous()
         gx0, gx1, d_w, d_g, d_b = conv2d_bn_act_train_bwd(gy, x0, weight, bn_weight, bn_bias, u, mean, invstd, x1=x1, stride=stride, act=act,
-                                                          slope=slope, need=(n[0] or n[1], n[2], n[4] or n[5]))
+                                                          slope=slope, need=(n[0] or n[1], n[2], n[4] or n[5]), up0=up0)
         # the conv bias cancels in u - mean: its gradient is exactly zero
         d_cb = torch.zeros(bias_shape, device=gy.device, dtype=torch.float32) if n[3] and bias_shape is not None else None
         return (gx0 if n[0] else None, gx1 if n[1] else None, d_w, d_cb, d_g if n[4] else None, d_b if n[5] else None,
-                gy if n[6] else None) + (None,) * 7
+                gy if n[6] else None) + (None,) * 8
 
 
 def conv2d_bn_act_train(x0, weight, conv_bias, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, x1=None,
-                        residual=None, stride=1, act=None, slope=0.1):
+                        residual=None, stride=1, act=None, slope=0.1, up0=False):
     """One FPN layer under model.train() with a backward, all in csrc/fpn_conv_train.hip (reference model/FPN.py:95-128, :43-66,
     model/network.py:66, 182, which torch autograd differentiates there):
 
-        u = conv(cat(x0, x1), weight)        out = act(batch_norm(u + conv_bias; the batch's own statistics)) + residual
+        u = conv(cat(x0', x1), weight)       out = act(batch_norm(u + conv_bias; the batch's own statistics)) + residual
 
-    x0 (B, C0, H, W); x1 (B, C1, H, W) or None; weight (Cout, C0 + C1, K, K), K in 1, 3, 5, 7, zero padding K // 2, stride 1 or 2;
+    x0 (B, C0, H, W), or with up0 (B, C0, H/2, W/2) read in both directions through F.interpolate(scale_factor=2, mode="bilinear",
+    align_corners=False) without writing the doubled map (stride 1 only; x1 and residual at (H, W), the gradient of x0 at its own
+    coarse shape); x1 (B, C1, H, W) or None; weight (Cout, C0 + C1, K, K), K in 1, 3, 5, 7, zero padding K // 2, stride 1 or 2;
     conv_bias (Cout) or None; bn_weight, bn_bias, running_mean, running_var (Cout); residual of the output's shape or None (it may be x0
-    or x1); act None, "leaky_relu" (with slope) or "swish".  Contiguous float32 CUDA tensors, the current stream.  There is no up0: pass
-    the doubled map as x0 (F.interpolate differentiates the upsample); the concatenation is not written in either direction.
+    or x1); act None, "leaky_relu" (with slope) or "swish".  Contiguous float32 CUDA tensors, the current stream.  The concatenation is not
+    written in either direction.
     running_mean / running_var are updated in place with `momentum` (a float) as torch does (unbiased variance, the conv bias in the
     mean), their version counters are bumped and num_batches_tracked, when given, is incremented -- also without grad mode (train()
     under no_grad: forward and buffers only, nothing saved).  Gradients flow to x0, x1, residual (gy itself), weight, bn_weight and
@@ -623,7 +637,7 @@ def conv2d_bn_act_train(x0, weight, conv_bias, bn_weight, bn_bias, running_mean,
     if momentum is None:
         raise ValueError("conv2d_bn_act_train: momentum must be a float (cumulative averaging, momentum=None, is not supported)")
     out = _Conv2dBnActTrainFn.apply(x0, x1, weight, conv_bias, bn_weight, bn_bias, residual, running_mean, running_var, float(momentum),
-                                    float(eps), stride, act, float(slope))
+                                    float(eps), stride, act, float(slope), bool(up0))
     # the kernels wrote the buffers through raw pointers: tell autograd's version counters
     torch.autograd.graph.increment_version(running_mean)
     torch.autograd.graph.increment_version(running_var)

@@ -44,8 +44,8 @@ def _check_choices(decoder, fpn, dino="checkout"):
 
 
 def _check_fpn_train_impl(fpn, fpn_train_impl):
-    if fpn_train_impl not in ("torch", "hip"):
-        raise ValueError(f"fpn_train_impl must be 'torch' or 'hip', got {fpn_train_impl!r}")
+    if fpn_train_impl not in ("torch", "hip", "hip_fused"):
+        raise ValueError(f"fpn_train_impl must be 'torch', 'hip' or 'hip_fused', got {fpn_train_impl!r}")
     if fpn_train_impl != "torch" and fpn != "hip":
         raise ValueError(f"fpn_train_impl={fpn_train_impl!r} needs fpn='hip': the checkout's FPN modules train through torch only")
 
@@ -120,8 +120,8 @@ class ReferenceBackbone(nn.Module):
     under the same parameter names (`dino_weights` load strictly, exactly as above) with its attention and the seams of its blocks
     in HIP in fp16 eval().  With decoder="hip", fpn="hip" and dino="hip" nothing of a checkout is imported.
 
-    fpn_train_impl: "torch" (default) or "hip", the train_conv_impl of the three native FPN modules: what they run under train() (see
-    gfnet_amd/model/fpn.py).  The checkout's modules have no such switch: anything but "torch" with fpn="checkout" raises ValueError.
+    fpn_train_impl: "torch" (default), "hip" or "hip_fused" ("hip" with the decoder's 2x upsample inside the innerN op), the
+    train_conv_impl of the three native FPN modules: what they run under train() (see gfnet_amd/model/fpn.py).  The checkout's modules have no such switch: anything but "torch" with fpn="checkout" raises ValueError.
 
     decoder_train_impl: "torch" (default) or "hip", the train_block_impl of the native cross-view decoder: "hip" trains its blocks
     through the backward kernels of csrc/decoder_block.hip under fp16 autocast (see gfnet_amd/model/crossview_decoder.py).  Anything

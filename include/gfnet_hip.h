@@ -719,7 +719,7 @@ int gfn_conv2d_bn_act_fwd(const float *x0, int C0, int up0, const float *x1, int
 
 /* The same layer in TRAINING mode (model.train(): the reference trains the whole FPN, trainer/train.py:108, through torch autograd);
  * csrc/fpn_conv_train.hip.  fp32, NCHW, contiguous, x = cat(x0, x1) with x0 (B, C0, H, W) and x1 (B, C1, H, W) or NULL with C1 = 0 (no
- * up0 here: the caller passes the doubled map as x0, F.interpolate differentiates the upsample):
+ * up0 in these three: x0 is read as it is; the gfn_conv2d_up_bn_act_train_* entry points below take the coarse map):
  *   u    = conv(x, weight)                      zero padding K/2; the conv bias is NOT in u
  *   mean, invstd (Cout) of u over B*Ho*Wo       biased variance, eps inside the root
  *   out  = act(bn_w * (u - mean) * invstd + bn_b) + residual             (evaluated as u * alpha + beta', alpha = bn_w * invstd)
@@ -754,6 +754,30 @@ int gfn_conv2d_bn_act_train_bwd(const float *gy, const float *x0, int C0, const 
                                 const float *bn_b, const float *u, const float *mean, const float *invstd, float *gx0, float *gx1,
                                 float *d_weight, float *d_bn_w, float *d_bn_b, int B, int H, int W, int Cout, int K, int stride, int act,
                                 float slope, int need, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+
+/* The training layer with the decoder's 2x upsample inside it (model/FPN.py:59, skip + innerN(cat(interpolate(intra), skip))): the three
+ * entry points above with `int up0` after C0; up0 = 0 is the entry point above, launch for launch.  With up0 != 0:
+ *   x0 is (B, C0, H/2, W/2) and stands for x0', exactly F.interpolate(x0, scale_factor=2, mode="bilinear", align_corners=False), in
+ *   both directions; x1, residual, u, out and gy are at (H, W); gx0 is (B, C0, H/2, W/2), the gradient of x0 itself.  x0' is never
+ *   written: the convolution interpolates while it stages its halo tile (gfn_conv2d_bn_act_fwd's up0), the weight gradient stages the
+ *   coarse footprint of its tile in LDS and interpolates from there with the same operations in the same order, so both directions
+ *   read the same x0' bit for bit.
+ *   gx0: the gradient of x0' is written at (H, W) into the workspace by the stride-1 input-gradient launch, and ft_up2_adjoint_kernel
+ *   applies the transposed upsample as a gather: per coarse value the rows 2c-1 .. 2c+2 and the columns likewise, weights 1/4, 3/4,
+ *   3/4, 1/4 each way, the border weights folded onto the first and last row and column as the forward's clamps fold them; 16 taps in
+ *   a fixed order, no atomics.  With a need mask without GFN_CBT_NEED_X neither is launched.
+ * Limits: those above, and with up0 H and W even and stride 1; the 2^31-byte bound on x0 is that of its doubled image.  Anything else
+ *   returns GFN_ERR_INVALID_ARG before a launch; gfn_conv2d_up_bn_act_train_ws_bytes returns 0 for it.
+ * ws: with up0 the backward size grows by B C0 H W floats (rounded up to 4), the gradient of x0'; the forward size is unchanged. */
+int64_t gfn_conv2d_up_bn_act_train_ws_bytes(int C0, int up0, int C1, int B, int H, int W, int Cout, int K, int stride, int backward);
+int gfn_conv2d_up_bn_act_train_fwd(const float *x0, int C0, int up0, const float *x1, int C1, const float *weight, const float *conv_bias,
+                                   const float *bn_w, const float *bn_b, float *running_mean, float *running_var, const float *residual,
+                                   float *u, float *mean, float *invstd, float *out, int B, int H, int W, int Cout, int K, int stride,
+                                   int act, float slope, double momentum, double eps, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+int gfn_conv2d_up_bn_act_train_bwd(const float *gy, const float *x0, int C0, int up0, const float *x1, int C1, const float *weight,
+                                   const float *bn_w, const float *bn_b, const float *u, const float *mean, const float *invstd, float *gx0,
+                                   float *gx1, float *d_weight, float *d_bn_w, float *d_bn_b, int B, int H, int W, int Cout, int K, int stride,
+                                   int act, float slope, int need, void *ws, int64_t ws_bytes, gfn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Self-attention forward of the DINOv2 ViT at head dim 64 -- model/transformer/layers/attention.py:77-101 (Attention.forward:

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Time the native FPN in TRAINING mode (gfnet_amd/model/fpn.py under train()): forward + backward with train_conv_impl "hip"
-(csrc/fpn_conv_train.hip: one op per layer, one saved map per layer) against the module's own torch path on the same commit
-(F.conv2d, BatchNorm2d on batch statistics, the activation, F.interpolate, torch.cat and autograd), same parameters and inputs.
+(csrc/fpn_conv_train.hip: one op per layer, one saved map per layer) and "hip_fused" (the same with the decoder's 2x upsample inside
+the inner1..3 ops: no doubled map) against the module's own torch path on the same commit (F.conv2d, BatchNorm2d on batch statistics,
+the activation, F.interpolate, torch.cat and autograd), same parameters and inputs.
 
     python tools/time_fpn_train.py [--images 16] [--sizes 448] [--rounds 7] [--reps 3] [--out fpn_train_timing.json]
 
 Per size: every layer forward + backward on its real input (the maps of one torch-path forward) with a fixed output gradient, then
 the three modules forward + backward, and for those the peak of torch.cuda.max_memory_allocated above what is allocated before the
-step.  The two paths ALTERNATE round by round; a round is `reps` back-to-back calls between two device events; reported per path
-are the median round and the spread (min .. max) over the rounds, in ms per call.  Every shape is warmed up on both paths first.
+step.  The paths ALTERNATE round by round ("hip_fused" is timed for inner1..3, the only layers it changes, and for the three
+modules); a round is `reps` back-to-back calls between two device events; reported per path are the median round and the spread
+(min .. max) over the rounds, in ms per call.  Every shape is warmed up on every path first.
 Needs a GPU; nothing here falls back."""
 import argparse
 import json
@@ -34,25 +36,28 @@ def build(device):
 
 
 def layer_calls(mods):
-    """[(name, input keys, call(hip, *inputs) -> map, parameters, key under which the map goes into ctx)] in forward order."""
+    """[(name, input keys, call(path, *inputs) -> map, parameters, key under which the map goes into ctx)] in forward order; path is
+    "torch", "hip" or "hip_fused"."""
     enc, dec, merge = mods["encoder"], mods["decoder"], mods["merge_layer"]
     calls, prev = [], "image"
     for name in ENCODER:
         layer = getattr(enc, name)
-        calls.append((name, (prev,), (lambda layer: lambda hip, x: layer.run(x, False, hip))(layer), list(layer.parameters()), name))
+        calls.append((name, (prev,), (lambda layer: lambda path, x: layer.run(x, False, path != "torch"))(layer), list(layer.parameters()), name))
         prev = name
 
-    def run_merge(hip, c3, side):
-        if hip:
+    def run_merge(path, c3, side):
+        if path != "torch":
             return fpn._hip_train_layer(*fpn._head(merge), c3, x1=side, residual=c3)
         return c3 + torch.nn.Sequential.forward(merge, torch.cat((c3, side), dim=1))
 
     def head(seq):
-        return lambda hip, x: fpn._hip_train_layer(*fpn._head(seq), x) if hip else seq(x)
+        return lambda path, x: fpn._hip_train_layer(*fpn._head(seq), x) if path != "torch" else seq(x)
 
     def inner(seq):
-        def run(hip, intra, skip):
-            if hip:
+        def run(path, intra, skip):
+            if path == "hip_fused":
+                return fpn._hip_train_layer(*fpn._head(seq), intra, x1=skip, residual=skip, up0=True)
+            if path == "hip":
                 return fpn._hip_train_layer(*fpn._head(seq), fpn._up2(intra), x1=skip, residual=skip)
             return skip + seq(torch.cat((fpn._up2(intra), skip), dim=1))
         return run
@@ -68,28 +73,28 @@ def layer_calls(mods):
     return calls
 
 
-def pyramid_step(mods, hip, image, side, gys):
+def pyramid_step(mods, path, image, side, gys):
     """The three modules forward and backward: gradients of sum_k (out_k * gy_k).sum() for every parameter and the side map."""
     for m in mods.values():
-        m.train_conv_impl = "hip" if hip else "torch"
+        m.train_conv_impl = path
     c0, c1, c2, c3 = mods["encoder"](image)
     outs = mods["decoder"](c0, c1, c2, mods["merge_layer"](c3, side))
     params = [p for m in mods.values() for p in m.parameters()]
     return torch.autograd.grad(outs, [side] + params, gys)
 
 
-def time_pair(fn, rounds, reps):
-    """fn(hip) timed on both paths, alternating: {"hip": [ms per call, one per round], "torch": [...]}."""
-    out = {"hip": [], "torch": []}
-    for hip in (True, False, True, False):  # warm-up: code objects, algorithm choice, allocator
-        fn(hip)
+def time_paths(fn, paths, rounds, reps):
+    """fn(path) timed on every path, alternating: {path: [ms per call, one per round]}."""
+    out = {path: [] for path in paths}
+    for path in paths * 2:  # warm-up: code objects, algorithm choice, allocator
+        fn(path)
     torch.cuda.synchronize()
     for _ in range(rounds):
-        for path in ("hip", "torch"):
+        for path in paths:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(reps):
-                fn(path == "hip")
+                fn(path)
             e1.record()
             e1.synchronize()
             out[path].append(e0.elapsed_time(e1) / reps)
@@ -132,37 +137,45 @@ def main():
         rows, worst = {}, 0.0
         for name, keys, call, params, key in calls:
             inputs = tuple(ctx[k] for k in keys)
+            paths = ("hip", "hip_fused", "torch") if name.startswith("inner") else ("hip", "torch")
             with torch.no_grad():
-                ref = call(False, *inputs)
-                diff = float((call(True, *inputs) - ref).abs().max())
+                ref = call("torch", *inputs)
+                diff = max(float((call(path, *inputs) - ref).abs().max()) for path in paths[:-1])
             ctx[key] = ref.detach().requires_grad_()
             worst = max(worst, diff)
             gy = torch.randn(ref.shape, device=dev, generator=g)
             wanted = [t for t in inputs if t.requires_grad] + params
 
-            def step(hip, call=call, inputs=inputs, gy=gy, wanted=wanted):
-                return torch.autograd.grad(call(hip, *inputs), wanted, gy)
+            def step(path, call=call, inputs=inputs, gy=gy, wanted=wanted):
+                return torch.autograd.grad(call(path, *inputs), wanted, gy)
 
-            t = time_pair(step, args.rounds, args.reps)
-            rows[name] = {"hip": summary(t["hip"]), "torch": summary(t["torch"]), "max_abs_diff": diff, "shape": list(ref.shape)}
+            t = time_paths(step, paths, args.rounds, args.reps)
+            rows[name] = {**{path: summary(t[path]) for path in paths}, "max_abs_diff": diff, "shape": list(ref.shape)}
             del ref, gy
         side = ctx["side"]
         image = ctx["image"]
         shapes = [ctx[k].shape for k in ("out0", "out1", "out2", "out3")]
         del ctx
         gys = [torch.randn(s, device=dev, generator=g) for s in shapes]
-        t = time_pair(lambda hip: pyramid_step(mods, hip, image, side, gys), args.rounds, args.reps)
-        total = {"hip": summary(t["hip"]), "torch": summary(t["torch"])}
-        memory = {path: peak_bytes(lambda: pyramid_step(mods, path == "hip", image, side, gys)) for path in ("hip", "torch")}
+        paths = ("hip", "hip_fused", "torch")
+        t = time_paths(lambda path: pyramid_step(mods, path, image, side, gys), paths, args.rounds, args.reps)
+        total = {path: summary(t[path]) for path in paths}
+        memory = {path: peak_bytes(lambda: pyramid_step(mods, path, image, side, gys)) for path in paths}
         result["sizes"][str(size)] = {"layers": rows, "total": total, "peak_bytes": memory, "max_abs_diff": worst}
         print(f"\n{args.images} images of {size} x {size} on {result['device']}, forward + backward: ms per call, median (min .. max) of "
               f"{args.rounds} rounds of {args.reps}")
-        print("| layer | output | HIP | torch | torch / HIP |\n|---|---|---|---|---|")
+        print("| layer | output | HIP | HIP fused | torch | torch / HIP | torch / HIP fused |\n|---|---|---|---|---|---|---|")
+
+        def cell(r):
+            return f"{r['median_ms']:.3f} ({r['min_ms']:.3f} .. {r['max_ms']:.3f})" if r else ""
+
         for name, r in list(rows.items()) + [("three modules", dict(total, shape=[]))]:
-            h, c = r["hip"], r["torch"]
-            print(f"| {name} | {'x'.join(str(v) for v in r['shape'][1:])} | {h['median_ms']:.3f} ({h['min_ms']:.3f} .. {h['max_ms']:.3f}) | "
-                  f"{c['median_ms']:.3f} ({c['min_ms']:.3f} .. {c['max_ms']:.3f}) | {c['median_ms'] / h['median_ms']:.2f} |")
-        print(f"peak memory of one step above the resident tensors: HIP {memory['hip'] / 2 ** 20:.0f} MiB, torch {memory['torch'] / 2 ** 20:.0f} MiB")
+            h, f, c = r["hip"], r.get("hip_fused"), r["torch"]
+            print(f"| {name} | {'x'.join(str(v) for v in r['shape'][1:])} | {cell(h)} | {cell(f)} | {cell(c)} | "
+                  f"{c['median_ms'] / h['median_ms']:.2f} | {c['median_ms'] / f['median_ms']:.2f} |" if f else
+                  f"| {name} | {'x'.join(str(v) for v in r['shape'][1:])} | {cell(h)} | | {cell(c)} | {c['median_ms'] / h['median_ms']:.2f} | |")
+        print(f"peak memory of one step above the resident tensors: HIP {memory['hip'] / 2 ** 20:.0f} MiB, HIP fused "
+              f"{memory['hip_fused'] / 2 ** 20:.0f} MiB, torch {memory['torch'] / 2 ** 20:.0f} MiB")
         print(f"largest difference between the two paths' layer outputs: {worst:.3e}")
         del gys, image, side
         torch.cuda.empty_cache()
