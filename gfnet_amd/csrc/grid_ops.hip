@@ -347,8 +347,8 @@ __global__ __launch_bounds__(256) void match_post_kernel(const float *__restrict
         }
         c = 1.f / (1.f + expf(-c));                          // :361
         if (fabsf(fx) > 1.f || fabsf(fy) > 1.f) c = 0.f;     // :368-370
-        fx = fminf(fmaxf(fx, -1.f), 1.f);                    // :371
-        fy = fminf(fmaxf(fy, -1.f), 1.f);
+        fx = fx < -1.f ? -1.f : (fx > 1.f ? 1.f : fx);       // :371, torch.clamp: a NaN component stays NaN (fminf / fmaxf drop it)
+        fy = fy < -1.f ? -1.f : (fy > 1.f ? 1.f : fy);
         const float gx = gfn::linspace_at(lo, hi, G, j), gy = gfn::linspace_at(lo, hi, G, i);  // :362-367
         const float4 w = second ? make_float4(fx, fy, gx, gy) : make_float4(gx, gy, fx, fy);   // :373-378
         reinterpret_cast<float4 *>(warp)[idx] = w;

@@ -299,7 +299,8 @@ int gfn_flow_update_resize_fwd(const float *flow_in, const float *cert_in, float
 /* match() post-processing -- model/network.py:332-338 + 358-384.
  *   flow (nb,2,G,G), certainty (nb,1,G,G) finest-scale logits, nb = 2*B_images when symmetric;
  *   cert16_or_null (nb,1,Gc,Gc): scale-16 certainty for the attenuation term, or NULL;
- *   warp (B_images, G, Gw, 4), cert_out (B_images, G, Gw), Gw = 2G (symmetric) or G. */
+ *   warp (B_images, G, Gw, 4), cert_out (B_images, G, Gw), Gw = 2G (symmetric) or G.
+ *   A NaN flow component stays NaN in the warp and does not touch the certainty, as torch.clamp and `> 1` do (:368-371). */
 int gfn_match_post_fwd(const float *flow, const float *certainty, const float *cert16_or_null, float *warp, float *cert_out,
                        int B_images, int G, int Gc, int symmetric, gfn_stream_t stream);
 
