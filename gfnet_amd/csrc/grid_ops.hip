@@ -8,6 +8,7 @@
 //                          reference's torch.cat copy of up to 417 channels disappears.
 //   gfn_grid_sample_fwd    F.grid_sample(bilinear, zeros, align_corners=False): gfn_grid_sample_mode_fwd (grid_modes.hip)
 //   gfn_interp_bilinear_fwd F.interpolate(mode='bilinear', align_corners=False), network.py:238-249,271-281
+//   gfn_interp_bilinear_bwd its adjoint as a gather (training: the backbone's ViT-map resize under deterministic algorithms)
 //   gfn_flow_update_fwd    displacement scaling / eval-time zeroing / accumulation, network.py:262-268
 //   gfn_flow_update_resize_fwd  a scale's last flow update and the resize to the next grid through one LDS tile,
 //                          network.py:262-268 + 271-281
@@ -194,6 +195,61 @@ __global__ __launch_bounds__(256) void interp_bilinear_pair_kernel(const float *
             op[p] = second ? out_b + (size_t)(i - BCa) * Ho * Wo : out_a + (size_t)i * Ho * Wo;
         }
         interp_quad(pl, op, min(kResizePlanes, BC - g), H, W, Ho, Wo, q, Wq);
+    }
+}
+
+// The resize's adjoint as a gather: an input pixel p of one axis is a tap of the outputs o whose source coordinate
+// (o + 1/2) n_in / n_out - 1/2 lies in (p - 1, p + 1).  That interval in closed form, widened by one output on each side against
+// the rounding of interp_tap's fp32 arithmetic (as dx_candidates does in refiner_input_bwd.hip); pixels 0 and 1 start at output 0,
+// where the source coordinate is clamped.  Whether a candidate really has the pixel as a tap, and with which weight, is decided by
+// interp_tap itself.
+__device__ __forceinline__ void interp_bwd_candidates(int p, int n_in, int n_out, int &first, int &last) {
+    const float r = (float)n_out / (float)n_in;
+    first = p <= 1 ? 0 : max(0, (int)floorf(((float)p - 0.5f) * r - 0.5f) - 1);
+    last = min(n_out - 1, (int)ceilf(((float)p + 1.5f) * r - 0.5f) + 1);
+}
+// the weight of input index p in one axis' tap; at the clamped far border both taps are the same pixel and both weights count
+__device__ __forceinline__ bool interp_bwd_weight(const Tap &t, int p, double &w) {
+    w = (t.i0 == p ? (double)t.h : 0.0) + (t.i1 == p ? (double)t.l : 0.0);
+    return (t.i0 == p) | (t.i1 == p);
+}
+
+// One thread per input pixel and up to kResizePlanes planes: the outputs that read the pixel, in ascending (row, column) order,
+// summed in double (a row's columns first, then the row's weight) and rounded to fp32 once.  No atomics; grad_in is overwritten.
+__global__ __launch_bounds__(256) void interp_bilinear_bwd_kernel(const float *__restrict__ gout, float *__restrict__ gin, int BC, int H,
+                                                                  int W, int Ho, int Wo) {
+    const unsigned pix = blockIdx.x * 256u + threadIdx.x;
+    if (pix >= (unsigned)(H * W)) return;
+    const int py = (int)(pix / (unsigned)W), px = (int)pix - py * W;
+    int y0, y1, x0, x1;
+    interp_bwd_candidates(py, H, Ho, y0, y1);
+    interp_bwd_candidates(px, W, Wo, x0, x1);
+    for (int g = blockIdx.y * kResizePlanes; g < BC; g += gridDim.y * kResizePlanes) {  // block-uniform
+        const int np = min(kResizePlanes, BC - g);
+        const float *__restrict__ src = gout + (size_t)g * Ho * Wo;
+        const size_t oplane = (size_t)Ho * Wo;
+        double acc[kResizePlanes];
+#pragma unroll
+        for (int p = 0; p < kResizePlanes; ++p) acc[p] = 0.0;
+        for (int y = y0; y <= y1; ++y) {
+            double wy;
+            if (!interp_bwd_weight(interp_tap(H, Ho, y), py, wy)) continue;
+            double row[kResizePlanes];
+#pragma unroll
+            for (int p = 0; p < kResizePlanes; ++p) row[p] = 0.0;
+            for (int x = x0; x <= x1; ++x) {
+                double wx;
+                if (!interp_bwd_weight(interp_tap(W, Wo, x), px, wx)) continue;
+#pragma unroll
+                for (int p = 0; p < kResizePlanes; ++p)
+                    if (p < np) row[p] += wx * (double)src[(size_t)p * oplane + (size_t)y * Wo + x];
+            }
+#pragma unroll
+            for (int p = 0; p < kResizePlanes; ++p) acc[p] += wy * row[p];
+        }
+#pragma unroll
+        for (int p = 0; p < kResizePlanes; ++p)
+            if (p < np) gin[(size_t)(g + p) * H * W + pix] = (float)acc[p];
     }
 }
 
@@ -410,6 +466,19 @@ GFN_EXPORT int gfn_interp_bilinear_fwd(const float *in, float *out, int BC, int 
     hipLaunchKernelGGL(interp_bilinear_kernel, dim3(gx, (unsigned)(groups < 65535 ? groups : 65535)), dim3(256), 0, (hipStream_t)stream, in,
                        out, BC, H, W, Ho, Wo);
     return gfn::check_launch("interp_bilinear_kernel");
+}
+
+GFN_EXPORT int gfn_interp_bilinear_bwd(const float *grad_out, float *grad_in, int BC, int H, int W, int Ho, int Wo, gfn_stream_t stream) {
+    if (!grad_out || !grad_in || BC < 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0)
+        return gfn::fail(GFN_ERR_INVALID_ARG, "interp_bilinear_bwd: bad argument");
+    if (BC == 0) return GFN_OK;
+    if ((long)H * W >= (1L << 31) || (long)Ho * Wo >= (1L << 31))
+        return gfn::fail(GFN_ERR_INVALID_ARG, "interp_bilinear_bwd: plane too large");
+    const unsigned gx = (unsigned)(((long)H * W + 255) / 256);
+    const int groups = (BC + kResizePlanes - 1) / kResizePlanes;
+    hipLaunchKernelGGL(interp_bilinear_bwd_kernel, dim3(gx, (unsigned)(groups < 65535 ? groups : 65535)), dim3(256), 0, (hipStream_t)stream,
+                       grad_out, grad_in, BC, H, W, Ho, Wo);
+    return gfn::check_launch("interp_bilinear_bwd_kernel");
 }
 
 GFN_EXPORT int gfn_interp_bilinear_pair_fwd(const float *in_a, float *out_a, int BCa, const float *in_b, float *out_b, int BCb, int H,

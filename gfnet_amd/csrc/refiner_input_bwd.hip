@@ -13,7 +13,17 @@
 //                                   of 8 channels) visits the cells whose centre can lie within one pixel of it and adds the ones
 //                                   that have it as a corner, in row-major cell order.  No atomics.
 // Every sample set-up is gfn_sm::bilin_setup / Taps<GFN_SAMPLE_BILINEAR> (sample_modes.h), the forward's own arithmetic, and the
-// cell centres are the forward's linspace_at values.  Only dy depends on the order in which atomics arrive.
+// cell centres are the forward's linspace_at values.  On the plain entry point only dy depends on the order in which atomics
+// arrive.
+//
+// gfn_refiner_input_bwd_det makes dy a function of the multiset of its terms: the same launches with the scatter in 64-bit fixed
+// point (integer addition commutes; the KDE column sums of kde.hip do the same), around them
+//   refiner_input_bwd_det_scale_kernel   M_b = the largest finite |g| of a sample's x_hat planes, an integer atomicMax on its bits
+//   refiner_input_bwd_det_finish_kernel  dy = (float)(acc * 2^-k_b), NaN where a non-finite term arrived (a flag bitmap)
+// with k_b = 62 - E_b - ceil(log2(G * G)) and M_b < 2^E_b: the bilinear weights lie in [0, 1] and a cell reaches an element at most
+// once, so |sum of term * 2^k_b| < 2^62 whatever the flow.
+#include <algorithm>
+
 #include "common.h"
 #include "refiner_input.h"
 #include "sample_modes.h"
@@ -31,7 +41,21 @@ struct RibArgs {
     float *dx, *dy, *dflow, *part;  // part: (3 Dd, B * blocks per sample) partial sums, NULL when dW / db are not wanted
     int B, C, Hs, Ws, G, Dd;
     float disp_scale;
+    // the deterministic dy (DET kernels only): 64-bit accumulators and a non-finite flag bit per dy element, max |g| bits per sample
+    unsigned long long *acc;
+    unsigned *flags;
+    unsigned *maxbits;
+    int lgg;  // ceil(log2(G * G))
 };
+
+// k_b of a sample from the bits of M_b > 0 (finite): M_b < 2^E as frexp gives it, subnormals included
+__device__ __forceinline__ int det_shift(unsigned maxbits, int lgg) {
+    const int e = (int)(maxbits >> 23);
+    const int E = e > 0 ? e - 126 : 32 - __clz((int)maxbits) - 149;
+    return 62 - E - lgg;
+}
+// 2^k as a double, k within [-1022, 1023] (det_shift gives [-128, 210] and its negation)
+__device__ __forceinline__ double det_pow2(int k) { return __longlong_as_double((long long)(1023 + k) << 52); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -39,7 +63,7 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-template <typename FT>
+template <typename FT, bool DET>
 __global__ __launch_bounds__(256) void refiner_input_bwd_cell_kernel(RibArgs q) {
     const int C = q.C, Hs = q.Hs, Ws = q.Ws, G = q.G, Dd = q.Dd;
     const unsigned plane = (unsigned)(Hs * Ws), GG = (unsigned)(G * G);
@@ -65,6 +89,11 @@ __global__ __launch_bounds__(256) void refiner_input_bwd_cell_kernel(RibArgs q) 
         const float tx = any ? ix - floorf(ix) : 0.f, ty = any ? iy - floorf(iy) : 0.f;
         const FT *__restrict__ yb = static_cast<const FT *>(q.y) + (size_t)b * C * plane;
         float *__restrict__ dyb = q.dy ? q.dy + (size_t)b * C * plane : nullptr;
+        double fix = 0.0;  // DET: 2^k_b, or 0 when the sample has no finite non-zero gradient (every finite term is then 0)
+        if (DET && dyb) {
+            const unsigned mb = q.maxbits[b];
+            if (mb) fix = det_pow2(det_shift(mb, q.lgg));
+        }
         float ax = 0.f, ay = 0.f;
         for (int c0 = 0; c0 < C; c0 += 4) {
             float gv[4], v[4][4];
@@ -80,8 +109,17 @@ __global__ __launch_bounds__(256) void refiner_input_bwd_cell_kernel(RibArgs q) 
                 if (dyb && live) {  // lanes = consecutive cells: under a smooth flow the four adds of a wave fall on neighbouring pixels
                     float *pl = dyb + (size_t)(c0 + k) * plane;
 #pragma unroll
-                    for (int n = 0; n < 4; ++n)
-                        if (in[n]) atomicAdd(pl + t.o[n], t.w[n] * gv[k]);
+                    for (int n = 0; n < 4; ++n) {
+                        if (!in[n]) continue;
+                        const float term = t.w[n] * gv[k];
+                        if (!DET) {
+                            atomicAdd(pl + t.o[n], term);
+                        } else {
+                            const size_t e = (size_t)(pl - q.dy) + (size_t)t.o[n];
+                            if (!(fabsf(term) <= 3.402823466e38f)) atomicOr(q.flags + (e >> 5), 1u << (unsigned)(e & 31));
+                            else if (fix != 0.0) atomicAdd(q.acc + e, (unsigned long long)llrint((double)term * fix));  // wraps: two's complement
+                        }
+                    }
                 }
                 if (q.dflow) {
                     const float v0 = in[0] ? v[k][0] : 0.f, v1 = in[1] ? v[k][1] : 0.f, v2 = in[2] ? v[k][2] : 0.f, v3 = in[3] ? v[k][3] : 0.f;
@@ -133,6 +171,34 @@ __global__ __launch_bounds__(256) void refiner_input_bwd_cell_kernel(RibArgs q) 
         float *o = q.dflow + (size_t)b * 2 * GG;
         o[cell] = gfx;
         o[GG + cell] = gfy;
+    }
+}
+
+// M_b: the largest finite |g| over grad_d[b, C:2C] (contiguous), as its bit pattern -- unsigned order is magnitude order there
+__global__ __launch_bounds__(256) void refiner_input_bwd_det_scale_kernel(RibArgs q) {
+    const int b = (int)blockIdx.y;
+    const size_t n = (size_t)q.C * (size_t)q.G * (size_t)q.G;
+    const float *__restrict__ g = q.g + (size_t)b * q.d_bs + n;
+    unsigned m = 0u;
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) {
+        const unsigned bits = __float_as_uint(g[i]) & 0x7fffffffu;
+        if (bits < 0x7f800000u) m = max(m, bits);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+    if ((threadIdx.x & 63u) == 0 && m) atomicMax(q.maxbits + b, m);
+}
+
+__global__ __launch_bounds__(256) void refiner_input_bwd_det_finish_kernel(RibArgs q) {
+    const size_t per = (size_t)q.C * (size_t)q.Hs * (size_t)q.Ws;
+    const int b = (int)blockIdx.y;
+    const unsigned mb = q.maxbits[b];
+    const double inv = mb ? det_pow2(-det_shift(mb, q.lgg)) : 0.0;
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < per; i += (size_t)gridDim.x * 256u) {
+        const size_t e = (size_t)b * per + i;
+        const bool bad = (q.flags[e >> 5] >> (unsigned)(e & 31)) & 1u;
+        const float v = (float)((double)(long long)q.acc[e] * inv);  // exact product (a power of two), one rounding to fp32
+        q.dy[e] = bad ? __uint_as_float(0x7fc00000u) : v;
     }
 }
 
@@ -214,18 +280,22 @@ __global__ __launch_bounds__(256) void refiner_input_bwd_dx_kernel(RibArgs q) {
 
 inline unsigned cell_blocks(int G) { return (unsigned)(((long)G * G + 255) / 256); }
 
-}  // namespace
-
-GFN_EXPORT int64_t gfn_refiner_input_bwd_scratch_bytes(int B, int G, int disp_dim) {
-    if (B <= 0 || G <= 0 || disp_dim < 0) return 0;
-    return (int64_t)B * cell_blocks(G) * 3 * (disp_dim > 0 ? disp_dim : 1) * (int64_t)sizeof(float);
+// The deterministic workspace: one 64-bit accumulator per dy element, one flag bit per element in 32-bit words, one 32-bit word per
+// sample; each of the three parts a multiple of 8 bytes.
+struct DetLayout {
+    int64_t acc_bytes, flag_bytes, max_bytes;
+    int64_t total() const { return acc_bytes + flag_bytes + max_bytes; }
+};
+inline DetLayout det_layout(int B, int C, int Hs, int Ws) {
+    const int64_t n = (int64_t)B * C * Hs * Ws;
+    return {n * 8, ((n + 31) / 32 * 4 + 7) / 8 * 8, ((int64_t)B * 4 + 7) / 8 * 8};
 }
 
-GFN_EXPORT int gfn_refiner_input_bwd(const float *grad_d, int64_t d_bs, const void *f1, int dtype, const float *flow, const float *disp_w,
-                                     const float *gf0, float *dx, float *dy, float *dflow, float *ddisp_w, float *ddisp_b, int B, int C,
-                                     int Hs, int Ws, int G, int disp_dim, int K, float disp_scale, void *scratch, int64_t scratch_bytes,
-                                     gfn_stream_t stream) {
-    const char *what = "refiner_input_bwd";
+// Both entry points.  det: dy through the fixed-point accumulators of `ws`; everything else is the same launches on the same arguments.
+int refiner_input_bwd_run(const char *what, bool det, const float *grad_d, int64_t d_bs, const void *f1, int dtype, const float *flow,
+                          const float *disp_w, const float *gf0, float *dx, float *dy, float *dflow, float *ddisp_w, float *ddisp_b, int B,
+                          int C, int Hs, int Ws, int G, int disp_dim, int K, float disp_scale, void *scratch, int64_t scratch_bytes, void *ws,
+                          int64_t ws_bytes, gfn_stream_t stream) {
     if (dtype != GFN_F32 && dtype != GFN_F16) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: feature dtype must be GFN_F32 or GFN_F16", what);
     if (!grad_d || !f1 || !flow || (disp_dim > 0 && !disp_w)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: null pointer", what);
     if (B < 0 || C <= 0 || Hs <= 0 || Ws <= 0 || G <= 0 || disp_dim < 0 || K < 0 || (long)C * Hs * Ws >= (1L << 31) ||
@@ -237,22 +307,50 @@ GFN_EXPORT int gfn_refiner_input_bwd(const float *grad_d, int64_t d_bs, const vo
     if (sums && (!scratch || scratch_bytes < gfn_refiner_input_bwd_scratch_bytes(B, G, disp_dim)))
         return gfn::fail(GFN_ERR_SCRATCH, "%s: scratch too small (%lld bytes needed)", what,
                          (long long)gfn_refiner_input_bwd_scratch_bytes(B, G, disp_dim));
+    det = det && dy;
+    const DetLayout lay = det_layout(B, C, Hs, Ws);
+    if (det && B > 0 && (!ws || ((uintptr_t)ws & 7) || ws_bytes < lay.total()))
+        return gfn::fail(GFN_ERR_SCRATCH, "%s: ws must be 8-byte aligned and hold %lld bytes", what, (long long)lay.total());
     if (B == 0) return GFN_OK;
     hipStream_t st = (hipStream_t)stream;
     RibArgs q;
     q.g = grad_d; q.d_bs = (long)d_bs; q.y = f1; q.flow = flow; q.dw = disp_w; q.gf0 = gf0;
     q.dx = dx; q.dy = dy; q.dflow = dflow; q.part = sums ? static_cast<float *>(scratch) : nullptr;
     q.B = B; q.C = C; q.Hs = Hs; q.Ws = Ws; q.G = G; q.Dd = disp_dim; q.disp_scale = disp_scale;
+    q.acc = nullptr; q.flags = nullptr; q.maxbits = nullptr; q.lgg = 0;
     const unsigned qb = cell_blocks(G);
-    if (dy) {  // the scatter adds into it
+    if (det) {  // accumulators, flags and the per-sample maxima all start at zero
+        char *w = static_cast<char *>(ws);
+        q.acc = reinterpret_cast<unsigned long long *>(w);
+        q.flags = reinterpret_cast<unsigned *>(w + lay.acc_bytes);
+        q.maxbits = reinterpret_cast<unsigned *>(w + lay.acc_bytes + lay.flag_bytes);
+        while ((1L << q.lgg) < (long)G * G) ++q.lgg;
+        const hipError_t e = hipMemsetAsync(ws, 0, (size_t)lay.total(), st);
+        if (e != hipSuccess) return gfn::fail(GFN_ERR_LAUNCH, "%s: hipMemsetAsync: %s", what, hipGetErrorString(e));
+        const size_t n = (size_t)C * G * G;
+        hipLaunchKernelGGL(refiner_input_bwd_det_scale_kernel, dim3((unsigned)std::min<size_t>((n + 1023) / 1024, 1024), (unsigned)B), dim3(256), 0,
+                           st, q);
+        if (int e2 = gfn::check_launch("refiner_input_bwd_det_scale_kernel")) return e2;
+    } else if (dy) {  // the scatter adds into it
         const hipError_t e = hipMemsetAsync(dy, 0, (size_t)B * C * Hs * Ws * sizeof(float), st);
         if (e != hipSuccess) return gfn::fail(GFN_ERR_LAUNCH, "%s: hipMemsetAsync: %s", what, hipGetErrorString(e));
     }
     if (dy || dflow || sums) {
         const dim3 grid(qb, (unsigned)B);
-        if (dtype == GFN_F16) hipLaunchKernelGGL(refiner_input_bwd_cell_kernel<_Float16>, grid, dim3(256), 0, st, q);
-        else hipLaunchKernelGGL(refiner_input_bwd_cell_kernel<float>, grid, dim3(256), 0, st, q);
+        if (det) {
+            if (dtype == GFN_F16) hipLaunchKernelGGL((refiner_input_bwd_cell_kernel<_Float16, true>), grid, dim3(256), 0, st, q);
+            else hipLaunchKernelGGL((refiner_input_bwd_cell_kernel<float, true>), grid, dim3(256), 0, st, q);
+        } else {
+            if (dtype == GFN_F16) hipLaunchKernelGGL((refiner_input_bwd_cell_kernel<_Float16, false>), grid, dim3(256), 0, st, q);
+            else hipLaunchKernelGGL((refiner_input_bwd_cell_kernel<float, false>), grid, dim3(256), 0, st, q);
+        }
         if (int e = gfn::check_launch("refiner_input_bwd_cell_kernel")) return e;
+    }
+    if (det) {
+        const size_t per = (size_t)C * Hs * Ws;
+        hipLaunchKernelGGL(refiner_input_bwd_det_finish_kernel, dim3((unsigned)std::min<size_t>((per + 255) / 256, 4096), (unsigned)B), dim3(256),
+                           0, st, q);
+        if (int e = gfn::check_launch("refiner_input_bwd_det_finish_kernel")) return e;
     }
     if (sums) {
         hipLaunchKernelGGL(refiner_input_bwd_sum_kernel, dim3(3u * (unsigned)disp_dim), dim3(256), 0, st, q.part, qb * (unsigned)B, disp_dim,
@@ -265,4 +363,32 @@ GFN_EXPORT int gfn_refiner_input_bwd(const float *grad_d, int64_t d_bs, const vo
         if (int e = gfn::check_launch("refiner_input_bwd_dx_kernel")) return e;
     }
     return GFN_OK;
+}
+
+}  // namespace
+
+GFN_EXPORT int64_t gfn_refiner_input_bwd_scratch_bytes(int B, int G, int disp_dim) {
+    if (B <= 0 || G <= 0 || disp_dim < 0) return 0;
+    return (int64_t)B * cell_blocks(G) * 3 * (disp_dim > 0 ? disp_dim : 1) * (int64_t)sizeof(float);
+}
+
+GFN_EXPORT int gfn_refiner_input_bwd(const float *grad_d, int64_t d_bs, const void *f1, int dtype, const float *flow, const float *disp_w,
+                                     const float *gf0, float *dx, float *dy, float *dflow, float *ddisp_w, float *ddisp_b, int B, int C,
+                                     int Hs, int Ws, int G, int disp_dim, int K, float disp_scale, void *scratch, int64_t scratch_bytes,
+                                     gfn_stream_t stream) {
+    return refiner_input_bwd_run("refiner_input_bwd", false, grad_d, d_bs, f1, dtype, flow, disp_w, gf0, dx, dy, dflow, ddisp_w, ddisp_b, B, C,
+                                 Hs, Ws, G, disp_dim, K, disp_scale, scratch, scratch_bytes, nullptr, 0, stream);
+}
+
+GFN_EXPORT int64_t gfn_refiner_input_bwd_det_ws_bytes(int B, int C, int Hs, int Ws) {
+    if (B <= 0 || C <= 0 || Hs <= 0 || Ws <= 0) return 0;
+    return det_layout(B, C, Hs, Ws).total();
+}
+
+GFN_EXPORT int gfn_refiner_input_bwd_det(const float *grad_d, int64_t d_bs, const void *f1, int dtype, const float *flow,
+                                         const float *disp_w, const float *gf0, float *dx, float *dy, float *dflow, float *ddisp_w,
+                                         float *ddisp_b, int B, int C, int Hs, int Ws, int G, int disp_dim, int K, float disp_scale,
+                                         void *scratch, int64_t scratch_bytes, void *ws, int64_t ws_bytes, gfn_stream_t stream) {
+    return refiner_input_bwd_run("refiner_input_bwd_det", true, grad_d, d_bs, f1, dtype, flow, disp_w, gf0, dx, dy, dflow, ddisp_w, ddisp_b, B,
+                                 C, Hs, Ws, G, disp_dim, K, disp_scale, scratch, scratch_bytes, ws, ws_bytes, stream);
 }

@@ -669,7 +669,7 @@ def pos_embed(corr_vol):
 
 
 def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_factor=1.0, corr_in_other=True, reuse=None,
-                  sample_mode="bilinear"):
+                  sample_mode="bilinear", deterministic=None):
     """The concat tensor `d` of ConvRefiner.forward (model/network.py:533-558):
     cat(grid_sample(x, cell centres), grid_sample(y, flow), disp_emb(40/32*scale_factor*(flow-centres)),
     local_correlation(...)) -- every slice written in place by the HIP kernels, no torch.cat.
@@ -681,12 +681,21 @@ def refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fact
     csrc/local_corr_modes.hip), never the tiled correlation or its plan.
     With grad mode on and any of x, y, flow, disp_w, disp_b requiring grad, a bilinear call on a plain batch is differentiable
     (_RefinerInputFn: the same launches forward, gfn_refiner_input_bwd backward; `reuse` is not taken, an autograd graph keeps d);
-    a symmetric batch that needs gradients raises NotImplementedError, as training does.  Every other call is the plain launch."""
+    a symmetric batch that needs gradients raises NotImplementedError, as training does.  Every other call is the plain launch.
+    deterministic: which backward the differentiable call gets (refiner_input_bwd's keyword): None (default) is
+    torch.are_deterministic_algorithms_enabled() at the time of this forward, so torch.use_deterministic_algorithms(True) makes
+    y's gradient bit-reproducible; the forward's bits do not depend on it."""
     if sample_mode == "bilinear" and torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, flow, disp_w, disp_b)):
         if flow.shape[0] != x.shape[0]:
             raise NotImplementedError("training-mode refiner input needs a plain batch (flow and features of equal batch size)")
-        return _RefinerInputFn.apply(x, y, flow, disp_w, disp_b, int(num_grid), int(local_radius), float(scale_factor), bool(corr_in_other))
+        return _RefinerInputFn.apply(x, y, flow, disp_w, disp_b, int(num_grid), int(local_radius), float(scale_factor), bool(corr_in_other),
+                                     resolve_deterministic(deterministic))
     return _refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_factor, corr_in_other, reuse, sample_mode)[0]
+
+
+def resolve_deterministic(deterministic):
+    """A `deterministic` keyword as a bool: None follows torch.are_deterministic_algorithms_enabled() now."""
+    return torch.are_deterministic_algorithms_enabled() if deterministic is None else bool(deterministic)
 
 
 def _refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_factor, corr_in_other, reuse, sample_mode):
@@ -750,12 +759,16 @@ def _refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_fac
     return d, y, fl, w
 
 
-def refiner_input_bwd(grad_d, y, flow, disp_w, local_radius, scale_factor=1.0, corr_in_other=True, need=(True,) * 5):
+def refiner_input_bwd(grad_d, y, flow, disp_w, local_radius, scale_factor=1.0, corr_in_other=True, need=(True,) * 5, deterministic=False):
     """Gradients of refiner_input's d (bilinear, plain batch) with respect to (x, y, flow, disp_w, disp_b) given grad_d = dL/dd:
     fp32 tensors, None where `need` says so (csrc/refiner_input_bwd.hip).  y (B,C,Hs,Ws) fp32 or fp16, flow (B,2,G,G) and disp_w
     (Dd,2) as the forward read them.  The local correlation passes its feature0 gradient on to x (gfn_local_corr_mode_bwd_f0 on
     grad_d's last planes); its feature1 and coordinates are detached, as in the reference (utils/local_correlation.py:54-60).
-    dy is accumulated with fp32 atomics: its last bits can differ between runs; every other result is reproducible."""
+    deterministic=False: dy is accumulated with fp32 atomics and its last bits can differ between runs; every other result is
+    reproducible.  deterministic=True (gfn_refiner_input_bwd_det): dy is the same sum in 64-bit fixed point, scaled per sample by
+    the largest finite |grad| of its x_hat planes -- the same bits on every run, whatever order the cells are visited in, NaN where
+    a non-finite gradient lands; the other four results are the plain call's bits.  It takes a workspace of 8 bytes and a bit per
+    element of dy."""
     dev = require_gpu(grad_d, y, flow, disp_w)
     (y, dt), fl, g = featc(y), f32c(flow), f32c(grad_d)
     w = f32c(disp_w).reshape(-1, 2)
@@ -781,8 +794,14 @@ def refiner_input_bwd(grad_d, y, flow, disp_w, local_radius, scale_factor=1.0, c
     dw, db = out(n_w, Dd, 2), out(n_b, Dd)
     nscr = int(_L().gfn_refiner_input_bwd_scratch_bytes(B, G, Dd)) if (n_w or n_b) else 0
     scr = torch.empty(nscr, device=dev, dtype=torch.uint8) if nscr > 0 else None  # (not the per-stream scratch: its header stays zeroed)
-    _L().gfn_refiner_input_bwd(ptr(g), CH * G * G, ptr(y), dt, ptr(fl), ptr(w), ptr(gf0), ptr(dx), ptr(dy), ptr(dfl), ptr(dw), ptr(db),
-                               B, C, Hs, Ws, G, Dd, K, float(40 / 32 * scale_factor), ptr(scr), nscr, st)
+    args = (ptr(g), CH * G * G, ptr(y), dt, ptr(fl), ptr(w), ptr(gf0), ptr(dx), ptr(dy), ptr(dfl), ptr(dw), ptr(db), B, C, Hs, Ws, G, Dd, K,
+            float(40 / 32 * scale_factor), ptr(scr), nscr)
+    if deterministic:
+        nws = int(_L().gfn_refiner_input_bwd_det_ws_bytes(B, C, Hs, Ws)) if n_y else 0
+        ws = torch.empty(nws // 8, device=dev, dtype=torch.int64) if nws > 0 else None  # (8-byte aligned; the call clears it)
+        _L().gfn_refiner_input_bwd_det(*args, ptr(ws), nws, st)
+    else:
+        _L().gfn_refiner_input_bwd(*args, st)
     return dx, dy, dfl, dw, db
 
 
@@ -791,22 +810,24 @@ class _RefinerInputFn(torch.autograd.Function):
     and disp_w; refiner_input_bwd backward."""
 
     @staticmethod
-    def forward(ctx, x, y, flow, disp_w, disp_b, num_grid, local_radius, scale_factor, corr_in_other):
+    def forward(ctx, x, y, flow, disp_w, disp_b, num_grid, local_radius, scale_factor, corr_in_other, deterministic=False):
         d, yk, fl, w = _refiner_input(num_grid, x, y, flow, disp_w, disp_b, local_radius, scale_factor, corr_in_other, None, "bilinear")
         ctx.save_for_backward(yk, fl, w)
         ctx.meta = (local_radius, scale_factor, corr_in_other, tuple(t.dtype for t in (x, y, flow, disp_w, disp_b)), disp_w.shape, disp_b.shape)
+        ctx.deterministic = deterministic  # resolved when the forward ran
         return d
 
     @staticmethod
     def backward(ctx, grad_d):
         yk, fl, w = ctx.saved_tensors
         r, scale_factor, corr_in_other, dtypes, w_shape, b_shape = ctx.meta
-        grads = list(refiner_input_bwd(grad_d, yk, fl, w, r, scale_factor, corr_in_other, need=ctx.needs_input_grad[:5]))
+        grads = list(refiner_input_bwd(grad_d, yk, fl, w, r, scale_factor, corr_in_other, need=ctx.needs_input_grad[:5],
+                                       deterministic=ctx.deterministic))
         if grads[3] is not None:
             grads[3] = grads[3].reshape(w_shape)
         if grads[4] is not None:
             grads[4] = grads[4].reshape(b_shape)
-        return tuple(None if t is None else t.to(dt) for t, dt in zip(grads, dtypes)) + (None,) * 4
+        return tuple(None if t is None else t.to(dt) for t, dt in zip(grads, dtypes)) + (None,) * 5
 
 
 def grid_sample(x, grid, mode="bilinear", padding_mode="zeros"):
@@ -833,6 +854,35 @@ def interpolate_bilinear(x, size):
     out = torch.empty((B, C, Ho, Wo), device=dev, dtype=torch.float32)
     _L().gfn_interp_bilinear_fwd(ptr(x), ptr(out), B * C, H, W, Ho, Wo, stream_ptr(dev))
     return out
+
+
+class _ResizeBilinearFn(torch.autograd.Function):
+    """interpolate_bilinear with a backward: the same launch forward, gfn_interp_bilinear_bwd (a gather, no atomics) backward."""
+
+    @staticmethod
+    def forward(ctx, x, size):
+        ctx.meta = (x.shape, x.dtype)
+        return interpolate_bilinear(x, size)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (B, C, H, W), dtype = ctx.meta
+        dev = require_gpu(grad_out)
+        g = f32c(grad_out)
+        Ho, Wo = g.shape[2:]
+        grad_in = torch.empty((B, C, H, W), device=dev, dtype=torch.float32)
+        _L().gfn_interp_bilinear_bwd(ptr(g), ptr(grad_in), B * C, H, W, Ho, Wo, stream_ptr(dev))
+        return grad_in.to(dtype), None
+
+
+def resize_bilinear(x, size):
+    """A differentiable F.interpolate(x, size=size, mode='bilinear', align_corners=False): interpolate_bilinear's launch and bits
+    forward (fp32 out), and a backward that gathers instead of scattering with atomics as torch's does on the GPU -- the same bits on
+    every run, and no refusal under torch.use_deterministic_algorithms(True).  interpolate_bilinear itself stays graph-free."""
+    require_gpu(x)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _ResizeBilinearFn.apply(x, size)
+    return interpolate_bilinear(x, size)
 
 
 def interpolate_bilinear_pair(a, b, size):

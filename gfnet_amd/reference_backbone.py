@@ -99,6 +99,17 @@ def _load_dino_weights(vit, dino_weights):
     return vit
 
 
+def _resize_side(vit_feat, size):
+    """The ViT map on the stride-8 grid (32 -> 56 at 448).  torch's GPU backward of F.interpolate scatters with atomics and raises
+    under torch.use_deterministic_algorithms(True); a GPU map that needs a gradient under that flag goes through ops.resize_bilinear
+    (the same resize, its backward a gather).  Every other call is F.interpolate."""
+    if vit_feat.is_cuda and vit_feat.requires_grad and torch.is_grad_enabled() and torch.are_deterministic_algorithms_enabled():
+        from . import ops
+
+        return ops.resize_bilinear(vit_feat, size)
+    return F.interpolate(vit_feat, size=size, mode="bilinear", align_corners=False)
+
+
 class ReferenceBackbone(nn.Module):
     """`backbone(images, upsample) -> (pyramid_A, pyramid_B)` from the checkout's DINOv2 + CrossVITDecoder_noself + FPN.
 
@@ -181,8 +192,7 @@ class ReferenceBackbone(nn.Module):
             va, vb = self.dino_decoder(ta, tb, vit_shape=(n2 // 2, ch, hv // 14, wv // 14))
         vit_feat = torch.cat((va.float(), vb.float()))
         c0, c1, c2, c3 = self.encoder(x)
-        side = vit_feat if tuple(vit_feat.shape[2:]) == (H // 8, W // 8) else \
-            F.interpolate(vit_feat, size=(H // 8, W // 8), mode="bilinear", align_corners=False)
+        side = vit_feat if tuple(vit_feat.shape[2:]) == (H // 8, W // 8) else _resize_side(vit_feat, (H // 8, W // 8))
         # (the native merge layer takes both maps and adds conv31 itself: one launch, no concatenation)
         c3 = self.merge_layer(c3, side) if self.fpn == "hip" else c3 + self.merge_layer(torch.cat((c3, side), dim=1))
         levels = [vit_feat] + list(self.decoder(c0, c1, c2, c3))

@@ -201,7 +201,8 @@ int gfn_refiner_input_plan_fwd_dt(const void *f0, const void *f1, int dtype, con
  * each may be NULL and is then not computed:
  *   dx      (B,C,Hs,Ws)  adjoint of sampling f0 at the cell centres, applied to grad_d[:, 0:C] + gf0: a gather, no atomics
  *   dy      (B,C,Hs,Ws)  adjoint of sampling f1 along the flow: a scatter with fp32 atomic adds; the call clears dy on `stream`
- *                        first.  The one output whose last bits can differ from run to run (the order the adds arrive in)
+ *                        first.  On this entry point its last bits can differ from run to run (the order the adds arrive in);
+ *                        gfn_refiner_input_bwd_det below gives the same sum bit for bit on every run
  *   dflow   (B,2,G,G)    derivative of x_hat with respect to the sampling coordinate (ATen's grid_sampler rule: corners outside
  *                        the image count as zeros; cells 10^6 pixels outside or non-finite get none) plus
  *                        disp_scale * disp_w^T grad_emb.  The local correlation adds nothing: the reference samples its window
@@ -215,6 +216,24 @@ int gfn_refiner_input_bwd(const float *grad_d, int64_t d_bs, const void *f1, int
                           const float *gf0, float *dx, float *dy, float *dflow, float *ddisp_w, float *ddisp_b, int B, int C, int Hs,
                           int Ws, int G, int disp_dim, int K, float disp_scale, void *scratch, int64_t scratch_bytes,
                           gfn_stream_t stream);
+/* gfn_refiner_input_bwd with a bit-reproducible dy: the same arguments, limits and launches, and dx, dflow, ddisp_w, ddisp_b are
+ * the plain call's bits.  dy[b] is the order-independent sum of the plain call's terms t = weight * g (fp32 products, g =
+ * grad_d[b, C + c, cell], one term per live cell, channel and corner inside the map) in 64-bit fixed point:
+ *   M_b = the largest finite |g| over grad_d[b, C:2C], M_b < 2^E_b (frexp), k_b = 62 - E_b - ceil(log2(G * G));
+ *   every finite term adds llrint((double)t * 2^k_b) to its element's 64-bit integer accumulator (integer addition commutes; the
+ *   weights lie in [0, 1] and at most G * G terms reach one element, so |sum| < 2^62 for every accepted input);
+ *   dy = (float)ldexp((double)acc, -k_b): within G * G * 2^-k_b / 2 of the exact sum of the terms, then one fp32 rounding.
+ * An element that received a non-finite term (g inf or NaN) is NaN -- exactly the elements the plain call makes non-finite -- and
+ * M_b ignores non-finite values, so every other element is unaffected.  M_b = 0 or no finite value: the finite terms are zeros.
+ * k_b is per sample: a sample's dy does not depend on its batch peers.
+ * ws: >= gfn_refiner_input_bwd_det_ws_bytes(B, C, Hs, Ws) bytes of 8-byte aligned device memory when dy is wanted (an accumulator
+ * and a flag bit per element, a word per sample; cleared by the call on `stream`, contents undefined afterwards); too small,
+ * misaligned or NULL: GFN_ERR_SCRATCH.  dy == NULL needs no workspace and is the plain call. */
+int64_t gfn_refiner_input_bwd_det_ws_bytes(int B, int C, int Hs, int Ws);
+int gfn_refiner_input_bwd_det(const float *grad_d, int64_t d_bs, const void *f1, int dtype, const float *flow, const float *disp_w,
+                              const float *gf0, float *dx, float *dy, float *dflow, float *ddisp_w, float *ddisp_b, int B, int C,
+                              int Hs, int Ws, int G, int disp_dim, int K, float disp_scale, void *scratch, int64_t scratch_bytes,
+                              void *ws, int64_t ws_bytes, gfn_stream_t stream);
 
 /* F.grid_sample(in, grid, mode='bilinear', padding_mode='zeros', align_corners=False):
  * in (B,C,H,W), grid (B,Ho,Wo,2) -> out (B,C,Ho,Wo) with batch stride out_bs.  This is gfn_grid_sample_mode_fwd with GFN_F32,
@@ -265,6 +284,11 @@ int gfn_refiner_input_mode_fwd_dt(const void *f0, const void *f1, int dtype, con
 /* F.interpolate(x, size=(Ho,Wo), mode='bilinear', align_corners=False) -- model/network.py:238-249,
  * 271-281, 333-335.  in (BC,H,W) -> out (BC,Ho,Wo). */
 int gfn_interp_bilinear_fwd(const float *in, float *out, int BC, int H, int W, int Ho, int Wo, gfn_stream_t stream);
+/* Its adjoint: grad_out (BC,Ho,Wo) -> grad_in (BC,H,W), OVERWRITTEN.  A gather: one thread per input pixel visits the outputs
+ * whose two source taps can include it (membership and weights from the forward's own tap set-up; at the clamped border both taps
+ * of an output can be the same pixel and both weights count) and adds them in ascending (row, column) order, in double, rounded to
+ * fp32 once.  No atomics: the same bits on every run.  Any ratio; same size limits as the forward. */
+int gfn_interp_bilinear_bwd(const float *grad_out, float *grad_in, int BC, int H, int W, int Ho, int Wo, gfn_stream_t stream);
 /* The same for two tensors of one spatial size in a single launch -- the flow (B,2,H,W) and certainty (B,1,H,W) pair the
  * scale loop resizes together at model/network.py:238-249 and 271-281. */
 int gfn_interp_bilinear_pair_fwd(const float *in_a, float *out_a, int BCa, const float *in_b, float *out_b, int BCb, int H, int W,

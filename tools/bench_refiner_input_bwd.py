@@ -5,6 +5,12 @@ conv, the stand-alone local correlation, torch.cat).  HIP events around `iters` 
 `rounds` times in one process; peak memory is torch.cuda.max_memory_allocated over one pass, above what the inputs already hold.
 
     python tools/bench_refiner_input_bwd.py [--rounds 7] [--iters 20] [--out profiles/refiner_input_bwd.md]
+
+--deterministic measures something else: the backward alone (ops.refiner_input_bwd, all five gradients, the local correlation's
+feature0 gradient included), deterministic=False against deterministic=True -- dy as the fp32 atomic scatter against the 64-bit
+fixed-point sum -- at the same three shapes, the two alternating `rounds` times, with the deterministic route's workspace in MB.
+
+    python tools/bench_refiner_input_bwd.py --deterministic [--rounds 7] [--iters 20] [--out FILE]
 """
 import argparse
 import os
@@ -38,12 +44,51 @@ def one_pass(ref, path, G, x, y, flow, grad_d):
     d.backward(grad_d)
 
 
+def deterministic_leg(a):
+    from gfnet_amd import _lib, ops
+
+    lines = ["| scale | C | map | G | r | plain bwd ms (median, min..max) | deterministic bwd ms (median, min..max) | det / plain | workspace MB |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    for scale, C, hs, G, r, Dd in SHAPES:
+        ref = _refiner_for(C, Dd, r).cuda().train()
+        x, y, flow = (t.detach() for t in inputs(C, hs, G, 1))
+        w = ref.disp_emb.weight.detach()
+        grad_d = torch.randn(B, 2 * C + Dd + ((2 * r + 1) ** 2 if r else 0), G, G, device="cuda")
+        run = lambda det: ops.refiner_input_bwd(grad_d, y, flow, w, r, 1.0, r > 0, deterministic=det)  # noqa: E731
+        series = {False: [], True: []}
+        for det in series:
+            for _ in range(3):
+                run(det)
+        torch.cuda.synchronize()
+        for _ in range(a.rounds):
+            for det in series:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.iters):
+                    run(det)
+                e1.record()
+                torch.cuda.synchronize()
+                series[det].append(e0.elapsed_time(e1) / a.iters)
+        fmt = lambda v: f"{statistics.median(v):.3f} ({min(v):.3f}..{max(v):.3f})"  # noqa: E731
+        mp, md = statistics.median(series[False]), statistics.median(series[True])
+        ws = int(_lib.lib().gfn_refiner_input_bwd_det_ws_bytes(B, C, hs, hs)) / 2 ** 20
+        lines.append(f"| {scale} | {C} | {hs} | {G} | {r} | {fmt(series[False])} | {fmt(series[True])} | {md / mp:.2f}x | {ws:.1f} |")
+        print(lines[-1], flush=True)
+        print(f"  series plain {[round(v, 3) for v in series[False]]} deterministic {[round(v, 3) for v in series[True]]}", flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--deterministic", action="store_true", help="the backward alone, plain against deterministic dy")
     a = ap.parse_args()
+    if a.deterministic:
+        return deterministic_leg(a)
     lines = ["| scale | C | map | G | r | torch path ms (median, min..max) | HIP path ms (median, min..max) | speed-up | torch peak MB | HIP peak MB | dy atomic GB/s |",
              "|---|---|---|---|---|---|---|---|---|---|---|"]
     for scale, C, hs, G, r, Dd in SHAPES:
