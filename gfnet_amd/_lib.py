@@ -1,7 +1,7 @@
 """ctypes binding of libgfnet_hip.so, derived from its C ABI: include/gfnet_hip.h is read at import.
 
 Every `gfn_*` prototype of the header gives the argument and return ctypes of its symbol, every `#define GFN_<NAME> <number>` a
-constant of this module (`GFN_RL_STATS` -> `RL_STATS`; `GFN_F32` / `GFN_F16` keep their prefix): nothing of the boundary is typed
+constant of this module (`GFN_RL_STATS` -> `RL_STATS`; `GFN_F32` / `GFN_F16` keep their prefix, `GFN_BF16` has both names): nothing of the boundary is typed
 a second time here.  A declaration the parser does not understand is an error at import, never a default.
 
 torch is imported first so that the library binds to the HIP runtime torch already loaded
@@ -67,6 +67,7 @@ try:
 except OSError as e:
     raise GfnError(f"the C ABI header is needed to bind the library: {e} (set GFNET_HIP_HEADER to include/gfnet_hip.h)") from None
 globals().update({name if name in ("GFN_F32", "GFN_F16") else name[len("GFN_"):]: value for name, value in CONSTANTS.items()})
+GFN_BF16 = CONSTANTS["GFN_BF16"]  # beside GFN_F32 / GFN_F16; the rule above also gives it as BF16
 # F.grid_sample's `mode` / `padding_mode` strings -> GFN_SAMPLE_* / GFN_PAD_*
 SAMPLE_MODES = {mode: CONSTANTS["GFN_SAMPLE_" + mode.upper()] for mode in ("bilinear", "nearest", "bicubic")}
 PADDING_MODES = {mode: CONSTANTS["GFN_PAD_" + mode.upper()] for mode in ("zeros", "border", "reflection")}

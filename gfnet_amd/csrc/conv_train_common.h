@@ -1,7 +1,8 @@
-// conv_train_common.h -- the refiner's training-mode conv block, said once for its two classes.  A class K tells what the maps hold in
+// conv_train_common.h -- the refiner's training-mode conv block, said once for its classes.  A class K tells what the maps hold in
 // HBM: K::map_t is the type of u, y, gy and gz, and K::value(v) the float a value becomes once it is stored in a map or read as an
-// operand -- F32Maps (conv_stack_train.hip): float, v itself; F16Maps (conv_stack_train_half.hip, the autocast class): _Float16, v
-// rounded to fp16.  Here, for both:
+// operand -- F32Maps (conv_stack_train.hip): float, v itself; F16Maps (conv_stack_train_half.hip, the fp16 autocast class): _Float16, v
+// rounded to fp16; BF16Maps (conv_stack_train_bf16.hip, the bf16 autocast class): __bf16, v rounded to bf16 -- the two 16-bit classes
+// being one template over their element (conv_train_16bit.h).  Here, for all:
 //   * BatchNorm as one multiply-add (bn_affine / bn_pre: forward and backward form their ReLU mask through it) and its per-row
 //     constants in LDS (stage_bn_rows)
 //   * the depthwise kernels ct_dw_fwd_kernel<K, XT> and ct_dw_bwd_kernel<K, XT> (XT: the type of x and gx) on the 32x32 tile with its
@@ -145,7 +146,8 @@ __device__ __forceinline__ void dw_param_partials(const float *Gs, const float *
 
 // ---- the two depthwise kernels ----------------------------------------------------------------------------------------------------
 // u = value(dw5x5(value(x), value(taps)) + b_dw) and the tile's (mean, M2 = sum (u - mean)^2) of the u that was stored: shifted sums,
-// safe against cancellation.  Products of two fp16 values are exact in fp32, so F16Maps runs the fp32 tap loop on rounded values
+// safe against cancellation.  Products of two fp16 or two bf16 values are exact in fp32, so F16Maps and BF16Maps run the fp32 tap loop
+// on rounded values
 template <class K, typename XT>
 __global__ __launch_bounds__(256) void ct_dw_fwd_kernel(const XT *__restrict__ x, const float *__restrict__ dw_w,
                                                         const float *__restrict__ dw_b, typename K::map_t *__restrict__ u,
@@ -179,7 +181,7 @@ __global__ __launch_bounds__(256) void ct_dw_fwd_kernel(const XT *__restrict__ x
         ok[q] = gy < G && gx0 + q < G;
         s += ok[q] ? uq[q] : 0.f;
     }
-    if (sizeof(map_t) == 2 && (G & 3) == 0) {  // fp16 planes, rows and the thread's four cells all start on 8 bytes
+    if (sizeof(map_t) == 2 && (G & 3) == 0) {  // 16-bit planes, rows and the thread's four cells all start on 8 bytes
         if (ok[0]) *reinterpret_cast<map_x4 *>(up) = map_x4{(map_t)uq[0], (map_t)uq[1], (map_t)uq[2], (map_t)uq[3]};
     } else {
 #pragma unroll
@@ -479,11 +481,12 @@ bool with_wgrad_shape(const TrainShape &p, F &&f) {
     return false;
 }
 
-// f(XT()) for the type of x and gx: fp32 maps go with fp32 x only
+// f(XT()) for the type of x and gx: fp32, or the class's own 16-bit map type (K::check_class has refused every other x_dtype);
+// fp32 maps go with fp32 x only
 template <class K, typename F>
 void with_x_type(int x_dtype, F &&f) {
     if constexpr (sizeof(typename K::map_t) == 2)
-        if (x_dtype == GFN_F16) return f(_Float16());
+        if (x_dtype != GFN_F32) return f(typename K::map_t());
     f(float());
 }
 

@@ -22,7 +22,9 @@ there); with `train_conv_impl = "hip"` on a refiner its nine blocks run on csrc/
 batch-statistic forward, running-buffer update and backward in HIP) in the fp32 class, and with `train_conv_impl = "hip_amp"` on
 an amp=True refiner on csrc/conv_stack_train_half.hip (ops.conv_block_train_amp) in the class the reference trains in: fp16 maps
 between the blocks, fp16 operands on the matrix core, fp32 sums, parameters and parameter gradients, overflow to inf for the loss
-scaler.  GroupNorm or other norm types, non-depthwise blocks and symmetric batches beyond what the nn path does are out of scope
+scaler; with `train_conv_impl = "hip_bf16"` on an amp=True, amp_dtype=torch.bfloat16 refiner on csrc/conv_stack_train_bf16.hip
+(ops.conv_block_train_bf16): the same with bf16 maps and operands, fp32's exponent range and no need for a loss scale.  GroupNorm or
+other norm types, non-depthwise blocks and symmetric batches beyond what the nn path does are out of scope
 and keep the modules.  Either way the refiner input is assembled with the same HIP launch as inference, which has a HIP backward
 (ops.refiner_input; csrc/refiner_input_bwd.hip).  Refiners with sample_mode "nearest" / "bicubic" train through differentiable
 torch ops instead.
@@ -54,7 +56,8 @@ class ConvRefiner(nn.Module):
     forward(num_grid, x, y, flow, scale_factor=1, logits=None) -> (delta_flow, delta_certainty,
     local_corr).  Input assembly (network.py:533-558) and, in eval mode, the conv stack
     (network.py:560-563) run in HIP; training mode keeps the nn modules unless `train_conv_impl`
-    is "hip" (fp32 class, csrc/conv_stack_train.hip) or "hip_amp" (fp16 autocast class, csrc/conv_stack_train_half.hip).
+    is "hip" (fp32 class, csrc/conv_stack_train.hip), "hip_amp" (fp16 autocast class, csrc/conv_stack_train_half.hip) or "hip_bf16"
+    (bf16 autocast class on a refiner with amp_dtype=torch.bfloat16, csrc/conv_stack_train_bf16.hip).
     """
 
     def __init__(self, in_dim=6, hidden_dim=16, out_dim=2, dw=False, kernel_size=5, hidden_blocks=3,
@@ -104,7 +107,9 @@ class ConvRefiner(nn.Module):
         self.conv_precision = "fp32"
         # training mode: "torch" keeps the nn modules (the default); "hip" runs block1 + hidden_blocks through
         # ops.conv_block_train where _hip_train_stack_supported() holds, "hip_amp" through ops.conv_block_train_amp (fp16 maps, the
-        # class of an amp=True refiner under autocast) where _hip_amp_train_stack_supported() holds; the modules otherwise
+        # class of an amp=True refiner under fp16 autocast) where _hip_amp_train_stack_supported() holds, "hip_bf16" through
+        # ops.conv_block_train_bf16 (bf16 maps, amp=True with amp_dtype=torch.bfloat16) where _hip_bf16_train_stack_supported()
+        # holds; the modules otherwise
         self.train_conv_impl = "torch"
         self.fold_out_conv = True  # multiply out_conv into the last block's 1x1 conv (see folded_stack)
 
@@ -207,10 +212,19 @@ class ConvRefiner(nn.Module):
             return False
         return self._train_blocks_supported(d)
 
+    def _hip_bf16_train_stack_supported(self, d):
+        """Training mode on csrc/conv_stack_train_bf16.hip: opt-in (`train_conv_impl = "hip_bf16"`) on a refiner that the modules would
+        run under bf16 autocast (amp set, amp_dtype bfloat16), same structure as "hip".  Anything else -- an fp16 refiner with this
+        switch, a bf16 refiner with "hip_amp" -- keeps the modules under autocast."""
+        if not self.training or self.train_conv_impl != "hip_bf16" or not self.amp or self.amp_dtype is not torch.bfloat16:
+            return False
+        return self._train_blocks_supported(d)
+
     def _train_stack_hip(self, d, amp=False):
-        """hidden_blocks(block1(d)) in training mode, network.py:560-562, one ops.conv_block_train per block (amp: one
-        ops.conv_block_train_amp; the first reads the fp32 d, the others the fp16 map before them)"""
-        block = ops.conv_block_train_amp if amp else ops.conv_block_train
+        """hidden_blocks(block1(d)) in training mode, network.py:560-562, one ops.conv_block_train per block (amp=True: one
+        ops.conv_block_train_amp, amp=torch.bfloat16: one ops.conv_block_train_bf16; the first reads the fp32 d, the others the
+        16-bit map before them)"""
+        block = ops.conv_block_train_bf16 if amp is torch.bfloat16 else ops.conv_block_train_amp if amp else ops.conv_block_train
         h = d
         for conv, norm, _, pw in [self.block1] + list(self.hidden_blocks):
             h = block(h, conv.weight, conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var,
@@ -299,6 +313,9 @@ class ConvRefiner(nn.Module):
         if self._hip_amp_train_stack_supported(d):
             # fp16 maps between the nine blocks; the last y is fp16 and out_conv runs on fp32, as network.py:563 does
             return self.out_conv(self._train_stack_hip(d, amp=True).float())
+        if self._hip_bf16_train_stack_supported(d):
+            # the same with bf16 maps
+            return self.out_conv(self._train_stack_hip(d, amp=torch.bfloat16).float())
         with torch.autocast("cuda", enabled=bool(self.amp), dtype=self.amp_dtype):
             h = self.hidden_blocks(self.block1(d))
         return self.out_conv(h.float())

@@ -1320,14 +1320,18 @@ def pointwise_conv(t, w, bias, out=None):
     return out
 
 
-# The two classes of the training conv block: what differs between conv_block_train (fp32 maps, csrc/conv_stack_train.hip) and
-# conv_block_train_amp (fp16 maps, csrc/conv_stack_train_half.hip).  label: in messages and _timed names; ws_bytes / fwd / bwd: the
-# entry points; map_dtype: u, y, gy; x_dtype: x may also be float16 and the entry points are told its dtype
+# The three classes of the training conv block: what differs between conv_block_train (fp32 maps, csrc/conv_stack_train.hip),
+# conv_block_train_amp (fp16 maps, csrc/conv_stack_train_half.hip) and conv_block_train_bf16 (bf16 maps,
+# csrc/conv_stack_train_bf16.hip).  label: in messages and _timed names; ws_bytes / fwd / bwd: the entry points; map_dtype: u, y, gy;
+# x_dtype: x may also have map_dtype and the entry points are told its dtype
 _TrainClass = collections.namedtuple("_TrainClass", "label ws_bytes fwd bwd map_dtype x_dtype")
 _FP32 = _TrainClass("conv_block_train", "gfn_conv_block_train_ws_bytes", "gfn_conv_block_train_fwd", "gfn_conv_block_train_bwd",
                     torch.float32, False)
 _AMP = _TrainClass("conv_block_train_amp", "gfn_conv_block_train_half_ws_bytes", "gfn_conv_block_train_half_fwd",
                    "gfn_conv_block_train_half_bwd", torch.float16, True)
+_BF16 = _TrainClass("conv_block_train_bf16", "gfn_conv_block_train_bf16_ws_bytes", "gfn_conv_block_train_bf16_fwd",
+                    "gfn_conv_block_train_bf16_bwd", torch.bfloat16, True)
+_MAP_DTYPE_ARG = {torch.float32: _lib.GFN_F32, torch.float16: _lib.GFN_F16, torch.bfloat16: _lib.GFN_BF16}
 
 
 def _conv_block_train_args(cls, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, pw_w, pw_b):
@@ -1349,8 +1353,9 @@ def _conv_block_train_args(cls, x, dw_w, dw_b, bn_weight, bn_bias, running_mean,
                              f"got {t.dtype}")
         if t.numel() != n:
             raise ValueError(f"{what}: {name} has {t.numel()} elements, C={C} and M={M} need {n}")
-    if x.dtype != torch.float32 and not (amp and x.dtype == torch.float16):
-        raise ValueError(f"{what}: x must be float32{' (a first block) or float16' if amp else ''}, got {x.dtype}")
+    if x.dtype != torch.float32 and not (amp and x.dtype == cls.map_dtype):
+        also = f" (a first block) or {str(cls.map_dtype).replace('torch.', '')}" if amp else ""
+        raise ValueError(f"{what}: x must be float32{also}, got {x.dtype}")
     if B * G * G < 2:
         raise ValueError(f"{what}: batch statistics need more than one value per channel")
     return B, C, M, G
@@ -1358,7 +1363,7 @@ def _conv_block_train_args(cls, x, dw_w, dw_b, bn_weight, bn_bias, running_mean,
 
 def _x_dtype_arg(cls, x):
     """The x_dtype argument of cls's entry points, where they take one."""
-    return (_lib.GFN_F16 if x.dtype == torch.float16 else _lib.GFN_F32,) if cls.x_dtype else ()
+    return (_MAP_DTYPE_ARG[x.dtype],) if cls.x_dtype else ()
 
 
 def _conv_block_train_fwd(cls, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, momentum, eps, pw_w, pw_b):
@@ -1386,8 +1391,9 @@ def _conv_block_train_bwd(cls, gy, x, u, mean, invstd, dw_w, bn_weight, bn_bias,
     M = pw_w.shape[0]
     if tuple(gy.shape) != (B, M, G, G):
         raise ValueError(f"{cls.label}_bwd: grad_y must be {(B, M, G, G)}, got {tuple(gy.shape)}")
-    if cls is _AMP and (u.dtype != torch.float16 or tuple(u.shape) != (B, C, G, G) or not u.is_contiguous() or not x.is_contiguous()):
-        raise ValueError("conv_block_train_amp_bwd: x and u are the contiguous maps of the forward, u float16")
+    if cls.x_dtype and (u.dtype != cls.map_dtype or x.dtype not in (torch.float32, cls.map_dtype) or tuple(u.shape) != (B, C, G, G)
+                        or not u.is_contiguous() or not x.is_contiguous()):
+        raise ValueError(f"{cls.label}_bwd: x and u are the contiguous maps of the forward, u {str(cls.map_dtype).replace('torch.', '')}")
     n_x, n_dww, n_dwb, n_g, n_b, n_pww, n_pwb = need
     n_dwb = n_dwb and has_dw_bias
     mask = (_lib.CBT_NEED_X if n_x else 0) | (_lib.CBT_NEED_DW if (n_dww or n_dwb) else 0) | \
@@ -1498,6 +1504,33 @@ def conv_block_train_amp(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, runnin
     core with fp32 accumulators; rounding overflows to inf, so a GradScaler (ops.FusedAdamWStep) sees a loss scale that is too large.
     Running buffers, num_batches_tracked, momentum and eps as conv_block_train; identical calls give identical bits."""
     return _conv_block_train(_AMP, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, pw_w,
+                             pw_b)
+
+
+def conv_block_train_bf16_fwd(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, momentum, eps, pw_w, pw_b):
+    """The forward launches of conv_block_train_bf16: returns (y, u, mean, invstd) -- y (B,M,G,G) and u (B,C,G,G) bfloat16, mean and
+    invstd float32 -- and updates running_mean / running_var in place (csrc/conv_stack_train_bf16.hip).  x contiguous float32 or
+    bfloat16, parameters contiguous float32."""
+    return _conv_block_train_fwd(_BF16, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, momentum, eps, pw_w, pw_b)
+
+
+def conv_block_train_bf16_bwd(gy, x, u, mean, invstd, dw_w, bn_weight, bn_bias, pw_w, need=(True,) * 7, has_dw_bias=True):
+    """Gradients of conv_block_train_bf16's y with respect to (x, dw_w, dw_b, bn_weight, bn_bias, pw_w, pw_b) given gy = dL/dy (rounded
+    to bfloat16 if it is not) and what the forward saved; None where `need` says so.  gx has x's dtype -- float32, unrounded, for a
+    first block -- and the parameter gradients are float32; every result is reproducible bit for bit."""
+    return _conv_block_train_bwd(_BF16, gy, x, u, mean, invstd, dw_w, bn_weight, bn_bias, pw_w, need, has_dw_bias)
+
+
+def conv_block_train_bf16(x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, pw_w, pw_b):
+    """conv_block_train in the bf16 autocast class -- what torch.autocast(dtype=torch.bfloat16) around block1 + hidden_blocks
+    (model/network.py:560-562) of a refiner built with amp_dtype=torch.bfloat16 runs -- on csrc/conv_stack_train_bf16.hip.  x (B,C,G,G)
+    float32 (a stack's first block: rounded to bf16 on load) or bfloat16 (the previous block's y); float16 raises ValueError; returns
+    y (B,M,G,G) bfloat16.  Parameters and their gradients are float32 (autocast would round the gradients to bf16; this class does
+    not); the gradient of x has x's dtype.  Maps in HBM (u, y, the backward's intermediate and gx) are bf16, every sum fp32, the three
+    1x1 products bf16 operands on the matrix core with fp32 accumulators; rounding is to nearest even without a clamp.  bf16 has
+    fp32's exponent range, so the step needs no loss scale: a gradient scaled by a power of two is the unscaled one times that power,
+    bit for bit.  Running buffers, num_batches_tracked, momentum and eps as conv_block_train; identical calls give identical bits."""
+    return _conv_block_train(_BF16, x, dw_w, dw_b, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, pw_w,
                              pw_b)
 
 

@@ -39,6 +39,8 @@ extern "C" {
  * backbone under autocast, utils/utils.py:306-320).  Arithmetic and every other tensor stay fp32. */
 #define GFN_F32 0
 #define GFN_F16 1
+/* bf16 maps: taken by the gfn_conv_block_train_bf16_* entry points only; every other entry point refuses it */
+#define GFN_BF16 2
 
 typedef void *gfn_stream_t; /* hipStream_t */
 
@@ -516,6 +518,29 @@ int gfn_conv_block_train_half_fwd(const void *x, int x_dtype, const float *dw_w,
                                   void *u, float *mean, float *invstd, void *y, int B, int C, int M, int G, double momentum,
                                   double eps, void *ws, int64_t ws_bytes, gfn_stream_t stream);
 int gfn_conv_block_train_half_bwd(const void *gy, const void *x, int x_dtype, const void *u, const float *mean, const float *invstd,
+                                  const float *dw_w, const float *bn_w, const float *bn_b, const float *pw_w, void *gx,
+                                  float *d_dw_w, float *d_dw_b, float *d_bn_w, float *d_bn_b, float *d_pw_w, float *d_pw_b, int B,
+                                  int C, int M, int G, int need, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+
+/* The same block in the bf16 autocast class (a ConvRefiner built with amp=True, amp_dtype=torch.bfloat16): bf16 maps in HBM;
+ * csrc/conv_stack_train_bf16.hip, the same kernels as the fp16 class over another element (csrc/conv_train_16bit.h).  bf16 keeps
+ * fp32's exponent range, so nothing overflows at 65504 and a step in this class needs no loss scale.
+ *
+ * Maps -- x, u, y, gy, gx -- are plain contiguous (B,C,G,G) bf16 (torch.bfloat16), any C and any G.  x_dtype = GFN_F32 makes x the
+ *   fp32 concat of a stack's first block: it is rounded to bf16 on load, and gx is then fp32, unrounded; x_dtype = GFN_BF16 a bf16
+ *   map; GFN_F16 is refused.  Parameters, their gradients, mean and invstd are fp32; depthwise taps and 1x1 weights are rounded to
+ *   bf16 where they are operands.  Every sum is fp32 (statistics merged in double); u is rounded once and statistics, normalisation
+ *   and backward read that rounded u; t = relu(bn(u)) is rounded as the 1x1 operand; the backward's gz map is rounded before
+ *   BatchNorm's backward reads it.  The three 1x1 products run on v_mfma_f32_32x32x16_bf16.  Rounding is to nearest even with no
+ *   clamp; inf and NaN propagate.
+ * Arguments, `need`, limits, the running-buffer update and bit-for-bit reproducibility are those of the fp32 entry points;
+ *   ws: gfn_conv_block_train_bf16_ws_bytes bytes, 16-byte aligned. */
+int64_t gfn_conv_block_train_bf16_ws_bytes(int B, int C, int M, int G, int backward);
+int gfn_conv_block_train_bf16_fwd(const void *x, int x_dtype, const float *dw_w, const float *dw_b, const float *bn_w,
+                                  const float *bn_b, float *running_mean, float *running_var, const float *pw_w, const float *pw_b,
+                                  void *u, float *mean, float *invstd, void *y, int B, int C, int M, int G, double momentum,
+                                  double eps, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+int gfn_conv_block_train_bf16_bwd(const void *gy, const void *x, int x_dtype, const void *u, const float *mean, const float *invstd,
                                   const float *dw_w, const float *bn_w, const float *bn_b, const float *pw_w, void *gx,
                                   float *d_dw_w, float *d_dw_b, float *d_bn_w, float *d_bn_b, float *d_pw_w, float *d_pw_b, int B,
                                   int C, int M, int G, int need, void *ws, int64_t ws_bytes, gfn_stream_t stream);

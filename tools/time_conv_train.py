@@ -1,11 +1,13 @@
 """Forward + backward time of one refiner's conv stack in train() (GPU): python tools/time_conv_train.py [--batch 8] [--reps 15] [--scales 16,8]
 
-Four paths on the same ConvRefiner weights, the same concat tensor d and the same output weighting, at the five GFNet widths on the
+Six paths on the same ConvRefiner weights, the same concat tensor d and the same output weighting, at the five GFNet widths on the
 grids bench.py's default 448 workload gives them (C, G = 417/32, 361/32, 177/64, 73/128, 24/256): `train_conv_impl = "hip"`
 (csrc/conv_stack_train.hip, fp32) and "torch" (the nn modules on MIOpen, fp32, amp off), and in the reference's autocast class
-"hip_amp" (csrc/conv_stack_train_half.hip, fp16 maps) and "torch_amp" (the nn modules under torch.autocast, amp on).  The runs
+"hip_amp" (csrc/conv_stack_train_half.hip, fp16 maps) and "torch_amp" (the nn modules under torch.autocast, amp on), and in the bf16
+autocast class "hip_bf16" (csrc/conv_stack_train_bf16.hip, bf16 maps) and "torch_bf16" (the nn modules under bf16 autocast).  The runs
 alternate in one process; every timed step is bracketed by device synchronisation; the figure is the median of --reps steps after
---warmup untimed ones, the spread their min .. max.  One JSON line per width, then a markdown table.  --scales picks widths, so
+--warmup untimed ones, the spread their min .. max; <path>_peak_mib is the peak of torch's allocator over one more step of that path
+alone (d, w and every path's parameters stay allocated throughout).  One JSON line per width, then a markdown table.  --scales picks widths, so
 that a job can give every width a process and a time limit of its own; --paths picks paths."""
 import argparse
 import copy
@@ -40,8 +42,21 @@ def timed(ref, d, w):
     return (time.perf_counter() - t0) * 1e3
 
 
-# path -> (train_conv_impl, amp)
-PATHS = {"hip": ("hip", False), "modules": ("torch", False), "hip_amp": ("hip_amp", True), "torch_amp": ("torch", True)}
+# path -> (train_conv_impl, amp, amp_dtype)
+PATHS = {"hip": ("hip", False, torch.float16), "modules": ("torch", False, torch.float16), "hip_amp": ("hip_amp", True, torch.float16),
+         "torch_amp": ("torch", True, torch.float16), "hip_bf16": ("hip_bf16", True, torch.bfloat16),
+         "torch_bf16": ("torch", True, torch.bfloat16)}
+
+
+def peak_mib(ref, d, w):
+    """the allocator's peak over one step, above nothing: MiB"""
+    d.grad = None
+    ref.zero_grad(set_to_none=True)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    step(ref, d, w)
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() / 2 ** 20
 
 
 def main():
@@ -68,8 +83,9 @@ def main():
         refs = {}
         for name in paths:
             refs[name] = copy.deepcopy(base)
-            refs[name].train_conv_impl, refs[name].amp = PATHS[name]
+            refs[name].train_conv_impl, refs[name].amp, refs[name].amp_dtype = PATHS[name]
             assert refs[name]._hip_train_stack_supported(d) == (name == "hip") and refs[name]._hip_amp_train_stack_supported(d) == (name == "hip_amp")
+            assert refs[name]._hip_bf16_train_stack_supported(d) == (name == "hip_bf16")
         for _ in range(args.warmup):
             for ref in refs.values():
                 step(ref, d, w)
@@ -80,15 +96,19 @@ def main():
         row = {"scale": scale, "C": dim, "G": G, "batch": args.batch}
         for name, t in times.items():
             row.update({name + "_ms": statistics.median(t), name + "_min": min(t), name + "_max": max(t)})
+        for name, ref in refs.items():
+            for other in refs.values():
+                other.zero_grad(set_to_none=True)
+            row[name + "_peak_mib"] = peak_mib(ref, d, w)
         rows.append(row)
         print(json.dumps(row), flush=True)
         del base, refs, d, w
         torch.cuda.empty_cache()
-    print("| C | G | batch | " + " | ".join(f"{name} ms (min .. max)" for name in paths) + " |")
+    print("| C | G | batch | " + " | ".join(f"{name} ms (min .. max), peak MiB" for name in paths) + " |")
     print("|---|---|---|" + "---|" * len(paths))
     for q in rows:
         print(f"| {q['C']} | {q['G']} | {q['batch']} | " +
-              " | ".join(f"{q[n + '_ms']:.2f} ({q[n + '_min']:.2f} .. {q[n + '_max']:.2f})" for n in paths) + " |")
+              " | ".join(f"{q[n + '_ms']:.2f} ({q[n + '_min']:.2f} .. {q[n + '_max']:.2f}), {q[n + '_peak_mib']:.0f}" for n in paths) + " |")
 
 
 if __name__ == "__main__":
