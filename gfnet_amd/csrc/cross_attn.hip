@@ -1,11 +1,11 @@
 // Cross-attention core of the cross-view decoder at head dim 8 (reference model/transformer/layers/attention.py:227-258, where
 // flash_attn_func does this work): out = softmax(scale * Q K^T) V per (batch, head), forward and backward, for (B, N, H, 8)
-// contiguous tensors in fp16 or fp32.  The N x N matrix is never written: the forward is an online softmax over key tiles, the
+// contiguous tensors in fp16, bf16 or fp32.  The N x N matrix is never written: the forward is an online softmax over key tiles, the
 // backward recomputes P from the forward's lse: a pass by query tile for delta = sum_j P dP, one by key tile for dK and dV and one by
 // query tile for dQ: no atomics, no scratch.
 //
 // One orientation serves all three kernels.  A head's rows are 8 values, the K of v_mfma_f32_32x32x8_f16, so a
-// 32 x 32 tile of raw scores is ONE matrix instruction (fp32 inputs: four v_mfma_f32_32x32x2_f32, an fmaf chain bit for bit).
+// 32 x 32 tile of raw scores is ONE matrix instruction (bf16 inputs: v_mfma_f32_32x32x8_bf16, the same shape; fp32 inputs: four v_mfma_f32_32x32x2_f32, an fmaf chain bit for bit).
 // The side a kernel keeps results for ("own": queries in the forward and in dQ, keys in dK/dV) is the B operand, so an own row
 // sits on a lane (column = lane & 31) and the 32 rows of the side that streams past through LDS sit in the lane's 16 accumulator
 // registers (rows acc_row(r, lane >> 5)): running maximum, running sum and the 8-wide fp32 results are per-lane registers, and
@@ -34,6 +34,10 @@ struct alignas(16) Row<_Float16> {
     _Float16 e[8];
 };
 template <>
+struct alignas(16) Row<__bf16> {
+    __bf16 e[8];
+};
+template <>
 struct alignas(16) Row<float> {
     float e[8];
 };
@@ -50,13 +54,17 @@ __device__ __forceinline__ Row<T> load_row(const T *p, bool ok) {
     return r;
 }
 
-// the MFMA operand fragment of lane half h for a row: fp16 -> values 4h..4h+3 (one 32x32x8 step); fp32 -> values h, h+2, h+4, h+6
-// (the four 32x32x2 steps)
+// the MFMA operand fragment of lane half h for a row: fp16, bf16 -> values 4h..4h+3 (one 32x32x8 step); fp32 -> values h, h+2, h+4,
+// h+6 (the four 32x32x2 steps)
 template <typename T>
 struct Frag;
 template <>
 struct Frag<_Float16> {
     h4 v;
+};
+template <>
+struct Frag<__bf16> {
+    b4 v;
 };
 template <>
 struct Frag<float> {
@@ -65,6 +73,12 @@ struct Frag<float> {
 
 __device__ __forceinline__ Frag<_Float16> frag_of(const Row<_Float16> &r, int h) {
     Frag<_Float16> f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f.v[j] = h ? r.e[4 + j] : r.e[j];
+    return f;
+}
+__device__ __forceinline__ Frag<__bf16> frag_of(const Row<__bf16> &r, int h) {
+    Frag<__bf16> f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) f.v[j] = h ? r.e[4 + j] : r.e[j];
     return f;
@@ -81,6 +95,10 @@ __device__ __forceinline__ f32x16 dot8(const Frag<_Float16> &a, const Frag<_Floa
     f32x16 z = {};
     return __builtin_amdgcn_mfma_f32_32x32x8f16(a.v, b.v, z, 0, 0, 0);
 }
+__device__ __forceinline__ f32x16 dot8(const Frag<__bf16> &a, const Frag<__bf16> &b) {  // v_mfma_f32_32x32x8_bf16: exact products too
+    f32x16 z = {};
+    return mfma8(a.v, b.v, z);
+}
 __device__ __forceinline__ f32x16 dot8(const Frag<float> &a, const Frag<float> &b) {
     f32x16 acc = {};
 #pragma unroll
@@ -88,18 +106,16 @@ __device__ __forceinline__ f32x16 dot8(const Frag<float> &a, const Frag<float> &
     return acc;
 }
 
-// LDS image of a staged chunk as the A operand.  fp16: the rows as stored, 16 bytes each: a wave's 64 fragment reads (8 bytes at
-// [row][4h]) cover 512 contiguous bytes, conflict free.  fp32: transposed, [value][row]: a 32x32x2 step reads one float per lane
+// LDS image of a staged chunk as the A operand.  fp16, bf16: the rows as stored, 16 bytes each: a wave's 64 fragment reads (8 bytes
+// at [row][4h]) cover 512 contiguous bytes, conflict free.  fp32: transposed, [value][row]: a 32x32x2 step reads one float per lane
 // from 32 consecutive addresses per half (row-major 32-byte rows would put rows r and r + 4 in one bank: 8-way).
 template <typename T>
-struct OpImg;
-template <>
-struct OpImg<_Float16> {
-    alignas(16) _Float16 m[kChunk * 8];
-    __device__ __forceinline__ void put(int row, const Row<_Float16> &r) { *reinterpret_cast<Row<_Float16> *>(&m[row * 8]) = r; }
-    __device__ __forceinline__ Frag<_Float16> get(int tile, int lane) const {
-        Frag<_Float16> f;
-        f.v = *reinterpret_cast<const h4 *>(&m[(tile * 32 + (lane & 31)) * 8 + 4 * (lane >> 5)]);
+struct OpImg {
+    alignas(16) T m[kChunk * 8];
+    __device__ __forceinline__ void put(int row, const Row<T> &r) { *reinterpret_cast<Row<T> *>(&m[row * 8]) = r; }
+    __device__ __forceinline__ Frag<T> get(int tile, int lane) const {
+        Frag<T> f;
+        f.v = *reinterpret_cast<const typename Vec4<T>::type *>(&m[(tile * 32 + (lane & 31)) * 8 + 4 * (lane >> 5)]);
         return f;
     }
 };
@@ -143,6 +159,14 @@ __device__ __forceinline__ void store_half_row(_Float16 *p, const float v[8], in
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = (_Float16)(h ? v[4 + j] : v[j]);
     *reinterpret_cast<h4 *>(p + 4 * h) = o;
+}
+// bf16: rounded to nearest even once (v_cvt_pk_bf16_f32); fp32's exponent range, so nothing overflows that was finite in fp32, and
+// there is no clamp: inf and NaN stay what they are
+__device__ __forceinline__ void store_half_row(__bf16 *p, const float v[8], int h) {
+    b4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = (__bf16)(h ? v[4 + j] : v[j]);
+    *reinterpret_cast<b4 *>(p + 4 * h) = o;
 }
 __device__ __forceinline__ void store_half_row(float *p, const float v[8], int h) {
     *reinterpret_cast<float4 *>(p + 4 * h) = h ? make_float4(v[4], v[5], v[6], v[7]) : make_float4(v[0], v[1], v[2], v[3]);
@@ -283,7 +307,8 @@ __global__ __launch_bounds__(kThreads) void cross_attn_fwd_kernel(const T *__res
 // autograd of the plain definition gives (measured: 110 x the fp32 bound).  Dividing by sum_j P (1 up to the rounding of lse) keeps
 // lse's rounding, which is common to a row's P, out of delta.  The key-tile pass needs every query's delta and the entry point has
 // no scratch: the pass leaves delta in the first four bytes of the query's row of dq, which the dQ pass, launched last, reads
-// before it overwrites the row.
+// before it overwrites the row.  The slot is an fp32 value in a row of 8 T: a bf16 row is 16 bytes and 16-byte aligned exactly as an
+// fp16 row is, so the parking carries over to bf16 unchanged (the narrowest row there is holds four floats).
 template <typename T>
 __device__ __forceinline__ float *delta_slot(T *dq_row) { return reinterpret_cast<float *>(dq_row); }
 
@@ -444,7 +469,8 @@ __global__ __launch_bounds__(kThreads) void cross_attn_bwd_dkv_kernel(const T *_
 
 int check_args(const char *what, int dtype, int B, int Nq, int Nk, int H, int D, float scale, std::initializer_list<const void *> ptrs) {
     if (D != 8) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: head dim %d is not supported, only D = 8 (one v_mfma_f32_32x32x8_f16 per score tile)", what, D);
-    if (dtype != GFN_F32 && dtype != GFN_F16) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: dtype must be GFN_F32 or GFN_F16, got %d", what, dtype);
+    if (dtype != GFN_F32 && dtype != GFN_F16 && dtype != GFN_BF16)
+        return gfn::fail(GFN_ERR_INVALID_ARG, "%s: dtype must be GFN_F32, GFN_F16 or GFN_BF16, got %d", what, dtype);
     if (B < 0 || Nq < 0 || Nk < 1 || H < 1) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: bad size (B=%d Nq=%d Nk=%d H=%d)", what, B, Nq, Nk, H);
     if (B > 65535 || H > 65535) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: B and H are grid dimensions, at most 65535 (B=%d H=%d)", what, B, H);
     if (!std::isfinite(scale)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: scale must be finite", what);
@@ -488,6 +514,7 @@ GFN_EXPORT int gfn_cross_attn_fwd(const void *q, const void *k, const void *v, i
     if (B == 0 || Nq == 0) return GFN_OK;
     if (!lse || ((uintptr_t)lse & 3)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: lse missing or not 4-byte aligned", what);
     hipStream_t s = (hipStream_t)stream;
+    if (dtype == GFN_BF16) return launch_fwd<__bf16>(q, k, v, out, lse, B, Nq, Nk, H, scale, s);
     return dtype == GFN_F16 ? launch_fwd<_Float16>(q, k, v, out, lse, B, Nq, Nk, H, scale, s)
                             : launch_fwd<float>(q, k, v, out, lse, B, Nq, Nk, H, scale, s);
 }
@@ -500,12 +527,13 @@ GFN_EXPORT int gfn_cross_attn_bwd(const void *q, const void *k, const void *v, c
     hipStream_t s = (hipStream_t)stream;
     if (Nq == 0) {  // no query: dK = dV = 0
         if (!dk || !dv) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: null pointer", what);
-        const size_t bytes = (size_t)B * Nk * H * 8 * (dtype == GFN_F16 ? 2 : 4);
+        const size_t bytes = (size_t)B * Nk * H * 8 * (dtype == GFN_F32 ? 4 : 2);
         if (hipMemsetAsync(dk, 0, bytes, s) != hipSuccess || hipMemsetAsync(dv, 0, bytes, s) != hipSuccess)
             return gfn::fail(GFN_ERR_LAUNCH, "%s: hipMemsetAsync failed", what);
         return GFN_OK;
     }
     if (!lse || ((uintptr_t)lse & 3)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: lse missing or not 4-byte aligned", what);
+    if (dtype == GFN_BF16) return launch_bwd<__bf16>(q, k, v, lse, dout, dq, dk, dv, B, Nq, Nk, H, scale, s);
     return dtype == GFN_F16 ? launch_bwd<_Float16>(q, k, v, lse, dout, dq, dk, dv, B, Nq, Nk, H, scale, s)
                             : launch_bwd<float>(q, k, v, lse, dout, dq, dk, dv, B, Nq, Nk, H, scale, s);
 }

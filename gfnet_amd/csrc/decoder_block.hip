@@ -1,15 +1,15 @@
-// A block of the cross-view decoder around its attention core, inference in the fp16 autocast class (reference
+// A block of the cross-view decoder around its attention core, in the fp16 or the bf16 autocast class (reference
 // model/transformer/layers/block.py:327-328 with attention.py:236-238 and :255, mlp.py and layer_scale.py): what comes before
 // gfn_cross_attn_fwd in one launch (norm1 and the three bias-free projections) and what comes after it in another (output
 // projection, LayerScale, residual, norm2, fc1, GELU, fc2, LayerScale, residual).  Width 64, hidden width 256.
 //
-// Every product is computed transposed on v_mfma_f32_32x32x8_f16, Y^T = W X^T: the A operand is a Linear weight as PyTorch stores
-// it, (out, in), read from LDS; a token is a column, so it sits on lane & 31 from the first product to the last, and lane half
-// h = lane >> 5 holds its channels 8g + 4h + j (g = 0..7, j = 0..3).  That is the B operand of k-step g, and it is also where the
+// Every product is computed transposed on v_mfma_f32_32x32x8_f16 (bf16 class: v_mfma_f32_32x32x8_bf16), Y^T = W X^T: the A operand
+// is a Linear weight as PyTorch stores it, (out, in), read from LDS; a token is a column, so it sits on lane & 31 from the first
+// product to the last, and lane half h = lane >> 5 holds its channels 8g + 4h + j (g = 0..7, j = 0..3).  That is the B operand of k-step g, and it is also where the
 // accumulator leaves output row 8g + 4h + j (register 4g + j, common.h acc_row): a product's result is the next product's operand
 // without moving between lanes, a LayerNorm is per-lane sums and one cross-half shuffle per statistic, and fc1 -> GELU -> fc2 never
-// leaves the registers.  Workgroups are persistent: the weights are converted to fp16 into LDS once and the waves loop over
-// 32-token tiles with no barrier in the loop.  No scratch, no atomics: identical calls give identical bits, and a token's result
+// leaves the registers.  Workgroups are persistent: the weights are converted to the class's element into LDS once and the waves
+// loop over 32-token tiles with no barrier in the loop.  No scratch, no atomics: identical calls give identical bits, and a token's result
 // does not depend on where it sits in a tile or which tile it is in.  The second half of the file is the backward of both launches,
 // for training in the same class (the forward kernels are the training forward as they are).
 #include <climits>
@@ -29,13 +29,22 @@ constexpr int kQkvThreads = 256, kPostThreads = 512;
 // start 34 (K = 64) or 130 (K = 256) dwords apart and cover all 64 banks once; a 128-byte pitch would put them all in one bank pair
 constexpr int kPitchC = kC + 4, kPitchH = kHidden + 4;
 
-// rows * cols fp32 values as stored -> fp16 rows of `pitch` halves in LDS (cols a multiple of 4, src 16-byte aligned)
-__device__ __forceinline__ void stage_weight(_Float16 *dst, const float *__restrict__ src, int rows, int cols, int pitch) {
+// The element E of a class, _Float16 (the fp16 autocast class) or __bf16 (the bf16 one), is a template parameter of everything below
+// that touches an operand or a 16-bit tensor; what it brings with it (attn_common.h): V4<E>, four elements as one register pair (an
+// operand fragment, an 8-byte access); (E)float, the rounding to nearest even (v_cvt_f16_f32 / v_cvt_pk_bf16_f32; no clamp, NaN
+// kept); and mfma8, v_mfma_f32_32x32x8_f16 / v_mfma_f32_32x32x8_bf16.  Both elements are 2 bytes, so LDS pitches, bank patterns and
+// the workspace are one set of numbers.  "half" below is a 2-byte element, "fp16(x)" in a formula is (E)x.
+template <typename E>
+using V4 = typename Vec4<E>::type;
+
+// rows * cols fp32 values as stored -> E rows of `pitch` halves in LDS (cols a multiple of 4, src 16-byte aligned)
+template <typename E>
+__device__ __forceinline__ void stage_weight(E *dst, const float *__restrict__ src, int rows, int cols, int pitch) {
     for (int i = threadIdx.x * 4; i < rows * cols; i += blockDim.x * 4) {
         const float4 f = *reinterpret_cast<const float4 *>(src + i);
-        h4 o;
-        o[0] = (_Float16)f.x, o[1] = (_Float16)f.y, o[2] = (_Float16)f.z, o[3] = (_Float16)f.w;
-        *reinterpret_cast<h4 *>(dst + (i / cols) * pitch + (i % cols)) = o;
+        V4<E> o;
+        o[0] = (E)f.x, o[1] = (E)f.y, o[2] = (E)f.z, o[3] = (E)f.w;
+        *reinterpret_cast<V4<E> *>(dst + (i / cols) * pitch + (i % cols)) = o;
     }
 }
 __device__ __forceinline__ void stage_vector(float *dst, const float *__restrict__ src, int n) {
@@ -65,12 +74,13 @@ __device__ __forceinline__ void store_tok(float *p, int h, const Tok &t) {
 // a per-channel vector in LDS at the lane half's channels (every lane of a half reads one address: a broadcast)
 __device__ __forceinline__ float4 chan4(const float *vec, int g, int h) { return *reinterpret_cast<const float4 *>(vec + 8 * g + 4 * h); }
 
-// the B operands of the 8 k-steps: the values rounded to fp16 once
-__device__ __forceinline__ void to_operand(const Tok &t, h4 b[8]) {
+// the B operands of the 8 k-steps: the values rounded to E once
+template <typename E>
+__device__ __forceinline__ void to_operand(const Tok &t, V4<E> b[8]) {
 #pragma unroll
     for (int g = 0; g < 8; ++g)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) b[g][j] = (_Float16)t.v[4 * g + j];
+        for (int j = 0; j < 4; ++j) b[g][j] = (E)t.v[4 * g + j];
 }
 
 // LayerNorm of a token's row in fp32, two-pass over the values as held (mean, then squared distances from it), biased variance;
@@ -100,36 +110,38 @@ __device__ __forceinline__ Tok layernorm(const Tok &t, const float *weight, cons
 }
 
 // acc += W[m0 .. m0 + 31][k0 .. k0 + 8 * KSTEPS - 1] * b: rows m0 + acc_row(r, h) of the product for the lane's token in acc[r]
-template <int KSTEPS>
-__device__ __forceinline__ f32x16 matmul(const _Float16 *w, int pitch, int m0, int k0, const h4 *b, f32x16 acc, int lane) {
-    const _Float16 *row = w + (m0 + (lane & 31)) * pitch + k0 + 4 * (lane >> 5);
+template <int KSTEPS, typename E>
+__device__ __forceinline__ f32x16 matmul(const E *w, int pitch, int m0, int k0, const V4<E> *b, f32x16 acc, int lane) {
+    const E *row = w + (m0 + (lane & 31)) * pitch + k0 + 4 * (lane >> 5);
 #pragma unroll
-    for (int g = 0; g < KSTEPS; ++g) acc = __builtin_amdgcn_mfma_f32_32x32x8f16(*reinterpret_cast<const h4 *>(row + 8 * g), b[g], acc, 0, 0, 0);
+    for (int g = 0; g < KSTEPS; ++g) acc = mfma8(*reinterpret_cast<const V4<E> *>(row + 8 * g), b[g], acc);
     return acc;
 }
 
-// output rows m0 .. m0 + 31 of a projection, rounded to fp16 once, into the token's row of a (rows, 64) fp16 tensor: register
+// output rows m0 .. m0 + 31 of a projection, rounded to E once, into the token's row of a (rows, 64) tensor of E: register
 // 4g + j is channel m0 + 8g + 4h + j, so each g is one 8-byte store (the half of head m0 / 8 + g this lane half holds)
-__device__ __forceinline__ void store_proj(_Float16 *p, int m0, int h, const f32x16 &acc) {
+template <typename E>
+__device__ __forceinline__ void store_proj(E *p, int m0, int h, const f32x16 &acc) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        h4 o;
+        V4<E> o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (_Float16)acc[4 * g + j];
-        *reinterpret_cast<h4 *>(p + m0 + 8 * g + 4 * h) = o;
+        for (int j = 0; j < 4; ++j) o[j] = (E)acc[4 * g + j];
+        *reinterpret_cast<V4<E> *>(p + m0 + 8 * g + 4 * h) = o;
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // before the attention: q = Wq fp16(LayerNorm(row)), k = Wk fp16(row), v = Wv fp16(row); k and v of row r land at row
 // (r + rows / 2) mod rows, the other view's batch entry
+template <typename E>
 __global__ __launch_bounds__(kQkvThreads) void decoder_qkv_kernel(const float *__restrict__ X, const float *__restrict__ norm_w,
                                                                   const float *__restrict__ norm_b, float eps,
                                                                   const float *__restrict__ wq, const float *__restrict__ wk,
-                                                                  const float *__restrict__ wv, _Float16 *__restrict__ q,
-                                                                  _Float16 *__restrict__ k, _Float16 *__restrict__ v, int64_t rows,
+                                                                  const float *__restrict__ wv, E *__restrict__ q,
+                                                                  E *__restrict__ k, E *__restrict__ v, int64_t rows,
                                                                   int ntiles) {
-    __shared__ alignas(16) _Float16 w[3][kC * kPitchC];
+    __shared__ alignas(16) E w[3][kC * kPitchC];
     __shared__ alignas(16) float nw[kC], nb[kC];
     stage_weight(w[0], wq, kC, kC, kPitchC);
     stage_weight(w[1], wk, kC, kC, kPitchC);
@@ -145,9 +157,9 @@ __global__ __launch_bounds__(kQkvThreads) void decoder_qkv_kernel(const float *_
         const int64_t row = (int64_t)tile * 32 + (lane & 31);
         const bool ok = row < rows;
         const Tok x = load_tok(X + (ok ? row : 0) * kC, h, ok);
-        h4 xb[8], nx[8];
-        to_operand(x, xb);
-        to_operand(layernorm(x, nw, nb, eps, h), nx);
+        V4<E> xb[8], nx[8];
+        to_operand<E>(x, xb);
+        to_operand<E>(layernorm(x, nw, nb, eps, h), nx);
         const int64_t other = row + rows / 2 < rows ? row + rows / 2 : row - rows / 2;
 #pragma unroll
         for (int m0 = 0; m0 < kC; m0 += 32) {
@@ -168,7 +180,8 @@ __global__ __launch_bounds__(kQkvThreads) void decoder_qkv_kernel(const float *_
 // fc2.  x_out may be x: a lane reads its token's values before the loop body's products and writes the same addresses after them.
 __device__ __forceinline__ float gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
-__global__ __launch_bounds__(kPostThreads) void decoder_post_kernel(const float *X, const _Float16 *__restrict__ attn,
+template <typename E>
+__global__ __launch_bounds__(kPostThreads) void decoder_post_kernel(const float *X, const E *__restrict__ attn,
                                                                     const float *__restrict__ wproj, const float *__restrict__ bproj,
                                                                     const float *__restrict__ gamma1, const float *__restrict__ norm_w,
                                                                     const float *__restrict__ norm_b, float eps,
@@ -176,9 +189,9 @@ __global__ __launch_bounds__(kPostThreads) void decoder_post_kernel(const float 
                                                                     const float *__restrict__ w2, const float *__restrict__ b2,
                                                                     const float *__restrict__ gamma2, float *X_out, int64_t rows,
                                                                     int ntiles) {
-    __shared__ alignas(16) _Float16 wp[kC * kPitchC];
-    __shared__ alignas(16) _Float16 wf1[kHidden * kPitchC];
-    __shared__ alignas(16) _Float16 wf2[kC * kPitchH];
+    __shared__ alignas(16) E wp[kC * kPitchC];
+    __shared__ alignas(16) E wf1[kHidden * kPitchC];
+    __shared__ alignas(16) E wf2[kC * kPitchH];
     __shared__ alignas(16) float bp[kC], g1[kC], nw[kC], nb[kC], bf2[kC], g2[kC], bf1[kHidden];
     stage_weight(wp, wproj, kC, kC, kPitchC);
     stage_weight(wf1, w1, kHidden, kC, kPitchC);
@@ -200,11 +213,11 @@ __global__ __launch_bounds__(kPostThreads) void decoder_post_kernel(const float 
         const bool ok = row < rows;
         const int64_t off = (ok ? row : 0) * kC;
         Tok x = load_tok(X + off, h, ok);
-        h4 ab[8];
+        V4<E> ab[8];
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
-            const h4 zero = {};
-            ab[g] = ok ? *reinterpret_cast<const h4 *>(attn + off + 8 * g + 4 * h) : zero;
+            const V4<E> zero = {};
+            ab[g] = ok ? *reinterpret_cast<const V4<E> *>(attn + off + 8 * g + 4 * h) : zero;
         }
         // x1 = x + g1 * (Wproj a + bproj)
 #pragma unroll
@@ -221,21 +234,21 @@ __global__ __launch_bounds__(kPostThreads) void decoder_post_kernel(const float 
                 x.v[4 * G + 3] = fmaf(s.w, p[4 * g + 3] + b.w, x.v[4 * G + 3]);
             }
         }
-        h4 nx[8];
-        to_operand(layernorm(x, nw, nb, eps, h), nx);
+        V4<E> nx[8];
+        to_operand<E>(layernorm(x, nw, nb, eps, h), nx);
         f32x16 y0 = {}, y1 = {};  // fc2's output rows 0..31 and 32..63
 #pragma unroll 1
         for (int c0 = 0; c0 < kHidden; c0 += 32) {
             const f32x16 z = {};
             const f32x16 u = matmul<8>(wf1, kPitchC, c0, 0, nx, z, lane);
-            h4 gb[4];
+            V4<E> gb[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const float4 b = *reinterpret_cast<const float4 *>(bf1 + c0 + 8 * g + 4 * h);
-                gb[g][0] = (_Float16)gelu(u[4 * g] + b.x);
-                gb[g][1] = (_Float16)gelu(u[4 * g + 1] + b.y);
-                gb[g][2] = (_Float16)gelu(u[4 * g + 2] + b.z);
-                gb[g][3] = (_Float16)gelu(u[4 * g + 3] + b.w);
+                gb[g][0] = (E)gelu(u[4 * g] + b.x);
+                gb[g][1] = (E)gelu(u[4 * g + 1] + b.y);
+                gb[g][2] = (E)gelu(u[4 * g + 2] + b.z);
+                gb[g][3] = (E)gelu(u[4 * g + 3] + b.w);
             }
             y0 = matmul<4>(wf2, kPitchH, 0, c0, gb, y0, lane);
             y1 = matmul<4>(wf2, kPitchH, 32, c0, gb, y1, lane);
@@ -290,12 +303,10 @@ int check_args(const char *what, int64_t rows, int C, int hidden, float eps, std
     return GFN_OK;
 }
 
-}  // namespace
-
-GFN_EXPORT int gfn_decoder_qkv_fwd(const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq,
-                                   const float *wk, const float *wv, int B2, int N, int C, void *q, void *k, void *v,
-                                   gfn_stream_t stream) {
-    const char *what = "gfn_decoder_qkv_fwd";
+// the two forward entries, said once for both classes
+template <typename E>
+int qkv_fwd(const char *what, const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq, const float *wk,
+            const float *wv, int B2, int N, int C, void *q, void *k, void *v, gfn_stream_t stream) {
     if (B2 < 0 || N < 1) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: bad size (batch %d, N %d)", what, B2, N);
     if (B2 & 1) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: the batch holds both views and must be even, got %d", what, B2);
     const int64_t rows = (int64_t)B2 * N;
@@ -306,16 +317,15 @@ GFN_EXPORT int gfn_decoder_qkv_fwd(const float *x, const float *norm_weight, con
     const int ntiles = (int)((rows + 31) / 32);
     int grid;
     if (int rc = grid_for(ntiles, kQkvThreads / 64, 2, &grid, what)) return rc;
-    hipLaunchKernelGGL(decoder_qkv_kernel, dim3(grid), dim3(kQkvThreads), 0, (hipStream_t)stream, x, norm_weight, norm_bias, eps, wq, wk, wv,
-                       (_Float16 *)q, (_Float16 *)k, (_Float16 *)v, rows, ntiles);
+    hipLaunchKernelGGL(decoder_qkv_kernel<E>, dim3(grid), dim3(kQkvThreads), 0, (hipStream_t)stream, x, norm_weight, norm_bias, eps, wq, wk, wv,
+                       (E *)q, (E *)k, (E *)v, rows, ntiles);
     return gfn::check_launch("decoder_qkv_kernel");
 }
 
-GFN_EXPORT int gfn_decoder_post_fwd(const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,
-                                    const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1,
-                                    const float *w2, const float *b2, const float *gamma2, int64_t rows, int C, int hidden, float *x_out,
-                                    gfn_stream_t stream) {
-    const char *what = "gfn_decoder_post_fwd";
+template <typename E>
+int post_fwd(const char *what, const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,
+             const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1, const float *w2, const float *b2,
+             const float *gamma2, int64_t rows, int C, int hidden, float *x_out, gfn_stream_t stream) {
     if (int rc = check_args(what, rows, C, hidden, eps,
                             {{x, "x"}, {attn, "attn"}, {wproj, "wproj"}, {bproj, "bproj"}, {gamma1, "gamma1"}, {norm_weight, "norm_weight"},
                              {norm_bias, "norm_bias"}, {w1, "w1"}, {b1, "b1"}, {w2, "w2"}, {b2, "b2"}, {gamma2, "gamma2"}, {x_out, "x_out"}}))
@@ -324,9 +334,37 @@ GFN_EXPORT int gfn_decoder_post_fwd(const float *x, const void *attn, const floa
     const int ntiles = (int)((rows + 31) / 32);
     int grid;
     if (int rc = grid_for(ntiles, kPostThreads / 64, 1, &grid, what)) return rc;
-    hipLaunchKernelGGL(decoder_post_kernel, dim3(grid), dim3(kPostThreads), 0, (hipStream_t)stream, x, (const _Float16 *)attn, wproj, bproj,
+    hipLaunchKernelGGL(decoder_post_kernel<E>, dim3(grid), dim3(kPostThreads), 0, (hipStream_t)stream, x, (const E *)attn, wproj, bproj,
                        gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, x_out, rows, ntiles);
     return gfn::check_launch("decoder_post_kernel");
+}
+
+}  // namespace
+
+GFN_EXPORT int gfn_decoder_qkv_fwd(const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq,
+                                   const float *wk, const float *wv, int B2, int N, int C, void *q, void *k, void *v,
+                                   gfn_stream_t stream) {
+    return qkv_fwd<_Float16>("gfn_decoder_qkv_fwd", x, norm_weight, norm_bias, eps, wq, wk, wv, B2, N, C, q, k, v, stream);
+}
+GFN_EXPORT int gfn_decoder_qkv_bf16_fwd(const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq,
+                                        const float *wk, const float *wv, int B2, int N, int C, void *q, void *k, void *v,
+                                        gfn_stream_t stream) {
+    return qkv_fwd<__bf16>("gfn_decoder_qkv_bf16_fwd", x, norm_weight, norm_bias, eps, wq, wk, wv, B2, N, C, q, k, v, stream);
+}
+
+GFN_EXPORT int gfn_decoder_post_fwd(const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,
+                                    const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1,
+                                    const float *w2, const float *b2, const float *gamma2, int64_t rows, int C, int hidden, float *x_out,
+                                    gfn_stream_t stream) {
+    return post_fwd<_Float16>("gfn_decoder_post_fwd", x, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, rows, C,
+                              hidden, x_out, stream);
+}
+GFN_EXPORT int gfn_decoder_post_bf16_fwd(const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,
+                                         const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1,
+                                         const float *w2, const float *b2, const float *gamma2, int64_t rows, int C, int hidden,
+                                         float *x_out, gfn_stream_t stream) {
+    return post_fwd<__bf16>("gfn_decoder_post_bf16_fwd", x, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, rows,
+                            C, hidden, x_out, stream);
 }
 
 // =================================================================================================================================
@@ -347,8 +385,9 @@ constexpr int kPartPost = kOffB1 + kHidden;                                     
 constexpr int kPartQkv = 3 * kC * kC + 2 * kC;                                      // qkv: gWq | gWk | gWv | norm1 weight | bias
 
 // W (rows, cols) fp32 as stored -> W^T, cols rows of `pitch` halves in LDS
-__device__ __forceinline__ void stage_weight_t(_Float16 *dst, const float *__restrict__ src, int rows, int cols, int pitch) {
-    for (int i = threadIdx.x; i < rows * cols; i += blockDim.x) dst[(i % cols) * pitch + i / cols] = (_Float16)src[i];
+template <typename E>
+__device__ __forceinline__ void stage_weight_t(E *dst, const float *__restrict__ src, int rows, int cols, int pitch) {
+    for (int i = threadIdx.x; i < rows * cols; i += blockDim.x) dst[(i % cols) * pitch + i / cols] = (E)src[i];
 }
 
 // LDS accesses of one wave complete in order; this keeps the compiler from moving a tile's reads across its writes
@@ -380,14 +419,15 @@ __device__ __forceinline__ Normed normalise(const Tok &t, float eps) {
     return r;
 }
 // its second half as the B operands: fp16(xhat * weight + bias), layernorm()'s bits
-__device__ __forceinline__ void affine_operand(const Tok &xhat, const float *weight, const float *bias, int h, h4 b[8]) {
+template <typename E>
+__device__ __forceinline__ void affine_operand(const Tok &xhat, const float *weight, const float *bias, int h, V4<E> b[8]) {
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
         const float4 w = chan4(weight, g, h), c = chan4(bias, g, h);
-        b[g][0] = (_Float16)fmaf(xhat.v[4 * g], w.x, c.x);
-        b[g][1] = (_Float16)fmaf(xhat.v[4 * g + 1], w.y, c.y);
-        b[g][2] = (_Float16)fmaf(xhat.v[4 * g + 2], w.z, c.z);
-        b[g][3] = (_Float16)fmaf(xhat.v[4 * g + 3], w.w, c.w);
+        b[g][0] = (E)fmaf(xhat.v[4 * g], w.x, c.x);
+        b[g][1] = (E)fmaf(xhat.v[4 * g + 1], w.y, c.y);
+        b[g][2] = (E)fmaf(xhat.v[4 * g + 2], w.z, c.z);
+        b[g][3] = (E)fmaf(xhat.v[4 * g + 3], w.w, c.w);
     }
 }
 // gradient of the row given gn = dL/d(xhat * weight + bias): rstd * (gh - mean(gh) - xhat * mean(gh * xhat)), gh = gn * weight
@@ -420,16 +460,18 @@ __device__ __forceinline__ Tok as_tok(const f32x16 &lo, const f32x16 &hi) {
     return t;
 }
 
-__device__ __forceinline__ void load_operand(const _Float16 *p, int h, bool ok, h4 b[8]) {
+template <typename E>
+__device__ __forceinline__ void load_operand(const E *p, int h, bool ok, V4<E> b[8]) {
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
-        const h4 zero = {};
-        b[g] = ok ? *reinterpret_cast<const h4 *>(p + 8 * g + 4 * h) : zero;
+        const V4<E> zero = {};
+        b[g] = ok ? *reinterpret_cast<const V4<E> *>(p + 8 * g + 4 * h) : zero;
     }
 }
 
 // x += g1 * (Wproj a + bproj), as decoder_post_kernel forms x1
-__device__ __forceinline__ void add_proj(Tok &x, const h4 ab[8], const _Float16 *wp, const float *bp, const float *g1, int lane, int h) {
+template <typename E>
+__device__ __forceinline__ void add_proj(Tok &x, const V4<E> ab[8], const E *wp, const float *bp, const float *g1, int lane, int h) {
 #pragma unroll
     for (int m0 = 0; m0 < kC; m0 += 32) {
         const f32x16 z = {};
@@ -453,20 +495,20 @@ __device__ __forceinline__ float gelu_grad(float x, float cdf) { return cdf + x 
 
 // G groups of 4 operand values (local channel 8g + 4h + j) of the lane's token into column lane & 31 of a [channel][token] tile;
 // a lane past the last row writes zeros, so that it adds nothing to a sum over tokens whatever it computed
-template <int G>
-__device__ __forceinline__ void put_columns(_Float16 *T, int pitch, int token, const h4 *b, bool ok, int h) {
-    _Float16 *col = T + 4 * h * pitch + token;
+template <int G, typename E>
+__device__ __forceinline__ void put_columns(E *T, int pitch, int token, const V4<E> *b, bool ok, int h) {
+    E *col = T + 4 * h * pitch + token;
 #pragma unroll
     for (int g = 0; g < G; ++g)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) col[(8 * g + j) * pitch] = ok ? b[g][j] : (_Float16)0.f;
+        for (int j = 0; j < 4; ++j) col[(8 * g + j) * pitch] = ok ? b[g][j] : (E)0.f;
 }
 // rows n0 .. n0 + 31 of a tile as the B operands of the KSTEPS k-steps over its 8 * KSTEPS tokens
-template <int KSTEPS>
-__device__ __forceinline__ void tile_operand(const _Float16 *T, int pitch, int n0, int lane, h4 *b) {
-    const _Float16 *row = T + (n0 + (lane & 31)) * pitch + 4 * (lane >> 5);
+template <int KSTEPS, typename E>
+__device__ __forceinline__ void tile_operand(const E *T, int pitch, int n0, int lane, V4<E> *b) {
+    const E *row = T + (n0 + (lane & 31)) * pitch + 4 * (lane >> 5);
 #pragma unroll
-    for (int s = 0; s < KSTEPS; ++s) b[s] = *reinterpret_cast<const h4 *>(row + 8 * s);
+    for (int s = 0; s < KSTEPS; ++s) b[s] = *reinterpret_cast<const V4<E> *>(row + 8 * s);
 }
 // sum over the 32 tokens of a lane half; both partners of every exchange form the same sum, so all 32 lanes end with the same bits
 __device__ __forceinline__ float sum_tokens(float v) {
@@ -484,15 +526,16 @@ __device__ __forceinline__ void store_block(float *M, int ld, int m0, int n0, co
 // post backward, first launch: gX, g_attn and the partial sums of everything 64-wide: norm2's gradients, s2 = sum g and s1 = sum g1.  Per token, g = gX_out:
 //   gy = gamma2 g;  per hidden chunk: u = W1 n + b1 (recomputed), gu = (W2^T gy) GELU'(u), gn += W1^T gu;
 //   g1 = g + LN2^T(gn);  gX = g1;  g_attn = fp16(Wproj^T (gamma1 g1))
+template <typename E>
 __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_data_kernel(
-    const float *__restrict__ X, const _Float16 *__restrict__ attn, const float *__restrict__ wproj, const float *__restrict__ bproj,
+    const float *__restrict__ X, const E *__restrict__ attn, const float *__restrict__ wproj, const float *__restrict__ bproj,
     const float *__restrict__ gamma1, const float *__restrict__ norm_w, const float *__restrict__ norm_b, float eps,
     const float *__restrict__ w1, const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ gamma2,
-    const float *__restrict__ gX_out, float *__restrict__ gX, _Float16 *__restrict__ g_attn, float *__restrict__ part, int64_t rows,
+    const float *__restrict__ gX_out, float *__restrict__ gX, E *__restrict__ g_attn, float *__restrict__ part, int64_t rows,
     int ntiles) {
-    __shared__ alignas(16) _Float16 wp[kC * kPitchC], wpt[kC * kPitchC];
-    __shared__ alignas(16) _Float16 wf1[kHidden * kPitchC], w1t[kC * kPitchH];
-    __shared__ alignas(16) _Float16 w2t[kHidden * kPitchC];
+    __shared__ alignas(16) E wp[kC * kPitchC], wpt[kC * kPitchC];
+    __shared__ alignas(16) E wf1[kHidden * kPitchC], w1t[kC * kPitchH];
+    __shared__ alignas(16) E w2t[kHidden * kPitchC];
     __shared__ alignas(16) float bp[kC], g1[kC], nw[kC], nb[kC], g2[kC], bf1[kHidden];
     __shared__ float red[kBwdWaves][kPartNorm];
     stage_weight(wp, wproj, kC, kC, kPitchC);
@@ -516,16 +559,16 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_data_kernel(
         const int64_t off = (ok ? row : 0) * kC;
         Tok x = load_tok(X + off, h, ok);
         const Tok g = load_tok(gX_out + off, h, ok);
-        h4 ab[8], nx[8], gyb[8];
+        V4<E> ab[8], nx[8], gyb[8];
         load_operand(attn + off, h, ok, ab);
         add_proj(x, ab, wp, bp, g1, lane, h);
         const Normed n = normalise(x, eps);
-        affine_operand(n.xhat, nw, nb, h, nx);
+        affine_operand<E>(n.xhat, nw, nb, h, nx);
 #pragma unroll
         for (int G = 0; G < 8; ++G) {
             const float4 s = chan4(g2, G, h);
-            gyb[G][0] = (_Float16)(s.x * g.v[4 * G]), gyb[G][1] = (_Float16)(s.y * g.v[4 * G + 1]);
-            gyb[G][2] = (_Float16)(s.z * g.v[4 * G + 2]), gyb[G][3] = (_Float16)(s.w * g.v[4 * G + 3]);
+            gyb[G][0] = (E)(s.x * g.v[4 * G]), gyb[G][1] = (E)(s.y * g.v[4 * G + 1]);
+            gyb[G][2] = (E)(s.z * g.v[4 * G + 2]), gyb[G][3] = (E)(s.w * g.v[4 * G + 3]);
         }
         f32x16 gn0 = {}, gn1 = {};  // W1^T gu, rows 0..31 and 32..63
 #pragma unroll 1
@@ -533,7 +576,7 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_data_kernel(
             const f32x16 z = {};
             const f32x16 u = matmul<8>(wf1, kPitchC, c0, 0, nx, z, lane);
             const f32x16 ga = matmul<8>(w2t, kPitchC, c0, 0, gyb, z, lane);
-            h4 gub[4];
+            V4<E> gub[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float4 b = *reinterpret_cast<const float4 *>(bf1 + c0 + 8 * q + 4 * h);
@@ -541,7 +584,7 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_data_kernel(
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float uu = u[4 * q + j] + bj[j];
-                    gub[q][j] = (_Float16)(ga[4 * q + j] * gelu_grad(uu, gelu_cdf(uu)));
+                    gub[q][j] = (E)(ga[4 * q + j] * gelu_grad(uu, gelu_cdf(uu)));
                 }
             }
             gn0 = matmul<4>(w1t, kPitchH, 0, c0, gub, gn0, lane);
@@ -556,14 +599,14 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_data_kernel(
             }
         }
         Tok gx = layernorm_bwd(gn, n, nw, h);
-        h4 gpb[8];
+        V4<E> gpb[8];
 #pragma unroll
         for (int G = 0; G < 8; ++G) {
             const float4 s = chan4(g1, G, h);
 #pragma unroll
             for (int j = 0; j < 4; ++j) gx.v[4 * G + j] += g.v[4 * G + j];
-            gpb[G][0] = (_Float16)(s.x * gx.v[4 * G]), gpb[G][1] = (_Float16)(s.y * gx.v[4 * G + 1]);
-            gpb[G][2] = (_Float16)(s.z * gx.v[4 * G + 2]), gpb[G][3] = (_Float16)(s.w * gx.v[4 * G + 3]);
+            gpb[G][0] = (E)(s.x * gx.v[4 * G]), gpb[G][1] = (E)(s.y * gx.v[4 * G + 1]);
+            gpb[G][2] = (E)(s.z * gx.v[4 * G + 2]), gpb[G][3] = (E)(s.w * gx.v[4 * G + 3]);
         }
         if (ok) {
             store_tok(gX + off, h, gx);
@@ -599,16 +642,17 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_data_kernel(
 //   R2 = g (x) act, gW1 = gu (x) n, gb1 = sum gu, Rp = g1 (x) a
 // A workgroup takes one 32-token tile at a time; its wave w owns hidden units 64w .. 64w + 63 (those columns of R2, rows of gW1) and
 // one 32 x 32 block of Rp, so each sum has one owner and no wave waits for another.
+template <typename E>
 __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_weight_kernel(
-    const float *__restrict__ X, const _Float16 *__restrict__ attn, const float *__restrict__ wproj, const float *__restrict__ bproj,
+    const float *__restrict__ X, const E *__restrict__ attn, const float *__restrict__ wproj, const float *__restrict__ bproj,
     const float *__restrict__ gamma1, const float *__restrict__ norm_w, const float *__restrict__ norm_b, float eps,
     const float *__restrict__ w1, const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ gamma2,
     const float *__restrict__ gX_out, const float *__restrict__ gX, float *__restrict__ part, int64_t rows, int ntiles) {
-    __shared__ alignas(16) _Float16 wp[kC * kPitchC];
-    __shared__ alignas(16) _Float16 wf1[kHidden * kPitchC];
-    __shared__ alignas(16) _Float16 w2t[kHidden * kPitchC];
+    __shared__ alignas(16) E wp[kC * kPitchC];
+    __shared__ alignas(16) E wf1[kHidden * kPitchC];
+    __shared__ alignas(16) E w2t[kHidden * kPitchC];
     __shared__ alignas(16) float bp[kC], g1[kC], nw[kC], nb[kC], g2[kC], bf1[kHidden];
-    __shared__ alignas(16) _Float16 tiles[kBwdWaves][(kC + kC + 32 + 32) * kPitchT];
+    __shared__ alignas(16) E tiles[kBwdWaves][(kC + kC + 32 + 32) * kPitchT];
     stage_weight(wp, wproj, kC, kC, kPitchC);
     stage_weight(wf1, w1, kHidden, kC, kPitchC);
     stage_weight_t(w2t, w2, kC, kHidden, kPitchC);
@@ -620,7 +664,7 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_weight_kernel(
     stage_vector(bf1, b1, kHidden);
     __syncthreads();
     const int lane = threadIdx.x & 63, h = lane >> 5, wave = threadIdx.x >> 6;
-    _Float16 *Tg = tiles[wave], *Tn = Tg + kC * kPitchT, *Ta = Tn + kC * kPitchT, *Tu = Ta + 32 * kPitchT;
+    E *Tg = tiles[wave], *Tn = Tg + kC * kPitchT, *Ta = Tn + kC * kPitchT, *Tu = Ta + 32 * kPitchT;
     f32x16 r2[2][2] = {}, gw1[2][2] = {}, rp = {};  // [hidden chunk of the wave][32-channel block]
     float gb1[2][16] = {};
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // (no workgroup barrier in the loop)
@@ -630,19 +674,19 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_weight_kernel(
         const int64_t off = (ok ? row : 0) * kC;
         Tok x = load_tok(X + off, h, ok);
         const Tok g = load_tok(gX_out + off, h, ok), gx = load_tok(gX + off, h, ok);
-        h4 ab[8], nx[8], gyb[8], gb[8], g1b[8];
+        V4<E> ab[8], nx[8], gyb[8], gb[8], g1b[8];
         load_operand(attn + off, h, ok, ab);
         add_proj(x, ab, wp, bp, g1, lane, h);
         const Normed n = normalise(x, eps);
-        affine_operand(n.xhat, nw, nb, h, nx);
+        affine_operand<E>(n.xhat, nw, nb, h, nx);
 #pragma unroll
         for (int G = 0; G < 8; ++G) {
             const float4 s = chan4(g2, G, h);
-            gyb[G][0] = (_Float16)(s.x * g.v[4 * G]), gyb[G][1] = (_Float16)(s.y * g.v[4 * G + 1]);
-            gyb[G][2] = (_Float16)(s.z * g.v[4 * G + 2]), gyb[G][3] = (_Float16)(s.w * g.v[4 * G + 3]);
+            gyb[G][0] = (E)(s.x * g.v[4 * G]), gyb[G][1] = (E)(s.y * g.v[4 * G + 1]);
+            gyb[G][2] = (E)(s.z * g.v[4 * G + 2]), gyb[G][3] = (E)(s.w * g.v[4 * G + 3]);
         }
-        to_operand(g, gb);
-        to_operand(gx, g1b);
+        to_operand<E>(g, gb);
+        to_operand<E>(gx, g1b);
         wave_sync();  // the previous tile's reads are done
         put_columns<8>(Tg, kPitchT, lane & 31, gb, ok, h);
         put_columns<8>(Tn, kPitchT, lane & 31, nx, ok, h);
@@ -652,7 +696,7 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_weight_kernel(
             const f32x16 z = {};
             const f32x16 u = matmul<8>(wf1, kPitchC, c0, 0, nx, z, lane);
             const f32x16 ga = matmul<8>(w2t, kPitchC, c0, 0, gyb, z, lane);
-            h4 actb[4], gub[4];
+            V4<E> actb[4], gub[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float4 b = *reinterpret_cast<const float4 *>(bf1 + c0 + 8 * q + 4 * h);
@@ -662,8 +706,8 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_weight_kernel(
                     const float uu = u[4 * q + j] + bj[j];
                     const float cdf = gelu_cdf(uu);
                     const float gu = ok ? ga[4 * q + j] * gelu_grad(uu, cdf) : 0.f;
-                    actb[q][j] = (_Float16)(uu * cdf);
-                    gub[q][j] = (_Float16)gu;
+                    actb[q][j] = (E)(uu * cdf);
+                    gub[q][j] = (E)gu;
                     gb1[cc][4 * q + j] += gu;
                 }
             }
@@ -671,7 +715,7 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_weight_kernel(
             put_columns<4>(Ta, kPitchT, lane & 31, actb, ok, h);
             put_columns<4>(Tu, kPitchT, lane & 31, gub, ok, h);
             wave_sync();
-            h4 b[4];
+            V4<E> b[4];
             tile_operand<4>(Ta, kPitchT, 0, lane, b);
             r2[cc][0] = matmul<4>(Tg, kPitchT, 0, 0, b, r2[cc][0], lane);
             r2[cc][1] = matmul<4>(Tg, kPitchT, 32, 0, b, r2[cc][1], lane);
@@ -687,7 +731,7 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_weight_kernel(
         if (wave & 1) put_columns<4>(Tu, kPitchT, lane & 31, ab + 4, ok, h);
         else put_columns<4>(Tu, kPitchT, lane & 31, ab, ok, h);
         wave_sync();
-        h4 b[4];
+        V4<E> b[4];
         tile_operand<4>(Tu, kPitchT, 0, lane, b);
         rp = matmul<4>(Ta, kPitchT, 0, 0, b, rp, lane);
     }
@@ -789,16 +833,17 @@ __global__ __launch_bounds__(256) void decoder_post_bwd_finish_kernel(const floa
 // takes four tiles at a time: wave w computes gX of tile w and leaves its five operands in the shared [channel][128 tokens] images,
 // then owns block (w >> 1, w & 1) of each of the three weight gradients over all 128 tokens.
 constexpr int kPitchQ = 32 * kBwdWaves + 4;  // 66 dwords a row: 32 rows' 8-byte reads cover all 64 banks once
+template <typename E>
 __global__ __launch_bounds__(kBwdThreads) void decoder_qkv_bwd_kernel(const float *__restrict__ X, const float *__restrict__ norm_w,
                                                                       const float *__restrict__ norm_b, float eps,
                                                                       const float *__restrict__ wq, const float *__restrict__ wk,
-                                                                      const float *__restrict__ wv, const _Float16 *__restrict__ gq,
-                                                                      const _Float16 *__restrict__ gk, const _Float16 *__restrict__ gv,
+                                                                      const float *__restrict__ wv, const E *__restrict__ gq,
+                                                                      const E *__restrict__ gk, const E *__restrict__ gv,
                                                                       float *__restrict__ gX, float *__restrict__ part, int64_t rows,
                                                                       int ntiles) {
-    __shared__ alignas(16) _Float16 wt[3][kC * kPitchC];
+    __shared__ alignas(16) E wt[3][kC * kPitchC];
     __shared__ alignas(16) float nw[kC], nb[kC];
-    __shared__ alignas(16) _Float16 T[5][kC * kPitchQ];  // gq | gk' | gv' | n | x
+    __shared__ alignas(16) E T[5][kC * kPitchQ];  // gq | gk' | gv' | n | x
     __shared__ float red[kBwdWaves][2 * kC];
     stage_weight_t(wt[0], wq, kC, kC, kPitchC);
     stage_weight_t(wt[1], wk, kC, kC, kPitchC);
@@ -815,13 +860,13 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_qkv_bwd_kernel(const floa
         const int64_t off = (ok ? row : 0) * kC;
         const int64_t other = (ok ? (row + rows / 2 < rows ? row + rows / 2 : row - rows / 2) : 0) * kC;
         const Tok x = load_tok(X + off, h, ok);
-        h4 xb[8], nx[8], gb[3][8];
+        V4<E> xb[8], nx[8], gb[3][8];
         load_operand(gq + off, h, ok, gb[0]);
         load_operand(gk + other, h, ok, gb[1]);
         load_operand(gv + other, h, ok, gb[2]);
-        to_operand(x, xb);
+        to_operand<E>(x, xb);
         const Normed n = normalise(x, eps);
-        affine_operand(n.xhat, nw, nb, h, nx);
+        affine_operand<E>(n.xhat, nw, nb, h, nx);
         __syncthreads();  // the weights are staged; the previous trip's reads of T are done
 #pragma unroll
         for (int p = 0; p < 3; ++p) put_columns<8>(T[p], kPitchQ, 32 * wave + (lane & 31), gb[p], ok, h);
@@ -845,7 +890,7 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_qkv_bwd_kernel(const floa
         __syncthreads();  // all four tiles' operands are in T
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
-            h4 b[4 * kBwdWaves];
+            V4<E> b[4 * kBwdWaves];
             tile_operand<4 * kBwdWaves>(T[p == 0 ? 3 : 4], kPitchQ, n0, lane, b);
             gw[p] = matmul<4 * kBwdWaves>(T[p], kPitchQ, m0, 0, b, gw[p], lane);
         }
@@ -905,18 +950,11 @@ int check_ws(const char *what, int64_t rows, int64_t ws_bytes) {
     return GFN_OK;
 }
 
-}  // namespace
-
-GFN_EXPORT int64_t gfn_decoder_bwd_ws_bytes(int64_t rows) {
-    if (rows <= 0 || rows > (int64_t)INT_MAX - 31) return 0;
-    return bwd_ws_floats(rows) * (int64_t)sizeof(float);
-}
-
-GFN_EXPORT int gfn_decoder_qkv_bwd(const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq,
-                                   const float *wk, const float *wv, const void *gq, const void *gk, const void *gv, int B2, int N, int C,
-                                   float *gx, float *g_wq, float *g_wk, float *g_wv, float *g_norm_weight, float *g_norm_bias, void *ws,
-                                   int64_t ws_bytes, gfn_stream_t stream) {
-    const char *what = "gfn_decoder_qkv_bwd";
+// the two backward entries, said once for both classes
+template <typename E>
+int qkv_bwd(const char *what, const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq, const float *wk,
+            const float *wv, const void *gq, const void *gk, const void *gv, int B2, int N, int C, float *gx, float *g_wq, float *g_wk,
+            float *g_wv, float *g_norm_weight, float *g_norm_bias, void *ws, int64_t ws_bytes, gfn_stream_t stream) {
     if (B2 < 0 || N < 1) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: bad size (batch %d, N %d)", what, B2, N);
     if (B2 & 1) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: the batch holds both views and must be even, got %d", what, B2);
     const int64_t rows = (int64_t)B2 * N;
@@ -928,8 +966,8 @@ GFN_EXPORT int gfn_decoder_qkv_bwd(const float *x, const float *norm_weight, con
     if (rows == 0) return GFN_OK;
     if (int rc = check_ws(what, rows, ws_bytes)) return rc;
     const int ntiles = (int)((rows + 31) / 32), groups = bwd_groups(rows, kDataTiles);
-    hipLaunchKernelGGL(decoder_qkv_bwd_kernel, dim3(groups), dim3(kBwdThreads), 0, (hipStream_t)stream, x, norm_weight, norm_bias, eps, wq, wk,
-                       wv, (const _Float16 *)gq, (const _Float16 *)gk, (const _Float16 *)gv, gx, (float *)ws, rows, ntiles);
+    hipLaunchKernelGGL(decoder_qkv_bwd_kernel<E>, dim3(groups), dim3(kBwdThreads), 0, (hipStream_t)stream, x, norm_weight, norm_bias, eps, wq, wk,
+                       wv, (const E *)gq, (const E *)gk, (const E *)gv, gx, (float *)ws, rows, ntiles);
     if (int rc = gfn::check_launch("decoder_qkv_bwd_kernel")) return rc;
     float *sums = (float *)ws + (int64_t)groups * kPartQkv;
     hipLaunchKernelGGL(decoder_bwd_sum_partials_kernel, dim3(kPartQkv / 32), dim3(kSumThreads), 0, (hipStream_t)stream, (const float *)ws, groups,
@@ -940,13 +978,12 @@ GFN_EXPORT int gfn_decoder_qkv_bwd(const float *x, const float *norm_weight, con
     return gfn::check_launch("decoder_qkv_bwd_finish_kernel");
 }
 
-GFN_EXPORT int gfn_decoder_post_bwd(const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,
-                                    const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1,
-                                    const float *w2, const float *b2, const float *gamma2, const float *gx_out, int64_t rows, int C,
-                                    int hidden, float *gx, void *g_attn, float *g_wproj, float *g_bproj, float *g_gamma1,
-                                    float *g_norm_weight, float *g_norm_bias, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
-                                    float *g_gamma2, void *ws, int64_t ws_bytes, gfn_stream_t stream) {
-    const char *what = "gfn_decoder_post_bwd";
+template <typename E>
+int post_bwd(const char *what, const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,
+             const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1, const float *w2, const float *b2,
+             const float *gamma2, const float *gx_out, int64_t rows, int C, int hidden, float *gx, void *g_attn, float *g_wproj,
+             float *g_bproj, float *g_gamma1, float *g_norm_weight, float *g_norm_bias, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
+             float *g_gamma2, void *ws, int64_t ws_bytes, gfn_stream_t stream) {
     if (int rc = check_args(what, rows, C, hidden, eps,
                             {{x, "x"}, {attn, "attn"}, {wproj, "wproj"}, {bproj, "bproj"}, {gamma1, "gamma1"}, {norm_weight, "norm_weight"},
                              {norm_bias, "norm_bias"}, {w1, "w1"}, {b1, "b1"}, {w2, "w2"}, {b2, "b2"}, {gamma2, "gamma2"}, {gx_out, "gx_out"},
@@ -958,10 +995,10 @@ GFN_EXPORT int gfn_decoder_post_bwd(const float *x, const void *attn, const floa
     if (int rc = check_ws(what, rows, ws_bytes)) return rc;
     const int ntiles = (int)((rows + 31) / 32), groups_n = bwd_groups(rows, kDataTiles), groups_w = bwd_groups(rows, kWeightTiles);
     float *pn = (float *)ws, *pw = pn + (int64_t)groups_n * kPartNorm, *sums = pw + (int64_t)groups_w * kPartPost;
-    hipLaunchKernelGGL(decoder_post_bwd_data_kernel, dim3(groups_n), dim3(kBwdThreads), 0, (hipStream_t)stream, x, (const _Float16 *)attn, wproj,
-                       bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, gamma2, gx_out, gx, (_Float16 *)g_attn, pn, rows, ntiles);
+    hipLaunchKernelGGL(decoder_post_bwd_data_kernel<E>, dim3(groups_n), dim3(kBwdThreads), 0, (hipStream_t)stream, x, (const E *)attn, wproj,
+                       bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, gamma2, gx_out, gx, (E *)g_attn, pn, rows, ntiles);
     if (int rc = gfn::check_launch("decoder_post_bwd_data_kernel")) return rc;
-    hipLaunchKernelGGL(decoder_post_bwd_weight_kernel, dim3(groups_w), dim3(kBwdThreads), 0, (hipStream_t)stream, x, (const _Float16 *)attn,
+    hipLaunchKernelGGL(decoder_post_bwd_weight_kernel<E>, dim3(groups_w), dim3(kBwdThreads), 0, (hipStream_t)stream, x, (const E *)attn,
                        wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, gamma2, gx_out, (const float *)gx, pw, rows, ntiles);
     if (int rc = gfn::check_launch("decoder_post_bwd_weight_kernel")) return rc;
     hipLaunchKernelGGL(decoder_bwd_sum_partials_kernel, dim3((kPartNorm + kPartPost) / 32), dim3(kSumThreads), 0, (hipStream_t)stream,
@@ -972,3 +1009,36 @@ GFN_EXPORT int gfn_decoder_post_bwd(const float *x, const void *attn, const floa
                        g_norm_bias, g_w1, g_b1, g_w2, g_b2, g_gamma2);
     return gfn::check_launch("decoder_post_bwd_finish_kernel");
 }
+
+}  // namespace
+
+// (one size serves both classes: the partial sums are fp32 whatever the element)
+GFN_EXPORT int64_t gfn_decoder_bwd_ws_bytes(int64_t rows) {
+    if (rows <= 0 || rows > (int64_t)INT_MAX - 31) return 0;
+    return bwd_ws_floats(rows) * (int64_t)sizeof(float);
+}
+
+#define GFN_DECODER_QKV_BWD(name, E)                                                                                                        \
+    GFN_EXPORT int name(const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq, const float *wk,      \
+                        const float *wv, const void *gq, const void *gk, const void *gv, int B2, int N, int C, float *gx, float *g_wq,      \
+                        float *g_wk, float *g_wv, float *g_norm_weight, float *g_norm_bias, void *ws, int64_t ws_bytes,                     \
+                        gfn_stream_t stream) {                                                                                              \
+        return qkv_bwd<E>(#name, x, norm_weight, norm_bias, eps, wq, wk, wv, gq, gk, gv, B2, N, C, gx, g_wq, g_wk, g_wv, g_norm_weight,     \
+                          g_norm_bias, ws, ws_bytes, stream);                                                                               \
+    }
+GFN_DECODER_QKV_BWD(gfn_decoder_qkv_bwd, _Float16)
+GFN_DECODER_QKV_BWD(gfn_decoder_qkv_bf16_bwd, __bf16)
+
+#define GFN_DECODER_POST_BWD(name, E)                                                                                                       \
+    GFN_EXPORT int name(const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,                      \
+                        const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1, const float *w2,     \
+                        const float *b2, const float *gamma2, const float *gx_out, int64_t rows, int C, int hidden, float *gx,              \
+                        void *g_attn, float *g_wproj, float *g_bproj, float *g_gamma1, float *g_norm_weight, float *g_norm_bias,            \
+                        float *g_w1, float *g_b1, float *g_w2, float *g_b2, float *g_gamma2, void *ws, int64_t ws_bytes,                    \
+                        gfn_stream_t stream) {                                                                                              \
+        return post_bwd<E>(#name, x, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, gx_out, rows, C,      \
+                           hidden, gx, g_attn, g_wproj, g_bproj, g_gamma1, g_norm_weight, g_norm_bias, g_w1, g_b1, g_w2, g_b2, g_gamma2,    \
+                           ws, ws_bytes, stream);                                                                                           \
+    }
+GFN_DECODER_POST_BWD(gfn_decoder_post_bwd, _Float16)
+GFN_DECODER_POST_BWD(gfn_decoder_post_bf16_bwd, __bf16)

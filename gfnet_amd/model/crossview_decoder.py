@@ -12,20 +12,20 @@ dropout 0.  Parameter names are the reference's, so the `dino_decoder.*` entries
     cross_attn_blocks.{i}.ls2.gamma
 
 The reference's attention calls flash_attn_func, which is absent on this platform (attention.py:230-231 then raises);
-here it is ops.cross_attention (csrc/cross_attn.hip), and both directions of a block -- x attending to y and y to x, with the same
+here it is ops.cross_attention (csrc/cross_attn.hip; ops.cross_attention_bf16 where bf16 autocast makes q, k, v bf16), and both directions of a block -- x attending to y and y to x, with the same
 weights (crossview_decoder_light.py:53-54) -- are ONE launch on the concatenated batch.  attn_impl="torch" routes the core through
 ops.reference_cross_attention instead: the same module on any device and dtype, which is how the tests run it in float64 on the CPU.
 
 block_impl="torch" (the default) leaves the linear layers, LayerNorm and the MLP of a block to torch.  block_impl="hip" runs a block
-in inference under fp16 autocast as three launches on the concatenated residual stream: ops.decoder_qkv (norm1 and the q, k, v
+in inference under fp16 or bf16 autocast as three launches on the concatenated residual stream: ops.decoder_qkv (norm1 and the q, k, v
 projections, csrc/decoder_block.hip), ops.cross_attention, ops.decoder_post (output projection, both LayerScales and residual adds,
 norm2 and the MLP); the entry projection and the position encoding stay torch.  Whatever that path is not built for -- train(),
-tensors off the GPU, no fp16 autocast, parameters that are not fp32, attn_impl="torch", anything that requires grad -- runs the
+tensors off the GPU, no fp16 or bf16 autocast, parameters that are not fp32, attn_impl="torch", anything that requires grad -- runs the
 torch blocks, exactly as block_impl="torch" does.
 
 train_block_impl="torch" (the default) leaves train() to those torch blocks and autograd.  train_block_impl="hip" trains the blocks
-in HIP: in train() with grad mode on, on CUDA tensors under fp16 autocast (the reference's training class, model/network.py:171)
-with fp32 parameters and the HIP attention, a block is ops.decoder_qkv_train -> ops.cross_attention -> ops.decoder_post_train on
+in HIP: in train() with grad mode on, on CUDA tensors under fp16 or bf16 autocast (the reference's training class,
+model/network.py:171, with its amp_dtype) with fp32 parameters and the HIP attention, a block is ops.decoder_qkv_train -> ops.cross_attention -> ops.decoder_post_train on
 cat(x, y), the same three forward launches (not in place) with the backward kernels of csrc/decoder_block.hip behind them; what
 autograd keeps per block is X, q, k, v, the attention output and its log-sum-exp.  The entry projection, the position encoding and
 the concatenation stay torch, so autograd carries the gradient on to proj.weight and the tokens.  Every other call is unchanged.
@@ -98,7 +98,10 @@ class CrossAttention(nn.Module):
         # attention.py:246-249: any softmax_scale setting selects the entropy-invariant scale, log_{train_avg_length}(N) / sqrt(d);
         # None leaves flash-attn's default 1 / sqrt(d)
         scale = self.scale if self.softmax_scale is None else self.scale * math.log(N, self.train_avg_length)
-        attend = ops.cross_attention if self.attn_impl == "hip" else ops.reference_cross_attention
+        if self.attn_impl != "hip":
+            attend = ops.reference_cross_attention
+        else:  # (bf16 autocast hands the projections back in bf16: the bf16 class has an op of its own name)
+            attend = ops.cross_attention_bf16 if q.dtype == torch.bfloat16 else ops.cross_attention
         return self.proj(attend(q, k, v, scale).reshape(B, N, C))
 
 
@@ -119,31 +122,34 @@ class CrossBlock(nn.Module):
         x = x + self.ls1(self.attn(self.norm1(x), kv))
         return x + self.ls2(self.mlp(self.norm2(x)))
 
-    def forward_fused(self, X):
+    def forward_fused(self, X, dtype=torch.float16):
         """The block on the residual stream X = cat(x, y), (2B, N, dim) fp32, updated in place: both directions in three launches,
-        in the fp16 autocast class (CrossViewDecoder._fused says when)."""
+        in the autocast class of `dtype`, fp16 or bf16 (CrossViewDecoder._fused says when)."""
         attn, N = self.attn, X.shape[1]
+        attend = ops.cross_attention_bf16 if dtype == torch.bfloat16 else ops.cross_attention
         q, k, v = ops.decoder_qkv(X, self.norm1.weight, self.norm1.bias, self.norm1.eps, attn.q_proj.weight, attn.k_proj.weight,
-                                  attn.v_proj.weight)
+                                  attn.v_proj.weight, dtype=dtype)
         scale = attn.scale if attn.softmax_scale is None else attn.scale * math.log(N, attn.train_avg_length)
         # (init_values None: no LayerScale, a gamma of 1)
         gamma1, gamma2 = (ls.gamma if isinstance(ls, LayerScale) else torch.ones_like(self.norm1.weight) for ls in (self.ls1, self.ls2))
-        return ops.decoder_post(X, ops.cross_attention(q, k, v, scale), attn.proj.weight, attn.proj.bias, gamma1, self.norm2.weight,
+        return ops.decoder_post(X, attend(q, k, v, scale), attn.proj.weight, attn.proj.bias, gamma1, self.norm2.weight,
                                 self.norm2.bias, self.norm2.eps, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight,
-                                self.mlp.fc2.bias, gamma2, inplace=True)
+                                self.mlp.fc2.bias, gamma2, inplace=True, dtype=dtype)
 
-    def forward_train(self, X):
+    def forward_train(self, X, dtype=torch.float16):
         """The block on X = cat(x, y), (2B, N, dim) fp32, differentiable and not in place: the same three launches with the HIP
-        backward behind each (CrossViewDecoder._train_fused says when).  Returns the new residual stream."""
+        backward behind each, in the autocast class of `dtype` (CrossViewDecoder._train_fused says when).  Returns the new residual
+        stream."""
         attn, N = self.attn, X.shape[1]
+        attend = ops.cross_attention_bf16 if dtype == torch.bfloat16 else ops.cross_attention
         q, k, v = ops.decoder_qkv_train(X, self.norm1.weight, self.norm1.bias, self.norm1.eps, attn.q_proj.weight, attn.k_proj.weight,
-                                        attn.v_proj.weight)
+                                        attn.v_proj.weight, dtype=dtype)
         scale = attn.scale if attn.softmax_scale is None else attn.scale * math.log(N, attn.train_avg_length)
         # (init_values None: no LayerScale, a constant gamma of 1 that takes no gradient)
         gamma1, gamma2 = (ls.gamma if isinstance(ls, LayerScale) else torch.ones_like(self.norm1.weight) for ls in (self.ls1, self.ls2))
-        return ops.decoder_post_train(X, ops.cross_attention(q, k, v, scale), attn.proj.weight, attn.proj.bias, gamma1, self.norm2.weight,
+        return ops.decoder_post_train(X, attend(q, k, v, scale), attn.proj.weight, attn.proj.bias, gamma1, self.norm2.weight,
                                       self.norm2.bias, self.norm2.eps, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight,
-                                      self.mlp.fc2.bias, gamma2)
+                                      self.mlp.fc2.bias, gamma2, dtype=dtype)
 
 
 def _check_cfg(cfg):
@@ -189,25 +195,26 @@ class CrossViewDecoder(nn.Module):
 
     def _train_fused(self, x, y):
         """Whether this call trains the blocks in HIP: train_block_impl="hip" with the HIP attention, train() with grad mode on,
-        CUDA tensors under fp16 autocast, fp32 parameters."""
+        CUDA tensors under fp16 or bf16 autocast, fp32 parameters."""
         if self.train_block_impl != "hip" or not self.training or not torch.is_grad_enabled():
             return False
         return self._kernel_class(x, y)
 
     def _fused(self, x, y):
         """Whether this call takes the fused blocks: block_impl="hip" with the HIP attention, inference (eval() and nothing that
-        requires grad) on CUDA tensors under fp16 autocast with fp32 parameters -- the class decoder_block.hip is written in."""
+        requires grad) on CUDA tensors under fp16 or bf16 autocast with fp32 parameters -- the classes decoder_block.hip is written in."""
         if self.block_impl != "hip" or self.training or not self._kernel_class(x, y):
             return False
         return not (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad or any(p.requires_grad for p in self.parameters())))
 
     def _kernel_class(self, x, y):
-        """The class decoder_block.hip is written in: the HIP attention, width 64, CUDA tensors under fp16 autocast, fp32 parameters."""
+        """The classes decoder_block.hip is written in: the HIP attention, width 64, CUDA tensors under fp16 or bf16 autocast (the
+        autocast dtype names the class), fp32 parameters."""
         if self.attn_impl != "hip" or not (x.is_cuda and y.is_cuda):
             return False
         if self.dim != ops.DECODER_DIM or any(b.attn.num_heads * 8 != self.dim for b in self.cross_attn_blocks):  # (the one width it is built for)
             return False
-        if not torch.is_autocast_enabled("cuda") or torch.get_autocast_dtype("cuda") != torch.float16:
+        if not torch.is_autocast_enabled("cuda") or torch.get_autocast_dtype("cuda") not in (torch.float16, torch.bfloat16):
             return False
         if any(p.dtype != torch.float32 or not p.is_cuda for p in self.parameters()):
             return False
@@ -219,16 +226,17 @@ class CrossViewDecoder(nn.Module):
         if x.dtype == torch.float64:
             pe = pe.double()
         fused, train_fused = self._fused(x, y), self._train_fused(x, y)
+        amp = torch.get_autocast_dtype("cuda") if fused or train_fused else None  # the kernel class of this call
         x, y = self.proj(x) + pe, self.proj(y) + pe
         if train_fused and x.dtype == torch.float32:
             X = torch.cat((x, y))
             for blk in self.cross_attn_blocks:
-                X = blk.forward_train(X)
+                X = blk.forward_train(X, amp)
             x, y = X.chunk(2)
-        elif fused and x.dtype == torch.float32:  # (fp16 projection + fp32 encoding: the residual stream is fp32 under autocast)
+        elif fused and x.dtype == torch.float32:  # (16-bit projection + fp32 encoding: the residual stream is fp32 under autocast)
             X = torch.cat((x, y))  # the one concatenation: k and v change sides inside decoder_qkv
             for blk in self.cross_attn_blocks:
-                blk.forward_fused(X)
+                blk.forward_fused(X, amp)
             x, y = X.chunk(2)
         else:
             for blk in self.cross_attn_blocks:

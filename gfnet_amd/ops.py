@@ -134,6 +134,8 @@ def reference_cross_attention(q, k, v, scale):
 
 
 _F16_F32 = (torch.float16, torch.float32)
+_BF16 = (torch.bfloat16,)
+_DTYPE_CODES = {torch.float16: _lib.GFN_F16, torch.bfloat16: _lib.GFN_BF16, torch.float32: _lib.GFN_F32}
 
 
 def _attn_args(what, names, allowed, *tensors):
@@ -149,14 +151,15 @@ def _attn_args(what, names, allowed, *tensors):
     for t in tensors:
         t = t.contiguous()
         out.append(t.clone() if t.data_ptr() % 16 else t)
-    return dev, out, (_lib.GFN_F16 if tensors[0].dtype == torch.float16 else _lib.GFN_F32)
+    return dev, out, _DTYPE_CODES[tensors[0].dtype]
 
 
-def cross_attention_fwd(q, k, v, scale):
-    """The forward launch (gfn_cross_attn_fwd): returns (out, lse, q, k, v) with q, k, v as the kernel read them; lse (B,H,Nq) fp32."""
+def cross_attention_fwd(q, k, v, scale, allowed=_F16_F32):
+    """The forward launch (gfn_cross_attn_fwd): returns (out, lse, q, k, v) with q, k, v as the kernel read them; lse (B,H,Nq) fp32.
+    `allowed`: the dtypes this name takes (cross_attention_bf16_fwd is this function with bfloat16 alone)."""
     if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2:] != k.shape[2:]:
         raise ValueError(f"cross_attention: q (B,Nq,H,D) and k, v (B,Nk,H,D) expected, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
-    dev, (q, k, v), dt = _attn_args("cross_attention", "q, k and v", _F16_F32, q, k, v)
+    dev, (q, k, v), dt = _attn_args("cross_attention", "q, k and v", allowed, q, k, v)
     B, Nq, H, D = q.shape
     Nk = k.shape[1]
     out = torch.empty_like(q)
@@ -166,10 +169,10 @@ def cross_attention_fwd(q, k, v, scale):
     return out, lse, q, k, v
 
 
-def cross_attention_bwd(q, k, v, out, lse, dout, scale):
+def cross_attention_bwd(q, k, v, out, lse, dout, scale, allowed=_F16_F32):
     """(dq, dk, dv) of cross_attention given dout = dL/dout and the forward's out and lse (gfn_cross_attn_bwd): no atomics, so two
-    calls give the same bits; in fp16 the results are rounded once and overflow to inf."""
-    dev, (q, k, v, out, dout), dt = _attn_args("cross_attention_bwd", "q, k and v", _F16_F32, q, k, v, out, dout)
+    calls give the same bits; in fp16 the results are rounded once and overflow to inf.  `allowed` as in cross_attention_fwd."""
+    dev, (q, k, v, out, dout), dt = _attn_args("cross_attention_bwd", "q, k and v", allowed, q, k, v, out, dout)
     B, Nq, H, D = q.shape
     Nk = k.shape[1]
     if dout.shape != q.shape or out.shape != q.shape or tuple(lse.shape) != (B, H, Nq):
@@ -185,27 +188,45 @@ class _CrossAttentionFn(torch.autograd.Function):
     """cross_attention with a backward; saves q, k, v, out and lse, never the Nq x Nk matrix."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale):
-        out, lse, q, k, v = cross_attention_fwd(q, k, v, scale)
+    def forward(ctx, q, k, v, scale, allowed=_F16_F32):
+        out, lse, q, k, v = cross_attention_fwd(q, k, v, scale, allowed)
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.scale = scale
+        ctx.scale, ctx.allowed = scale, allowed
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, lse = ctx.saved_tensors
-        dq, dk, dv = cross_attention_bwd(q, k, v, out, lse, dout.to(q.dtype), ctx.scale)
-        return dq, dk, dv, None
+        dq, dk, dv = cross_attention_bwd(q, k, v, out, lse, dout.to(q.dtype), ctx.scale, ctx.allowed)
+        return dq, dk, dv, None, None
 
 
-def cross_attention(q, k, v, scale):
+def cross_attention(q, k, v, scale, _allowed=_F16_F32):
     """The attention core of the reference's CrossFlashAttention2 (model/transformer/layers/attention.py:252, flash_attn_func with
     dropout 0 and causal=False) at head dim 8: q (B,Nq,H,8), k, v (B,Nk,H,8), fp16 or fp32 -> out of q's shape and dtype =
     softmax(scale * q k^T) v per batch and head.  Differentiable (gfn_cross_attn_bwd).  CPU tensors raise: reference_cross_attention
-    is the definition for every device, this is the product path."""
+    is the definition for every device, this is the product path.  bf16 tensors are refused here and taken by cross_attention_bf16."""
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        return _CrossAttentionFn.apply(q, k, v, float(scale))
-    return cross_attention_fwd(q, k, v, scale)[0]
+        return _CrossAttentionFn.apply(q, k, v, float(scale), _allowed)
+    return cross_attention_fwd(q, k, v, scale, _allowed)[0]
+
+
+def cross_attention_bf16(q, k, v, scale):
+    """cross_attention for the bf16 autocast class: q (B,Nq,H,8), k, v (B,Nk,H,8) bfloat16 -> out bfloat16, the same kernels on
+    v_mfma_f32_32x32x8_bf16 (gfn_cross_attn_fwd / _bwd with GFN_BF16).  Softmax, lse, P and dS are fp32 as in the fp16 class; results
+    are rounded to bf16 to nearest even once, and with fp32's exponent range nothing overflows or is clamped.  Differentiable; any
+    other dtype raises TypeError."""
+    return cross_attention(q, k, v, scale, _BF16)
+
+
+def cross_attention_bf16_fwd(q, k, v, scale):
+    """cross_attention_fwd for bfloat16 q, k, v: (out, lse, q, k, v)."""
+    return cross_attention_fwd(q, k, v, scale, _BF16)
+
+
+def cross_attention_bf16_bwd(q, k, v, out, lse, dout, scale):
+    """cross_attention_bwd for bfloat16 tensors: (dq, dk, dv) in bfloat16, rounded once."""
+    return cross_attention_bwd(q, k, v, out, lse, dout, scale, _BF16)
 
 
 def reference_self_attention(qkv, scale):
@@ -289,7 +310,17 @@ def _decoder_args(what, tensors, shapes, forward_only=True):
     return dev, out
 
 
-def decoder_qkv(X, norm_weight, norm_bias, eps, wq, wk, wv):
+_DECODER_CLASSES = {torch.float16: "", torch.bfloat16: "_bf16"}  # the element of a decoder-block class -> its entry points' infix
+
+
+def _decoder_entry(what, stem, direction, dtype):
+    """gfn_decoder_<stem>[_bf16]_<direction> of the class whose 16-bit tensors are `dtype`; any other dtype is a TypeError."""
+    if dtype not in _DECODER_CLASSES:
+        raise TypeError(f"{what}: dtype must be torch.float16 or torch.bfloat16 (the two classes the blocks are built in), got {dtype}")
+    return getattr(_L(), f"gfn_decoder_{stem}{_DECODER_CLASSES[dtype]}_{direction}")
+
+
+def decoder_qkv(X, norm_weight, norm_bias, eps, wq, wk, wv, dtype=torch.float16):
     """What a cross-view decoder block does before its attention, in one launch (gfn_decoder_qkv_fwd; reference
     model/transformer/layers/block.py:327 and attention.py:236-238) in the fp16 autocast class:
 
@@ -298,8 +329,12 @@ def decoder_qkv(X, norm_weight, norm_bias, eps, wq, wk, wv):
     X (2B, N, 64) fp32, the residual stream cat(x, y) of both views; norm_weight, norm_bias (64) and wq, wk, wv (64, 64) fp32 as the
     module stores them.  Returns q, k, v (2B, N, 8, 8) fp16 for ops.cross_attention, with k and v of batch entry b written at
     (b + B) mod 2B: every view's queries meet the OTHER view's keys, without the concatenated copy.  Contiguous CUDA tensors, the
-    current stream, forward only: raises if grad mode is on and an input requires grad."""
+    current stream, forward only: raises if grad mode is on and an input requires grad.
+
+    dtype=torch.bfloat16 is the bf16 autocast class (gfn_decoder_qkv_bf16_fwd): read bf16 for fp16 above; q, k, v are bfloat16, for
+    ops.cross_attention_bf16."""
     what, C = "decoder_qkv", DECODER_DIM
+    entry = _decoder_entry(what, "qkv", "fwd", dtype)
     if X.dim() != 3 or X.shape[0] % 2 or X.shape[1] < 1:
         raise ValueError(f"{what}: X must be (2B, N, {C}) with an even batch and N >= 1, got {tuple(X.shape)}")
     f32 = torch.float32
@@ -307,13 +342,13 @@ def decoder_qkv(X, norm_weight, norm_bias, eps, wq, wk, wv):
                            {"X": (f32, (X.shape[0], X.shape[1], C)), "norm_weight": (f32, (C,)), "norm_bias": (f32, (C,)),
                             "wq": (f32, (C, C)), "wk": (f32, (C, C)), "wv": (f32, (C, C))})
     B2, N = X.shape[:2]
-    q, k, v = (torch.empty((B2, N, 8, C // 8), device=dev, dtype=torch.float16) for _ in range(3))
-    _timed("decoder_qkv", lambda: _L().gfn_decoder_qkv_fwd(ptr(t["X"]), ptr(t["norm_weight"]), ptr(t["norm_bias"]), float(eps), ptr(t["wq"]),
-                                                           ptr(t["wk"]), ptr(t["wv"]), B2, N, C, ptr(q), ptr(k), ptr(v), stream_ptr(dev)))
+    q, k, v = (torch.empty((B2, N, 8, C // 8), device=dev, dtype=dtype) for _ in range(3))
+    _timed("decoder_qkv", lambda: entry(ptr(t["X"]), ptr(t["norm_weight"]), ptr(t["norm_bias"]), float(eps), ptr(t["wq"]), ptr(t["wk"]),
+                                        ptr(t["wv"]), B2, N, C, ptr(q), ptr(k), ptr(v), stream_ptr(dev)))
     return q, k, v
 
 
-def decoder_post(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, inplace=False):
+def decoder_post(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, inplace=False, dtype=torch.float16):
     """What a cross-view decoder block does after its attention, in one launch (gfn_decoder_post_fwd; reference
     model/transformer/layers/attention.py:255, block.py:327-328, mlp.py, layer_scale.py) in the fp16 autocast class:
 
@@ -323,8 +358,11 @@ def decoder_post(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1,
     X (..., 64) fp32, attn of as many rows of 64 in fp16 (ops.cross_attention's (2B, N, 8, 8) output as it is); wproj (64, 64),
     w1 (256, 64), w2 (64, 256), bproj, gamma1, norm_weight, norm_bias, b2, gamma2 (64) and b1 (256) fp32 as the module stores them.
     Returns X_out, fp32 of X's shape; inplace=True writes it over X.  Contiguous CUDA tensors, the current stream, forward only:
-    raises if grad mode is on and an input requires grad."""
+    raises if grad mode is on and an input requires grad.
+
+    dtype=torch.bfloat16 is the bf16 autocast class (gfn_decoder_post_bf16_fwd): read bf16 for fp16 above; attn must be bfloat16."""
     what, C, Hd = "decoder_post", DECODER_DIM, DECODER_HIDDEN
+    entry = _decoder_entry(what, "post", "fwd", dtype)
     if X.dim() < 1 or X.shape[-1] != C:
         raise ValueError(f"{what}: X must be (..., {C}), got {tuple(X.shape)}")
     if attn.numel() != X.numel():
@@ -333,11 +371,11 @@ def decoder_post(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1,
     vec = (f32, (C,))
     dev, t = _decoder_args(what, {"X": X, "attn": attn, "wproj": wproj, "bproj": bproj, "gamma1": gamma1, "norm_weight": norm_weight,
                                   "norm_bias": norm_bias, "w1": w1, "b1": b1, "w2": w2, "b2": b2, "gamma2": gamma2},
-                           {"X": (f32, X.shape), "attn": (torch.float16, attn.shape), "wproj": (f32, (C, C)), "bproj": vec, "gamma1": vec,
+                           {"X": (f32, X.shape), "attn": (dtype, attn.shape), "wproj": (f32, (C, C)), "bproj": vec, "gamma1": vec,
                             "norm_weight": vec, "norm_bias": vec, "w1": (f32, (Hd, C)), "b1": (f32, (Hd,)), "w2": (f32, (C, Hd)), "b2": vec,
                             "gamma2": vec})
     out = t["X"] if inplace else torch.empty_like(t["X"])
-    _timed("decoder_post", lambda: _L().gfn_decoder_post_fwd(
+    _timed("decoder_post", lambda: entry(
         ptr(t["X"]), ptr(t["attn"]), ptr(t["wproj"]), ptr(t["bproj"]), ptr(t["gamma1"]), ptr(t["norm_weight"]), ptr(t["norm_bias"]), float(eps),
         ptr(t["w1"]), ptr(t["b1"]), ptr(t["w2"]), ptr(t["b2"]), ptr(t["gamma2"]), X.numel() // C, C, Hd, ptr(out), stream_ptr(dev)))
     if inplace and out.data_ptr() != X.data_ptr():  # (a misaligned X was copied for the kernel)
@@ -350,16 +388,18 @@ def _decoder_bwd_ws(dev, rows):
     return torch.empty(max(nws, 16), device=dev, dtype=torch.uint8), nws
 
 
-def decoder_qkv_bwd(X, norm_weight, norm_bias, eps, wq, wk, wv, gq, gk, gv):
+def decoder_qkv_bwd(X, norm_weight, norm_bias, eps, wq, wk, wv, gq, gk, gv, dtype=torch.float16):
     """The backward of decoder_qkv (gfn_decoder_qkv_bwd), differentiating the forward as the kernel computes it with every fp16
     rounding taken as the identity: X and the parameters as decoder_qkv took them, gq, gk, gv (2B, N, 8, 8) fp16 as
     cross_attention_bwd returns them (gk and gv of a row are read where its k and v were written, at the other view's batch entry).
-    Returns (gX, g_wq, g_wk, g_wv, g_norm_weight, g_norm_bias), all fp32.  No atomics: two calls give the same bits."""
+    Returns (gX, g_wq, g_wk, g_wv, g_norm_weight, g_norm_bias), all fp32.  No atomics: two calls give the same bits.
+    dtype=torch.bfloat16: the bf16 class (gfn_decoder_qkv_bf16_bwd), gq, gk, gv bfloat16."""
     what, C = "decoder_qkv_bwd", DECODER_DIM
+    entry = _decoder_entry(what, "qkv", "bwd", dtype)
     if X.dim() != 3 or X.shape[0] % 2 or X.shape[1] < 1:
         raise ValueError(f"{what}: X must be (2B, N, {C}) with an even batch and N >= 1, got {tuple(X.shape)}")
     f32, B2, N = torch.float32, X.shape[0], X.shape[1]
-    grad = (torch.float16, (B2, N, 8, C // 8))
+    grad = (dtype, (B2, N, 8, C // 8))
     dev, t = _decoder_args(what, {"X": X, "norm_weight": norm_weight, "norm_bias": norm_bias, "wq": wq, "wk": wk, "wv": wv, "gq": gq, "gk": gk,
                                   "gv": gv},
                            {"X": (f32, (B2, N, C)), "norm_weight": (f32, (C,)), "norm_bias": (f32, (C,)), "wq": (f32, (C, C)),
@@ -368,19 +408,20 @@ def decoder_qkv_bwd(X, norm_weight, norm_bias, eps, wq, wk, wv, gq, gk, gv):
     g_wq, g_wk, g_wv = (torch.empty((C, C), device=dev, dtype=f32) for _ in range(3))
     g_nw, g_nb = (torch.empty((C,), device=dev, dtype=f32) for _ in range(2))
     ws, nws = _decoder_bwd_ws(dev, B2 * N)
-    _timed("decoder_qkv_bwd", lambda: _L().gfn_decoder_qkv_bwd(
+    _timed("decoder_qkv_bwd", lambda: entry(
         ptr(t["X"]), ptr(t["norm_weight"]), ptr(t["norm_bias"]), float(eps), ptr(t["wq"]), ptr(t["wk"]), ptr(t["wv"]), ptr(t["gq"]), ptr(t["gk"]),
         ptr(t["gv"]), B2, N, C, ptr(gX), ptr(g_wq), ptr(g_wk), ptr(g_wv), ptr(g_nw), ptr(g_nb), ptr(ws), nws, stream_ptr(dev)))
     return gX, g_wq, g_wk, g_wv, g_nw, g_nb
 
 
-def decoder_post_bwd(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, gX_out):
+def decoder_post_bwd(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, gX_out, dtype=torch.float16):
     """The backward of decoder_post (gfn_decoder_post_bwd): X, attn and the parameters as decoder_post took them (x1, norm2, fc1 and
     the GELU are recomputed from them, nothing of the forward is saved), gX_out fp32 of X's shape.  Returns (gX, g_attn, g_wproj,
     g_bproj, g_gamma1, g_norm_weight, g_norm_bias, g_w1, g_b1, g_w2, g_b2, g_gamma2): gX fp32 of X's shape, g_attn fp16 of attn's
     shape (rounded once, overflow to inf: the dout of cross_attention_bwd), the rest fp32 of the parameters' shapes.  No atomics:
-    two calls give the same bits."""
+    two calls give the same bits.  dtype=torch.bfloat16: the bf16 class (gfn_decoder_post_bf16_bwd), attn and g_attn bfloat16."""
     what, C, Hd = "decoder_post_bwd", DECODER_DIM, DECODER_HIDDEN
+    entry = _decoder_entry(what, "post", "bwd", dtype)
     if X.dim() < 1 or X.shape[-1] != C:
         raise ValueError(f"{what}: X must be (..., {C}), got {tuple(X.shape)}")
     if attn.numel() != X.numel():
@@ -389,7 +430,7 @@ def decoder_post_bwd(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps,
     vec = (f32, (C,))
     dev, t = _decoder_args(what, {"X": X, "attn": attn, "wproj": wproj, "bproj": bproj, "gamma1": gamma1, "norm_weight": norm_weight,
                                   "norm_bias": norm_bias, "w1": w1, "b1": b1, "w2": w2, "b2": b2, "gamma2": gamma2, "gX_out": gX_out},
-                           {"X": (f32, X.shape), "attn": (torch.float16, attn.shape), "wproj": (f32, (C, C)), "bproj": vec, "gamma1": vec,
+                           {"X": (f32, X.shape), "attn": (dtype, attn.shape), "wproj": (f32, (C, C)), "bproj": vec, "gamma1": vec,
                             "norm_weight": vec, "norm_bias": vec, "w1": (f32, (Hd, C)), "b1": (f32, (Hd,)), "w2": (f32, (C, Hd)), "b2": vec,
                             "gamma2": vec, "gX_out": (f32, X.shape)}, forward_only=False)
     rows = X.numel() // C
@@ -397,7 +438,7 @@ def decoder_post_bwd(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps,
     names = ("wproj", "bproj", "gamma1", "norm_weight", "norm_bias", "w1", "b1", "w2", "b2", "gamma2")
     grads = [torch.empty_like(t[n]) for n in names]
     ws, nws = _decoder_bwd_ws(dev, rows)
-    _timed("decoder_post_bwd", lambda: _L().gfn_decoder_post_bwd(
+    _timed("decoder_post_bwd", lambda: entry(
         ptr(t["X"]), ptr(t["attn"]), ptr(t["wproj"]), ptr(t["bproj"]), ptr(t["gamma1"]), ptr(t["norm_weight"]), ptr(t["norm_bias"]), float(eps),
         ptr(t["w1"]), ptr(t["b1"]), ptr(t["w2"]), ptr(t["b2"]), ptr(t["gamma2"]), ptr(t["gX_out"]), rows, C, Hd, ptr(gX), ptr(g_attn),
         *(ptr(g) for g in grads), ptr(ws), nws, stream_ptr(dev)))
@@ -408,46 +449,50 @@ class _DecoderQkvFn(torch.autograd.Function):
     """decoder_qkv with a backward: the same launch forward (same bits), decoder_qkv_bwd backward; saves its inputs only."""
 
     @staticmethod
-    def forward(ctx, X, norm_weight, norm_bias, eps, wq, wk, wv):
+    def forward(ctx, X, norm_weight, norm_bias, eps, wq, wk, wv, dtype=torch.float16):
         ctx.save_for_backward(X, norm_weight, norm_bias, wq, wk, wv)
-        ctx.eps = eps
-        return decoder_qkv(X, norm_weight, norm_bias, eps, wq, wk, wv)  # (grad mode is off in here)
+        ctx.eps, ctx.dtype = eps, dtype
+        return decoder_qkv(X, norm_weight, norm_bias, eps, wq, wk, wv, dtype=dtype)  # (grad mode is off in here)
 
     @staticmethod
     def backward(ctx, gq, gk, gv):
         X, norm_weight, norm_bias, wq, wk, wv = ctx.saved_tensors
-        gq, gk, gv = (g.to(torch.float16).contiguous() for g in (gq, gk, gv))
-        gX, g_wq, g_wk, g_wv, g_nw, g_nb = decoder_qkv_bwd(X, norm_weight, norm_bias, ctx.eps, wq, wk, wv, gq, gk, gv)
-        return gX, g_nw, g_nb, None, g_wq, g_wk, g_wv
+        gq, gk, gv = (g.to(ctx.dtype).contiguous() for g in (gq, gk, gv))
+        gX, g_wq, g_wk, g_wv, g_nw, g_nb = decoder_qkv_bwd(X, norm_weight, norm_bias, ctx.eps, wq, wk, wv, gq, gk, gv, dtype=ctx.dtype)
+        return gX, g_nw, g_nb, None, g_wq, g_wk, g_wv, None
 
 
 class _DecoderPostFn(torch.autograd.Function):
     """decoder_post (not in place) with a backward: saves X, attn and the parameters; everything between them is recomputed."""
 
     @staticmethod
-    def forward(ctx, X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2):
+    def forward(ctx, X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, dtype=torch.float16):
         ctx.save_for_backward(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, w1, b1, w2, b2, gamma2)
-        ctx.eps = eps
-        return decoder_post(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, inplace=False)
+        ctx.eps, ctx.dtype = eps, dtype
+        return decoder_post(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, inplace=False, dtype=dtype)
 
     @staticmethod
     def backward(ctx, gX_out):
         X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, w1, b1, w2, b2, gamma2 = ctx.saved_tensors
         g = decoder_post_bwd(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, ctx.eps, w1, b1, w2, b2, gamma2,
-                             gX_out.to(torch.float32).contiguous())
-        return (*g[:7], None, *g[7:])
+                             gX_out.to(torch.float32).contiguous(), dtype=ctx.dtype)
+        return (*g[:7], None, *g[7:], None)
 
 
-def decoder_qkv_train(X, norm_weight, norm_bias, eps, wq, wk, wv):
+def decoder_qkv_train(X, norm_weight, norm_bias, eps, wq, wk, wv, dtype=torch.float16):
     """decoder_qkv, differentiable with respect to X and the five parameters (gfn_decoder_qkv_bwd): the training forward is the
-    same launch, in the reference's fp16 autocast class (model/network.py:171).  Saves its inputs, nothing else."""
-    return _DecoderQkvFn.apply(X, norm_weight, norm_bias, float(eps), wq, wk, wv)
+    same launch, in the reference's fp16 autocast class (model/network.py:171), or with dtype=torch.bfloat16 in its bf16 one.
+    Saves its inputs, nothing else."""
+    _decoder_entry("decoder_qkv_train", "qkv", "fwd", dtype)
+    return _DecoderQkvFn.apply(X, norm_weight, norm_bias, float(eps), wq, wk, wv, dtype)
 
 
-def decoder_post_train(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2):
+def decoder_post_train(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, eps, w1, b1, w2, b2, gamma2, dtype=torch.float16):
     """decoder_post(..., inplace=False), differentiable with respect to X, attn and the ten parameters (gfn_decoder_post_bwd).
-    Saves its inputs, nothing else: x1, norm2, the 256-wide fc1 and GELU outputs are recomputed in the backward."""
-    return _DecoderPostFn.apply(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, float(eps), w1, b1, w2, b2, gamma2)
+    Saves its inputs, nothing else: x1, norm2, the 256-wide fc1 and GELU outputs are recomputed in the backward.
+    dtype=torch.bfloat16: the bf16 class, attn and its gradient bfloat16."""
+    _decoder_entry("decoder_post_train", "post", "fwd", dtype)
+    return _DecoderPostFn.apply(X, attn, wproj, bproj, gamma1, norm_weight, norm_bias, float(eps), w1, b1, w2, b2, gamma2, dtype)
 
 
 CONV_ACTS = {None: 0, "none": 0, "leaky_relu": 1, "swish": 2}

@@ -119,7 +119,7 @@ class ReferenceBackbone(nn.Module):
     decoder: "checkout" (default) builds the checkout's CrossVITDecoder_noself, which with the shipped attention_type "FLASH2" raises
     on its first forward where flash_attn is missing; "hip" builds gfnet_amd.model.crossview_decoder.CrossViewDecoder, the same
     module under the same parameter names with its attention core in HIP, and does not import the checkout's decoder;
-    "hip_fused" builds the same module with block_impl="hip": in inference under fp16 autocast each block is three HIP launches
+    "hip_fused" builds the same module with block_impl="hip": in inference under fp16 or bf16 autocast (amp_dtype) each block is three HIP launches
     (csrc/decoder_block.hip around the attention), every other call is "hip" exactly.
 
     fpn: "checkout" (default) builds the checkout's FPNEncoder, FPNDecoder_concat and merge layer; "hip" builds
@@ -135,7 +135,8 @@ class ReferenceBackbone(nn.Module):
     train_conv_impl of the three native FPN modules: what they run under train() (see gfnet_amd/model/fpn.py).  The checkout's modules have no such switch: anything but "torch" with fpn="checkout" raises ValueError.
 
     decoder_train_impl: "torch" (default) or "hip", the train_block_impl of the native cross-view decoder: "hip" trains its blocks
-    through the backward kernels of csrc/decoder_block.hip under fp16 autocast (see gfnet_amd/model/crossview_decoder.py).  Anything
+    through the backward kernels of csrc/decoder_block.hip under fp16 or bf16 autocast: amp_dtype=torch.bfloat16 selects the bf16 class of
+    the attention and of the blocks, with nothing else to set (see gfnet_amd/model/crossview_decoder.py).  Anything
     but "torch" with decoder="checkout" raises ValueError."""
 
     def __init__(self, conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout",

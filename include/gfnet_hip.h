@@ -39,7 +39,9 @@ extern "C" {
  * backbone under autocast, utils/utils.py:306-320).  Arithmetic and every other tensor stay fp32. */
 #define GFN_F32 0
 #define GFN_F16 1
-/* bf16 maps: taken by the gfn_conv_block_train_bf16_* entry points only; every other entry point refuses it */
+/* bf16 tensors: taken by the gfn_conv_block_train_bf16_* entry points (maps) and by gfn_cross_attn_fwd / gfn_cross_attn_bwd (q, k, v,
+ * out and the gradients); the gfn_decoder_*_bf16_* entry points are the bf16 class by name and take no dtype.  Every other entry
+ * point refuses it */
 #define GFN_BF16 2
 
 typedef void *gfn_stream_t; /* hipStream_t */
@@ -730,12 +732,14 @@ int gfn_photo_jitter_blur(const void *const *src, const int *dims, const int *pa
  * where flash_attn is absent); csrc/cross_attn.hip.  Per batch b and head h, with s[i][j] = scale * sum_d q[b,i,h,d] * k[b,j,h,d]:
  *   out[b,i,h,:] = sum_j softmax_j(s[i][j]) * v[b,j,h,:]        lse[b,h,i] = max_j s[i][j] + log sum_j exp(s[i][j] - max)
  * q, out, dout, dq (B,Nq,H,D) and k, v, dk, dv (B,Nk,H,D), contiguous (what q_proj(x).reshape(B,N,H,D) gives and flash_attn_func
- * takes: no transposes), stored as dtype = GFN_F32 or GFN_F16, 16-byte aligned; lse (B,H,Nq) fp32.  D must be 8 (dim 64 over 8
- * heads: the K of v_mfma_f32_32x32x8_f16); any other D returns GFN_ERR_INVALID_ARG.  H, Nq, Nk >= 1 are arbitrary (tails, Nk = 1),
+ * takes: no transposes), stored as dtype = GFN_F32, GFN_F16 or GFN_BF16, 16-byte aligned; lse (B,H,Nq) fp32.  D must be 8 (dim 64
+ * over 8 heads: the K of v_mfma_f32_32x32x8_f16 and of v_mfma_f32_32x32x8_bf16); any other D returns GFN_ERR_INVALID_ARG.  H, Nq, Nk >= 1 are arbitrary (tails, Nk = 1),
  * scale any finite value (0 gives the mean of v); B, H <= 65535.  No scratch, no allocation, the N x N matrix is never written.
  * Arithmetic: the raw scores on the matrix core with fp32 accumulation (fp16 inputs: exact products; fp32 inputs: the fp32-input
  * instruction, an fmaf chain bit for bit), online softmax and P V in fp32 (P is never rounded), fp16 results rounded to nearest
  * once, overflow to inf.  A key past Nk in a tail tile weighs exactly zero.
+ * GFN_BF16 is the fp16 path on the bf16 instruction: exact products, everything between them fp32, results rounded to bf16 to
+ * nearest even once; bf16 has fp32's exponent range, so nothing finite in fp32 overflows and nothing is clamped.
  * gfn_cross_attn_fwd writes out and lse. */
 int gfn_cross_attn_fwd(const void *q, const void *k, const void *v, int dtype, int B, int Nq, int Nk, int H, int D, float scale,
                        void *out, float *lse, gfn_stream_t stream);
@@ -744,7 +748,7 @@ int gfn_cross_attn_fwd(const void *q, const void *k, const void *v, int dtype, i
  * tile, dk and dv by key tile, dq by query tile.  delta is formed as that sum and not as sum_d dout * out: the saved out carries its
  * own rounding, which for a row whose weight sits on one key of large norm would exceed the row's whole gradient; `out` is therefore
  * checked like the other pointers but not read.  Between the launches delta lives in the first four bytes of each row of dq (the
- * caller's buffer, overwritten by the last launch): no scratch.  No atomics, so identical calls give identical bits.  Sums are
+ * caller's buffer, overwritten by the last launch; a bf16 row is 16 bytes as an fp16 row is): no scratch.  No atomics, so identical calls give identical bits.  Sums are
  * fp32, fp16 results are rounded once and overflow to inf (never clamped), so a loss scale that is too large shows. */
 int gfn_cross_attn_bwd(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *dout, int dtype,
                        int B, int Nq, int Nk, int H, int D, float scale, void *dq, void *dk, void *dv, gfn_stream_t stream);
@@ -922,6 +926,37 @@ int gfn_decoder_post_bwd(const float *x, const void *attn, const float *wproj, c
                          void *g_attn, float *g_wproj, float *g_bproj, float *g_gamma1, float *g_norm_weight, float *g_norm_bias,
                          float *g_w1, float *g_b1, float *g_w2, float *g_b2, float *g_gamma2, void *ws, int64_t ws_bytes,
                          gfn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The same four entry points in the bf16 autocast class (model/network.py:171 with amp_dtype = torch.bfloat16); the same kernels of
+ * csrc/decoder_block.hip instantiated for the other element.  Argument for argument their fp16 siblings, with bf16 wherever those
+ * have fp16: q, k, v, attn, gq, gk, gv and g_attn are bf16 tensors, parameters and operands are rounded to bf16 once (to nearest
+ * even, NaN kept, no clamp: bf16 has fp32's exponent range, so there is no overflow to inf to speak of), every product runs on
+ * v_mfma_f32_32x32x8_bf16 with fp32 accumulation.  Everything the fp16 class keeps in fp32 stays fp32: X, LayerNorm, GELU, all
+ * parameters and their gradients, the partial sums.  Same sizes, same refusals, same grids, same determinism; the workspace is
+ * gfn_decoder_bwd_ws_bytes(rows), which serves both classes (the partials are fp32).
+ * gfn_decoder_qkv_bf16_fwd -- block.py:327, attention.py:236-238, crossview_decoder_light.py:53-54, as gfn_decoder_qkv_fwd. */
+int gfn_decoder_qkv_bf16_fwd(const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq, const float *wk,
+                             const float *wv, int B2, int N, int C, void *q, void *k, void *v, gfn_stream_t stream);
+/* gfn_decoder_post_bf16_fwd -- attention.py:255, block.py:327-328, layer_scale.py, mlp.py, as gfn_decoder_post_fwd. */
+int gfn_decoder_post_bf16_fwd(const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,
+                              const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1,
+                              const float *w2, const float *b2, const float *gamma2, int64_t rows, int C, int hidden, float *x_out,
+                              gfn_stream_t stream);
+/* gfn_decoder_qkv_bf16_bwd -- backward of gfn_decoder_qkv_bf16_fwd (block.py:327, attention.py:236-238,
+ * crossview_decoder_light.py:53-54), as gfn_decoder_qkv_bwd; gq, gk, gv bf16 as gfn_cross_attn_bwd writes them with GFN_BF16. */
+int gfn_decoder_qkv_bf16_bwd(const float *x, const float *norm_weight, const float *norm_bias, float eps, const float *wq, const float *wk,
+                             const float *wv, const void *gq, const void *gk, const void *gv, int B2, int N, int C, float *gx,
+                             float *g_wq, float *g_wk, float *g_wv, float *g_norm_weight, float *g_norm_bias, void *ws, int64_t ws_bytes,
+                             gfn_stream_t stream);
+/* gfn_decoder_post_bf16_bwd -- backward of gfn_decoder_post_bf16_fwd (attention.py:255, block.py:327-328, layer_scale.py, mlp.py), as
+ * gfn_decoder_post_bwd; g_attn (rows, 64) bf16, rounded once: the dout of gfn_cross_attn_bwd with GFN_BF16. */
+int gfn_decoder_post_bf16_bwd(const float *x, const void *attn, const float *wproj, const float *bproj, const float *gamma1,
+                              const float *norm_weight, const float *norm_bias, float eps, const float *w1, const float *b1,
+                              const float *w2, const float *b2, const float *gamma2, const float *gx_out, int64_t rows, int C,
+                              int hidden, float *gx, void *g_attn, float *g_wproj, float *g_bproj, float *g_gamma1,
+                              float *g_norm_weight, float *g_norm_bias, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
+                              float *g_gamma2, void *ws, int64_t ws_bytes, gfn_stream_t stream);
 
 #ifdef __cplusplus
 }
