@@ -379,6 +379,8 @@ int gfn_balance_weights(const float *density, float *p, int64_t n, float min_den
  * the num_samples largest keys win) with a counter-based generator: same distribution, its own random stream, the same
  * result for the same seed.  weights (Bt,N) with row stride row_stride (non-negative; zero-weight entries are drawn only
  * when fewer than K positive ones exist), out (Bt,K) int64 indices in increasing order, scratch: Bt*(N + 2048) ints.
+ * After the call, scratch[:Bt*N] holds the keys as bit patterns and the next Bt*2048 ints hold the first-pass histogram
+ * (per row, the counts of the keys' top 11 bits).
  * one_above: weights above it count as 1 -- the certainty threshold of model/network.py:391-393 applied on the fly
  * (+INFINITY: off). */
 int gfn_sample_without_replacement(const float *weights, int64_t row_stride, int64_t *out, int *scratch, int Bt, int N, int K,
