@@ -549,56 +549,134 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
     }
 }
 
-template <int MT, int TW, int NS, bool F16, int NB, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1>
-int launch_fused_mt(const float *x, const float *packed, float *y, int B, int M, int K, int G, hipStream_t s) {
-    constexpr int TH = kBN * NB / TW;
-    const int tiles_x = (G + TW - 1) / TW, tiles_y = (G + TH - 1) / TH;
-    const int ngrp = (M + 32 * MT * NS - 1) / (32 * MT * NS);
-    const long nwork = (long)B * tiles_x * tiles_y * ngrp;
+// ---- the launch decision, stated once ---------------------------------------------------------------
+// Which kernels a conv block call runs, over what grid: conv_route() works it out on the host from the entry point, its variant
+// or map dtypes and the shape -- no device, no pointers.  The launchers below and in conv_stack.hip / conv_stack_half.hip switch on
+// this struct and on nothing else, and gfn_conv_block_route (include/gfnet_hip.h, GFN_CBR_*) hands the same struct to the tests,
+// so the query and the launch cannot drift apart.
+struct ConvRoute {
+    int fused;               // 1: dwpw_fused_kernel; 0: the two-pass form, dw5x5_kernel -> t_scratch -> pw_gemm_kernel
+    int TW, MT, NS, NB, KW;  // fused: the kernel's template parameters
+    int F16, HIN, HOUT, MM;  // fp16 1x1 operands; fp16 map in / out; matrix-core depthwise
+    int ngrp, nwork, tpb;    // fused: slab groups of 32*MT*NS output channels, work items, items per workgroup
+    int VEC, nblk, mt;       // two-pass: cells per depthwise thread; row blocks and row tiles of the GEMM
+    int tiles_x, tiles_y;    // fused: cell tiles of TW x (128*NB/TW) cells per map
+};
+
+// GFN_OK and *r, or the refusal of the entry point (gfn::fail).  a, b: `variant` of gfn_conv_block_fwd (b unused), x_dtype and
+// y_dtype of gfn_conv_block_half_fwd.
+inline int conv_route(int entry, int a, int b, int B, int C, int M, int G, ConvRoute *r) {
+    *r = ConvRoute{};
+    bool fused = true;
+    if (entry == GFN_CBR_ENTRY_FWD) {
+        if (B < 0 || C <= 0 || M <= 0 || G <= 0) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: bad argument");
+        if ((long)C * G * G > 0x1fffffffL) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: a map (C*G*G floats) must stay below 2 GB");
+        if (a < 0 || a > 3) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: variant must be 0..3 (got %d)", a);
+        r->F16 = (a & 2) != 0;
+        fused = !(a & 1) && (G & 3) == 0;
+    } else if (entry == GFN_CBR_ENTRY_HALF) {
+        if (B < 0 || C <= 0 || M <= 0 || G <= 0) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: bad argument");
+        if ((a != GFN_F32 && a != GFN_F16) || (b != GFN_F32 && b != GFN_F16))
+            return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: map dtypes must be GFN_F32 or GFN_F16");
+        if (a == GFN_F32 && b == GFN_F32)
+            return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: fp32 in and out is gfn_conv_block_fwd (variant 2)");
+        if (G & 3) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: grid side must be a multiple of 4 (got %d)", G);
+        if ((long)C * G * G > 0x1fffffffL)
+            return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: a map (C*G*G elements) must stay below 2 GB");
+        r->F16 = r->MM = 1, r->HIN = a == GFN_F16, r->HOUT = b == GFN_F16;
+    } else {
+        return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_route: entry must be GFN_CBR_ENTRY_FWD or GFN_CBR_ENTRY_HALF (got %d)", entry);
+    }
+    if (!fused) {
+        if ((long)B * C > 0x7fffff || B > 65535) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: batch too large for the two-pass variant");
+        r->VEC = (G & 3) == 0 ? 4 : 1;
+        slab_shape(M, &r->nblk, &r->mt);
+        return GFN_OK;
+    }
+    r->fused = 1, r->NS = 1, r->NB = 1, r->KW = 1;
+    // tile width: full 128-byte rows where the map allows, narrower tiles for the 5*2^k grids
+    r->TW = (G % 32 == 0 || G > 160) ? 32 : (G % 16 == 0 || G > 64) ? 16 : 8;
+    // output channels: one workgroup computes all of them where they fit 2 slabs of <= 7 MFMA row tiles (M <= 448: every
+    // refiner), so the depthwise arithmetic of a cell tile is done once.  Narrow blocks (M <= 96: the fine scales, bound by LDS
+    // and HBM traffic rather than the matrix core) take 256-cell tiles with two output rows per depthwise thread when the map
+    // divides into them (fp32: the larger tiles cost a resident workgroup (LDS)).
+    const int tiles = (M + 31) / 32;
+    if (r->F16 && tiles <= 3 && r->TW >= 16 && G % (2 * kBN / r->TW) == 0) {
+        r->MT = tiles, r->NB = 2;
+    } else if (tiles <= 7) {
+        r->MT = tiles;
+    } else {
+        const int ngrp = (tiles + 13) / 14;
+        r->MT = ((tiles + ngrp - 1) / ngrp + 1) / 2, r->NS = 2;  // row tiles per slab: 4 .. 7
+    }
+    // blocks between two half maps, wide enough for more than three accumulator row tiles: two K tiles per iteration
+    if (r->HIN && r->HOUT && M > 96) r->KW = 2;
+    const int TH = kBN * r->NB / r->TW;
+    r->tiles_x = (G + r->TW - 1) / r->TW, r->tiles_y = (G + TH - 1) / TH;
+    r->ngrp = (M + 32 * r->MT * r->NS - 1) / (32 * r->MT * r->NS);
+    const long nwork = (long)B * r->tiles_x * r->tiles_y * r->ngrp;
     if (nwork > 0x7fffffffL) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: too many tiles");
-    // work items per workgroup (pipelined back to back)
-    const int tpb = nwork >= 16384 ? 2 : 1;  // measured: pays only on the largest grids
-    const unsigned grid = (unsigned)((nwork + tpb - 1) / tpb);
-    hipLaunchKernelGGL((dwpw_fused_kernel<MT, TW, NS, F16, NB, HIN, HOUT, MM, KW>), dim3(grid), dim3(256 * NS), 0, s, x, packed, y, M, K, G, tiles_x,
-                       tiles_y, ngrp, (unsigned)nwork, tpb);
+    r->nwork = (int)nwork;
+    r->tpb = nwork >= 16384 ? 2 : 1;  // work items per workgroup (pipelined back to back); measured: pays only on the largest grids
+    return GFN_OK;
+}
+
+inline int no_fused_kernel(const ConvRoute &r) {
+    return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: no fused kernel for TW %d MT %d NS %d NB %d KW %d (F16 %d HIN %d HOUT %d MM %d)", r.TW,
+                     r.MT, r.NS, r.NB, r.KW, r.F16, r.HIN, r.HOUT, r.MM);
+}
+
+template <int MT, int TW, int NS, bool F16, int NB, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1>
+int launch_fused_mt(const ConvRoute &r, const float *x, const float *packed, float *y, int M, int K, int G, hipStream_t s) {
+    const unsigned grid = (unsigned)(((long)r.nwork + r.tpb - 1) / r.tpb);
+    hipLaunchKernelGGL((dwpw_fused_kernel<MT, TW, NS, F16, NB, HIN, HOUT, MM, KW>), dim3(grid), dim3(256 * NS), 0, s, x, packed, y, M, K, G,
+                       r.tiles_x, r.tiles_y, r.ngrp, (unsigned)r.nwork, r.tpb);
     return gfn::check_launch("dwpw_fused_kernel");
 }
 
-// output channels: one workgroup computes all of them where they fit 2 slabs of <= 7 MFMA row tiles
-// (M <= 448: every refiner), so the depthwise arithmetic of a cell tile is done once.  Narrow blocks
-// (M <= 96: the fine scales, bound by LDS and HBM traffic rather than the matrix core) take 256-cell
-// tiles with two output rows per depthwise thread when the map divides into them.
+// r.MT, r.NS and r.NB of one tile width and class.  KW applies from four row tiles on (conv_route sets it there only).
 template <int TW, bool F16, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1>
-int launch_fused(const float *x, const float *packed, float *y, int B, int M, int K, int G, hipStream_t s) {
-    const int tiles = (M + 31) / 32;
-    if (F16 && tiles <= 3 && TW >= 16 && G % (2 * kBN / TW) == 0) {  // fp32: the larger tiles cost a resident workgroup (LDS)
+int launch_fused(const ConvRoute &r, const float *x, const float *packed, float *y, int M, int K, int G, hipStream_t s) {
+    if (r.NB == 2) {
         if constexpr (F16 && TW >= 16) {
-            switch (tiles) {
-                case 1: return launch_fused_mt<1, TW, 1, F16, 2, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
-                case 2: return launch_fused_mt<2, TW, 1, F16, 2, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
-                default: return launch_fused_mt<3, TW, 1, F16, 2, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
+            switch (r.NS == 1 ? r.MT : 0) {
+                case 1: return launch_fused_mt<1, TW, 1, F16, 2, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
+                case 2: return launch_fused_mt<2, TW, 1, F16, 2, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
+                case 3: return launch_fused_mt<3, TW, 1, F16, 2, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
             }
         }
+        return no_fused_kernel(r);
     }
-    if (tiles <= 7) {
-        switch (tiles) {
-            case 1: return launch_fused_mt<1, TW, 1, F16, 1, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
-            case 2: return launch_fused_mt<2, TW, 1, F16, 1, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
-            case 3: return launch_fused_mt<3, TW, 1, F16, 1, HIN, HOUT, MM>(x, packed, y, B, M, K, G, s);
-            case 4: return launch_fused_mt<4, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
-            case 5: return launch_fused_mt<5, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
-            case 6: return launch_fused_mt<6, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
-            default: return launch_fused_mt<7, TW, 1, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
+    if (r.NS == 1) {
+        switch (r.MT) {
+            case 1: return launch_fused_mt<1, TW, 1, F16, 1, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
+            case 2: return launch_fused_mt<2, TW, 1, F16, 1, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
+            case 3: return launch_fused_mt<3, TW, 1, F16, 1, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
+            case 4: return launch_fused_mt<4, TW, 1, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+            case 5: return launch_fused_mt<5, TW, 1, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+            case 6: return launch_fused_mt<6, TW, 1, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+            case 7: return launch_fused_mt<7, TW, 1, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
         }
+        return no_fused_kernel(r);
     }
-    const int ngrp = (tiles + 13) / 14;
-    const int mt = ((tiles + ngrp - 1) / ngrp + 1) / 2;  // row tiles per slab
-    switch (mt) {
-        case 4: return launch_fused_mt<4, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
-        case 5: return launch_fused_mt<5, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
-        case 6: return launch_fused_mt<6, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
-        default: return launch_fused_mt<7, TW, 2, F16, 1, HIN, HOUT, MM, KW>(x, packed, y, B, M, K, G, s);
+    switch (r.NS == 2 ? r.MT : 0) {
+        case 4: return launch_fused_mt<4, TW, 2, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+        case 5: return launch_fused_mt<5, TW, 2, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+        case 6: return launch_fused_mt<6, TW, 2, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+        case 7: return launch_fused_mt<7, TW, 2, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
     }
+    return no_fused_kernel(r);
+}
+
+// r.TW of one class
+template <bool F16, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1>
+int launch_fused_tw(const ConvRoute &r, const float *x, const float *packed, float *y, int M, int K, int G, hipStream_t s) {
+    switch (r.TW) {
+        case 32: return launch_fused<32, F16, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+        case 16: return launch_fused<16, F16, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+        case 8: return launch_fused<8, F16, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+    }
+    return no_fused_kernel(r);
 }
 
 }  // namespace

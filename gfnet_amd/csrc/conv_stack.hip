@@ -226,37 +226,37 @@ GFN_EXPORT int gfn_conv_block_fwd(const float *x, const float *packed, float *y,
     if (x == y) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: in-place is not supported (cells read their neighbours)");
     if (B == 0) return GFN_OK;
     hipStream_t s = (hipStream_t)stream;
-    if ((long)C * G * G > 0x1fffffffL) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: a map (C*G*G floats) must stay below 2 GB");
-    if (variant < 0 || variant > 3) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: variant must be 0..3 (got %d)", variant);
-    const bool f16 = (variant & 2) != 0;
-    const bool fused = !(variant & 1) && (G & 3) == 0;
-    if (fused) {
-        // tile width: full 128-byte rows where the map allows, narrower tiles for the 5*2^k grids
-        if (G % 32 == 0 || G > 160)
-            return f16 ? launch_fused<32, true>(x, packed, y, B, M, C, G, s) : launch_fused<32, false>(x, packed, y, B, M, C, G, s);
-        if (G % 16 == 0 || G > 64)
-            return f16 ? launch_fused<16, true>(x, packed, y, B, M, C, G, s) : launch_fused<16, false>(x, packed, y, B, M, C, G, s);
-        return f16 ? launch_fused<8, true>(x, packed, y, B, M, C, G, s) : launch_fused<8, false>(x, packed, y, B, M, C, G, s);
-    }
-    int nblk, mt;
-    slab_shape(M, &nblk, &mt);
+    ConvRoute r;
+    if (int rc = conv_route(GFN_CBR_ENTRY_FWD, variant, 0, B, C, M, G, &r)) return rc;
+    if (r.fused)
+        return r.F16 ? launch_fused_tw<true>(r, x, packed, y, M, C, G, s) : launch_fused_tw<false>(r, x, packed, y, M, C, G, s);
     if (!t_scratch) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: the two-pass variant needs t_scratch (B*C*G*G floats)");
-    if ((long)B * C > 0x7fffff || B > 65535) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: batch too large for the two-pass variant");
     const int N = G * G;
-    if ((G & 3) == 0) {
-        const int bpp = (G * (G / 4) + 255) / 256;
-        hipLaunchKernelGGL((dw5x5_kernel<4>), dim3((unsigned)(B * C * bpp)), dim3(256), 0, s, x, t_scratch, packed, C, G, bpp);
-    } else {
-        const int bpp = (N + 255) / 256;
-        hipLaunchKernelGGL((dw5x5_kernel<1>), dim3((unsigned)(B * C * bpp)), dim3(256), 0, s, x, t_scratch, packed, C, G, bpp);
-    }
+    const int bpp = (G * (G / r.VEC) + 255) / 256;
+    if (r.VEC == 4) hipLaunchKernelGGL((dw5x5_kernel<4>), dim3((unsigned)(B * C * bpp)), dim3(256), 0, s, x, t_scratch, packed, C, G, bpp);
+    else hipLaunchKernelGGL((dw5x5_kernel<1>), dim3((unsigned)(B * C * bpp)), dim3(256), 0, s, x, t_scratch, packed, C, G, bpp);
     if (int rc = gfn::check_launch("dw5x5_kernel")) return rc;
-    const dim3 grid((N + kBN - 1) / kBN, nblk, B), block(256);
-    with_row_tiles(mt, [&](auto MT) {
-        if (f16) hipLaunchKernelGGL((pw_gemm_kernel<decltype(MT)::value, true>), grid, block, 0, s, packed, (const float *)t_scratch, y, M, C, N);
+    const dim3 grid((N + kBN - 1) / kBN, r.nblk, B), block(256);
+    with_row_tiles(r.mt, [&](auto MT) {
+        if (r.F16) hipLaunchKernelGGL((pw_gemm_kernel<decltype(MT)::value, true>), grid, block, 0, s, packed, (const float *)t_scratch, y, M, C, N);
         else hipLaunchKernelGGL((pw_gemm_kernel<decltype(MT)::value, false>), grid, block, 0, s, packed, (const float *)t_scratch, y, M, C, N);
     });
     return gfn::check_launch("pw_gemm_kernel");
+}
+
+GFN_EXPORT int gfn_conv_block_route(int entry, int a, int b, int B, int C, int M, int G, int *route, int route_len) {
+    if (!route || route_len < GFN_CBR_FIELDS) {
+        gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_route: route must hold GFN_CBR_FIELDS (%d) ints", GFN_CBR_FIELDS);
+        return 0;
+    }
+    ConvRoute r;
+    if (conv_route(entry, a, b, B, C, M, G, &r)) return 0;
+    route[GFN_CBR_FUSED] = r.fused, route[GFN_CBR_TW] = r.TW, route[GFN_CBR_MT] = r.MT, route[GFN_CBR_NS] = r.NS;
+    route[GFN_CBR_NB] = r.NB, route[GFN_CBR_KW] = r.KW, route[GFN_CBR_F16] = r.F16, route[GFN_CBR_HIN] = r.HIN;
+    route[GFN_CBR_HOUT] = r.HOUT, route[GFN_CBR_MM] = r.MM, route[GFN_CBR_NGRP] = r.ngrp, route[GFN_CBR_NWORK] = r.nwork;
+    route[GFN_CBR_TPB] = r.tpb, route[GFN_CBR_VEC] = r.VEC, route[GFN_CBR_NBLK] = r.nblk, route[GFN_CBR_GEMM_MT] = r.mt;
+    route[GFN_CBR_TILES_X] = r.tiles_x, route[GFN_CBR_TILES_Y] = r.tiles_y;
+    return GFN_CBR_FIELDS;
 }
 
 GFN_EXPORT int gfn_pointwise_conv_fwd(const float *w, const float *bias, const float *t, float *y, int B, int M, int K, int N,

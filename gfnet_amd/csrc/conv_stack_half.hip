@@ -11,36 +11,27 @@
 namespace {
 
 template <bool HIN, bool HOUT>
-int launch_half(const void *x, const float *packed, void *y, int B, int C, int M, int G, hipStream_t s) {
+int launch_half(const ConvRoute &r, const void *x, const float *packed, void *y, int C, int M, int G, hipStream_t s) {
     const float *xf = (const float *)x;
     float *yf = (float *)y;
     if constexpr (HIN && HOUT) {  // blocks between two half maps, wide enough for more than three accumulator row tiles
-        if (M > 96) {
-            if (G % 32 == 0 || G > 160) return launch_fused<32, true, HIN, HOUT, true, 2>(xf, packed, yf, B, M, C, G, s);
-            if (G % 16 == 0 || G > 64) return launch_fused<16, true, HIN, HOUT, true, 2>(xf, packed, yf, B, M, C, G, s);
-            return launch_fused<8, true, HIN, HOUT, true, 2>(xf, packed, yf, B, M, C, G, s);
-        }
+        if (r.KW == 2) return launch_fused_tw<true, HIN, HOUT, true, 2>(r, xf, packed, yf, M, C, G, s);
     }
-    if (G % 32 == 0 || G > 160) return launch_fused<32, true, HIN, HOUT, true>(xf, packed, yf, B, M, C, G, s);
-    if (G % 16 == 0 || G > 64) return launch_fused<16, true, HIN, HOUT, true>(xf, packed, yf, B, M, C, G, s);
-    return launch_fused<8, true, HIN, HOUT, true>(xf, packed, yf, B, M, C, G, s);
+    if (r.KW != 1) return no_fused_kernel(r);
+    return launch_fused_tw<true, HIN, HOUT, true>(r, xf, packed, yf, M, C, G, s);
 }
 
 }  // namespace
 
 GFN_EXPORT int gfn_conv_block_half_fwd(const void *x, int x_dtype, const float *packed, void *y, int y_dtype, int B, int C, int M,
                                        int G, gfn_stream_t stream) {
-    if (!x || !packed || !y || B < 0 || C <= 0 || M <= 0 || G <= 0) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: bad argument");
-    if ((x_dtype != GFN_F32 && x_dtype != GFN_F16) || (y_dtype != GFN_F32 && y_dtype != GFN_F16))
-        return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: map dtypes must be GFN_F32 or GFN_F16");
-    if (x_dtype == GFN_F32 && y_dtype == GFN_F32)
-        return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: fp32 in and out is gfn_conv_block_fwd (variant 2)");
+    if (!x || !packed || !y) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: bad argument");
     if (x == y) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: in-place is not supported (cells read their neighbours)");
-    if (G & 3) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: grid side must be a multiple of 4 (got %d)", G);
-    if ((long)C * G * G > 0x1fffffffL) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: a map (C*G*G elements) must stay below 2 GB");
+    ConvRoute r;
+    if (int rc = conv_route(GFN_CBR_ENTRY_HALF, x_dtype, y_dtype, B, C, M, G, &r)) return rc;
     if (B == 0) return GFN_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == GFN_F32) return launch_half<false, true>(x, packed, y, B, C, M, G, s);
-    if (y_dtype == GFN_F32) return launch_half<true, false>(x, packed, y, B, C, M, G, s);
-    return launch_half<true, true>(x, packed, y, B, C, M, G, s);
+    if (!r.HIN) return launch_half<false, true>(r, x, packed, y, C, M, G, s);
+    if (!r.HOUT) return launch_half<true, false>(r, x, packed, y, C, M, G, s);
+    return launch_half<true, true>(r, x, packed, y, C, M, G, s);
 }

@@ -1352,6 +1352,27 @@ def half_map_to_float(h, C):
     return h.permute(0, 1, 4, 2, 3).reshape(B, 2 * NP, G, G2)[:, :C].float()
 
 
+CONV_ROUTE_FIELDS = ("fused", "TW", "MT", "NS", "NB", "KW", "F16", "HIN", "HOUT", "MM", "ngrp", "nwork", "tpb", "VEC", "nblk", "mt",
+                     "tiles_x", "tiles_y")
+
+
+def conv_block_route(B, C, M, G, variant=None, x_half=None, out_half=None):
+    """The launch decision of conv_block (give `variant`) or conv_block_half (give `x_half` and `out_half`) for a shape, as a dict
+    over CONV_ROUTE_FIELDS: gfn_conv_block_route (include/gfnet_hip.h), the struct the launchers switch on.  Answered on the host,
+    no GPU needed.  None where the entry point would refuse the shape."""
+    import ctypes
+
+    route = (ctypes.c_int * _lib.CBR_FIELDS)()
+    if variant is not None:
+        n = _L().gfn_conv_block_route(_lib.CBR_ENTRY_FWD, int(variant), 0, B, C, M, G, route, _lib.CBR_FIELDS)
+    else:
+        n = _L().gfn_conv_block_route(_lib.CBR_ENTRY_HALF, _lib.GFN_F16 if x_half else _lib.GFN_F32,
+                                      _lib.GFN_F16 if out_half else _lib.GFN_F32, B, C, M, G, route, _lib.CBR_FIELDS)
+    if n != _lib.CBR_FIELDS:
+        return None
+    return {f: int(route[_lib.CBR_GEMM_MT if f == "mt" else getattr(_lib, "CBR_" + f.upper())]) for f in CONV_ROUTE_FIELDS}
+
+
 def pointwise_conv(t, w, bias, out=None):
     """Conv2d(K, M, 1)(t) for a few output channels: out_conv (model/network.py:505,563).  w (M,K)."""
     dev = require_gpu(t, w)

@@ -468,9 +468,47 @@ int gfn_pointwise_conv_fwd(const float *w, const float *bias, const float *t, fl
  *   also a first block's fp32 concat -- and the folded taps rounded to fp16, fp32 accumulation), BatchNorm + ReLU fp32, ReLU output
  *   and 1x1 weights fp16, fp32 accumulation.  A map of dtype GFN_F16 is (B, ceil(C/2), G, G) of half2: channels 2p and 2p+1 of
  *   a cell side by side, the odd channel past C zero (the kernel writes it so).  x_dtype / y_dtype: GFN_F32 (B, C, G, G) floats or GFN_F16; at least one of them GFN_F16 (a
- *   stack's first block reads the fp32 concat, its last one writes fp32).  G must be a multiple of 4. */
+ *   stack's first block reads the fp32 concat, its last one writes fp32).  G must be a multiple of 4.
+ *   Locality of a non-finite input: gfn_conv_block_fwd multiplies a cell only by the taps that reach it, so an inf / NaN at cell
+ *   (i, j) of one channel makes y non-finite (over all M) at most at |drow| <= 2, |dcol| <= 2.  Here the depthwise is a banded
+ *   matrix product: a 16-cell window of a halo row is multiplied by the band's zero entries too (0 * inf = NaN), and the two
+ *   channels of a pair share the window.  y may be non-finite at |drow| <= 2, |dcol| <= 11 of the cell, whichever channel of
+ *   the pair held it -- the zero odd channel past M of a half map included (0 * inf) --; every other value of y has the bits
+ *   of the call without it.  In both entry points a NaN that reaches the ReLU ends there (fmaxf(NaN, 0) = 0: such a cell
+ *   contributes 0 to the 1x1 conv, where torch's relu would hand the NaN on); +inf passes it. */
 int gfn_conv_block_half_fwd(const void *x, int x_dtype, const float *packed, void *y, int y_dtype, int B, int C, int M, int G,
                             gfn_stream_t stream);
+
+/* gfn_conv_block_route: the launch decision of gfn_conv_block_fwd (entry = GFN_CBR_ENTRY_FWD, a = variant, b ignored) or
+ *   gfn_conv_block_half_fwd (entry = GFN_CBR_ENTRY_HALF, a = x_dtype, b = y_dtype) for a shape, answered on the host: no device,
+ *   no stream (csrc/conv_block_fused.h conv_route, the struct the launchers themselves switch on).  Fills route[GFN_CBR_*]
+ *   (route_len >= GFN_CBR_FIELDS ints) and returns GFN_CBR_FIELDS; returns 0, route untouched, where the entry point would refuse
+ *   the shape (gfn_last_error says why).  FUSED: 1 = dwpw_fused_kernel, then TW, MT, NS, NB, KW are its template parameters, NGRP
+ *   slab groups of 32*MT*NS output channels, TILES_X x TILES_Y cell tiles of TW x (128*NB/TW) cells per map, NWORK = B * tiles *
+ *   NGRP work items, TPB of them per workgroup; 0 = the two-pass form: dw5x5_kernel<VEC>, then pw_gemm_kernel<GEMM_MT> over NBLK
+ *   row blocks.  F16: fp16 1x1 operands; HIN / HOUT: fp16 map in / out; MM: matrix-core depthwise.  Fields of the other form: 0. */
+#define GFN_CBR_ENTRY_FWD 0
+#define GFN_CBR_ENTRY_HALF 1
+#define GFN_CBR_FUSED 0
+#define GFN_CBR_TW 1
+#define GFN_CBR_MT 2
+#define GFN_CBR_NS 3
+#define GFN_CBR_NB 4
+#define GFN_CBR_KW 5
+#define GFN_CBR_F16 6
+#define GFN_CBR_HIN 7
+#define GFN_CBR_HOUT 8
+#define GFN_CBR_MM 9
+#define GFN_CBR_NGRP 10
+#define GFN_CBR_NWORK 11
+#define GFN_CBR_TPB 12
+#define GFN_CBR_VEC 13
+#define GFN_CBR_NBLK 14
+#define GFN_CBR_GEMM_MT 15
+#define GFN_CBR_TILES_X 16
+#define GFN_CBR_TILES_Y 17
+#define GFN_CBR_FIELDS 18
+int gfn_conv_block_route(int entry, int a, int b, int B, int C, int M, int G, int *route, int route_len);
 
 /* One conv block in TRAINING mode (model.train(); ConvRefiner.create_block / forward, model/network.py:471-487, 560-563, which
  * torch autograd differentiates in the reference): Conv2d(C,C,5,pad 2,groups=C[,bias]) -> BatchNorm2d on the batch's own
