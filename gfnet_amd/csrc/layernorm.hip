@@ -15,6 +15,7 @@ constexpr int kThreads = 256, kRowsPerBlock = kThreads / 64;
 constexpr int kMaxC = 8192;
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef __bf16 b8 __attribute__((ext_vector_type(8)));
 
 // 8 consecutive values of a row, widened
 struct V8 {
@@ -23,6 +24,13 @@ struct V8 {
 
 __device__ __forceinline__ V8 load8(const _Float16 *p) {
     const h8 v = *reinterpret_cast<const h8 *>(p);
+    V8 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r.e[j] = (float)v[j];
+    return r;
+}
+__device__ __forceinline__ V8 load8(const __bf16 *p) {
+    const b8 v = *reinterpret_cast<const b8 *>(p);
     V8 r;
 #pragma unroll
     for (int j = 0; j < 8; ++j) r.e[j] = (float)v[j];
@@ -38,6 +46,12 @@ __device__ __forceinline__ void store8(_Float16 *p, const V8 &r) {
     for (int j = 0; j < 8; ++j) v[j] = (_Float16)r.e[j];
     *reinterpret_cast<h8 *>(p) = v;
 }
+__device__ __forceinline__ void store8(__bf16 *p, const V8 &r) {
+    b8 v;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (__bf16)r.e[j];  // to nearest even
+    *reinterpret_cast<b8 *>(p) = v;
+}
 __device__ __forceinline__ void store8(float *p, const V8 &r) {
     reinterpret_cast<float4 *>(p)[0] = make_float4(r.e[0], r.e[1], r.e[2], r.e[3]);
     reinterpret_cast<float4 *>(p)[1] = make_float4(r.e[4], r.e[5], r.e[6], r.e[7]);
@@ -45,6 +59,7 @@ __device__ __forceinline__ void store8(float *p, const V8 &r) {
 
 // what the stream holds after a store: the value rounded to its storage type
 __device__ __forceinline__ float as_stored(float v, const _Float16 *) { return (float)(_Float16)v; }
+__device__ __forceinline__ float as_stored(float v, const __bf16 *) { return (float)(__bf16)v; }
 __device__ __forceinline__ float as_stored(float v, const float *) { return v; }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -132,12 +147,9 @@ void launch_for(int C, const void *x, const void *y, const void *gamma, const vo
         launch<T, 16>(x, y, gamma, weight, bias, eps, rows, C, x_out, h_out, s);
 }
 
-}  // namespace
-
-GFN_EXPORT int gfn_ls_add_layernorm_fwd(const void *x, const void *y, const void *gamma, const void *weight, const void *bias, float eps,
-                                        int dtype, int64_t rows, int C, void *x_out, void *h_out, gfn_stream_t stream) {
-    const char *what = "gfn_ls_add_layernorm_fwd";
-    if (dtype != GFN_F32 && dtype != GFN_F16) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: dtype must be GFN_F32 or GFN_F16, got %d", what, dtype);
+// the checks and the launch of both entry points; dtype is one of the three storage types (the callers have seen to that)
+int seam_fwd(const char *what, const void *x, const void *y, const void *gamma, const void *weight, const void *bias, float eps, int dtype,
+             int64_t rows, int C, void *x_out, void *h_out, gfn_stream_t stream) {
     if (C < 8 || C > kMaxC || (C & 7))
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: C must be a multiple of 8 up to %d (a row is held in registers as 8-value vectors), got %d", what, kMaxC, C);
     if (rows < 0 || (rows + kRowsPerBlock - 1) / kRowsPerBlock > INT_MAX) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: bad rows %lld", what, (long long)rows);
@@ -158,7 +170,24 @@ GFN_EXPORT int gfn_ls_add_layernorm_fwd(const void *x, const void *y, const void
     hipStream_t s = (hipStream_t)stream;
     if (dtype == GFN_F16)
         launch_for<_Float16>(C, x, y, gamma, weight, bias, eps, rows, x_out, h_out, s);
+    else if (dtype == GFN_BF16)
+        launch_for<__bf16>(C, x, y, gamma, weight, bias, eps, rows, x_out, h_out, s);
     else
         launch_for<float>(C, x, y, gamma, weight, bias, eps, rows, x_out, h_out, s);
     return gfn::check_launch("ls_add_layernorm_kernel");
+}
+
+}  // namespace
+
+GFN_EXPORT int gfn_ls_add_layernorm_fwd(const void *x, const void *y, const void *gamma, const void *weight, const void *bias, float eps,
+                                        int dtype, int64_t rows, int C, void *x_out, void *h_out, gfn_stream_t stream) {
+    const char *what = "gfn_ls_add_layernorm_fwd";
+    if (dtype != GFN_F32 && dtype != GFN_F16)
+        return gfn::fail(GFN_ERR_INVALID_ARG, "%s: dtype must be GFN_F32 or GFN_F16, got %d (bf16 tensors: gfn_ls_add_layernorm_bf16_fwd)", what, dtype);
+    return seam_fwd(what, x, y, gamma, weight, bias, eps, dtype, rows, C, x_out, h_out, stream);
+}
+
+GFN_EXPORT int gfn_ls_add_layernorm_bf16_fwd(const void *x, const void *y, const void *gamma, const void *weight, const void *bias, float eps,
+                                             int64_t rows, int C, void *x_out, void *h_out, gfn_stream_t stream) {
+    return seam_fwd("gfn_ls_add_layernorm_bf16_fwd", x, y, gamma, weight, bias, eps, GFN_BF16, rows, C, x_out, h_out, stream);
 }

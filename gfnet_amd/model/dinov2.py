@@ -10,12 +10,12 @@ reference's, so the official `dinov2_vitl14_pretrain.pth` loads with strict=True
 
 Every parameter is frozen, as the reference's constructor leaves them (dinov2.py:154-155).  Two paths over the same parameters:
 
-  * impl "hip" (the default), taken in eval() on CUDA in fp16 at head dim 64 without masks: attention is ONE
-    ops.self_attention launch on the packed qkv projection (csrc/self_attn.hip: no permutes, no copies), and each of a block's two
-    seams -- LayerScale multiply, residual add, the LayerNorm that follows -- ONE ops.ls_add_layernorm launch
+  * impl "hip" (the default), taken in eval() on CUDA in fp16 or bf16 at head dim 64 without masks: attention is ONE
+    ops.self_attention (fp16) or ops.self_attention_bf16 launch on the packed qkv projection (csrc/self_attn.hip: no permutes, no
+    copies), and each of a block's two seams -- LayerScale multiply, residual add, the LayerNorm that follows -- ONE ops.ls_add_layernorm launch
     (csrc/layernorm.hip); the last block's second seam carries the model's final `norm`.  Linear layers, the patch convolution and
     GELU are torch ops.  No autograd on this path.
-  * everything else -- the CPU, fp32 or bf16, `masks` given, train(), impl "torch" -- runs torch ops as the reference writes
+  * everything else -- the CPU, fp32, `masks` given, train(), impl "torch" -- runs torch ops as the reference writes
     them (F.scaled_dot_product_attention on the permuted projection).
 """
 import math
@@ -28,6 +28,7 @@ from .. import ops
 
 IMPLS = ("hip", "torch")
 HIP_HEAD_DIM = 64
+HIP_DTYPES = (torch.float16, torch.bfloat16)  # the two 16-bit classes the kernels are instantiated for
 
 
 def _check_impl(impl):
@@ -69,7 +70,8 @@ class Attention(nn.Module):
         B, N, C = x.shape
         qkv = self.qkv(x).reshape(B, N, 3, self.num_heads, C // self.num_heads)
         if hip:
-            return self.proj(ops.self_attention(qkv, self.scale).reshape(B, N, C))
+            attn = ops.self_attention_bf16 if qkv.dtype == torch.bfloat16 else ops.self_attention
+            return self.proj(attn(qkv, self.scale).reshape(B, N, C))
         q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)
         return self.proj(F.scaled_dot_product_attention(q, k, v, scale=self.scale).transpose(1, 2).reshape(B, N, C))
 
@@ -214,8 +216,8 @@ class DinoVisionTransformer(nn.Module):
 
     def _use_hip(self, x, masks):
         _check_impl(self.impl)
-        return (self.impl == "hip" and not self.training and masks is None and x.is_cuda and x.dtype == torch.float16
-                and self.pos_embed.dtype == torch.float16 and self.embed_dim == self.num_heads * HIP_HEAD_DIM
+        return (self.impl == "hip" and not self.training and masks is None and x.is_cuda and x.dtype in HIP_DTYPES
+                and self.pos_embed.dtype == x.dtype and self.embed_dim == self.num_heads * HIP_HEAD_DIM
                 and not (torch.is_grad_enabled() and x.requires_grad))
 
     def forward_features(self, x, masks=None):

@@ -238,34 +238,48 @@ def reference_self_attention(qkv, scale):
     return reference_cross_attention(q, k, v, scale)
 
 
+def _self_attention(what, allowed, qkv, scale):
+    """The one body of self_attention and self_attention_bf16 (gfn_self_attn_fwd): `allowed` is the dtype the name `what` takes."""
+    if qkv.dim() != 5 or qkv.shape[2] != 3:
+        raise ValueError(f"{what}: qkv (B,N,3,H,D) expected, got {tuple(qkv.shape)}")
+    dev, (qkv,), dt = _attn_args(what, "qkv", allowed, qkv)
+    B, N, _, H, D = qkv.shape
+    out = torch.empty((B, N, H, D), device=dev, dtype=qkv.dtype)
+    _timed("self_attn_fwd", lambda: _L().gfn_self_attn_fwd(ptr(qkv), dt, B, N, H, D, float(scale), ptr(out), stream_ptr(dev)))
+    return out
+
+
 def self_attention(qkv, scale):
     """The attention core of the reference's ViT (model/transformer/layers/attention.py:96, F.scaled_dot_product_attention) at head
     dim 64 on the packed projection: qkv (B,N,3,H,64) fp16, as `self.qkv(x).reshape(B, N, 3, H, C // H)` gives it -> out
     (B,N,H,64) fp16 = softmax(scale * q k^T) v per batch and head, so `out.reshape(B, N, C)` feeds proj (gfn_self_attn_fwd: one
     launch, nothing N x N written).  Forward only, no autograd.  CPU tensors raise: reference_self_attention is the definition for
-    every device, this is the product path."""
-    if qkv.dim() != 5 or qkv.shape[2] != 3:
-        raise ValueError(f"self_attention: qkv (B,N,3,H,D) expected, got {tuple(qkv.shape)}")
-    dev, (qkv,), dt = _attn_args("self_attention", "qkv", (torch.float16,), qkv)
-    B, N, _, H, D = qkv.shape
-    out = torch.empty((B, N, H, D), device=dev, dtype=torch.float16)
-    _timed("self_attn_fwd", lambda: _L().gfn_self_attn_fwd(ptr(qkv), dt, B, N, H, D, float(scale), ptr(out), stream_ptr(dev)))
-    return out
+    every device, this is the product path.  bf16 tensors are refused here and taken by self_attention_bf16."""
+    return _self_attention("self_attention", (torch.float16,), qkv, scale)
+
+
+def self_attention_bf16(qkv, scale):
+    """self_attention for the bf16 autocast class: qkv (B,N,3,H,64) bfloat16 -> out (B,N,H,64) bfloat16, the same kernel on
+    v_mfma_f32_32x32x16_bf16 (gfn_self_attn_fwd with GFN_BF16).  Scores, maximum, exp2 and the row sum are fp32 as in the fp16 class;
+    P and the results are rounded to bf16 to nearest even once each.  With fp32's exponent range nothing overflows on the way out and
+    nothing is clamped; results are finite where N * max|v| is below fp32's largest value.  Any other dtype raises TypeError; CPU
+    tensors raise."""
+    return _self_attention("self_attention_bf16", _BF16, qkv, scale)
 
 
 def ls_add_layernorm(x, y, gamma, weight, bias, eps, inplace=False):
-    """The seam of a ViT block in one launch (gfn_ls_add_layernorm_fwd; reference model/transformer/layers/block.py:83-106):
+    """The seam of a ViT block in one launch (gfn_ls_add_layernorm_fwd, for bfloat16 gfn_ls_add_layernorm_bf16_fwd; reference model/transformer/layers/block.py:83-106):
 
         x_out = x + gamma * y          h = LayerNorm(x_out) * weight + bias over the last dim, from x_out as stored
 
-    x, y (..., C) of one shape, gamma, weight, bias (C), all fp16 or all fp32, C a multiple of 8 up to 8192.  y None: the plain
+    x, y (..., C) of one shape, gamma, weight, bias (C), all fp16, all bf16 or all fp32, C a multiple of 8 up to 8192.  y None: the plain
     LayerNorm of x (gamma is not read).  weight None: only the residual update (bias and eps are not read).  inplace=True writes
     x_out into x (which must then be contiguous).  Returns (x_out, h): x itself where y is None, h None where weight is None.
     Contiguous CUDA tensors, the current stream, no autograd."""
     tensors = {"x": x, "y": y, "gamma": gamma if y is not None else None, "weight": weight, "bias": bias if weight is not None else None}
     dev = require_gpu(*tensors.values())
-    if x.dtype not in (torch.float16, torch.float32) or any(t is not None and t.dtype != x.dtype for t in tensors.values()):
-        raise TypeError("ls_add_layernorm: every tensor must share one dtype, float16 or float32, got "
+    if x.dtype not in _DTYPE_CODES or any(t is not None and t.dtype != x.dtype for t in tensors.values()):
+        raise TypeError("ls_add_layernorm: every tensor must share one dtype, float16, bfloat16 or float32, got "
                         f"{ {n: str(t.dtype) for n, t in tensors.items() if t is not None} }")
     if y is None and weight is None:
         raise ValueError("ls_add_layernorm: nothing to compute (y and weight are both None)")
@@ -280,9 +294,12 @@ def ls_add_layernorm(x, y, gamma, weight, bias, eps, inplace=False):
     x_out = None if y is None else (x if inplace else torch.empty_like(x))
     h = None if weight is None else torch.empty_like(x)
     rows = x.numel() // C if C else 0
-    _timed("ls_add_layernorm", lambda: _L().gfn_ls_add_layernorm_fwd(ptr(x), ptr(y), ptr(gamma), ptr(weight), ptr(bias), float(eps),
-                                                                      _lib.GFN_F16 if x.dtype == torch.float16 else _lib.GFN_F32, rows, C,
-                                                                      ptr(x_out), ptr(h), stream_ptr(dev)))
+    head = (ptr(x), ptr(y), ptr(gamma), ptr(weight), ptr(bias), float(eps))
+    tail = (rows, C, ptr(x_out), ptr(h), stream_ptr(dev))
+    if x.dtype == torch.bfloat16:  # the bf16 class is an entry point of its own, named for it
+        _timed("ls_add_layernorm", lambda: _L().gfn_ls_add_layernorm_bf16_fwd(*head, *tail))
+    else:
+        _timed("ls_add_layernorm", lambda: _L().gfn_ls_add_layernorm_fwd(*head, _DTYPE_CODES[x.dtype], *tail))
     return (x if y is None else x_out), h
 
 

@@ -129,7 +129,7 @@ class ReferenceBackbone(nn.Module):
     dino: which ViT is built where none is passed in.  "checkout" (default) builds the checkout's `vit_large`, which imports
     `model.transformer` and with it the checkout's third-party imports; "hip" builds gfnet_amd.model.dinov2.vit_large, the same model
     under the same parameter names (`dino_weights` load strictly, exactly as above) with its attention and the seams of its blocks
-    in HIP in fp16 eval().  With decoder="hip", fpn="hip" and dino="hip" nothing of a checkout is imported.
+    in HIP in eval() in either 16-bit class: the ViT is cast to amp_dtype, and fp16 and bf16 both run its kernels.  With decoder="hip", fpn="hip" and dino="hip" nothing of a checkout is imported.
 
     fpn_train_impl: "torch" (default), "hip" or "hip_fused" ("hip" with the decoder's 2x upsample inside the innerN op), the
     train_conv_impl of the three native FPN modules: what they run under train() (see gfnet_amd/model/fpn.py).  The checkout's modules have no such switch: anything but "torch" with fpn="checkout" raises ValueError.

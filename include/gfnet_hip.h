@@ -39,9 +39,9 @@ extern "C" {
  * backbone under autocast, utils/utils.py:306-320).  Arithmetic and every other tensor stay fp32. */
 #define GFN_F32 0
 #define GFN_F16 1
-/* bf16 tensors: taken by the gfn_conv_block_train_bf16_* entry points (maps) and by gfn_cross_attn_fwd / gfn_cross_attn_bwd (q, k, v,
- * out and the gradients); the gfn_decoder_*_bf16_* entry points are the bf16 class by name and take no dtype.  Every other entry
- * point refuses it */
+/* bf16 tensors: taken by the gfn_conv_block_train_bf16_* entry points (maps), by gfn_cross_attn_fwd / gfn_cross_attn_bwd (q, k, v,
+ * out and the gradients), by gfn_self_attn_fwd (qkv, out); the gfn_decoder_*_bf16_* entry points and
+ * gfn_ls_add_layernorm_bf16_fwd are the bf16 class by name and take no dtype.  Every other entry point refuses it */
 #define GFN_BF16 2
 
 typedef void *gfn_stream_t; /* hipStream_t */
@@ -880,13 +880,18 @@ int gfn_conv2d_up_bn_act_train_bwd(const float *gy, const float *x0, int C0, int
  *   out[b,i,h,:] = sum_j softmax_j(s[i][j]) * v[b,j,h,:]
  * qkv is the PACKED projection (B,N,3,H,D) contiguous -- what self.qkv(x).reshape(B,N,3,H,C/H) gives: q = qkv[:,:,0], k = [:,:,1],
  * v = [:,:,2], no permutes and no copies -- and out (B,N,H,D) contiguous, so out.reshape(B,N,C) feeds proj; both 16-byte aligned.
- * dtype must be GFN_F16 and D must be 64; N, H >= 1 are arbitrary (tails on both axes), scale any finite value (0 gives the mean of
+ * dtype must be GFN_F16 or GFN_BF16 (qkv and out in that type) and D must be 64; N, H >= 1 are arbitrary (tails on both axes), scale any finite value (0 gives the mean of
  * v); B * H * ceil(N / 128) is the grid, at most 2^31 - 1.  Anything else returns GFN_ERR_INVALID_ARG before a launch; B = 0 returns
  * GFN_OK.  No scratch, no allocation, nothing N x N is written.  Forward only: the reference freezes the ViT.
  * Arithmetic: the raw scores on the matrix core (exact products, fp32 accumulation), online softmax in fp32 from a running maximum
  * that starts at -inf, a key past N in a tail tile weighs exactly zero (selected by its index); the weights are rounded to fp16
  * once for P V on the matrix core (fp32 accumulation; the row sum takes the unrounded weights), results rounded to fp16 once,
- * overflow to inf.  No atomics: identical calls give identical bits. */
+ * overflow to inf.  No atomics: identical calls give identical bits.
+ * GFN_BF16 is the same kernel on v_mfma_f32_32x32x16_bf16: exact products, everything between them fp32 as above, the weights
+ * rounded to bf16 to nearest even once, results divided once and rounded to bf16 to nearest even once.  One limit of its own: the
+ * fp32 accumulator of P V holds sum_j p_j v_j with weights relative to the running maximum (each at most 1) until the one division,
+ * so it can reach N * max|v|.  In fp16 that cannot leave fp32's range; in bf16 it can.  Results are finite where N * max|v| is
+ * below fp32's largest value (3.4e38); nothing is clamped, past that the result is inf or NaN. */
 int gfn_self_attn_fwd(const void *qkv, int dtype, int B, int N, int H, int D, float scale, void *out, gfn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
@@ -898,9 +903,15 @@ int gfn_self_attn_fwd(const void *qkv, int dtype, int B, int N, int H, int D, fl
  * update (weight and bias may then be NULL).  Both NULL is an error.  x_out may alias x; h_out may alias nothing.  C a multiple of
  * 8 from 8 to 8192 (the row is held in registers), rows >= 0 arbitrary; anything else returns GFN_ERR_INVALID_ARG before a launch.
  * Arithmetic: fp32; x_out = fma(gamma, y, x) rounded to the storage type once; mean and variance two-pass (sum of squared
- * distances from the mean) over x_out AS STORED, i.e. after that rounding, which is what a following norm reads in the reference. */
+ * distances from the mean) over x_out AS STORED, i.e. after that rounding, which is what a following norm reads in the reference.
+ * GFN_BF16 is refused here: bf16 tensors go to gfn_ls_add_layernorm_bf16_fwd below. */
 int gfn_ls_add_layernorm_fwd(const void *x, const void *y, const void *gamma, const void *weight, const void *bias, float eps,
                              int dtype, int64_t rows, int C, void *x_out, void *h_out, gfn_stream_t stream);
+/* The same seam with every tensor stored as bf16 (GFN_BF16; the class is in the name, so there is no dtype argument): the same
+ * kernel, argument rules and refusals.  16-byte accesses of eight values, widened exactly; x_out and h_out rounded to bf16 to nearest
+ * even once each; the statistics are the same two fp32 passes over x_out as stored in bf16. */
+int gfn_ls_add_layernorm_bf16_fwd(const void *x, const void *y, const void *gamma, const void *weight, const void *bias, float eps,
+                                  int64_t rows, int C, void *x_out, void *h_out, gfn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A block of the cross-view decoder around its attention core, inference in the fp16 autocast class; csrc/decoder_block.hip.

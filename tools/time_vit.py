@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the native DINOv2 ViT (gfnet_amd/model/dinov2.py) and its two kernels against the torch ops they replace, on the same data.
 
-    python tools/time_vit.py --leg attn|seam|model [--rounds 7] [--reps 5] [--out vit_timing.json]
+    python tools/time_vit.py --leg attn|seam|model [--dtype fp16|bf16] [--rounds 7] [--reps 5] [--out vit_timing.json]
 
   attn    ops.self_attention on the packed fp16 projection against F.scaled_dot_product_attention on the permuted tensors (what the
           reference's Attention.forward runs), B = 64, H = 16, N in 1025, 1601
@@ -13,7 +13,10 @@
 The two paths ALTERNATE round by round; a round is `reps` back-to-back calls between two device events; reported per path are the
 median round and the spread (min .. max) over the rounds, in ms per call.  Every shape is warmed up on both paths first.  The
 largest difference between the two paths' outputs is printed beside the times.  Run one leg per process.  Needs a GPU; nothing here
-falls back."""
+falls back.
+
+--dtype bf16 runs all three legs in the bf16 class: tensors and models in bfloat16, ops.self_attention_bf16 for the attention, and
+on the torch side the same torch ops on bfloat16 tensors.  The default, fp16, is what the text above describes."""
 import argparse
 import json
 import os
@@ -57,15 +60,19 @@ def row(name, t, diff, extra=""):
     return {"hip": h, "torch": c, "max_abs_diff": diff}
 
 
+DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
+
+
 def leg_attn(args, dev):
     B, H, D, res = 64, 16, 64, {}
+    attn = ops.self_attention_bf16 if args.dtype == "bf16" else ops.self_attention
     print("| B x N x H | HIP | SDPA | SDPA / HIP | max diff | HIP TFLOP/s |\n|---|---|---|---|---|---|")
     for N in (1025, 1601):
-        qkv = torch.randn(B, N, 3, H, D, device=dev, dtype=torch.float16)
+        qkv = torch.randn(B, N, 3, H, D, device=dev, dtype=DTYPES[args.dtype])
         q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)
 
         def fn(hip):
-            return ops.self_attention(qkv, D ** -0.5) if hip else F.scaled_dot_product_attention(q, k, v, scale=D ** -0.5).transpose(1, 2)
+            return attn(qkv, D ** -0.5) if hip else F.scaled_dot_product_attention(q, k, v, scale=D ** -0.5).transpose(1, 2)
 
         diff = float((fn(True).float() - fn(False).float()).abs().max())
         t = time_pair(fn, args.rounds, args.reps)
@@ -76,8 +83,9 @@ def leg_attn(args, dev):
 
 def leg_seam(args, dev):
     rows, C = 64 * 1025, 1024
-    x0, y = torch.randn(rows, C, device=dev, dtype=torch.float16), torch.randn(rows, C, device=dev, dtype=torch.float16)
-    gamma, w, b = (torch.rand(C, device=dev, dtype=torch.float16) + 0.5 for _ in range(3))
+    dtype = DTYPES[args.dtype]
+    x0, y = torch.randn(rows, C, device=dev, dtype=dtype), torch.randn(rows, C, device=dev, dtype=dtype)
+    gamma, w, b = (torch.rand(C, device=dev, dtype=dtype) + 0.5 for _ in range(3))
     x = x0.clone()
 
     def fn(hip):
@@ -96,11 +104,11 @@ def leg_seam(args, dev):
 
 def leg_model(args, dev):
     torch.manual_seed(0)
-    vit = dinov2.vit_large().to(dev, torch.float16).train(False)
+    vit = dinov2.vit_large().to(dev, DTYPES[args.dtype]).train(False)
     res = {}
     print("| images | impl hip | impl torch | torch / hip | max diff of patch tokens |\n|---|---|---|---|---|")
     for B, size in ((64, 448), (16, 560)):
-        x = torch.rand(B, 3, size, size, device=dev, dtype=torch.float16) * 2 - 1
+        x = torch.rand(B, 3, size, size, device=dev, dtype=DTYPES[args.dtype]) * 2 - 1
 
         def fn(hip):
             vit.impl = "hip" if hip else "torch"
@@ -114,6 +122,7 @@ def leg_model(args, dev):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--leg", choices=("attn", "seam", "model"), required=True)
+    ap.add_argument("--dtype", choices=tuple(DTYPES), default="fp16", help="the 16-bit class all tensors and models are built in")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None, help="write the numbers as JSON here")
@@ -121,9 +130,9 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("time_vit.py needs a GPU")
     dev = torch.device("cuda")
-    print(f"{args.leg} on {torch.cuda.get_device_name(0)}: ms per call, median (min .. max) of {args.rounds} rounds of {args.reps}")
+    print(f"{args.leg}{'' if args.dtype == 'fp16' else ' in ' + args.dtype} on {torch.cuda.get_device_name(0)}: ms per call, median (min .. max) of {args.rounds} rounds of {args.reps}")
     with torch.no_grad():
-        result = {"device": torch.cuda.get_device_name(0), "leg": args.leg, "rounds": args.rounds, "reps": args.reps,
+        result = {"device": torch.cuda.get_device_name(0), "leg": args.leg, "dtype": args.dtype, "rounds": args.rounds, "reps": args.reps,
                   "rows": {"attn": leg_attn, "seam": leg_seam, "model": leg_model}[args.leg](args, dev)}
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
