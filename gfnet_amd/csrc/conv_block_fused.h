@@ -1,15 +1,12 @@
 // conv_block_fused.h -- the fused conv block (depthwise 5x5 + BatchNorm + ReLU + 1x1 conv in one kernel) of csrc/conv_stack.hip
 // and csrc/conv_stack_half.hip (the same kernel on fp16 maps).  Opens its own anonymous namespace.
 #pragma once
+#include "elem16.h"
 #include "pw_gemm_tile.h"  // kKT, kBN, f32x16
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using gfn::f16x2, gfn::f16x4, gfn::f16x8, gfn::f32x2, gfn::f32x4;
 
 constexpr int kNP = 8;     // channel pairs per K tile
 constexpr int kCP2 = 64;   // floats per channel PAIR in the packed depthwise parameters
@@ -338,7 +335,6 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
         __syncthreads();
         if (t + 1 < total) issue();
         if constexpr (MM) {
-            typedef float f32x4v __attribute__((ext_vector_type(4)));
             const int n = lane & 15, xo = n >> 1, ch = n & 1, kg = lane >> 4, mrow = lane & 15;
             const int ar = mrow % RS, ac = mrow / RS;  // A operand: this lane's row segment
             const float *xbase = &Xs[ar * PH + 8 * ac + 4 * kg];
@@ -356,17 +352,17 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
                 f16x8 T[5];
 #pragma unroll
                 for (int dy = 0; dy < 5; ++dy) {
-                    const f32x4v t = {tw[tix[0] + 8 * dy], tw[tix[1] + 8 * dy], tw[tix[2] + 8 * dy], tw[tix[3] + 8 * dy]};
+                    const f32x4 t = {tw[tix[0] + 8 * dy], tw[tix[1] + 8 * dy], tw[tix[2] + 8 * dy], tw[tix[3] + 8 * dy]};
                     T[dy] = __builtin_bit_cast(f16x8, t);
                 }
                 const float cb = tw[80 + ch], al = tw[82 + ch], be = tw[84 + ch];
 #pragma unroll
                 for (int sub = 0; sub < NB; ++sub) {
-                    f32x4v d = {0.f, 0.f, 0.f, 0.f};
+                    f32x4 d = {0.f, 0.f, 0.f, 0.f};
                     const float *xs = xbase + pr_ * (HR * PH) + sub * RS * PH;
 #pragma unroll
                     for (int dy = 0; dy < 5; ++dy) {
-                        const f16x8 a = __builtin_bit_cast(f16x8, *reinterpret_cast<const f32x4v *>(xs + dy * PH));
+                        const f16x8 a = __builtin_bit_cast(f16x8, *reinterpret_cast<const f32x4 *>(xs + dy * PH));
                         d = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, T[dy], d, 0, 0, 0);
                     }
 #pragma unroll

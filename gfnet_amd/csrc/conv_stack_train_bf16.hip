@@ -4,9 +4,9 @@
 // hidden_blocks (network.py:560-562) train under bf16 autocast.  bf16 keeps fp32's exponent range: nothing overflows at 65504 and
 // the step needs no loss scale.  The block is that of conv_stack_train.hip,
 //   Conv2d(C, C, 5x5, padding 2, groups=C[, bias])  ->  BatchNorm2d (batch statistics)  ->  ReLU  ->  Conv2d(C, M, 1x1),
-// conv_train_common.h writes it once for all classes and conv_train_16bit.h the classes with 16-bit maps once over an element trait:
-// the three GEMM kernels, the split sum and the four launches.  This file is the bf16 class, BF16Maps = Maps16<BF16Elem>, beside
-// F16Maps of conv_stack_train_half.hip: the trait and the C entry points.  What the class means:
+// conv_train_common.h writes it once for all classes and conv_train_16bit.h the classes with 16-bit maps once over their element
+// (elem16.h): the three GEMM kernels, the split sum and the four launches.  This file is the bf16 class, BF16Maps = Maps16<__bf16>,
+// beside F16Maps of conv_stack_train_half.hip: its C entry points.  What the class means:
 //   * maps in HBM are plain contiguous (B, C, G, G) bf16: x (the previous block's y), u, y, the backward's gz and gx.  Any C, any
 //     G: with odd G a plane starts on a 2-byte boundary, so maps are read and written 2 bytes at a time unless G % 4 == 0 (G % 8 == 0
 //     for the 16-byte loads of the weight gradient) makes a wider access aligned.  A stack's first block reads the fp32 concat and
@@ -24,16 +24,7 @@
 
 namespace {
 
-struct BF16Elem {
-    using elem_t = __bf16;
-    typedef __bf16 vec8 __attribute__((ext_vector_type(8)));
-    static constexpr int kDtype = GFN_BF16;
-    static constexpr const char *kDtypeName = "GFN_BF16";
-    static __device__ __forceinline__ float value(float v) { return (float)(__bf16)v; }
-    static __device__ __forceinline__ float value(__bf16 v) { return (float)v; }
-    static __device__ __forceinline__ f32x16 mfma(vec8 a, vec8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-using BF16Maps = Maps16<BF16Elem>;
+using BF16Maps = Maps16<__bf16>;
 
 }  // namespace
 

@@ -5,9 +5,9 @@
 //   Conv2d(C, C, 5x5, padding 2, groups=C[, bias])  ->  BatchNorm2d (batch statistics)  ->  ReLU  ->  Conv2d(C, M, 1x1),
 // and conv_train_common.h writes it once for all classes: the depthwise kernels, the small reductions, the prologues and epilogues
 // of the 1x1 kernels, the workspace plan, the argument checks, the `need` mask and the launch sequence (train_fwd / train_bwd).
-// conv_train_16bit.h writes the classes with 16-bit maps once over an element trait: the three GEMM kernels (ct_half_pw_fwd / _bwd /
-// _wgrad_kernel), the split sum and the four launches.  This file is the fp16 class, F16Maps = Maps16<F16Elem>: the trait and the C
-// entry points (conv_stack_train_bf16.hip is the bf16 class).  What the class means:
+// conv_train_16bit.h writes the classes with 16-bit maps once over their element (elem16.h): the three GEMM kernels (ct_half_pw_fwd /
+// _bwd / _wgrad_kernel), the split sum and the four launches.  This file is the fp16 class, F16Maps = Maps16<_Float16>: its C entry
+// points (conv_stack_train_bf16.hip is the bf16 class).  What the class means:
 //   * maps in HBM are plain contiguous (B, C, G, G) fp16: x (the previous block's y), u, y, the backward's gz and gx.  Any C, any
 //     G: with odd G a plane starts on a 2-byte boundary, so maps are read and written half by half unless G % 4 == 0 (G % 8 == 0
 //     for the 16-byte loads of the weight gradient) makes a wider access aligned.  A stack's first block reads the fp32 concat and
@@ -19,24 +19,13 @@
 //     directions, so both ReLU masks agree bit for bit
 //   * the three 1x1 products (y = W.t, gt = W^T.gy, dW = gy.t^T with its column of ones) run on v_mfma_f32_32x32x16_f16 with fp32
 //     accumulators
-//   * every rounding is to nearest even and overflows to inf (F16Elem::value): a loss scale that is too large shows as inf / nan
+//   * every rounding is to nearest even and overflows to inf (Elem16<_Float16>::round): a loss scale that is too large shows as inf / nan
 // No floating-point atomics: two identical calls give identical bits.
 #include "conv_train_16bit.h"
 
 namespace {
 
-// float -> fp16 is v_cvt_f16_f32: to nearest even, and past 65504 to inf -- never a clamp, or overflow would be hidden from the
-// loss scaler
-struct F16Elem {
-    using elem_t = _Float16;
-    typedef _Float16 vec8 __attribute__((ext_vector_type(8)));
-    static constexpr int kDtype = GFN_F16;
-    static constexpr const char *kDtypeName = "GFN_F16";
-    static __device__ __forceinline__ float value(float v) { return (float)(_Float16)v; }
-    static __device__ __forceinline__ float value(_Float16 v) { return (float)v; }
-    static __device__ __forceinline__ f32x16 mfma(vec8 a, vec8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-using F16Maps = Maps16<F16Elem>;
+using F16Maps = Maps16<_Float16>;
 
 }  // namespace
 

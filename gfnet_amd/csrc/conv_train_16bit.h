@@ -1,10 +1,8 @@
 // conv_train_16bit.h -- the refiner's training-mode conv block in a class whose maps hold 16-bit floats, said once for fp16
-// (conv_stack_train_half.hip) and bf16 (conv_stack_train_bf16.hip).  An element trait E tells the two apart:
-//   E::elem_t   the 16-bit type of a map value and of a matrix-core operand (_Float16, __bf16)
-//   E::vec8     eight of them, one register quad: a lane's operand fragment and a 16-byte access
-//   E::kDtype   the GFN_* constant of a map of elem_t;  E::kDtypeName: its name in messages
-//   E::value(v) the float a value becomes once it is rounded to elem_t (to nearest even, no clamp: past the format's range it is inf)
-//   E::mfma     the 32x32x16 matrix instruction on two vec8 fragments with fp32 accumulators
+// (conv_stack_train_half.hip) and bf16 (conv_stack_train_bf16.hip).  The element E, _Float16 or __bf16, tells the two apart, and
+// elem16.h says what comes with it: V8<E> = Elem16<E>::vec8, a lane's operand fragment and a 16-byte access; Elem16<E>::round(v), the
+// float a value becomes once it is rounded to E (to nearest even, no clamp: past the format's range it is inf); and mfma16, the
+// 32x32x16 matrix instruction on two V8<E> fragments with fp32 accumulators.
 // Maps16<E> is the class K of conv_train_common.h, which writes everything around the 1x1 products once for all classes.  Here: the
 // matrix-core tile beside the exact-fp32 tile of pw_gemm_tile.h whose accumulators (PwAcc) and 128-cell workgroup tile it keeps, the
 // three GEMM kernels (ct_half_pw_fwd / _bwd / _wgrad_kernel), the split sum of the weight gradient and the class's four launches.
@@ -16,8 +14,14 @@
 // banks once.  Opens its own anonymous namespace.
 #pragma once
 #include "conv_train_common.h"
+#include "elem16.h"
 
 namespace {
+
+using gfn::Elem16;
+using gfn::mfma16;
+template <typename E>
+using V8 = typename Elem16<E>::vec8;
 
 constexpr int kHKT = 32;  // channels per K tile of the forward and the input-gradient GEMM: two MFMA steps
 constexpr int half_pitch(int kt) { return kt + 8; }
@@ -31,49 +35,46 @@ constexpr int kHBM = 32;
 // T[row][k8 .. k8 + 7] (zeros where the source ends).  ROWS_FIRST: consecutive lanes take consecutive rows -- for a source whose
 // rows are contiguous in memory and whose k is strided (a map's cells under its channels); otherwise consecutive lanes take
 // consecutive pieces of one row (a source with k contiguous).
-template <class E, int ROWS, int KT, bool ROWS_FIRST, typename V>
-__device__ __forceinline__ void stage_half_tile(typename E::elem_t *T, int tid, V piece) {
+template <typename E, int ROWS, int KT, bool ROWS_FIRST, typename V>
+__device__ __forceinline__ void stage_half_tile(E *T, int tid, V piece) {
     constexpr int P = half_pitch(KT), G8 = KT / 8;
     for (int e = tid; e < ROWS * G8; e += 256) {
         const int row = ROWS_FIRST ? e % ROWS : e / G8, k8 = (ROWS_FIRST ? e / ROWS : e % G8) * 8;
-        *reinterpret_cast<typename E::vec8 *>(&T[row * P + k8]) = piece(row, k8);
+        *reinterpret_cast<V8<E> *>(&T[row * P + k8]) = piece(row, k8);
     }
 }
 
 // eight consecutive elements src[0 .. 7] of which the first `valid` exist; vec: src is 16-byte aligned (the caller's promise)
-template <class E>
-__device__ __forceinline__ typename E::vec8 load_half8(const typename E::elem_t *src, int valid, bool vec) {
-    using elem_t = typename E::elem_t;
-    if (vec && valid >= 8) return *reinterpret_cast<const typename E::vec8 *>(src);
-    typename E::vec8 h;
+template <typename E>
+__device__ __forceinline__ V8<E> load_half8(const E *src, int valid, bool vec) {
+    if (vec && valid >= 8) return *reinterpret_cast<const V8<E> *>(src);
+    V8<E> h;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = j < valid ? src[j] : (elem_t)0.f;
+    for (int j = 0; j < 8; ++j) h[j] = j < valid ? src[j] : (E)0.f;
     return h;
 }
 
 // STEPS MFMA steps of 16 k: a, b point at the lane's own fragment of the first step (row or column `col`, k = 8 kh) in tiles of
 // pitch AP and BP; row tile i of A lies 32 rows further
-template <class E, int MT, int STEPS, int AP>
-__device__ __forceinline__ void half_products(PwAcc<MT> &acc, const typename E::elem_t *a, const typename E::elem_t *b) {
-    using vec8 = typename E::vec8;
+template <typename E, int MT, int STEPS, int AP>
+__device__ __forceinline__ void half_products(PwAcc<MT> &acc, const E *a, const E *b) {
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
-        const vec8 bv = *reinterpret_cast<const vec8 *>(b + 16 * s);
+        const V8<E> bv = *reinterpret_cast<const V8<E> *>(b + 16 * s);
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
-            const vec8 av = *reinterpret_cast<const vec8 *>(a + i * 32 * AP + 16 * s);
-            acc.a[i] = E::mfma(av, bv, acc.a[i]);
+            const V8<E> av = *reinterpret_cast<const V8<E> *>(a + i * 32 * AP + 16 * s);
+            acc.a[i] = mfma16(av, bv, acc.a[i]);
         }
     }
 }
 
-// the class: maps hold E::elem_t; a value is rounded where it is stored in a map or becomes an operand.  x is fp32 (a stack's first
-// block: rounded on load, its gx written fp32) or elem_t
-template <class E>
+// the class: maps hold E; a value is rounded where it is stored in a map or becomes an operand.  x is fp32 (a stack's first
+// block: rounded on load, its gx written fp32) or E
+template <typename E>
 struct Maps16 {
-    using map_t = typename E::elem_t;
-    template <typename T>
-    static __device__ __forceinline__ float value(T v) { return E::value(v); }
+    using map_t = E;
+    static __device__ __forceinline__ float value(float v) { return Elem16<E>::round(v); }
     static int check_class(const char *what, int x_dtype, int C, int M);
     static int pw_fwd(const TrainPlan &p, hipStream_t s, const map_t *u, const float *bn_w, const float *bn_b, const float *mean,
                       const float *invstd, const float *pw_w, const float *pw_b, map_t *y, int B, int C, int M, int N);
@@ -86,39 +87,35 @@ struct Maps16 {
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------------
 // the B operand tile of a (K, N) map: Bs[cell][k] = f(k, map[k0 + k][n0 + cell]); channels past K and cells past N are zero
-template <class E, typename F>
-__device__ __forceinline__ void stage_map_cells(typename E::elem_t *Bs, const typename E::elem_t *map, int k0, int K, int n0, int N, int tid,
-                                                F f) {
-    using elem_t = typename E::elem_t;
+template <typename E, typename F>
+__device__ __forceinline__ void stage_map_cells(E *Bs, const E *map, int k0, int K, int n0, int N, int tid, F f) {
     stage_half_tile<E, kBN, kHKT, true>(Bs, tid, [&](int cell, int k8) {
         const int n = n0 + cell;
-        typename E::vec8 h;
+        V8<E> h;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int kk = k0 + k8 + j;
             const bool ok = n < N && kk < K;
-            const elem_t v = map[ok ? (size_t)kk * N + n : 0];
-            h[j] = ok ? f(k8 + j, v) : (elem_t)0.f;
+            const E v = map[ok ? (size_t)kk * N + n : 0];
+            h[j] = ok ? f(k8 + j, v) : (E)0.f;
         }
         return h;
     });
 }
 
 // y[b] = elem(W . t + bias), t = elem(relu(u[b]*alpha + beta')); W (M, K) row major
-template <class E>
-__global__ __launch_bounds__(256, 2) void ct_half_pw_fwd_kernel(const typename E::elem_t *__restrict__ u, const float *__restrict__ gamma,
+template <typename E>
+__global__ __launch_bounds__(256, 2) void ct_half_pw_fwd_kernel(const E *__restrict__ u, const float *__restrict__ gamma,
                                                                 const float *__restrict__ beta, const float *__restrict__ mean,
                                                                 const float *__restrict__ invstd, const float *__restrict__ pw_w,
-                                                                const float *__restrict__ pw_b, typename E::elem_t *__restrict__ y, int M,
-                                                                int K, int N) {
-    using elem_t = typename E::elem_t;
+                                                                const float *__restrict__ pw_b, E *__restrict__ y, int M, int K, int N) {
     constexpr int BM = kHBM, P = half_pitch(kHKT);
-    __shared__ __attribute__((aligned(16))) elem_t As[BM * P];
-    __shared__ __attribute__((aligned(16))) elem_t Bs[kBN * P];
+    __shared__ __attribute__((aligned(16))) E As[BM * P];
+    __shared__ __attribute__((aligned(16))) E Bs[kBN * P];
     __shared__ float Al[2][kHKT], Be[2][kHKT];  // the K tile's alpha, beta': the next tile's are formed while this one is staged
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.z, m0 = blockIdx.y * BM, n0 = blockIdx.x * kBN;
-    const elem_t *ub = u + (size_t)b * K * N;
+    const E *ub = u + (size_t)b * K * N;
     const int col = lane & 31, kh = lane >> 5;
     auto affine = [&](int buf, int k0) {
         if (tid < kHKT) {
@@ -135,17 +132,17 @@ __global__ __launch_bounds__(256, 2) void ct_half_pw_fwd_kernel(const typename E
     for (int k0 = 0, buf = 0; k0 < K; k0 += kHKT, buf ^= 1) {
         stage_half_tile<E, BM, kHKT, false>(As, tid, [&](int row, int k8) {
             const int m = m0 + row;
-            typename E::vec8 h;
+            V8<E> h;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const bool ok = m < M && k0 + k8 + j < K;
                 const float v = pw_w[ok ? (size_t)m * K + k0 + k8 + j : 0];
-                h[j] = ok ? (elem_t)v : (elem_t)0.f;
+                h[j] = ok ? (E)v : (E)0.f;
             }
             return h;
         });
         stage_map_cells<E>(Bs, ub, k0, K, n0, N, tid,
-                           [&](int k, elem_t v) { return (elem_t)fmaxf(bn_pre((float)v, Al[buf][k], Be[buf][k]), 0.f); });
+                           [&](int k, E v) { return (E)fmaxf(bn_pre((float)v, Al[buf][k], Be[buf][k]), 0.f); });
         affine(buf ^ 1, k0 + kHKT);
         __syncthreads();
         half_products<E, 1, kHKT / 16, P>(acc, &As[col * P + 8 * kh], &Bs[(wave * 32 + col) * P + 8 * kh]);
@@ -153,10 +150,10 @@ __global__ __launch_bounds__(256, 2) void ct_half_pw_fwd_kernel(const typename E
     }
     const int n = n0 + wave * 32 + col;
     if (n < N) {
-        elem_t *yb = y + (size_t)b * M * N + n;
+        E *yb = y + (size_t)b * M * N + n;
         acc.each(kh, [&](int row, float v) {
             const int m = m0 + row;
-            if (m < M) yb[(size_t)m * N] = (elem_t)(v + pw_b[m]);
+            if (m < M) yb[(size_t)m * N] = (E)(v + pw_b[m]);
         });
     }
 }
@@ -164,38 +161,35 @@ __global__ __launch_bounds__(256, 2) void ct_half_pw_fwd_kernel(const typename E
 // ---- backward --------------------------------------------------------------------------------------------------------------------
 // gt[b] = W^T . gy[b] (rows = the C channels, k = the M output channels); pw_bwd_finish: gz = elem(gt) where u*alpha + beta' > 0,
 // written as a C map, and the per-workgroup partial sums of that rounded gz and of gz*u_hat.  part: (C, B * gridDim.x, 2).
-template <class E>
-__global__ __launch_bounds__(256, 2) void ct_half_pw_bwd_kernel(const typename E::elem_t *__restrict__ gy,
-                                                                const typename E::elem_t *__restrict__ u, const float *__restrict__ gamma,
+template <typename E>
+__global__ __launch_bounds__(256, 2) void ct_half_pw_bwd_kernel(const E *__restrict__ gy, const E *__restrict__ u, const float *__restrict__ gamma,
                                                                 const float *__restrict__ beta, const float *__restrict__ mean,
                                                                 const float *__restrict__ invstd, const float *__restrict__ pw_w,
-                                                                typename E::elem_t *__restrict__ gz, float *__restrict__ part, int M, int C,
-                                                                int N) {
-    using elem_t = typename E::elem_t;
+                                                                E *__restrict__ gz, float *__restrict__ part, int M, int C, int N) {
     constexpr int BM = kHBM, P = half_pitch(kHKT);
-    __shared__ __attribute__((aligned(16))) elem_t As[BM * P];
-    __shared__ __attribute__((aligned(16))) elem_t Bs[kBN * P];
+    __shared__ __attribute__((aligned(16))) E As[BM * P];
+    __shared__ __attribute__((aligned(16))) E Bs[kBN * P];
     __shared__ float Al[BM], Be[BM], Mn[BM], Is[BM];
     __shared__ float red[4][BM][2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.z, c0 = blockIdx.y * BM, n0 = blockIdx.x * kBN;
-    const elem_t *gb = gy + (size_t)b * M * N;
+    const E *gb = gy + (size_t)b * M * N;
     const int col = lane & 31, kh = lane >> 5;
     stage_bn_rows(BM, c0, C, gamma, beta, mean, invstd, Al, Be, Mn, Is);  // read after the loop's barriers
     PwAcc<1> acc;
     acc.zero();
     for (int k0 = 0; k0 < M; k0 += kHKT) {
         stage_half_tile<E, BM, kHKT, true>(As, tid, [&](int cc, int k8) {  // A[c][m] = W[m][c]: consecutive lanes, consecutive c
-            typename E::vec8 h;
+            V8<E> h;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const bool ok = k0 + k8 + j < M && c0 + cc < C;
                 const float v = pw_w[ok ? (size_t)(k0 + k8 + j) * C + c0 + cc : 0];
-                h[j] = ok ? (elem_t)v : (elem_t)0.f;
+                h[j] = ok ? (E)v : (E)0.f;
             }
             return h;
         });
-        stage_map_cells<E>(Bs, gb, k0, M, n0, N, tid, [](int, elem_t v) { return v; });
+        stage_map_cells<E>(Bs, gb, k0, M, n0, N, tid, [](int, E v) { return v; });
         __syncthreads();
         half_products<E, 1, kHKT / 16, P>(acc, &As[col * P + 8 * kh], &Bs[(wave * 32 + col) * P + 8 * kh]);
         __syncthreads();
@@ -206,16 +200,14 @@ __global__ __launch_bounds__(256, 2) void ct_half_pw_bwd_kernel(const typename E
 // One split of dW[m, c] = sum_p gy[m, p] t[c, p], c = C being a row of ones (db_pw); the workgroup and wave shapes of
 // ct_pw_wgrad_kernel.  Both operands have their k -- the cells -- contiguous in HBM: the tiles are plain copies of map rows
 // (16 bytes at a time where vec says every piece is aligned), t recomputed from u on the way.
-template <class E, int MT, int CW>
-__global__ __launch_bounds__(256) void ct_half_pw_wgrad_kernel(const typename E::elem_t *__restrict__ gy, const typename E::elem_t *__restrict__ u,
+template <typename E, int MT, int CW>
+__global__ __launch_bounds__(256) void ct_half_pw_wgrad_kernel(const E *__restrict__ gy, const E *__restrict__ u,
                                                                const float *__restrict__ gamma, const float *__restrict__ beta,
                                                                const float *__restrict__ mean, const float *__restrict__ invstd,
                                                                float *__restrict__ part, int M, int C, int N, int S, int chunk, int vec) {
-    using elem_t = typename E::elem_t;
-    using vec8 = typename E::vec8;
     constexpr int KS = 4 / CW, KTS = kWgCells * KS, BM = 32 * MT, BC = 32 * CW, P = half_pitch(KTS);
-    __shared__ __attribute__((aligned(16))) elem_t As[BM * P];
-    __shared__ __attribute__((aligned(16))) elem_t Bs[BC * P];
+    __shared__ __attribute__((aligned(16))) E As[BM * P];
+    __shared__ __attribute__((aligned(16))) E Bs[BC * P];
     __shared__ float Al[BC], Be[BC];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cw = wave % CW, ks = wave / CW;
@@ -223,8 +215,8 @@ __global__ __launch_bounds__(256) void ct_half_pw_wgrad_kernel(const typename E:
     const int c0 = blockIdx.x * BC, m0 = blockIdx.y * BM;
     const int b = blockIdx.z / S, sp = blockIdx.z - b * S;
     const int n_begin = sp * chunk, n_end = min(N, n_begin + chunk);
-    const elem_t *gb = gy + (size_t)b * M * N;
-    const elem_t *ub = u + (size_t)b * C * N;
+    const E *gb = gy + (size_t)b * M * N;
+    const E *ub = u + (size_t)b * C * N;
     stage_bn_rows(BC, c0, C, gamma, beta, mean, invstd, Al, Be);
     __syncthreads();
     PwAcc<MT> acc;
@@ -237,12 +229,12 @@ __global__ __launch_bounds__(256) void ct_half_pw_wgrad_kernel(const typename E:
         stage_half_tile<E, BC, KTS, false>(Bs, tid, [&](int row, int k8) {
             const int c = c0 + row, cells = n_end - (nb + k8);
             const int valid = c < C ? cells : 0;
-            const vec8 uu = load_half8<E>(ub + (valid > 0 ? (size_t)c * N + nb + k8 : 0), valid, vec);
-            vec8 h;
+            const V8<E> uu = load_half8<E>(ub + (valid > 0 ? (size_t)c * N + nb + k8 : 0), valid, vec);
+            V8<E> h;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const elem_t t = (elem_t)fmaxf(bn_pre((float)uu[j], Al[row], Be[row]), 0.f);
-                h[j] = j < valid ? t : (elem_t)(c == C && j < cells ? 1.f : 0.f);
+                const E t = (E)fmaxf(bn_pre((float)uu[j], Al[row], Be[row]), 0.f);
+                h[j] = j < valid ? t : (E)(c == C && j < cells ? 1.f : 0.f);
             }
             return h;
         });
@@ -277,14 +269,14 @@ __global__ __launch_bounds__(256) void ct_half_pw_wgrad_sum_kernel(const float *
 }
 
 // ---- host: the class's check and four launches for train_fwd / train_bwd -----------------------------------------------------------
-template <class E>
+template <typename E>
 int Maps16<E>::check_class(const char *what, int x_dtype, int C, int M) {
-    if (x_dtype != GFN_F32 && x_dtype != E::kDtype) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: x_dtype must be GFN_F32 or %s", what, E::kDtypeName);
+    if (x_dtype != GFN_F32 && x_dtype != Elem16<E>::kDtype) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: x_dtype must be GFN_F32 or %s", what, Elem16<E>::kDtypeName);
     if (C > 65535 * kHBM || M > 65535 * kHBM) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: more than %d channels", what, 65535 * kHBM);
     return GFN_OK;
 }
 
-template <class E>
+template <typename E>
 int Maps16<E>::pw_fwd(const TrainPlan &p, hipStream_t s, const map_t *u, const float *bn_w, const float *bn_b, const float *mean,
                       const float *invstd, const float *pw_w, const float *pw_b, map_t *y, int B, int C, int M, int N) {
     const dim3 grid((unsigned)p.ntn, (unsigned)((M + kHBM - 1) / kHBM), (unsigned)B);
@@ -292,7 +284,7 @@ int Maps16<E>::pw_fwd(const TrainPlan &p, hipStream_t s, const map_t *u, const f
     return gfn::check_launch("ct_half_pw_fwd_kernel");
 }
 
-template <class E>
+template <typename E>
 int Maps16<E>::pw_bwd(const TrainPlan &p, hipStream_t s, const map_t *gy, const map_t *u, const float *bn_w, const float *bn_b,
                       const float *mean, const float *invstd, const float *pw_w, map_t *gz, float *part_bn, int B, int C, int M, int N) {
     const dim3 grid((unsigned)p.ntn, (unsigned)((C + kHBM - 1) / kHBM), (unsigned)B);
@@ -300,7 +292,7 @@ int Maps16<E>::pw_bwd(const TrainPlan &p, hipStream_t s, const map_t *gy, const 
     return gfn::check_launch("ct_half_pw_bwd_kernel");
 }
 
-template <class E>
+template <typename E>
 int Maps16<E>::pw_wgrad(const char *what, const TrainPlan &p, hipStream_t s, const map_t *gy, const map_t *u, const float *bn_w,
                         const float *bn_b, const float *mean, const float *invstd, float *part_pw, int B, int C, int M, int N) {
     const dim3 grid((unsigned)p.wg_tc, (unsigned)p.wg_tm, (unsigned)(B * p.wg_s));
@@ -315,7 +307,7 @@ int Maps16<E>::pw_wgrad(const char *what, const TrainPlan &p, hipStream_t s, con
     return gfn::check_launch("ct_half_pw_wgrad_kernel");
 }
 
-template <class E>
+template <typename E>
 int Maps16<E>::pw_wgrad_sum(hipStream_t s, const float *part_pw, int nparts, int M, int C, float *d_pw_w, float *d_pw_b) {
     hipLaunchKernelGGL(ct_half_pw_wgrad_sum_kernel, dim3((unsigned)((M * (C + 1) + 15) / 16)), dim3(256), 0, s, part_pw, nparts, M, C, d_pw_w,
                        d_pw_b);

@@ -16,8 +16,13 @@
 // Fixed-order sums everywhere, no floating-point atomics.  Opens its own anonymous namespace.
 #pragma once
 #include "pw_gemm_tile.h"
+#include "reduce.h"
 
 namespace {
+
+using gfn::block_sum;
+using gfn::half_wave_sum;
+using gfn::wave_sum;
 
 constexpr int kTile = 32;         // depthwise tile side in cells: 256 threads x 4 cells of a row
 constexpr int kHalo = kTile + 4;  // staged side (2 cells of halo all round)
@@ -47,25 +52,6 @@ __device__ __forceinline__ void stage_bn_rows(int rows, int c0, int C, const flo
         Al[tid] = al, Be[tid] = be;
         if (Mn) Mn[tid] = mn, Is[tid] = is;
     }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ float half_wave_sum(float v) {  // over the 32 lanes that share lane >> 5
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-// sum over the workgroup's 256 threads in a fixed order, returned to every thread; red: 4 floats of LDS
-__device__ __forceinline__ float block_sum(float v, float *red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 struct TileId {

@@ -1,12 +1,11 @@
 // corr_common.h -- what the global-correlation kernels (corr_softargmax.hip, corr_softargmax_bwd.hip) say about a 32 x 32 tile, once:
 // the B-grid cell of a position, the fp32 tile product, the virtual symmetric direction and the host-side argument checks (the
-// accumulator layout, f32x16 and acc_row, is common.h's: the 1x1 conv tile reads it too).  split3 and bf16x8 also serve kde.hip.
+// accumulator layout, f32x16 and acc_row, is common.h's: the 1x1 conv tile reads it too).  split3 also serves kde.hip.
 #pragma once
-#include "common.h"
+#include "elem16.h"
+#include "reduce.h"
 
 namespace gfn {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // x = h + m + l exactly (three round-to-nearest bf16 pieces of 8 significant bits each cover the 24 of an fp32 value)
 __device__ __forceinline__ void split3(float v, __bf16 &h, __bf16 &m, __bf16 &l) {

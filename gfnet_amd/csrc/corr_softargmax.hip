@@ -27,7 +27,7 @@ using namespace gfn;
 
 // merge the two half-waves (same column i, disjoint rows j) and write flow[b, :, i]
 __device__ __forceinline__ void finish_flow(float m, float l, float ax, float ay, float *__restrict__ flow, int b, int N0, int i, int h) {
-    const float m2 = __shfl_xor(m, 32), l2 = __shfl_xor(l, 32), ax2 = __shfl_xor(ax, 32), ay2 = __shfl_xor(ay, 32);
+    const float m2 = other_half(m), l2 = other_half(l), ax2 = other_half(ax), ay2 = other_half(ay);
     const float mn = fmaxf(m, m2);
     const float s1 = __expf(m - mn), s2 = __expf(m2 - mn);
     const float lt = l * s1 + l2 * s2;

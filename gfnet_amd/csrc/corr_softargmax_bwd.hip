@@ -92,7 +92,7 @@ __global__ __launch_bounds__(64) void bwd_f0_kernel(const FT *__restrict__ f0, c
         float mt = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) mt = fmaxf(mt, j0 + acc_row(r, h) < N1 ? acc[r] : -INFINITY);
-        mt = fmaxf(mt, __shfl_xor(mt, 32));
+        mt = fmaxf(mt, other_half(mt));
         const float mn = fmaxf(m, mt);  // finite: row j0 of every tile is a position
         const float sc = __builtin_amdgcn_exp2f((m - mn) * e_scale);  // m = -inf on the first tile -> 0
         float w[16], lt = 0.f;
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(64) void bwd_f0_kernel(const FT *__restrict__ f0, c
             load_tile(a_cur, j0 + 32);
         }
     }
-    l += __shfl_xor(l, 32);
+    l += other_half(l);
     const float inv = 1.f / (l * sqrt_c);
     if (want && i < N0) {
 #pragma unroll

@@ -17,8 +17,7 @@
 
 namespace {
 
-using gfn::acc_row;
-using gfn::f32x16;
+using namespace gfn;
 using namespace gfn::attn;
 
 constexpr int kThreads = 256;           // 4 waves: 4 own tiles of 32 rows per workgroup
@@ -28,18 +27,8 @@ constexpr int kRowImg = kChunk * 8 + kChunk;  // floats of a row image: 8 per ro
 
 // one 8-value row as stored
 template <typename T>
-struct Row;
-template <>
-struct alignas(16) Row<_Float16> {
-    _Float16 e[8];
-};
-template <>
-struct alignas(16) Row<__bf16> {
-    __bf16 e[8];
-};
-template <>
-struct alignas(16) Row<float> {
-    float e[8];
+struct alignas(16) Row {
+    T e[8];
 };
 
 template <typename T>
@@ -57,28 +46,17 @@ __device__ __forceinline__ Row<T> load_row(const T *p, bool ok) {
 // the MFMA operand fragment of lane half h for a row: fp16, bf16 -> values 4h..4h+3 (one 32x32x8 step); fp32 -> values h, h+2, h+4,
 // h+6 (the four 32x32x2 steps)
 template <typename T>
-struct Frag;
-template <>
-struct Frag<_Float16> {
-    h4 v;
-};
-template <>
-struct Frag<__bf16> {
-    b4 v;
+struct Frag {
+    typename Elem16<T>::vec4 v;
 };
 template <>
 struct Frag<float> {
     float v[4];
 };
 
-__device__ __forceinline__ Frag<_Float16> frag_of(const Row<_Float16> &r, int h) {
-    Frag<_Float16> f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f.v[j] = h ? r.e[4 + j] : r.e[j];
-    return f;
-}
-__device__ __forceinline__ Frag<__bf16> frag_of(const Row<__bf16> &r, int h) {
-    Frag<__bf16> f;
+template <typename T>
+__device__ __forceinline__ Frag<T> frag_of(const Row<T> &r, int h) {
+    Frag<T> f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) f.v[j] = h ? r.e[4 + j] : r.e[j];
     return f;
@@ -91,11 +69,9 @@ __device__ __forceinline__ Frag<float> frag_of(const Row<float> &r, int h) {
 }
 
 // D[i][j] = sum_k a[i][k] * b[k][j] over the 8 values: a's row on lane & 31 gives accumulator row i, b's row on lane & 31 column j
-__device__ __forceinline__ f32x16 dot8(const Frag<_Float16> &a, const Frag<_Float16> &b) {
-    f32x16 z = {};
-    return __builtin_amdgcn_mfma_f32_32x32x8f16(a.v, b.v, z, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 dot8(const Frag<__bf16> &a, const Frag<__bf16> &b) {  // v_mfma_f32_32x32x8_bf16: exact products too
+// (fp16, bf16: one v_mfma_f32_32x32x8_f16 / _bf16, exact products in both)
+template <typename T>
+__device__ __forceinline__ f32x16 dot8(const Frag<T> &a, const Frag<T> &b) {
     f32x16 z = {};
     return mfma8(a.v, b.v, z);
 }
@@ -115,7 +91,7 @@ struct OpImg {
     __device__ __forceinline__ void put(int row, const Row<T> &r) { *reinterpret_cast<Row<T> *>(&m[row * 8]) = r; }
     __device__ __forceinline__ Frag<T> get(int tile, int lane) const {
         Frag<T> f;
-        f.v = *reinterpret_cast<const typename Vec4<T>::type *>(&m[(tile * 32 + (lane & 31)) * 8 + 4 * (lane >> 5)]);
+        f.v = *reinterpret_cast<const typename Elem16<T>::vec4 *>(&m[(tile * 32 + (lane & 31)) * 8 + 4 * (lane >> 5)]);
         return f;
     }
 };
@@ -152,21 +128,15 @@ __device__ __forceinline__ void get_row(const float *img, int row, float out[8])
     out[0] = a.x, out[1] = a.y, out[2] = a.z, out[3] = a.w, out[4] = b.x, out[5] = b.y, out[6] = b.z, out[7] = b.w;
 }
 
-// lane half h stores values 4h..4h+3 of its row's 8 results (both halves hold all 8 after the merge); fp16: rounded to nearest
-// even once, overflow to inf
-__device__ __forceinline__ void store_half_row(_Float16 *p, const float v[8], int h) {
-    h4 o;
+// lane half h stores values 4h..4h+3 of its row's 8 results (both halves hold all 8 after the merge).  fp16, bf16: rounded to nearest
+// even once (v_cvt_f16_f32 / v_cvt_pk_bf16_f32) with no clamp: fp16 overflows to inf; bf16 has fp32's exponent range, so nothing
+// overflows that was finite in fp32, and inf and NaN stay what they are
+template <typename T>
+__device__ __forceinline__ void store_half_row(T *p, const float v[8], int h) {
+    typename Elem16<T>::vec4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = (_Float16)(h ? v[4 + j] : v[j]);
-    *reinterpret_cast<h4 *>(p + 4 * h) = o;
-}
-// bf16: rounded to nearest even once (v_cvt_pk_bf16_f32); fp32's exponent range, so nothing overflows that was finite in fp32, and
-// there is no clamp: inf and NaN stay what they are
-__device__ __forceinline__ void store_half_row(__bf16 *p, const float v[8], int h) {
-    b4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = (__bf16)(h ? v[4 + j] : v[j]);
-    *reinterpret_cast<b4 *>(p + 4 * h) = o;
+    for (int j = 0; j < 4; ++j) o[j] = (T)(h ? v[4 + j] : v[j]);
+    *reinterpret_cast<typename Elem16<T>::vec4 *>(p + 4 * h) = o;
 }
 __device__ __forceinline__ void store_half_row(float *p, const float v[8], int h) {
     *reinterpret_cast<float4 *>(p + 4 * h) = h ? make_float4(v[4], v[5], v[6], v[7]) : make_float4(v[0], v[1], v[2], v[3]);
@@ -514,9 +484,8 @@ GFN_EXPORT int gfn_cross_attn_fwd(const void *q, const void *k, const void *v, i
     if (B == 0 || Nq == 0) return GFN_OK;
     if (!lse || ((uintptr_t)lse & 3)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: lse missing or not 4-byte aligned", what);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == GFN_BF16) return launch_fwd<__bf16>(q, k, v, out, lse, B, Nq, Nk, H, scale, s);
-    return dtype == GFN_F16 ? launch_fwd<_Float16>(q, k, v, out, lse, B, Nq, Nk, H, scale, s)
-                            : launch_fwd<float>(q, k, v, out, lse, B, Nq, Nk, H, scale, s);
+    if (dtype == GFN_F32) return launch_fwd<float>(q, k, v, out, lse, B, Nq, Nk, H, scale, s);
+    return with_elem16(dtype, [&](auto e) { return launch_fwd<decltype(e)>(q, k, v, out, lse, B, Nq, Nk, H, scale, s); });
 }
 
 GFN_EXPORT int gfn_cross_attn_bwd(const void *q, const void *k, const void *v, const void *out, const float *lse, const void *dout, int dtype,
@@ -533,7 +502,6 @@ GFN_EXPORT int gfn_cross_attn_bwd(const void *q, const void *k, const void *v, c
         return GFN_OK;
     }
     if (!lse || ((uintptr_t)lse & 3)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: lse missing or not 4-byte aligned", what);
-    if (dtype == GFN_BF16) return launch_bwd<__bf16>(q, k, v, lse, dout, dq, dk, dv, B, Nq, Nk, H, scale, s);
-    return dtype == GFN_F16 ? launch_bwd<_Float16>(q, k, v, lse, dout, dq, dk, dv, B, Nq, Nk, H, scale, s)
-                            : launch_bwd<float>(q, k, v, lse, dout, dq, dk, dv, B, Nq, Nk, H, scale, s);
+    if (dtype == GFN_F32) return launch_bwd<float>(q, k, v, lse, dout, dq, dk, dv, B, Nq, Nk, H, scale, s);
+    return with_elem16(dtype, [&](auto e) { return launch_bwd<decltype(e)>(q, k, v, lse, dout, dq, dk, dv, B, Nq, Nk, H, scale, s); });
 }

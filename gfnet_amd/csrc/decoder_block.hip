@@ -13,15 +13,15 @@
 // does not depend on where it sits in a tile or which tile it is in.  The second half of the file is the backward of both launches,
 // for training in the same class (the forward kernels are the training forward as they are).
 #include <climits>
+#include <cmath>
 #include <initializer_list>
 
-#include "attn_common.h"
+#include "elem16.h"
+#include "reduce.h"
 
 namespace {
 
-using gfn::acc_row;
-using gfn::f32x16;
-using namespace gfn::attn;
+using namespace gfn;
 
 constexpr int kC = 64, kHidden = 256;
 constexpr int kQkvThreads = 256, kPostThreads = 512;
@@ -30,12 +30,12 @@ constexpr int kQkvThreads = 256, kPostThreads = 512;
 constexpr int kPitchC = kC + 4, kPitchH = kHidden + 4;
 
 // The element E of a class, _Float16 (the fp16 autocast class) or __bf16 (the bf16 one), is a template parameter of everything below
-// that touches an operand or a 16-bit tensor; what it brings with it (attn_common.h): V4<E>, four elements as one register pair (an
+// that touches an operand or a 16-bit tensor; what it brings with it (elem16.h): V4<E>, four elements as one register pair (an
 // operand fragment, an 8-byte access); (E)float, the rounding to nearest even (v_cvt_f16_f32 / v_cvt_pk_bf16_f32; no clamp, NaN
 // kept); and mfma8, v_mfma_f32_32x32x8_f16 / v_mfma_f32_32x32x8_bf16.  Both elements are 2 bytes, so LDS pitches, bank patterns and
 // the workspace are one set of numbers.  "half" below is a 2-byte element, "fp16(x)" in a formula is (E)x.
 template <typename E>
-using V4 = typename Vec4<E>::type;
+using V4 = typename Elem16<E>::vec4;
 
 // rows * cols fp32 values as stored -> E rows of `pitch` halves in LDS (cols a multiple of 4, src 16-byte aligned)
 template <typename E>
@@ -510,12 +510,6 @@ __device__ __forceinline__ void tile_operand(const E *T, int pitch, int n0, int 
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) b[s] = *reinterpret_cast<const V4<E> *>(row + 8 * s);
 }
-// sum over the 32 tokens of a lane half; both partners of every exchange form the same sum, so all 32 lanes end with the same bits
-__device__ __forceinline__ float sum_tokens(float v) {
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 // acc[r] is element (m0 + acc_row(r, h), n0 + lane & 31) of a row-major matrix with `ld` columns
 __device__ __forceinline__ void store_block(float *M, int ld, int m0, int n0, const f32x16 &acc, int lane) {
 #pragma unroll
@@ -623,7 +617,7 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_data_kernel(
     // this workgroup's partial: tokens of a wave first, then the waves in order
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
-        const float sw = sum_tokens(acc_w.v[i]), sb = sum_tokens(acc_b.v[i]), t2 = sum_tokens(s2.v[i]), t1 = sum_tokens(s1.v[i]);
+        const float sw = half_wave_sum(acc_w.v[i]), sb = half_wave_sum(acc_b.v[i]), t2 = half_wave_sum(s2.v[i]), t1 = half_wave_sum(s1.v[i]);
         if ((lane & 31) == 0) {
             const int c = 8 * (i >> 2) + 4 * h + (i & 3);
             red[wave][c] = sw, red[wave][kC + c] = sb, red[wave][2 * kC + c] = t2, red[wave][3 * kC + c] = t1;
@@ -746,7 +740,7 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_post_bwd_weight_kernel(
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const float s = sum_tokens(gb1[cc][i]);
+            const float s = half_wave_sum(gb1[cc][i]);
             if ((lane & 31) == 0) P[kOffB1 + c0 + 8 * (i >> 2) + 4 * h + (i & 3)] = s;
         }
     }
@@ -900,7 +894,7 @@ __global__ __launch_bounds__(kBwdThreads) void decoder_qkv_bwd_kernel(const floa
     for (int p = 0; p < 3; ++p) store_block(P + p * kC * kC, kC, m0, n0, gw[p], lane);
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
-        const float sw = sum_tokens(acc_w.v[i]), sb = sum_tokens(acc_b.v[i]);
+        const float sw = half_wave_sum(acc_w.v[i]), sb = half_wave_sum(acc_b.v[i]);
         if ((lane & 31) == 0) {
             const int c = 8 * (i >> 2) + 4 * h + (i & 3);
             red[wave][c] = sw, red[wave][kC + c] = sb;

@@ -27,6 +27,7 @@
 // hypothesis are bit-identical to the oracle.
 #include "common.h"
 #include "ge_solve8.h"
+#include "reduce.h"
 
 namespace {
 
@@ -227,9 +228,7 @@ __global__ __launch_bounds__(256) void score_kernel(const float *__restrict__ pt
     }
 #pragma unroll
     for (int h = 0; h < kHypPerWave; ++h) {
-        int s = valid[h] ? c[h] : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        const int s = gfn::wave_sum(valid[h] ? c[h] : 0);
         if (lane == 0 && t0 + h < T) counts[(size_t)b * T + t0 + h] = s;
     }
 }
@@ -311,8 +310,7 @@ __global__ __launch_bounds__(kHeadThreads) void ransac_head_kernel(const float *
         const bool valid = H[8] == 1.0;  // NaN marks an invalid hypothesis
         int c = 0;
         for (int n = lane; n < N; n += 64) c += is_inlier(H, p[n], thr2) ? 1 : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+        c = gfn::wave_sum(c);
         if (lane == 0) sCnt[wave] = valid ? c : 0;
     }
     __syncthreads();
@@ -612,8 +610,7 @@ __global__ __launch_bounds__(kFinThreads) void finish_kernel(FinParams P) {
             if (mask) mask[n] = in ? 1 : 0;
             c += in ? 1 : 0;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+        c = gfn::wave_sum(c);
         if (lane == 0) sh.cnt[wave] = c;
         __syncthreads();
         if (tid == 0) {

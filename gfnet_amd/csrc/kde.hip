@@ -12,13 +12,15 @@
 // matrix product); fp32 accumulation.  When N is too small to fill the chip the M range is split
 // over blockIdx.y and the partial sums are reduced by a second tiny kernel (deterministic, no
 // float atomics).
-#include "corr_common.h"  // split3, bf16x8; with it common.h: f32x16, acc_row
+#include "corr_common.h"  // split3; with it elem16.h, reduce.h and common.h: f32x16, acc_row
 #include <cstdlib>
 
 namespace {
 
+using gfn::f32x2;
+using gfn::other_half;
+
 constexpr int kKdeThreads = 256;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // Pre-pass (D = 4): scale the coordinates once and lay the reference points out as pairs,
 // ys[bt][m/2][d][2], so that the main loop reads (a_d, c_d) of two points as one SGPR pair and
@@ -263,8 +265,8 @@ __global__ __launch_bounds__(256) void kde4_bbox_kernel(const float *__restrict_
     }
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
-        lo[d] = fminf(lo[d], __shfl_xor(lo[d], 32));
-        hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], 32));
+        lo[d] = fminf(lo[d], other_half(lo[d]));
+        hi[d] = fmaxf(hi[d], other_half(hi[d]));
     }
     if (lane < 4) box[wid * 8 + lane] = lo[lane];
     else if (lane < 8) box[wid * 8 + lane] = hi[lane - 4];
@@ -493,8 +495,8 @@ __global__ __launch_bounds__(kKdeThreads, 4) void kde4_mfma_kernel(const float *
             if (SYM && cur != qblk) {  // wave-uniform
                 // rows 4kh.. of both row tiles are in this lane, the other half of the rows in lane ^ 32
                 float s0 = cs0, s1 = cs1;
-                s0 += __shfl_xor(s0, 32);
-                s1 += __shfl_xor(s1, 32);
+                s0 += other_half(s0);
+                s1 += other_half(s1);
                 const float sv = kh ? s1 : s0;  // lanes 0-31: column tile 0, lanes 32-63: column tile 1
                 const int pt = cur * 64 + lane;
                 if (pt < N) atomicAdd(cacc + pt, (unsigned long long)(sv * kKdeFixScale));

@@ -7,30 +7,25 @@
 #include <climits>
 #include <cmath>
 
-#include "common.h"
+#include "elem16.h"
+#include "reduce.h"
 
 namespace {
 
+using gfn::Elem16;
+using gfn::wave_sum;
+
 constexpr int kThreads = 256, kRowsPerBlock = kThreads / 64;
 constexpr int kMaxC = 8192;
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
 
 // 8 consecutive values of a row, widened
 struct V8 {
     float e[8];
 };
 
-__device__ __forceinline__ V8 load8(const _Float16 *p) {
-    const h8 v = *reinterpret_cast<const h8 *>(p);
-    V8 r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r.e[j] = (float)v[j];
-    return r;
-}
-__device__ __forceinline__ V8 load8(const __bf16 *p) {
-    const b8 v = *reinterpret_cast<const b8 *>(p);
+template <typename T>
+__device__ __forceinline__ V8 load8(const T *p) {
+    const auto v = *reinterpret_cast<const typename Elem16<T>::vec8 *>(p);
     V8 r;
 #pragma unroll
     for (int j = 0; j < 8; ++j) r.e[j] = (float)v[j];
@@ -40,17 +35,12 @@ __device__ __forceinline__ V8 load8(const float *p) {
     const float4 a = reinterpret_cast<const float4 *>(p)[0], b = reinterpret_cast<const float4 *>(p)[1];
     return {{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
 }
-__device__ __forceinline__ void store8(_Float16 *p, const V8 &r) {
-    h8 v;
+template <typename T>
+__device__ __forceinline__ void store8(T *p, const V8 &r) {
+    typename Elem16<T>::vec8 v;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (_Float16)r.e[j];
-    *reinterpret_cast<h8 *>(p) = v;
-}
-__device__ __forceinline__ void store8(__bf16 *p, const V8 &r) {
-    b8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (__bf16)r.e[j];  // to nearest even
-    *reinterpret_cast<b8 *>(p) = v;
+    for (int j = 0; j < 8; ++j) v[j] = (T)r.e[j];  // to nearest even
+    *reinterpret_cast<typename Elem16<T>::vec8 *>(p) = v;
 }
 __device__ __forceinline__ void store8(float *p, const V8 &r) {
     reinterpret_cast<float4 *>(p)[0] = make_float4(r.e[0], r.e[1], r.e[2], r.e[3]);
@@ -58,15 +48,9 @@ __device__ __forceinline__ void store8(float *p, const V8 &r) {
 }
 
 // what the stream holds after a store: the value rounded to its storage type
-__device__ __forceinline__ float as_stored(float v, const _Float16 *) { return (float)(_Float16)v; }
-__device__ __forceinline__ float as_stored(float v, const __bf16 *) { return (float)(__bf16)v; }
+template <typename T>
+__device__ __forceinline__ float as_stored(float v, const T *) { return Elem16<T>::round(v); }
 __device__ __forceinline__ float as_stored(float v, const float *) { return v; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);  // a butterfly: every lane ends with the same bits
-    return v;
-}
 
 // VPL: 8-value vectors per lane; lane i holds vectors i, i + 64, ... of the row (those below C / 8)
 template <typename T, int VPL>

@@ -1,7 +1,7 @@
 // local_corr_common.h -- what every local-correlation kernel shares: the launch constants, the kernel argument block (LcParams)
 // with its host-side checks and filler, and the device helpers of the per-tap routine, the cell coordinates and the wave reductions.
 #pragma once
-#include "common.h"
+#include "elem16.h"
 #include "sample_modes.h"
 
 struct LcParams {

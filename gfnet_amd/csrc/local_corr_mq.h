@@ -257,18 +257,18 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_mq_kernel(LcParams p) 
         const bool more = ch + 1 < NCH;
         const unsigned next_off = (unsigned)(ch + 1) * chunk_off;
         if (more) mm_issue<true, FT, true>(pre, f1r, next_off, H, W, u, ipw, ml);  // next chunk's loads: in flight across the products
-        const bf16x8_t b1 = *reinterpret_cast<const bf16x8_t *>(f0b + b_addr + ch * 64);
-        const bf16x8_t b2 = *reinterpret_cast<const bf16x8_t *>(f0b + b_addr + ch * 64 + 32);
+        const bf16x8 b1 = *reinterpret_cast<const bf16x8 *>(f0b + b_addr + ch * 64);
+        const bf16x8 b2 = *reinterpret_cast<const bf16x8 *>(f0b + b_addr + ch * 64 + 32);
         unsigned slot_c = slot0;
         asm volatile("" : "+v"(slot_c));   // operand addresses re-derived per chunk: kept across the chunks they cost NBW registers
         auto a_op = [&](int i) {
             const unsigned s = slot_c + (unsigned)i * sstep;
-            return *reinterpret_cast<const bf16x8_t *>(smem + s * (unsigned)M::SLOT + (((unsigned)mq ^ mm_swz<16>(s)) << 4));
+            return *reinterpret_cast<const bf16x8 *>(smem + s * (unsigned)M::SLOT + (((unsigned)mq ^ mm_swz<16>(s)) << 4));
         };
 #pragma unroll
         for (int i0 = 0; i0 < NBW; i0 += 2) {
             if (i0 < nb) {  // scalar.  A row past the group's box repeats its last row into values nobody files
-                bf16x8_t a[2];
+                bf16x8 a[2];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) a[j] = a_op(min(i0 + j, nb - 1));
 #pragma unroll

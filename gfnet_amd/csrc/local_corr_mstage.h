@@ -19,17 +19,14 @@
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+using gfn::bf16x2, gfn::bf16x8, gfn::f32x2, gfn::u32x2;
 
 // (a, b) -> packed bf16 pairs (hi, lo) with a = hi.x + lo.x + O(2^-18 a)
 __device__ __forceinline__ void split_pair(float a, float b, unsigned &hi, unsigned &lo) {
-    const f32x2_t v = {a, b};
-    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-    const f32x2_t h = {__builtin_bit_cast(float, hi << 16), __builtin_bit_cast(float, hi & 0xffff0000u)};
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(v - h, bf16x2_t));
+    const f32x2 v = {a, b};
+    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+    const f32x2 h = {__builtin_bit_cast(float, hi << 16), __builtin_bit_cast(float, hi & 0xffff0000u)};
+    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(v - h, bf16x2));
 }
 
 // swizzle of a slot's 16-byte pieces: piece p of slot s lives at physical piece p ^ mm_swz<KC>(s).  KC = 32 (8 pieces, slot stride
@@ -120,7 +117,7 @@ __device__ __forceinline__ void mm_issue(MmRegs<FT> &r, rsrc_t f1r, unsigned pas
 // one item's 4 pixels x 4 channels -> bf16 hi / lo pieces
 template <typename M, bool CHECK, typename FT>
 __device__ __forceinline__ void mm_commit_one(unsigned char *stage, const typename QuadRaw<FT>::type (&a)[4], unsigned meta) {
-    u32x2_t *s8 = reinterpret_cast<u32x2_t *>(stage);
+    u32x2 *s8 = reinterpret_cast<u32x2 *>(stage);
     const unsigned a01 = meta & 0x3FFFFu;                         // hi piece half of pixels 0-1, in units of 8 bytes
     const unsigned a23 = M::KC == 32 ? a01 ^ 2u : a01;            // pixels 2-3: slot + 2 flips bit 0 of the KC = 32 swizzle
     constexpr unsigned LO = M::NPIECE;                            // lo piece = hi piece ^ (NPIECE / 2) = ^ NPIECE units of 8 bytes
@@ -135,8 +132,8 @@ __device__ __forceinline__ void mm_commit_one(unsigned char *stage, const typena
         split_pair(in ? w0[k] : 0.f, in ? w1[k] : 0.f, h01, l01);
         split_pair(in ? w2[k] : 0.f, in ? w3[k] : 0.f, h23, l23);
         const unsigned hi8 = (k < 2 ? a01 : a23) + (unsigned)k * SL;  // k * SL leaves the piece bits alone
-        s8[hi8] = u32x2_t{h01, h23};
-        s8[hi8 ^ LO] = u32x2_t{l01, l23};
+        s8[hi8] = u32x2{h01, h23};
+        s8[hi8 ^ LO] = u32x2{l01, l23};
     }
 }
 

@@ -15,7 +15,7 @@ struct RowPlan {  // block-uniform (scalars)
 
 // ---- buffer addressing --------------------------------------------------------------------------------------------
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using gfn::f16x4, gfn::f32x4;
 __device__ __forceinline__ rsrc_t make_rsrc(const void *base, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);  // raw buffer, 32-bit data format
 }
@@ -25,7 +25,6 @@ __device__ __forceinline__ float buf_ld(rsrc_t r, unsigned voff, unsigned soff) 
 __device__ __forceinline__ f32x4 buf_ld4(rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
 }
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f16x4 buf_ld_h4(rsrc_t r, unsigned voff, unsigned soff) {
     // the builtin's result is bit-cast as a whole: picking the two dwords apart (.x / .y of a 2-vector) made hipcc 7.2 narrow the
     // load to one dword and reuse it for both halves

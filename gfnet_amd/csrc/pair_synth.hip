@@ -9,16 +9,16 @@
 //   warp_perspective_kernel : crop + warp + centre crop are one projective map from output pixels to source pixels, so an image is
 //                             gathered once, straight from its source, with the Normalize fused; the intermediates are never made
 // -ffp-contract=off: the fp32 blend rounds in the order written, so a float64 restatement of it is unambiguous.
-#include "common.h"
+#include "elem16.h"
 #include "ge_solve8.h"
 
 namespace {
 
+using gfn::f32x4;
 using gfn::ge_solve8;
 using gfn::lane_get;
 
 #define GFN_GLOBAL __attribute__((address_space(1)))
-typedef float vf4 __attribute__((ext_vector_type(4)));
 
 // inverse of a 3 x 3 matrix as adjugate / determinant: exact for the identity and for integer translations (every product is exact
 // and the determinant is 1).  A singular matrix gives non-finite entries, which the warp reads as "outside".
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void warp_perspective_kernel(const float *cons
         }
         GFN_GLOBAL float *oc = op + (long)c * Ho * Wo;
         if (VEC) {
-            *reinterpret_cast<GFN_GLOBAL vf4 *>(oc) = vf4{r[0], r[1], r[2], r[3]};
+            *reinterpret_cast<GFN_GLOBAL f32x4 *>(oc) = f32x4{r[0], r[1], r[2], r[3]};
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j)

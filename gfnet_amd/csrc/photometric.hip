@@ -16,6 +16,7 @@
 // region, whose outer ring a pass may spoil by r + 1 pixels: three passes per axis spoil exactly the halo).
 // -ffp-contract=off: the float blends and the HSV conversions round in the order written, which is Pillow's.
 #include "common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -215,8 +216,7 @@ __global__ __launch_bounds__(256) void photo_stats_kernel(const u8 *const *__res
             sum += (unsigned)grey_l(r, g, b);
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+    sum = gfn::wave_sum(sum);
     if ((threadIdx.x & 63) == 0) atomicAdd(sums + img, (unsigned long long)sum);  // integer: the total does not depend on the order
 }
 

@@ -25,10 +25,13 @@
 #include <algorithm>
 
 #include "common.h"
+#include "reduce.h"
 #include "refiner_input.h"
 #include "sample_modes.h"
 
 namespace {
+
+using gfn::wave_sum;
 
 constexpr int kEmbChunk = 16;  // displacement-embedding channels reduced per barrier pair
 constexpr int kDxChannels = 8; // channels per thread of the dx gather
@@ -56,12 +59,6 @@ __device__ __forceinline__ int det_shift(unsigned maxbits, int lgg) {
 }
 // 2^k as a double, k within [-1022, 1023] (det_shift gives [-128, 210] and its negation)
 __device__ __forceinline__ double det_pow2(int k) { return __longlong_as_double((long long)(1023 + k) << 52); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
 
 template <typename FT, bool DET>
 __global__ __launch_bounds__(256) void refiner_input_bwd_cell_kernel(RibArgs q) {

@@ -15,8 +15,11 @@
 #include <cmath>
 
 #include "common.h"
+#include "reduce.h"
 
 namespace {
+
+using gfn::wave_sum_lane0;
 
 constexpr int kMaxItr = GFN_RL_MAX_ITR;
 constexpr int kThreads = 256;
@@ -117,12 +120,6 @@ __device__ __forceinline__ void group_cell(unsigned gi, int h, int w, int &b, in
     fo = ((size_t)b * 2 * h + y) * w + x0;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 template <int VEC>
 __global__ __launch_bounds__(kThreads) void rl_fwd_kernel(ItrMaps it, Warp g, float *__restrict__ epe_last, float *__restrict__ part,
                                                           int n_itr, unsigned groups, float a_half, float cs, float cs_pow_a, float pck_thr) {
@@ -168,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void rl_fwd_kernel(ItrMaps it, Warp g, fl
             }
         }
     }
-    float q[kQuant] = {wave_sum(s_ce), wave_sum(s_rho), wave_sum(s_cnt), wave_sum(s_pck)};
+    float q[kQuant] = {wave_sum_lane0(s_ce), wave_sum_lane0(s_rho), wave_sum_lane0(s_cnt), wave_sum_lane0(s_pck)};
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
 #pragma unroll

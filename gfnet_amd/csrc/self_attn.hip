@@ -17,8 +17,7 @@
 
 namespace {
 
-using gfn::acc_row;
-using gfn::f32x16;
+using namespace gfn;
 using namespace gfn::attn;
 
 constexpr int kD = 64;         // head dim: four k-steps of v_mfma_f32_32x32x16_{f16,bf16} per score tile
@@ -32,8 +31,8 @@ constexpr int kKPitch = 72, kVPitch = 68;
 
 // the 16-byte piece of a staged chunk that piece index p (0..511) names: key p >> 3 of the chunk, values 8 (p & 7) ...
 template <typename T>
-__device__ __forceinline__ typename Vec8<T>::type load_piece(const T *__restrict__ base, int64_t token_stride, int key0, int N, int p) {
-    using t8 = typename Vec8<T>::type;
+__device__ __forceinline__ typename Elem16<T>::vec8 load_piece(const T *__restrict__ base, int64_t token_stride, int key0, int N, int p) {
+    using t8 = typename Elem16<T>::vec8;
     const int key = key0 + (p >> 3);
     t8 z = {};
     return key < N ? *reinterpret_cast<const t8 *>(base + key * token_stride + 8 * (p & 7)) : z;  // a key past N is staged as zeros
@@ -42,8 +41,8 @@ __device__ __forceinline__ typename Vec8<T>::type load_piece(const T *__restrict
 template <typename T>
 __global__ __launch_bounds__(kThreads) void self_attn_fwd_kernel(const T *__restrict__ qkv, T *__restrict__ out, int N, int H, int nqb,
                                                                  float scale) {
-    using t4 = typename Vec4<T>::type;
-    using t8 = typename Vec8<T>::type;
+    using t4 = typename Elem16<T>::vec4;
+    using t8 = typename Elem16<T>::vec8;
     __shared__ alignas(16) T ks[kChunk * kKPitch];  // K rows as stored: the A operand of S^T = K Q^T
     __shared__ alignas(16) T vt[kD * kVPitch];      // V transposed, [d][key]: the A operand of O^T = V^T P^T
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c = lane & 31;
@@ -182,9 +181,8 @@ GFN_EXPORT int gfn_self_attn_fwd(const void *qkv, int dtype, int B, int N, int H
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: B * H * ceil(N / %d) is the grid, at most 2^31 - 1 (B=%d N=%d H=%d)", what, kOwn, B, N, H);
     if (!qkv || !out) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: null pointer (%s)", what, !qkv ? "qkv" : "out");
     if (((uintptr_t)qkv | (uintptr_t)out) & 15) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: qkv and out must be 16-byte aligned (rows are read as vectors)", what);
-    if (dtype == GFN_BF16)
-        launch<__bf16>(qkv, out, B, N, H, nqb, scale, (hipStream_t)stream);
-    else
-        launch<_Float16>(qkv, out, B, N, H, nqb, scale, (hipStream_t)stream);
-    return gfn::check_launch("self_attn_fwd_kernel");
+    return with_elem16(dtype, [&](auto e) {
+        launch<decltype(e)>(qkv, out, B, N, H, nqb, scale, (hipStream_t)stream);
+        return gfn::check_launch("self_attn_fwd_kernel");
+    });
 }

@@ -25,9 +25,13 @@
 // No atomics: identical calls give identical bits.
 #include <cmath>
 
-#include "common.h"
+#include "elem16.h"
+#include "reduce.h"
 
 namespace {
+
+using gfn::f32x4;
+using gfn::wave_sum_lane0;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -73,21 +77,14 @@ struct Coef {           // per tensor, fp32 as torch's kernels receive them
 
 __device__ __forceinline__ bool nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // GradScaler.unscale_ multiplies by scale.double().reciprocal().float()
 __device__ __forceinline__ float inverse_scale(float scale) { return (float)(1.0 / (double)scale); }
 
 #define GFN_GLOBAL __attribute__((address_space(1)))
-typedef float vf4 __attribute__((ext_vector_type(4)));
 typedef GFN_GLOBAL float *gptr;
 typedef const GFN_GLOBAL float *cgptr;
-typedef GFN_GLOBAL vf4 *gptr4;
-typedef const GFN_GLOBAL vf4 *cgptr4;
+typedef GFN_GLOBAL f32x4 *gptr4;
+typedef const GFN_GLOBAL f32x4 *cgptr4;
 
 // per-lane accumulators of the norm pass
 struct NormAcc {
@@ -100,13 +97,13 @@ struct NormAcc {
         sg = fma(gu, gu, sg);
         sp = fma(pd, pd, sp);
     }
-    __device__ __forceinline__ void add4(vf4 gv, vf4 pv) { add(gv.x, pv.x), add(gv.y, pv.y), add(gv.z, pv.z), add(gv.w, pv.w); }
+    __device__ __forceinline__ void add4(f32x4 gv, f32x4 pv) { add(gv.x, pv.x), add(gv.y, pv.y), add(gv.z, pv.z), add(gv.w, pv.w); }
 };
 
 // N unconditional loads per array, all issued before the first use
 template <int N>
 __device__ __forceinline__ void norm_vec_round(NormAcc &a, cgptr4 g4, cgptr4 p4, int i) {
-    vf4 gv[N], pv[N];
+    f32x4 gv[N], pv[N];
 #pragma unroll
     for (int k = 0; k < N; ++k) gv[k] = g4[i + k * kThreads], pv[k] = p4[i + k * kThreads];
 #pragma unroll
@@ -149,7 +146,7 @@ __global__ __launch_bounds__(kThreads) void ts_norm_kernel(const TensorRec *__re
         for (; base + kScalarBatch * kThreads <= count; base += kScalarBatch * kThreads) norm_scalar_round<kScalarBatch>(a, g, p, base + tid);
         for (int i = base + tid; i < count; i += kThreads) a.add(g[i], p[i]);
     }
-    const double sg = wave_sum(a.sg), sp = wave_sum(a.sp);
+    const double sg = wave_sum_lane0(a.sg), sp = wave_sum_lane0(a.sp);
     const bool wave_bad = __ballot(a.bad) != 0ull;
     const int lane = tid & 63, wave = tid >> 6;
     if (lane == 0) red[wave][0] = sg, red[wave][1] = sp, red_bad[wave] = wave_bad;
@@ -257,7 +254,7 @@ struct Adam {
         const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;      // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
         p = p + c.neg_step * m / denom;                         // param.addcdiv_(exp_avg, denom, value=-step_size)
     }
-    __device__ __forceinline__ void four(vf4 g, vf4 &p, vf4 &m, vf4 &v) const {
+    __device__ __forceinline__ void four(f32x4 g, f32x4 &p, f32x4 &m, f32x4 &v) const {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float pe = p[e], me = m[e], ve = v[e];
@@ -270,7 +267,7 @@ struct Adam {
 // N vectors per array and thread: every load unconditional and issued before the first use, then the stores
 template <int N>
 __device__ __forceinline__ void update_vec_round(const Adam &a, gptr4 g4, gptr4 p4, gptr4 m4, gptr4 v4, int i, int zero_grads) {
-    vf4 g[N], p[N], m[N], v[N];
+    f32x4 g[N], p[N], m[N], v[N];
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         const int j = i + k * kThreads;
@@ -282,7 +279,7 @@ __device__ __forceinline__ void update_vec_round(const Adam &a, gptr4 g4, gptr4 
     for (int k = 0; k < N; ++k) {
         const int j = i + k * kThreads;
         p4[j] = p[k], m4[j] = m[k], v4[j] = v[k];
-        if (zero_grads) g4[j] = (vf4)(0.f);
+        if (zero_grads) g4[j] = (f32x4)(0.f);
     }
 }
 
@@ -315,7 +312,7 @@ __global__ __launch_bounds__(kThreads) void ts_update_kernel(const TensorRec *__
     const int nv = t.vec16 ? count >> 2 : 0;
     const gptr4 g4 = (gptr4)g;
     if (skip) {             // only the gradients change: zero_grad
-        for (int i = tid; i < nv; i += kThreads) g4[i] = (vf4)(0.f);
+        for (int i = tid; i < nv; i += kThreads) g4[i] = (f32x4)(0.f);
         for (int i = nv * 4 + tid; i < count; i += kThreads) g[i] = 0.f;
         return;
     }
