@@ -92,7 +92,8 @@ class StandInRefiner(nn.Module):
     stack (network.py:560-563): like a trained refiner it returns the increment that moves the flow onto the
     true warp plus sub-pixel noise (N(0, (0.5/S)^2), a fresh seeded realisation per refiner iteration) and a
     constant certainty increment.  One torch elementwise op; everything else is the real path.  With
-    --conv-stack the reference's conv stack runs too (random-init, its output weighted 0)."""
+    --conv-stack the reference's conv stack runs too (random-init, its output weighted 0): conv_stack is "off" or a
+    ConvRefiner.conv_precision -- "fp32", "fp16", "amp" or "bf16"."""
 
     def __init__(self, feat, disp, radius, scale, targets, num_itr, conv_stack="off"):
         super().__init__()

@@ -1,5 +1,5 @@
 // conv_block_fused.h -- the fused conv block (depthwise 5x5 + BatchNorm + ReLU + 1x1 conv in one kernel) of csrc/conv_stack.hip
-// and csrc/conv_stack_half.hip (the same kernel on fp16 maps).  Opens its own anonymous namespace.
+// and csrc/conv_stack_half.hip / csrc/conv_stack_bf16.hip (the same kernel on fp16 / bf16 maps).  Opens its own anonymous namespace.
 #pragma once
 #include "elem16.h"
 #include "pw_gemm_tile.h"  // kKT, kBN, f32x16
@@ -18,6 +18,8 @@ __host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m *
 // [ cp: Kp/2 x 64 ][ wt: Kp x Mp weights, zero padded, in MFMA operand order ][ bias: Mp ],  Kp = ceil16(C), Mp = ceil32(M)
 // wt: W[m][k] sits at wt_index(k, m): per K tile of 16 the order is [k half sg][k parity kh][m][j], k = 16*kt + 8*sg + 2*j + kh,
 // so that one 16-byte LDS read hands a lane its A operands of four consecutive MFMA k-steps.
+// The two 16-bit sections below (wt16, mm) hold fp16 values from gfn_conv_block_pack and bf16 values from gfn_conv_block_pack_bf16,
+// same places and sizes: a block is packed for the class whose entry point it is handed to.
 // cp row of channel pair (2p, 2p+1): float 2t+h = parameter t of channel 2p+h; t = 0..24 the 5x5 taps
 // (row major), 25 = conv bias, 26 = alpha, 27 = beta -- the layout the packed-fp32 (v_pk_fma_f32)
 // depthwise loop reads as register pairs.
@@ -94,7 +96,10 @@ __device__ __forceinline__ f32x2 dw_finish2(f32x2 acc, f32x2 cb, f32x2 al, f32x2
 // through six short barrier-separated phases per K tile (3.2 k cycles, a third of it fixed latencies); 32 channels per
 // iteration halve the barriers and the waits.  A block whose channel count leaves a single K tile for the last iteration
 // reads zeros for the missing one (descriptor range checks on the map, the weights and the parameters).
-template <int MT, int TW, int NS, bool F16, int NB, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1>
+//
+// E: the 16-bit element of the class (elem16.h), wherever the text above says fp16: _Float16, or __bf16 for the bf16 maps of
+// csrc/conv_stack_bf16.hip -- the same kernel on v_mfma_f32_16x16x32_bf16 / v_mfma_f32_32x32x16_bf16, every rounding a float -> bf16 one.
+template <int MT, int TW, int NS, bool F16, int NB, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1, typename E = _Float16>
 // (a fourth workgroup per CU for the narrowest blocks -- 128 VGPRs, 32 KB of LDS -- measured slower: 146/265 vs 143/218 us at
 // C = 24, 256^2 / 320^2 maps; the memory system, not the CU, is what these blocks wait for)
 __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(const float *__restrict__ x,
@@ -102,6 +107,9 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
                                                                                float *__restrict__ y, int M, int K, int G,
                                                                                int tiles_x, int tiles_y, int ngrp, unsigned nwork,
                                                                                int tpb) {
+    typedef typename gfn::Elem16<E>::vec2 e16x2;
+    typedef typename gfn::Elem16<E>::vec4 e16x4;
+    typedef typename gfn::Elem16<E>::vec8 e16x8;
     static_assert(F16 || !(HIN || HOUT), "fp16 maps go with fp16 1x1 operands");
     static_assert(!MM || F16, "the matrix-core depthwise takes fp16 operands");
     static_assert(KW == 1 || (KW == 2 && MM && F16), "two K tiles per iteration: matrix-core depthwise only");
@@ -263,8 +271,8 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
                     if constexpr (HIN) {
                         v = f32x4{xr0[i].x, xr0[i].y, xr0[i].z, xr0[i].w};
                     } else {  // the fp32 concat: round to fp16 here (what autocast does to the first conv's input)
-                        const f16x8 h = {(_Float16)xr0[i].x, (_Float16)xr1[i].x, (_Float16)xr0[i].y, (_Float16)xr1[i].y,
-                                         (_Float16)xr0[i].z, (_Float16)xr1[i].z, (_Float16)xr0[i].w, (_Float16)xr1[i].w};
+                        const e16x8 h = {(E)xr0[i].x, (E)xr1[i].x, (E)xr0[i].y, (E)xr1[i].y,
+                                         (E)xr0[i].z, (E)xr1[i].z, (E)xr0[i].w, (E)xr1[i].w};
                         v = __builtin_bit_cast(f32x4, h);
                     }
                     *reinterpret_cast<f32x4 *>(&Xs[xl[i]]) = v;
@@ -276,7 +284,7 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
             if (r_valid & (1 << i)) {
                 f32x4 lo, hi;
                 if constexpr (HIN) {
-                    const f16x8 h = __builtin_bit_cast(f16x8, xr0[i]);
+                    const e16x8 h = __builtin_bit_cast(e16x8, xr0[i]);
                     lo = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
                     hi = f32x4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
                 } else {
@@ -338,7 +346,7 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
             const int n = lane & 15, xo = n >> 1, ch = n & 1, kg = lane >> 4, mrow = lane & 15;
             const int ar = mrow % RS, ac = mrow / RS;  // A operand: this lane's row segment
             const float *xbase = &Xs[ar * PH + 8 * ac + 4 * kg];
-            _Float16 *bs16 = reinterpret_cast<_Float16 *>(Bs);
+            E *bs16 = reinterpret_cast<E *>(Bs);
             int tix[4];  // table entry of this lane's k pair i (cell 4kg + i of the window) for its output cell xo; 5 = zero
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -349,11 +357,11 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
             for (int pi = 0; pi < NPT / (4 * NS); ++pi) {
                 const int pr_ = wave + 4 * NS * pi;  // channel pair of the K tile
                 const float *tw = &Ps[pr_ * kMM2];
-                f16x8 T[5];
+                e16x8 T[5];
 #pragma unroll
                 for (int dy = 0; dy < 5; ++dy) {
                     const f32x4 t = {tw[tix[0] + 8 * dy], tw[tix[1] + 8 * dy], tw[tix[2] + 8 * dy], tw[tix[3] + 8 * dy]};
-                    T[dy] = __builtin_bit_cast(f16x8, t);
+                    T[dy] = __builtin_bit_cast(e16x8, t);
                 }
                 const float cb = tw[80 + ch], al = tw[82 + ch], be = tw[84 + ch];
 #pragma unroll
@@ -362,14 +370,14 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
                     const float *xs = xbase + pr_ * (HR * PH) + sub * RS * PH;
 #pragma unroll
                     for (int dy = 0; dy < 5; ++dy) {
-                        const f16x8 a = __builtin_bit_cast(f16x8, *reinterpret_cast<const f32x4 *>(xs + dy * PH));
-                        d = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, T[dy], d, 0, 0, 0);
+                        const e16x8 a = __builtin_bit_cast(e16x8, *reinterpret_cast<const f32x4 *>(xs + dy * PH));
+                        d = gfn::mfma32(a, T[dy], d);
                     }
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {  // D row 4kg + j = row segment (r, c); column n = (cell xo, channel ch)
                         const int m = 4 * kg + j, r = m % RS, c = m / RS;
                         const int cell = (sub * RS + r) * TW + 8 * c + xo;
-                        bs16[(pr_ * BN + cell) * 2 + ch] = (_Float16)dw_finish(d[j], cb, al, be);
+                        bs16[(pr_ * BN + cell) * 2 + ch] = (E)dw_finish(d[j], cb, al, be);
                     }
                 }
             }
@@ -412,11 +420,10 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
                 float *dst = dw_dst + ro * TW;
                 if constexpr (F16) {  // CPT cells x half2: one 16-byte (8-byte) write
                     if constexpr (CPT == 4) {
-                        const f16x8 h = {(_Float16)t[0].x, (_Float16)t[0].y, (_Float16)t[1].x, (_Float16)t[1].y,
-                                         (_Float16)t[2].x, (_Float16)t[2].y, (_Float16)t[3].x, (_Float16)t[3].y};
+                        const e16x8 h = {(E)t[0].x, (E)t[0].y, (E)t[1].x, (E)t[1].y, (E)t[2].x, (E)t[2].y, (E)t[3].x, (E)t[3].y};
                         *reinterpret_cast<f32x4 *>(dst) = __builtin_bit_cast(f32x4, h);
                     } else {
-                        const f16x4 h = {(_Float16)t[0].x, (_Float16)t[0].y, (_Float16)t[1].x, (_Float16)t[1].y};
+                        const e16x4 h = {(E)t[0].x, (E)t[0].y, (E)t[1].x, (E)t[1].y};
                         *reinterpret_cast<f32x2 *>(dst) = __builtin_bit_cast(f32x2, h);
                     }
                 } else if constexpr (CPT == 4) {
@@ -438,13 +445,13 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
                 for (int ks = 0; ks < KW; ++ks) {
                     const float *bp = &Bs[(8 * ks + 4 * kh) * BN + cell];
                     const f32x4 bq = {bp[0], bp[BN], bp[2 * BN], bp[3 * BN]};
-                    const f16x8 bv = __builtin_bit_cast(f16x8, bq);
-                    const f16x8 *asrc = reinterpret_cast<const f16x8 *>(&As4[buf][(ks * GP + kh) * BMS + slab * BM + col]);
-                    f16x8 avv[MT];
+                    const e16x8 bv = __builtin_bit_cast(e16x8, bq);
+                    const e16x8 *asrc = reinterpret_cast<const e16x8 *>(&As4[buf][(ks * GP + kh) * BMS + slab * BM + col]);
+                    e16x8 avv[MT];
 #pragma unroll
                     for (int i = 0; i < MT; ++i) avv[i] = asrc[i * 32];
 #pragma unroll
-                    for (int i = 0; i < MT; ++i) acc[g * MT + i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(avv[i], bv, acc[g * MT + i], 0, 0, 0);
+                    for (int i = 0; i < MT; ++i) acc[g * MT + i] = gfn::mfma16(avv[i], bv, acc[g * MT + i]);
                 }
             } else {
                 // B operands of all 8 k-steps and the A operands of k-steps 0..3 are fetched up front; each row
@@ -503,8 +510,8 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int m = mb + 8 * q + 4 * kh;
-                    const f16x2 h0 = {(_Float16)(acc[g * MT + i][4 * q] + bq[q].x), (_Float16)(acc[g * MT + i][4 * q + 1] + bq[q].y)};
-                    const f16x2 h1 = {(_Float16)(acc[g * MT + i][4 * q + 2] + bq[q].z), (_Float16)(acc[g * MT + i][4 * q + 3] + bq[q].w)};
+                    const e16x2 h0 = {(E)(acc[g * MT + i][4 * q] + bq[q].x), (E)(acc[g * MT + i][4 * q + 1] + bq[q].y)};
+                    const e16x2 h1 = {(E)(acc[g * MT + i][4 * q + 2] + bq[q].z), (E)(acc[g * MT + i][4 * q + 3] + bq[q].w)};
                     // streaming stores where a wave's 32 lanes cover whole 64/128-byte lines: measured 5-12 % at C = 73 .. 417, a
                     // loss on the 8-cell-wide tiles (32-byte row segments) and at C = 24 (one slab: 149/246 vs 143/218 us)
                     if constexpr (TW >= 16 && MT >= 2) {
@@ -548,19 +555,19 @@ __global__ __launch_bounds__(256 * NS, NS == 1 ? 2 : 1) void dwpw_fused_kernel(c
 // ---- the launch decision, stated once ---------------------------------------------------------------
 // Which kernels a conv block call runs, over what grid: conv_route() works it out on the host from the entry point, its variant
 // or map dtypes and the shape -- no device, no pointers.  The launchers below and in conv_stack.hip / conv_stack_half.hip switch on
-// this struct and on nothing else, and gfn_conv_block_route (include/gfnet_hip.h, GFN_CBR_*) hands the same struct to the tests,
+// this struct (csrc/conv_stack_bf16.hip too) and on nothing else, and gfn_conv_block_route (include/gfnet_hip.h, GFN_CBR_*) hands the same struct to the tests,
 // so the query and the launch cannot drift apart.
 struct ConvRoute {
     int fused;               // 1: dwpw_fused_kernel; 0: the two-pass form, dw5x5_kernel -> t_scratch -> pw_gemm_kernel
     int TW, MT, NS, NB, KW;  // fused: the kernel's template parameters
-    int F16, HIN, HOUT, MM;  // fp16 1x1 operands; fp16 map in / out; matrix-core depthwise
+    int F16, HIN, HOUT, MM;  // 16-bit 1x1 operands; 16-bit map in / out (fp16 or bf16: the entry says which); matrix-core depthwise
     int ngrp, nwork, tpb;    // fused: slab groups of 32*MT*NS output channels, work items, items per workgroup
     int VEC, nblk, mt;       // two-pass: cells per depthwise thread; row blocks and row tiles of the GEMM
     int tiles_x, tiles_y;    // fused: cell tiles of TW x (128*NB/TW) cells per map
 };
 
 // GFN_OK and *r, or the refusal of the entry point (gfn::fail).  a, b: `variant` of gfn_conv_block_fwd (b unused), x_dtype and
-// y_dtype of gfn_conv_block_half_fwd.
+// y_dtype of gfn_conv_block_half_fwd (GFN_CBR_ENTRY_HALF) and of gfn_conv_block_bf16_fwd (GFN_CBR_ENTRY_BF16).
 inline int conv_route(int entry, int a, int b, int B, int C, int M, int G, ConvRoute *r) {
     *r = ConvRoute{};
     bool fused = true;
@@ -570,18 +577,24 @@ inline int conv_route(int entry, int a, int b, int B, int C, int M, int G, ConvR
         if (a < 0 || a > 3) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: variant must be 0..3 (got %d)", a);
         r->F16 = (a & 2) != 0;
         fused = !(a & 1) && (G & 3) == 0;
-    } else if (entry == GFN_CBR_ENTRY_HALF) {
-        if (B < 0 || C <= 0 || M <= 0 || G <= 0) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: bad argument");
-        if ((a != GFN_F32 && a != GFN_F16) || (b != GFN_F32 && b != GFN_F16))
-            return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: map dtypes must be GFN_F32 or GFN_F16");
+    } else if (entry == GFN_CBR_ENTRY_HALF || entry == GFN_CBR_ENTRY_BF16) {
+        // the two 16-bit map classes: one route for both (they share tile shapes on purpose), each with its own map dtype
+        const bool bf = entry == GFN_CBR_ENTRY_BF16;
+        const int d16 = bf ? GFN_BF16 : GFN_F16;
+        const char *who = bf ? "conv_block_bf16" : "conv_block_half";
+        if (B < 0 || C <= 0 || M <= 0 || G <= 0) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: bad argument", who);
+        if ((a != GFN_F32 && a != d16) || (b != GFN_F32 && b != d16))
+            return bf ? gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_bf16: map dtypes must be GFN_F32 or GFN_BF16 (fp16 maps are gfn_conv_block_half_fwd)")
+                      : gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: map dtypes must be GFN_F32 or GFN_F16");
         if (a == GFN_F32 && b == GFN_F32)
-            return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: fp32 in and out is gfn_conv_block_fwd (variant 2)");
-        if (G & 3) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: grid side must be a multiple of 4 (got %d)", G);
-        if ((long)C * G * G > 0x1fffffffL)
-            return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: a map (C*G*G elements) must stay below 2 GB");
-        r->F16 = r->MM = 1, r->HIN = a == GFN_F16, r->HOUT = b == GFN_F16;
+            return bf ? gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_bf16: fp32 in and out has no bf16 form (one of the maps must be GFN_BF16)")
+                      : gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_half: fp32 in and out is gfn_conv_block_fwd (variant 2)");
+        if (G & 3) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: grid side must be a multiple of 4 (got %d)", who, G);
+        if ((long)C * G * G > 0x1fffffffL) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: a map (C*G*G elements) must stay below 2 GB", who);
+        r->F16 = r->MM = 1, r->HIN = a == d16, r->HOUT = b == d16;
     } else {
-        return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_route: entry must be GFN_CBR_ENTRY_FWD or GFN_CBR_ENTRY_HALF (got %d)", entry);
+        return gfn::fail(GFN_ERR_INVALID_ARG,
+                         "conv_block_route: entry must be GFN_CBR_ENTRY_FWD, GFN_CBR_ENTRY_HALF or GFN_CBR_ENTRY_BF16 (got %d)", entry);
     }
     if (!fused) {
         if ((long)B * C > 0x7fffff || B > 65535) return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block: batch too large for the two-pass variant");
@@ -622,55 +635,55 @@ inline int no_fused_kernel(const ConvRoute &r) {
                      r.MT, r.NS, r.NB, r.KW, r.F16, r.HIN, r.HOUT, r.MM);
 }
 
-template <int MT, int TW, int NS, bool F16, int NB, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1>
+template <int MT, int TW, int NS, bool F16, int NB, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1, typename E = _Float16>
 int launch_fused_mt(const ConvRoute &r, const float *x, const float *packed, float *y, int M, int K, int G, hipStream_t s) {
     const unsigned grid = (unsigned)(((long)r.nwork + r.tpb - 1) / r.tpb);
-    hipLaunchKernelGGL((dwpw_fused_kernel<MT, TW, NS, F16, NB, HIN, HOUT, MM, KW>), dim3(grid), dim3(256 * NS), 0, s, x, packed, y, M, K, G,
+    hipLaunchKernelGGL((dwpw_fused_kernel<MT, TW, NS, F16, NB, HIN, HOUT, MM, KW, E>), dim3(grid), dim3(256 * NS), 0, s, x, packed, y, M, K, G,
                        r.tiles_x, r.tiles_y, r.ngrp, (unsigned)r.nwork, r.tpb);
     return gfn::check_launch("dwpw_fused_kernel");
 }
 
 // r.MT, r.NS and r.NB of one tile width and class.  KW applies from four row tiles on (conv_route sets it there only).
-template <int TW, bool F16, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1>
+template <int TW, bool F16, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1, typename E = _Float16>
 int launch_fused(const ConvRoute &r, const float *x, const float *packed, float *y, int M, int K, int G, hipStream_t s) {
     if (r.NB == 2) {
         if constexpr (F16 && TW >= 16) {
             switch (r.NS == 1 ? r.MT : 0) {
-                case 1: return launch_fused_mt<1, TW, 1, F16, 2, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
-                case 2: return launch_fused_mt<2, TW, 1, F16, 2, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
-                case 3: return launch_fused_mt<3, TW, 1, F16, 2, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
+                case 1: return launch_fused_mt<1, TW, 1, F16, 2, HIN, HOUT, MM, 1, E>(r, x, packed, y, M, K, G, s);
+                case 2: return launch_fused_mt<2, TW, 1, F16, 2, HIN, HOUT, MM, 1, E>(r, x, packed, y, M, K, G, s);
+                case 3: return launch_fused_mt<3, TW, 1, F16, 2, HIN, HOUT, MM, 1, E>(r, x, packed, y, M, K, G, s);
             }
         }
         return no_fused_kernel(r);
     }
     if (r.NS == 1) {
         switch (r.MT) {
-            case 1: return launch_fused_mt<1, TW, 1, F16, 1, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
-            case 2: return launch_fused_mt<2, TW, 1, F16, 1, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
-            case 3: return launch_fused_mt<3, TW, 1, F16, 1, HIN, HOUT, MM>(r, x, packed, y, M, K, G, s);
-            case 4: return launch_fused_mt<4, TW, 1, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
-            case 5: return launch_fused_mt<5, TW, 1, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
-            case 6: return launch_fused_mt<6, TW, 1, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
-            case 7: return launch_fused_mt<7, TW, 1, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+            case 1: return launch_fused_mt<1, TW, 1, F16, 1, HIN, HOUT, MM, 1, E>(r, x, packed, y, M, K, G, s);
+            case 2: return launch_fused_mt<2, TW, 1, F16, 1, HIN, HOUT, MM, 1, E>(r, x, packed, y, M, K, G, s);
+            case 3: return launch_fused_mt<3, TW, 1, F16, 1, HIN, HOUT, MM, 1, E>(r, x, packed, y, M, K, G, s);
+            case 4: return launch_fused_mt<4, TW, 1, F16, 1, HIN, HOUT, MM, KW, E>(r, x, packed, y, M, K, G, s);
+            case 5: return launch_fused_mt<5, TW, 1, F16, 1, HIN, HOUT, MM, KW, E>(r, x, packed, y, M, K, G, s);
+            case 6: return launch_fused_mt<6, TW, 1, F16, 1, HIN, HOUT, MM, KW, E>(r, x, packed, y, M, K, G, s);
+            case 7: return launch_fused_mt<7, TW, 1, F16, 1, HIN, HOUT, MM, KW, E>(r, x, packed, y, M, K, G, s);
         }
         return no_fused_kernel(r);
     }
     switch (r.NS == 2 ? r.MT : 0) {
-        case 4: return launch_fused_mt<4, TW, 2, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
-        case 5: return launch_fused_mt<5, TW, 2, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
-        case 6: return launch_fused_mt<6, TW, 2, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
-        case 7: return launch_fused_mt<7, TW, 2, F16, 1, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+        case 4: return launch_fused_mt<4, TW, 2, F16, 1, HIN, HOUT, MM, KW, E>(r, x, packed, y, M, K, G, s);
+        case 5: return launch_fused_mt<5, TW, 2, F16, 1, HIN, HOUT, MM, KW, E>(r, x, packed, y, M, K, G, s);
+        case 6: return launch_fused_mt<6, TW, 2, F16, 1, HIN, HOUT, MM, KW, E>(r, x, packed, y, M, K, G, s);
+        case 7: return launch_fused_mt<7, TW, 2, F16, 1, HIN, HOUT, MM, KW, E>(r, x, packed, y, M, K, G, s);
     }
     return no_fused_kernel(r);
 }
 
 // r.TW of one class
-template <bool F16, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1>
+template <bool F16, bool HIN = false, bool HOUT = false, bool MM = false, int KW = 1, typename E = _Float16>
 int launch_fused_tw(const ConvRoute &r, const float *x, const float *packed, float *y, int M, int K, int G, hipStream_t s) {
     switch (r.TW) {
-        case 32: return launch_fused<32, F16, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
-        case 16: return launch_fused<16, F16, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
-        case 8: return launch_fused<8, F16, HIN, HOUT, MM, KW>(r, x, packed, y, M, K, G, s);
+        case 32: return launch_fused<32, F16, HIN, HOUT, MM, KW, E>(r, x, packed, y, M, K, G, s);
+        case 16: return launch_fused<16, F16, HIN, HOUT, MM, KW, E>(r, x, packed, y, M, K, G, s);
+        case 8: return launch_fused<8, F16, HIN, HOUT, MM, KW, E>(r, x, packed, y, M, K, G, s);
     }
     return no_fused_kernel(r);
 }

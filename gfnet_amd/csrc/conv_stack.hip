@@ -24,6 +24,9 @@
 
 namespace {
 
+// E: the 16-bit element the wt16 and mm sections are rounded to (gfn_conv_block_pack: fp16, gfn_conv_block_pack_bf16: bf16); every
+// other section is fp32 and the same in both
+template <typename E>
 __global__ __launch_bounds__(256) void pack_block_kernel(const float *__restrict__ dw_w, const float *__restrict__ dw_b,
                                                          const float *__restrict__ alpha, const float *__restrict__ beta,
                                                          const float *__restrict__ pw_w, const float *__restrict__ pw_b,
@@ -53,20 +56,20 @@ __global__ __launch_bounds__(256) void pack_block_kernel(const float *__restrict
             const int pair = (int)((i - d.mm_off()) / kMM2), j = (int)((i - d.mm_off()) % kMM2);
             if (j < 80) {
                 const int ch = j / 40, dy = (j % 40) >> 3, dx = j & 7, k = 2 * pair + ch;
-                _Float16 h[2] = {(_Float16)0.f, (_Float16)0.f};
-                if (dx < 5 && k < C) h[ch] = (_Float16)dw_w[(size_t)k * 25 + dy * 5 + dx];
+                E h[2] = {(E)0.f, (E)0.f};
+                if (dx < 5 && k < C) h[ch] = (E)dw_w[(size_t)k * 25 + dy * 5 + dx];
                 __builtin_memcpy(&v, h, 4);
             } else if (j < 86) {
                 const int k = 2 * pair + (j & 1), t = (j - 80) >> 1;
                 if (k < C) v = t == 0 ? (dw_b ? dw_b[k] : 0.f) : t == 1 ? alpha[k] : beta[k];
             }
         } else {  // invert wt16_index for the two halfs of this slot
-            _Float16 h[2];
+            E h[2];
             for (int e2 = 0; e2 < 2; ++e2) {
                 const size_t hidx = 2 * (i - d.wt16_off()) + e2;
                 const int j = (int)(hidx & 7), m = (int)((hidx >> 3) % d.Mp), g = (int)((hidx >> 3) / d.Mp);
                 const int k = (g >> 1) * 16 + (g & 1) * 8 + j;
-                h[e2] = (k < C && m < M) ? (_Float16)pw_w[(size_t)m * C + k] : (_Float16)0.f;
+                h[e2] = (k < C && m < M) ? (E)pw_w[(size_t)m * C + k] : (E)0.f;
             }
             __builtin_memcpy(&v, h, 4);
         }
@@ -211,13 +214,24 @@ GFN_EXPORT int64_t gfn_conv_block_packed_floats(int C, int M) {
     return (int64_t)PackDims(C, M).total();
 }
 
-GFN_EXPORT int gfn_conv_block_pack(const float *dw_w, const float *dw_b, const float *bn_alpha, const float *bn_beta,
-                                   const float *pw_w, const float *pw_b, float *packed, int C, int M, gfn_stream_t stream) {
+template <typename E>
+int pack_block(const float *dw_w, const float *dw_b, const float *bn_alpha, const float *bn_beta, const float *pw_w, const float *pw_b,
+               float *packed, int C, int M, gfn_stream_t stream) {
     if (!dw_w || !bn_alpha || !bn_beta || !pw_w || !pw_b || !packed || C <= 0 || M <= 0)
         return gfn::fail(GFN_ERR_INVALID_ARG, "conv_block_pack: bad argument");
-    hipLaunchKernelGGL(pack_block_kernel, dim3(grid_for((long)PackDims(C, M).total(), 1024)), dim3(256), 0, (hipStream_t)stream, dw_w,
+    hipLaunchKernelGGL(pack_block_kernel<E>, dim3(grid_for((long)PackDims(C, M).total(), 1024)), dim3(256), 0, (hipStream_t)stream, dw_w,
                        dw_b, bn_alpha, bn_beta, pw_w, pw_b, packed, C, M);
     return gfn::check_launch("pack_block_kernel");
+}
+
+GFN_EXPORT int gfn_conv_block_pack(const float *dw_w, const float *dw_b, const float *bn_alpha, const float *bn_beta,
+                                   const float *pw_w, const float *pw_b, float *packed, int C, int M, gfn_stream_t stream) {
+    return pack_block<_Float16>(dw_w, dw_b, bn_alpha, bn_beta, pw_w, pw_b, packed, C, M, stream);
+}
+
+GFN_EXPORT int gfn_conv_block_pack_bf16(const float *dw_w, const float *dw_b, const float *bn_alpha, const float *bn_beta,
+                                        const float *pw_w, const float *pw_b, float *packed, int C, int M, gfn_stream_t stream) {
+    return pack_block<__bf16>(dw_w, dw_b, bn_alpha, bn_beta, pw_w, pw_b, packed, C, M, stream);
 }
 
 GFN_EXPORT int gfn_conv_block_fwd(const float *x, const float *packed, float *y, float *t_scratch, int B, int C, int M, int G,

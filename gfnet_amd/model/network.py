@@ -15,9 +15,10 @@ code stays PyTorch-ROCm for the FPN/transformer backbone"): pass it in as `backb
 `backbone(images, upsample) -> (pyramid_A, pyramid_B)` with the dict layout of
 GFNet.extract_features (model/network.py:156-201), or feed pyramids directly to
 `forward_pyramids` / `match_pyramids`.  The refiner's depthwise/pointwise conv stack
-(model/network.py:560-563) runs on csrc/conv_stack.hip / conv_stack_half.hip in eval mode (`conv_precision`:
-"fp32" exact fp32 products, "fp16" fp16 1x1 operands, "amp" the class the reference's amp=True refiners run in under
-torch.autocast -- fp16 maps between the blocks).  Training mode keeps the nn modules by default (BatchNorm uses batch statistics
+(model/network.py:560-563) runs on csrc/conv_stack.hip / conv_stack_half.hip / conv_stack_bf16.hip in eval mode (SURVEY 8(f) N1;
+`conv_precision`: "fp32" exact fp32 products, "fp16" fp16 1x1 operands, "amp" the class the reference's amp=True refiners run in
+under torch.autocast -- fp16 maps between the blocks --, "bf16" the same under amp_dtype=torch.bfloat16: bf16 maps and operands,
+for a model trained in that class).  Training mode keeps the nn modules by default (BatchNorm uses batch statistics
 there); with `train_conv_impl = "hip"` on a refiner its nine blocks run on csrc/conv_stack_train.hip instead (ops.conv_block_train:
 batch-statistic forward, running-buffer update and backward in HIP) in the fp32 class, and with `train_conv_impl = "hip_amp"` on
 an amp=True refiner on csrc/conv_stack_train_half.hip (ops.conv_block_train_amp) in the class the reference trains in: fp16 maps
@@ -103,7 +104,9 @@ class ConvRefiner(nn.Module):
         # under autocast as in the reference (always used in training mode)
         self.conv_impl = "hip"
         # 1x1 conv operands on the HIP path: "fp32" (exact fp32 products, the CPU reference's class) or "fp16"
-        # (operands rounded to fp16, fp32 accumulation: the autocast class the reference runs these refiners in on GPU)
+        # (operands rounded to fp16, fp32 accumulation: the autocast class the reference runs these refiners in on GPU); "amp": fp16
+        # operands and fp16 maps between the blocks; "bf16": the same with bf16 operands and maps (csrc/conv_stack_bf16.hip), the
+        # class to evaluate a bf16-trained model in -- nothing is held inside fp16's range, and no fp16 kernel ever runs in it
         self.conv_precision = "fp32"
         # training mode: "torch" keeps the nn modules (the default); "hip" runs block1 + hidden_blocks through
         # ops.conv_block_train where _hip_train_stack_supported() holds, "hip_amp" through ops.conv_block_train_amp (fp16 maps, the
@@ -231,15 +234,17 @@ class ConvRefiner(nn.Module):
                       norm.num_batches_tracked, norm.momentum, norm.eps, pw.weight, pw.bias)
         return h
 
-    def folded_stack(self):
+    def folded_stack(self, bf16=False):
         """Per block the packed parameters of ops.conv_block (eval-mode BatchNorm folded to
         y = x*alpha + beta in float64); cached until a parameter or running statistic changes.
+        bf16: packed for ops.conv_block_bf16 (the 16-bit sections of a block rounded to bf16) instead of for ops.conv_block /
+        ops.conv_block_half (fp16); which of the two is part of the cache key.
         out_conv follows the last block's 1x1 conv with nothing in between (network.py:487,563), so the
         two linear maps are multiplied out in float64 (W = W_out W_pw, b = W_out b_pw + b_out): the last
         block writes the 3 output channels directly instead of C channels that out_conv re-reads."""
         blocks = [self.block1] + list(self.hidden_blocks)
         key = tuple(t._version for blk in blocks for t in list(blk.parameters()) + list(blk.buffers())) + \
-            tuple(p._version for p in self.out_conv.parameters()) + (str(self.out_conv.weight.device), self.fold_out_conv)
+            tuple(p._version for p in self.out_conv.parameters()) + (str(self.out_conv.weight.device), self.fold_out_conv, "bf16" if bf16 else "fp16")
         if getattr(self, "_fold_key", None) == key:
             return self._fold
         fold = []
@@ -247,6 +252,7 @@ class ConvRefiner(nn.Module):
             oc = self.out_conv
             ow = oc.weight.float().reshape(oc.out_channels, oc.in_channels).contiguous()
             ob = oc.bias.float().contiguous()
+            pack = ops.conv_block_pack_bf16 if bf16 else ops.conv_block_pack
             for n, (conv, norm, _, pw) in enumerate(blocks):
                 alpha = (norm.weight.double() / torch.sqrt(norm.running_var.double() + norm.eps)).float()
                 beta = (norm.bias.double() - norm.running_mean.double() * alpha.double()).float()
@@ -254,17 +260,27 @@ class ConvRefiner(nn.Module):
                 if self.fold_out_conv and n == len(blocks) - 1:
                     pw_b = (ow.double() @ pw_b.double() + ob.double()).float()
                     pw_w = (ow.double() @ pw_w.double()).float()
-                fold.append((ops.conv_block_pack(conv.weight, conv.bias, alpha, beta, pw_w, pw_b), pw_w.shape[0]))
+                fold.append((pack(conv.weight, conv.bias, alpha, beta, pw_w, pw_b), pw_w.shape[0]))
         self._fold_key, self._fold = key, (fold, None if self.fold_out_conv else (ow, ob))
         return self._fold
 
     def conv_stack(self, d, variant=None):
         """out_conv(hidden_blocks(block1(d))), network.py:560-563, on csrc/conv_stack.hip: one fused
         kernel per block, two ping-pong maps."""
+        if variant is None:
+            if self.conv_precision not in ("fp32", "fp16", "amp", "bf16"):
+                raise ValueError("conv_precision must be 'fp32', 'fp16' (1x1 operands), 'amp' (fp16 operands and maps) or 'bf16' "
+                                 "(bf16 operands and maps)")
+            if self.conv_precision == "bf16":
+                # the same conditions as "amp" below; where they do not hold there is no fp32-map kernel with bf16 operands to fall
+                # back on, and an fp16 kernel is not this class: the modules under torch's own bf16 autocast
+                if d.shape[-1] % 4 == 0 and d.shape[-1] == d.shape[-2] and len(self.hidden_blocks) > 0:
+                    return self._conv_stack_bf16(d, *self.folded_stack(bf16=True))
+                with torch.autocast("cuda", dtype=torch.bfloat16):
+                    h = self.hidden_blocks(self.block1(d))
+                return self.out_conv(h.float())
         fold, out_conv = self.folded_stack()
         if variant is None:
-            if self.conv_precision not in ("fp32", "fp16", "amp"):
-                raise ValueError("conv_precision must be 'fp32', 'fp16' (1x1 operands) or 'amp' (fp16 operands and maps)")
             # (a one-block stack has no map between blocks: fp32 in, fp32 out is the fp16-operand kernel's job -- ADVICE r2)
             if self.conv_precision == "amp" and d.shape[-1] % 4 == 0 and d.shape[-1] == d.shape[-2] and len(fold) > 1:
                 return self._conv_stack_half(d, fold, out_conv)
@@ -276,18 +292,23 @@ class ConvRefiner(nn.Module):
             x = ops.conv_block(x, packed, M, out=bufs[i & 1], variant=variant)
         return x if out_conv is None else ops.pointwise_conv(x, out_conv[0], out_conv[1])
 
-    def _conv_stack_half(self, d, fold, out_conv):
+    def _conv_stack_half(self, d, fold, out_conv, block=ops.conv_block_half):
         """The reference's amp=True class (network.py:560-562: autocast around block1 + hidden_blocks): the maps between
         blocks are float16 in HBM (ops.conv_block_half); out_conv runs on float32 (`.float()`, :563) -- folded into the
         last block, which then writes float32."""
         x, C, bufs = d, d.shape[1], [None, None]
         for i, (packed, M) in enumerate(fold):
             last = i == len(fold) - 1
-            x = ops.conv_block_half(x, packed, C, M, out=None if last else bufs[i & 1], out_half=not last)
+            x = block(x, packed, C, M, None if last else bufs[i & 1], not last)
             if not last:
                 bufs[i & 1] = x
             C = M
         return x if out_conv is None else ops.pointwise_conv(x, out_conv[0], out_conv[1])
+
+    def _conv_stack_bf16(self, d, fold, out_conv):
+        """The same under amp_dtype=torch.bfloat16: bf16 maps between the blocks (ops.conv_block_bf16), fold packed by
+        folded_stack(bf16=True); the first block reads the float32 d, the last one writes float32."""
+        return self._conv_stack_half(d, fold, out_conv, block=ops.conv_block_bf16)
 
     def forward(self, num_grid, x, y, flow, scale_factor=1, logits=None, reuse_d=None):
         """reuse_d (not in the reference): a one-element list owned by the caller's loop over the iterations at one scale

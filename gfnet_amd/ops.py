@@ -1301,14 +1301,24 @@ def resize_normalise(im, size, mode="bicubic", mean=IMAGENET_MEAN, std=IMAGENET_
 def conv_block_pack(dw_w, dw_b, bn_alpha, bn_beta, pw_w, pw_b):
     """Pack one ConvRefiner block (model/network.py:471-487) for conv_block: dw_w (C,25) or (C,1,5,5),
     dw_b (C) or None, eval-mode BatchNorm as y = x*alpha + beta, pw_w (M,C[,1,1]), pw_b (M)."""
+    return _conv_block_pack("gfn_conv_block_pack", dw_w, dw_b, bn_alpha, bn_beta, pw_w, pw_b)
+
+
+def conv_block_pack_bf16(dw_w, dw_b, bn_alpha, bn_beta, pw_w, pw_b):
+    """conv_block_pack for conv_block_bf16: the same arguments, layout and size, with the two 16-bit sections (the 1x1 weights and the
+    banded depthwise taps) rounded to bf16 instead of fp16.  A block packed here goes to conv_block_bf16 and nowhere else."""
+    return _conv_block_pack("gfn_conv_block_pack_bf16", dw_w, dw_b, bn_alpha, bn_beta, pw_w, pw_b)
+
+
+def _conv_block_pack(entry, dw_w, dw_b, bn_alpha, bn_beta, pw_w, pw_b):
     dev = require_gpu(dw_w, pw_w)
     C, M = dw_w.shape[0], pw_w.shape[0]
     dw_w, pw_w = f32c(dw_w.reshape(C, 25)), f32c(pw_w.reshape(M, C))
     al, be, pb = f32c(bn_alpha), f32c(bn_beta), f32c(pw_b)
     db = f32c(dw_b) if dw_b is not None else None
     packed = torch.empty(int(_L().gfn_conv_block_packed_floats(C, M)), device=dev, dtype=torch.float32)
-    _L().gfn_conv_block_pack(ptr(dw_w), ptr(db) if db is not None else None, ptr(al), ptr(be), ptr(pw_w), ptr(pb), ptr(packed),
-                             C, M, stream_ptr(dev))
+    getattr(_L(), entry)(ptr(dw_w), ptr(db) if db is not None else None, ptr(al), ptr(be), ptr(pw_w), ptr(pb), ptr(packed),
+                         C, M, stream_ptr(dev))
     return packed
 
 
@@ -1339,27 +1349,48 @@ def conv_block_half(x, packed, C, M, out=None, out_half=True):
     half map (B,ceil(C/2),G,G,2) float16 (channel pairs side by side); returns a half map (B,ceil(M/2),G,G,2), or (B,M,G,G)
     float32 with out_half=False.  The autocast class: depthwise 5x5 and 1x1 operands fp16 (the input halo, the folded taps, the
     ReLU output and the 1x1 weights are rounded), every accumulation, BatchNorm and ReLU fp32 (include/gfnet_hip.h)."""
+    return _conv_block_16(_MAP_HALF, x, packed, C, M, out, out_half)
+
+
+def conv_block_bf16(x, packed, C, M, out=None, out_bf16=True):
+    """conv_block on bf16 maps -- the refiners under torch.autocast(dtype=torch.bfloat16) (model/network.py:560-562 with
+    amp_dtype=torch.bfloat16), the class a bf16-trained model is evaluated in: x is (B,C,G,G) float32 or a bf16 map
+    (B,ceil(C/2),G,G,2) bfloat16 (the half map's layout); packed comes from conv_block_pack_bf16; returns a bf16 map
+    (B,ceil(M/2),G,G,2), or (B,M,G,G) float32 with out_bf16=False.  conv_block_half's kernel on the bf16 matrix instructions: the input
+    halo, the folded taps, the ReLU output and the 1x1 weights are rounded to bf16, every accumulation, BatchNorm and ReLU fp32;
+    nothing that is finite in fp32 overflows (include/gfnet_hip.h)."""
+    return _conv_block_16(_MAP_BF16, x, packed, C, M, out, out_bf16)
+
+
+# What differs between conv_block_half and conv_block_bf16: name, entry point, torch dtype and GFN_* constant of a 16-bit map
+_MAP_HALF = ("conv_block_half", "gfn_conv_block_half_fwd", torch.float16, _lib.GFN_F16, "half")
+_MAP_BF16 = ("conv_block_bf16", "gfn_conv_block_bf16_fwd", torch.bfloat16, _lib.GFN_BF16, "bf16")
+
+
+def _conv_block_16(cls, x, packed, C, M, out, out_16):
+    name, entry, dt16, gfn16, word = cls
     dev = require_gpu(x, packed)
-    x_half = x.dtype == torch.float16
-    if x_half:
+    x_16 = x.dtype == dt16
+    if x_16:
         if x.dim() != 5 or x.shape[1] != (C + 1) // 2 or x.shape[4] != 2 or not x.is_contiguous():
-            raise ValueError("conv_block_half: a half map is a contiguous (B, ceil(C/2), G, G, 2) float16 tensor")
+            raise ValueError("%s: a %s map is a contiguous (B, ceil(C/2), G, G, 2) %s tensor" % (name, word, str(dt16)[6:]))
     else:
+        if x.dim() == 5 and x.dtype in (torch.float16, torch.bfloat16):
+            raise ValueError("%s: x is a %s map; this entry takes float32 (B, C, G, G) or a %s map" % (name, str(x.dtype)[6:], word))
         x = f32c(x)
         if x.dim() != 4 or x.shape[1] != C:
-            raise ValueError("conv_block_half: x must be (B, C, G, G)")
+            raise ValueError("%s: x must be (B, C, G, G)" % name)
     B, G, G2 = x.shape[0], x.shape[2], x.shape[3]
     if G != G2:
-        raise ValueError("conv_block_half: square grids only")
+        raise ValueError("%s: square grids only" % name)
     if packed.numel() != int(_L().gfn_conv_block_packed_floats(C, M)):
-        raise ValueError("conv_block_half: packed parameters do not match (C=%d, M=%d)" % (C, M))
-    shape = (B, (M + 1) // 2, G, G, 2) if out_half else (B, M, G, G)
-    dt = torch.float16 if out_half else torch.float32
+        raise ValueError("%s: packed parameters do not match (C=%d, M=%d)" % (name, C, M))
+    shape = (B, (M + 1) // 2, G, G, 2) if out_16 else (B, M, G, G)
+    dt = dt16 if out_16 else torch.float32
     if out is None or tuple(out.shape) != shape or out.dtype != dt:
         out = torch.empty(shape, device=dev, dtype=dt)
-    _timed("conv_block_half_c%d_g%d" % (C, G), lambda: _L().gfn_conv_block_half_fwd(
-        ptr(x), _lib.GFN_F16 if x_half else _lib.GFN_F32, ptr(packed), ptr(out), _lib.GFN_F16 if out_half else _lib.GFN_F32, B, C, M, G,
-        stream_ptr(dev)))
+    _timed("%s_c%d_g%d" % (name, C, G), lambda: getattr(_L(), entry)(
+        ptr(x), gfn16 if x_16 else _lib.GFN_F32, ptr(packed), ptr(out), gfn16 if out_16 else _lib.GFN_F32, B, C, M, G, stream_ptr(dev)))
     return out
 
 
@@ -1369,19 +1400,29 @@ def half_map_to_float(h, C):
     return h.permute(0, 1, 4, 2, 3).reshape(B, 2 * NP, G, G2)[:, :C].float()
 
 
+def bf16_map_to_float(h, C):
+    """(B, ceil(C/2), G, G, 2) bfloat16 map -> (B, C, G, G) float32 (tests, debugging)."""
+    return half_map_to_float(h, C)
+
+
 CONV_ROUTE_FIELDS = ("fused", "TW", "MT", "NS", "NB", "KW", "F16", "HIN", "HOUT", "MM", "ngrp", "nwork", "tpb", "VEC", "nblk", "mt",
                      "tiles_x", "tiles_y")
 
 
-def conv_block_route(B, C, M, G, variant=None, x_half=None, out_half=None):
-    """The launch decision of conv_block (give `variant`) or conv_block_half (give `x_half` and `out_half`) for a shape, as a dict
-    over CONV_ROUTE_FIELDS: gfn_conv_block_route (include/gfnet_hip.h), the struct the launchers switch on.  Answered on the host,
+def conv_block_route(B, C, M, G, variant=None, x_half=None, out_half=None, x_bf16=None, out_bf16=None):
+    """The launch decision of conv_block (give `variant`), conv_block_half (give `x_half` and `out_half`) or conv_block_bf16 (give
+    `x_bf16` and `out_bf16`) for a shape, as a dict over CONV_ROUTE_FIELDS (F16, HIN, HOUT: 16-bit operands and maps of the entry's class): gfn_conv_block_route (include/gfnet_hip.h), the struct the launchers switch on.  Answered on the host,
     no GPU needed.  None where the entry point would refuse the shape."""
     import ctypes
 
     route = (ctypes.c_int * _lib.CBR_FIELDS)()
     if variant is not None:
         n = _L().gfn_conv_block_route(_lib.CBR_ENTRY_FWD, int(variant), 0, B, C, M, G, route, _lib.CBR_FIELDS)
+    elif x_bf16 is not None or out_bf16 is not None:
+        if x_half is not None or out_half is not None:
+            raise ValueError("conv_block_route: x_half / out_half and x_bf16 / out_bf16 name two different entry points")
+        n = _L().gfn_conv_block_route(_lib.CBR_ENTRY_BF16, _lib.GFN_BF16 if x_bf16 else _lib.GFN_F32,
+                                      _lib.GFN_BF16 if out_bf16 else _lib.GFN_F32, B, C, M, G, route, _lib.CBR_FIELDS)
     else:
         n = _L().gfn_conv_block_route(_lib.CBR_ENTRY_HALF, _lib.GFN_F16 if x_half else _lib.GFN_F32,
                                       _lib.GFN_F16 if out_half else _lib.GFN_F32, B, C, M, G, route, _lib.CBR_FIELDS)

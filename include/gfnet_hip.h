@@ -39,7 +39,7 @@ extern "C" {
  * backbone under autocast, utils/utils.py:306-320).  Arithmetic and every other tensor stay fp32. */
 #define GFN_F32 0
 #define GFN_F16 1
-/* bf16 tensors: taken by the gfn_conv_block_train_bf16_* entry points (maps), by gfn_cross_attn_fwd / gfn_cross_attn_bwd (q, k, v,
+/* bf16 tensors: taken by gfn_conv_block_bf16_fwd and the gfn_conv_block_train_bf16_* entry points (maps), by gfn_cross_attn_fwd / gfn_cross_attn_bwd (q, k, v,
  * out and the gradients), by gfn_self_attn_fwd (qkv, out); the gfn_decoder_*_bf16_* entry points and
  * gfn_ls_add_layernorm_bf16_fwd are the bf16 class by name and take no dtype.  Every other entry point refuses it */
 #define GFN_BF16 2
@@ -479,16 +479,41 @@ int gfn_pointwise_conv_fwd(const float *w, const float *bias, const float *t, fl
 int gfn_conv_block_half_fwd(const void *x, int x_dtype, const float *packed, void *y, int y_dtype, int B, int C, int M, int G,
                             gfn_stream_t stream);
 
-/* gfn_conv_block_route: the launch decision of gfn_conv_block_fwd (entry = GFN_CBR_ENTRY_FWD, a = variant, b ignored) or
- *   gfn_conv_block_half_fwd (entry = GFN_CBR_ENTRY_HALF, a = x_dtype, b = y_dtype) for a shape, answered on the host: no device,
+/* gfn_conv_block_bf16_fwd: the same block with bf16 maps in HBM -- the refiners under torch.autocast(dtype=torch.bfloat16)
+ *   (model/network.py:560-562 under amp_dtype=torch.bfloat16), the class a model trained with gfn_conv_block_train_bf16_* is
+ *   evaluated in.  gfn_conv_block_half_fwd's kernel on the bf16 instructions, the same tile shapes and routes.
+ *   Arithmetic class: depthwise 5x5 on v_mfma_f32_16x16x32_bf16 (the input halo -- also a first block's fp32 concat -- and the
+ *   folded taps rounded to bf16, fp32 accumulation), BatchNorm + ReLU fp32, ReLU output and 1x1 weights bf16 on
+ *   v_mfma_f32_32x32x16_bf16, fp32 accumulation and bias; a bf16 output is rounded once, to nearest even.  bf16 has fp32's exponent
+ *   range: nothing that is finite in fp32 becomes inf here (an fp16 map ends at 65504).
+ *   packed: from gfn_conv_block_pack_bf16 -- the arguments, layout and gfn_conv_block_packed_floats size of gfn_conv_block_pack, with
+ *   the two 16-bit sections (1x1 weights, banded depthwise taps) rounded to bf16 instead of fp16; every fp32 section is the same.
+ *   A block packed for one class must not be handed to the other entry point (the sizes agree: nothing can check it).
+ *   A map of dtype GFN_BF16 is (B, ceil(C/2), G, G) of bf16 pairs: the half map's layout, the odd channel past C zero (the kernel
+ *   writes it so).  x_dtype / y_dtype: GFN_F32 or GFN_BF16, at least one of them GFN_BF16; GFN_F16 is refused with a message.
+ *   G % 4 == 0, x != y, and the size limits of gfn_conv_block_half_fwd.
+ *   Locality of a non-finite input: gfn_conv_block_half_fwd's envelope -- y may differ from the call without the value at
+ *   |drow| <= 2, |dcol| <= 11 of its cell, in every output channel, whichever channel of the pair held it (the zero odd channel
+ *   past M of a bf16 map included); every other value of y keeps its bits.  A NaN that reaches the ReLU ends there, +inf passes. */
+int gfn_conv_block_pack_bf16(const float *dw_w, const float *dw_b, const float *bn_alpha, const float *bn_beta, const float *pw_w,
+                             const float *pw_b, float *packed, int C, int M, gfn_stream_t stream);
+int gfn_conv_block_bf16_fwd(const void *x, int x_dtype, const float *packed, void *y, int y_dtype, int B, int C, int M, int G,
+                            gfn_stream_t stream);
+
+/* gfn_conv_block_route: the launch decision of gfn_conv_block_fwd (entry = GFN_CBR_ENTRY_FWD, a = variant, b ignored),
+ *   gfn_conv_block_half_fwd (entry = GFN_CBR_ENTRY_HALF, a = x_dtype, b = y_dtype) or gfn_conv_block_bf16_fwd (entry =
+ *   GFN_CBR_ENTRY_BF16, a = x_dtype, b = y_dtype: field for field the answer of GFN_CBR_ENTRY_HALF for the same shape with GFN_F16
+ *   where this one has GFN_BF16) for a shape, answered on the host: no device,
  *   no stream (csrc/conv_block_fused.h conv_route, the struct the launchers themselves switch on).  Fills route[GFN_CBR_*]
  *   (route_len >= GFN_CBR_FIELDS ints) and returns GFN_CBR_FIELDS; returns 0, route untouched, where the entry point would refuse
  *   the shape (gfn_last_error says why).  FUSED: 1 = dwpw_fused_kernel, then TW, MT, NS, NB, KW are its template parameters, NGRP
  *   slab groups of 32*MT*NS output channels, TILES_X x TILES_Y cell tiles of TW x (128*NB/TW) cells per map, NWORK = B * tiles *
  *   NGRP work items, TPB of them per workgroup; 0 = the two-pass form: dw5x5_kernel<VEC>, then pw_gemm_kernel<GEMM_MT> over NBLK
- *   row blocks.  F16: fp16 1x1 operands; HIN / HOUT: fp16 map in / out; MM: matrix-core depthwise.  Fields of the other form: 0. */
+ *   row blocks.  F16: 16-bit 1x1 operands; HIN / HOUT: 16-bit map in / out (fp16 or bf16, as the entry says); MM: matrix-core
+ *   depthwise.  Fields of the other form: 0. */
 #define GFN_CBR_ENTRY_FWD 0
 #define GFN_CBR_ENTRY_HALF 1
+#define GFN_CBR_ENTRY_BF16 2
 #define GFN_CBR_FUSED 0
 #define GFN_CBR_TW 1
 #define GFN_CBR_MT 2
