@@ -23,16 +23,16 @@ __device__ __forceinline__ BilinP bilin_pairs(float gx, float gy, int W, int H) 
     BilinP c;
     const int ox = min(max(s.x0, 0), W - 2);
     // fetched left pixel = column ox, right = ox + 1; corner columns are x0 (weights w*0) and x0+1 (weights w*1)
-    const float l0 = (s.xa & (s.x0 == ox)) ? 1.f : 0.f, l1 = (s.xb & (s.x0 + 1 == ox)) ? 1.f : 0.f;      // left stands for x0 / x0+1
-    const float r0 = (s.xa & (s.x0 == ox + 1)) ? 1.f : 0.f, r1 = (s.xb & (s.x0 + 1 == ox + 1)) ? 1.f : 0.f;  // right stands for x0 / x0+1
-    const float ta = s.ya ? 1.f : 0.f, tb = s.yb ? 1.f : 0.f;
+    const bool l0 = s.xa & (s.x0 == ox), l1 = s.xb & (s.x0 + 1 == ox);          // left stands for x0 / x0+1
+    const bool r0 = s.xa & (s.x0 == ox + 1), r1 = s.xb & (s.x0 + 1 == ox + 1);  // right stands for x0 / x0+1
     c.o[0] = (unsigned)((s.ya ? s.y0 : 0) * W + ox);
     c.o[1] = (unsigned)((s.yb ? s.y0 + 1 : 0) * W + ox);
-    // exactly one of (l0, l1) and one of (r0, r1) can be 1, so each product below is w or 0 -- no rounding added
-    c.w[0] = ta * (l0 * s.w00 + l1 * s.w01);
-    c.w[1] = ta * (r0 * s.w00 + r1 * s.w01);
-    c.w[2] = tb * (l0 * s.w10 + l1 * s.w11);
-    c.w[3] = tb * (r0 * s.w10 + r1 * s.w11);
+    // at most one of (l0, l1) and one of (r0, r1) holds: each weight is w or 0.  Selected, not multiplied by 0 or 1: a non-finite
+    // coordinate has every corner outside and NaN weights, and reads zeros like the four-tap set-up (0 * NaN would be NaN)
+    c.w[0] = s.ya ? (l0 ? s.w00 : l1 ? s.w01 : 0.f) : 0.f;
+    c.w[1] = s.ya ? (r0 ? s.w00 : r1 ? s.w01 : 0.f) : 0.f;
+    c.w[2] = s.yb ? (l0 ? s.w10 : l1 ? s.w11 : 0.f) : 0.f;
+    c.w[3] = s.yb ? (r0 ? s.w10 : r1 ? s.w11 : 0.f) : 0.f;
     return c;
 }
 

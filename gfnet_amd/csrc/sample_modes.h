@@ -13,6 +13,10 @@
 //
 // Coordinates whose floor lies 10^6 pixels or more outside the image, and non-finite ones, read zeros in every mode (the
 // `sane` guard of the bilinear kernels); F.grid_sample's CPU and GPU implementations disagree with each other there.
+//
+// tests/test_sampling_exact_gpu.py pins the decisions taken here -- the nearest ties (half to even), the mirrors at -0.5 and
+// size - 0.5 and their multiples, the border clamp at size - 1, the corners and taps outside the image, the guard at +-10^6 -- by
+// equality with a float64 oracle on data that leaves fp32 no rounding (tests/golden/sampling_cases.py).
 #pragma once
 #include <type_traits>
 

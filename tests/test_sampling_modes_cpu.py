@@ -38,6 +38,30 @@ def restated_local_correlation(f0, f1, r, G, flow=None, sample_mode="bilinear", 
     return torch.cat(levels, 1)
 
 
+def restated_case(c, sm, pm, dtype=torch.float32, f0=None):
+    """restated_local_correlation of a case of tests/golden/sampling_cases.py (f0, f1, flow, r, G, grid_based, num_level, shape).
+    The restatement pools once more than it needs, which a map one pixel high cannot: there the same formula runs over the case
+    oracle's own tap coordinates (which the other cases pin)."""
+    import sampling_cases as sc
+
+    B, C, H, W = c["shape"]
+    f0 = torch.from_numpy(c["f0"]).to(dtype) if f0 is None else f0
+    f1 = torch.from_numpy(c["f1"]).to(dtype)
+    flow = None if c["flow"] is None else torch.from_numpy(c["flow"]).to(dtype)
+    if flow is None and dtype != torch.float32:  # the restatement's identity grid is fp32: hand it over widened
+        lin = torch.linspace(-1 + 1 / W, 1 - 1 / W, W)
+        flow = torch.stack(torch.meshgrid(lin, lin, indexing="xy"))[None].expand(B, 2, W, W).to(dtype)
+    if min(H, W) > 1:
+        return restated_local_correlation(f0, f1, c["r"], c["G"], flow=flow, sample_mode=sm, padding_mode=pm, grid_based=c["grid_based"],
+                                          num_level=c["num_level"])
+    assert c["num_level"] == 1
+    G, K = c["G"], (2 * c["r"] + 1) ** 2
+    gx, gy = sc.tap_coords(c["flow"], B, G, H, W, c["r"], c["grid_based"])
+    grid = torch.from_numpy(np.stack((gx, gy), -1)).to(dtype).reshape(B, K * G, G, 2)
+    s = F.grid_sample(f1, grid, mode=sm, padding_mode=pm, align_corners=False).reshape(B, C, K, G, G)
+    return (f0[:, :, None] / C ** 0.5 * s).sum(1)
+
+
 def _refiner(sample_mode):
     from gfnet_amd.model.network import ConvRefiner
 

@@ -22,8 +22,9 @@ def dev(a):
 
 
 def uniform(shape, seed, scale):
-    """Uniform in [-scale, scale): plain random floats (the k/4096 lattice of synth.lattice_uniform would put nearest-mode samples
-    on exact .5 ties, where rounding may legitimately go either way)."""
+    """Uniform in [-scale, scale): plain random floats, generic coordinates for the 1e-4 comparisons of this module.  The decision
+    points (the k/4096 lattice of synth.lattice_uniform would put nearest-mode samples on exact .5 ties) are not left open: a tie
+    rounds half to even, in the kernels as in ATen, and test_sampling_exact_gpu.py pins the ties, mirrors and clamps by equality."""
     return (torch.rand(shape, generator=torch.Generator().manual_seed(seed)) * (2 * scale) - scale).cuda()
 
 
