@@ -32,7 +32,16 @@ Three paths over the same parameters:
     F.conv2d, BatchNorm, the activation, F.interpolate and torch.cat, as the reference writes them; differentiable, and the
     BatchNorm buffers move as in the reference.
 
-The top-level module's conv_impl and train_conv_impl govern its children (run(x, hip, train_hip)).
+The top-level module's conv_impl, train_conv_impl and conv_precision govern its children (run(x, hip, train_hip, half)).
+
+conv_precision "fp32" (the default, all of the above) or "fp16": an opt-in fp16 CLASS of the first path, and of that path only.
+Exactly where the fp32 HIP path runs -- eval(), CUDA, conv_impl "hip" -- every layer is then ONE ops.conv2d_bn_act_half launch
+(csrc/fpn_conv_half.hip): the image and the merge layer's side map are cast to fp16 on entry, every map between layers is fp16 in
+memory, the convolution is an implicit GEMM on the matrix core (fp16 products, fp32 sums and epilogue, one rounding per stored
+value), and EVERY RETURNED MAP IS fp16 -- the dtype of the result differs from the default's.  A layer that class cannot run (Cout
+no multiple of 8) raises NotImplementedError naming the layer.  train(), CPU tensors and conv_impl "torch" run what they run under
+"fp32", in fp32, whatever conv_precision says.  The reference runs its FPN in fp32 outside autocast: "fp16" is this package's
+option, not the reference's arithmetic.
 """
 import torch
 import torch.nn as nn
@@ -42,6 +51,7 @@ from .. import ops
 
 CONV_IMPLS = ("hip", "torch")
 TRAIN_CONV_IMPLS = ("hip", "hip_fused", "torch")  # "hip_fused": "hip" with the decoder's 2x upsample inside the innerN op
+CONV_PRECISIONS = ("fp32", "fp16")  # "fp16": fp16 maps and the matrix core on the eval() HIP path (module docstring)
 LEAKY_SLOPE = 0.1  # FPN.py:127
 
 
@@ -55,6 +65,19 @@ def _check_train_impl(train_conv_impl):
     if train_conv_impl not in TRAIN_CONV_IMPLS:
         raise ValueError(f"train_conv_impl must be one of {TRAIN_CONV_IMPLS}, got {train_conv_impl!r}")
     return train_conv_impl
+
+
+def _check_precision(conv_precision):
+    if conv_precision not in CONV_PRECISIONS:
+        raise ValueError(f"conv_precision must be one of {CONV_PRECISIONS}, got {conv_precision!r}")
+    return conv_precision
+
+
+def _use_half(module, x):
+    """The fp16 class: where the fp32 HIP path would run, on an fp32 or fp16 map (cast to fp16 on entry)."""
+    _check_impl(module.conv_impl)
+    return (_check_precision(module.conv_precision) == "fp16" and module.conv_impl == "hip" and not module.training and x.is_cuda
+            and x.dtype in (torch.float32, torch.float16))
 
 
 def _use_hip(module, x):
@@ -105,10 +128,16 @@ def _hip_train_layer(conv, bn, act, x0, x1=None, residual=None, up0=False):
                                    slope=LEAKY_SLOPE, up0=up0)
 
 
-def _hip_layer(conv, bn, act, x0, x1=None, up0=False, residual=None):
+def _hip_layer(conv, bn, act, x0, x1=None, up0=False, residual=None, half=False):
     _check_conv(conv, "conv_impl")
     scale, shift = _fold(conv, bn)
     x0, x1, residual = (None if t is None else t.contiguous() for t in (x0, x1, residual))
+    if half:
+        if conv.out_channels % 8:
+            raise NotImplementedError(f"conv_precision='fp16' runs layers whose output channels are a multiple of 8; got {conv}: "
+                                      "construct with conv_precision='fp32'")
+        return ops.conv2d_bn_act_half(x0, conv.weight.detach().contiguous(), scale.float(), shift.float(), x1=x1, up0=up0,
+                                      residual=residual, stride=conv.stride[0], act=act, slope=LEAKY_SLOPE)
     return ops.conv2d_bn_act(x0, conv.weight.detach().contiguous(), scale, shift, x1=x1, up0=up0, residual=residual, stride=conv.stride[0],
                              act=act, slope=LEAKY_SLOPE)
 
@@ -128,8 +157,9 @@ class Conv2d(nn.Module):
     reference's "IN" (InstanceNorm, which GFNet never builds) raises NotImplementedError."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, relu=True, bn=True, bn_momentum=0.1, norm_type="BN",
-                 conv_impl="hip", train_conv_impl="torch", **kwargs):
+                 conv_impl="hip", train_conv_impl="torch", conv_precision="fp32", **kwargs):
         super().__init__()
+        self.conv_precision = _check_precision(conv_precision)
         if norm_type != "BN":
             raise NotImplementedError(f"Conv2d: norm_type = {norm_type!r} is not supported, only 'BN' (what GFNet builds)")
         self.conv_impl = _check_impl(conv_impl)
@@ -140,9 +170,9 @@ class Conv2d(nn.Module):
         self.bn = nn.BatchNorm2d(out_channels, momentum=bn_momentum) if bn else None
         self.relu = relu
 
-    def run(self, x, hip, train_hip=False):
+    def run(self, x, hip, train_hip=False, half=False):
         if hip:
-            return _hip_layer(self.conv, self.bn, "leaky_relu" if self.relu else None, x)
+            return _hip_layer(self.conv, self.bn, "leaky_relu" if self.relu else None, x.half() if half else x, half=half)
         if train_hip:
             return _hip_train_layer(self.conv, self.bn, "leaky_relu" if self.relu else None, x)
         y = self.conv(x)
@@ -151,21 +181,23 @@ class Conv2d(nn.Module):
         return F.leaky_relu(y, LEAKY_SLOPE, inplace=True) if self.relu else y
 
     def forward(self, x):
-        return self.run(x, _use_hip(self, x), _use_train_hip(self, x))
+        half = _use_half(self, x)
+        return self.run(x, half or _use_hip(self, x), _use_train_hip(self, x), half)
 
 
 class FPNEncoder(nn.Module):
     """FPN.py:5-36: images (B, 3, H, W) -> [conv01, conv11, conv21, conv31] at strides 1, 2, 4, 8 with feat_chs channels (fine to
     coarse).  H and W must be multiples of 8 (the reference fails later, inside the decoder's torch.cat)."""
 
-    def __init__(self, feat_chs, norm_type="BN", conv_impl="hip", train_conv_impl="torch"):
+    def __init__(self, feat_chs, norm_type="BN", conv_impl="hip", train_conv_impl="torch", conv_precision="fp32"):
         super().__init__()
+        self.conv_precision = _check_precision(conv_precision)
         if norm_type != "BN":
             raise NotImplementedError(f"FPNEncoder: norm_type = {norm_type!r} is not supported, only 'BN' (what GFNet builds)")
         self.conv_impl = _check_impl(conv_impl)
         self.train_conv_impl = _check_train_impl(train_conv_impl)
         c = feat_chs
-        kw = {"norm_type": norm_type, "conv_impl": conv_impl, "train_conv_impl": train_conv_impl}
+        kw = {"norm_type": norm_type, "conv_impl": conv_impl, "train_conv_impl": train_conv_impl, "conv_precision": conv_precision}
         self.conv00 = Conv2d(3, c[0], 7, 1, padding=3, **kw)
         self.conv01 = Conv2d(c[0], c[0], 5, 1, padding=2, **kw)
 
@@ -184,11 +216,12 @@ class FPNEncoder(nn.Module):
     def forward(self, x):
         if x.dim() != 4 or x.shape[2] % 8 or x.shape[3] % 8:
             raise ValueError(f"FPNEncoder: height and width must be multiples of 8, got an input of shape {tuple(x.shape)}")
-        hip, th = _use_hip(self, x), _use_train_hip(self, x)
-        conv01 = self.conv01.run(self.conv00.run(x, hip, th), hip, th)
-        conv11 = self.conv11.run(self.conv10.run(self.downsample1.run(conv01, hip, th), hip, th), hip, th)
-        conv21 = self.conv21.run(self.conv20.run(self.downsample2.run(conv11, hip, th), hip, th), hip, th)
-        conv31 = self.conv31.run(self.conv30.run(self.downsample3.run(conv21, hip, th), hip, th), hip, th)
+        half = _use_half(self, x)  # (the image is cast to fp16 by the first layer's run, every later map already is)
+        hip, th = half or _use_hip(self, x), _use_train_hip(self, x)
+        conv01 = self.conv01.run(self.conv00.run(x, hip, th, half), hip, th, half)
+        conv11 = self.conv11.run(self.conv10.run(self.downsample1.run(conv01, hip, th, half), hip, th, half), hip, th, half)
+        conv21 = self.conv21.run(self.conv20.run(self.downsample2.run(conv11, hip, th, half), hip, th, half), hip, th, half)
+        conv31 = self.conv31.run(self.conv30.run(self.downsample3.run(conv21, hip, th, half), hip, th, half), hip, th, half)
         return [conv01, conv11, conv21, conv31]
 
 
@@ -200,14 +233,18 @@ class merge_layer(nn.Sequential):
     """network.py:66, 182: `conv31 + Sequential(conv3x3(2 ch -> ch), BatchNorm, Swish)(cat(conv31, side))`, the addition included:
     forward(conv31, side) -> the merged stride-8 map."""
 
-    def __init__(self, ch, conv_impl="hip", train_conv_impl="torch"):
+    def __init__(self, ch, conv_impl="hip", train_conv_impl="torch", conv_precision="fp32"):
         super().__init__(nn.Conv2d(2 * ch, ch, kernel_size=3, padding=1), nn.BatchNorm2d(ch), Swish())
+        self.conv_precision = _check_precision(conv_precision)
         self.conv_impl = _check_impl(conv_impl)
         self.train_conv_impl = _check_train_impl(train_conv_impl)
 
     def forward(self, conv31, side):
         if conv31.shape != side.shape:
             raise ValueError(f"merge_layer: conv31 {tuple(conv31.shape)} and the side map {tuple(side.shape)} must have one shape")
+        if _use_half(self, conv31) and _use_half(self, side):
+            conv31 = conv31.half()
+            return _hip_layer(*_head(self), conv31, x1=side.half(), residual=conv31, half=True)
         if _use_hip(self, conv31) and side.is_cuda and side.dtype == torch.float32:
             return _hip_layer(*_head(self), conv31, x1=side, residual=conv31)
         if _use_train_hip(self, conv31) and side.is_cuda and side.dtype == torch.float32:
@@ -218,8 +255,9 @@ class merge_layer(nn.Sequential):
 class FPNDecoder_concat(nn.Module):
     """FPN.py:39-69: (conv01, conv11, conv21, conv31) -> [out0, out1, out2, out3] at strides 8, 4, 2, 1."""
 
-    def __init__(self, feat_chs, conv_impl="hip", train_conv_impl="torch"):
+    def __init__(self, feat_chs, conv_impl="hip", train_conv_impl="torch", conv_precision="fp32"):
         super().__init__()
+        self.conv_precision = _check_precision(conv_precision)
         self.conv_impl = _check_impl(conv_impl)
         self.train_conv_impl = _check_train_impl(train_conv_impl)
         c = feat_chs
@@ -244,7 +282,11 @@ class FPNDecoder_concat(nn.Module):
             if fine.shape[0] != coarse.shape[0] or tuple(fine.shape[2:]) != (2 * coarse.shape[2], 2 * coarse.shape[3]):
                 raise ValueError(f"FPNDecoder_concat: every level must double the one below it, got {[tuple(m.shape) for m in maps]} "
                                  "(image heights and widths must be multiples of 8)")
-        hip = _use_hip(self, conv31) and all(m.is_cuda and m.dtype == torch.float32 for m in maps)
+        half = all(_use_half(self, m) for m in maps)
+        if half:
+            conv01, conv11, conv21, conv31 = (m.half() for m in (conv01, conv11, conv21, conv31))
+            maps = (conv31, conv21, conv11, conv01)
+        hip = half or (_use_hip(self, conv31) and all(m.is_cuda and m.dtype == torch.float32 for m in maps))
         th = _use_train_hip(self, conv31) and all(m.is_cuda and m.dtype == torch.float32 for m in maps)
         intra = conv31
         outs = []
@@ -252,12 +294,12 @@ class FPNDecoder_concat(nn.Module):
                                  (self.inner3, self.out3, conv01)):
             if inner is not None:  # FPN.py:59: skip + inner(cat(interpolate(intra), skip))
                 if hip:
-                    intra = _hip_layer(*_head(inner), intra, x1=skip, up0=True, residual=skip)
+                    intra = _hip_layer(*_head(inner), intra, x1=skip, up0=True, residual=skip, half=half)
                 elif th and self.train_conv_impl == "hip_fused":  # the upsample inside the op, in both directions
                     intra = _hip_train_layer(*_head(inner), intra, x1=skip, residual=skip, up0=True)
                 elif th:  # the doubled map from torch, which differentiates the upsample; still no concatenation
                     intra = _hip_train_layer(*_head(inner), _up2(intra), x1=skip, residual=skip)
                 else:
                     intra = skip + inner(torch.cat((_up2(intra), skip), dim=1))
-            outs.append(_hip_layer(*_head(out), intra) if hip else _hip_train_layer(*_head(out), intra) if th else out(intra))
+            outs.append(_hip_layer(*_head(out), intra, half=half) if hip else _hip_train_layer(*_head(out), intra) if th else out(intra))
         return outs

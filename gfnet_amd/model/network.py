@@ -375,11 +375,14 @@ class GFNet(nn.Module):
             # csrc/decoder_block.hip (train_block_impl="hip"); unset: torch autograd, as before
             # GFNET_COMPAT_FPN=hip: the native FPN encoder, merge layer and decoder (model/fpn.py) in place of the checkout's
             # `model.FPN`, one fused launch per layer in eval(); unset: the checkout's classes, as before
+            # GFNET_COMPAT_FPN_PRECISION=fp16 (with GFNET_COMPAT_FPN=hip): the native FPN in its fp16 class, fp16 pyramids handed to
+            # the matcher as stored; unset: fp32, as before
             # GFNET_COMPAT_DINO=hip: the native DINOv2 ViT (model/dinov2.py) in place of the checkout's `model.transformer`, attention
             # and block seams in HIP in fp16 eval(); unset: the checkout's class, as before
             backbone = reference_backbone(conf, amp=amp, amp_dtype=amp_dtype, decoder=os.environ.get("GFNET_COMPAT_DECODER") or "checkout",
                                           fpn=os.environ.get("GFNET_COMPAT_FPN") or "checkout",
                                           dino=os.environ.get("GFNET_COMPAT_DINO") or "checkout",
+                                          fpn_precision=os.environ.get("GFNET_COMPAT_FPN_PRECISION") or "fp32",
                                           decoder_train_impl=os.environ.get("GFNET_COMPAT_DECODER_TRAIN") or "torch")
         self.backbone = backbone
         if conv_refiner is None:

@@ -553,6 +553,60 @@ def conv2d_bn_act(x0, weight, scale, shift, x1=None, up0=False, residual=None, s
     return out
 
 
+def conv2d_pack_half(weight):
+    """The (Cout, Cin, K, K) weight rounded once to fp16 and packed for gfn_conv2d_bn_act_half_fwd (include/gfnet_hip.h):
+
+        packed[co, cg, u, c] = weight[co, 8 cg + c, u // K, u % K]        (CoutP, ceil(Cin / 8), UP, 8), fp16
+
+    with UP = K K rounded up to a multiple of 4 and CoutP = Cout rounded up to a multiple of 16 below 32 output channels, of 32 from
+    there; zero past Cin, K K and Cout.  A few torch ops on the weight's device; nothing is cached."""
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
+        raise ValueError(f"conv2d_pack_half: weight (Cout,Cin,K,K) expected, got {tuple(weight.shape)}")
+    Cout, Cin, K, _ = weight.shape
+    CG, UP, n = -(-Cin // 8), -(-K * K // 4) * 4, 16 if Cout < 32 else 32
+    w = weight.detach().to(torch.float16).reshape(Cout, Cin, K * K)
+    w = torch.nn.functional.pad(w, (0, UP - K * K, 0, CG * 8 - Cin, 0, -(-Cout // n) * n - Cout))
+    return w.reshape(-1, CG, 8, UP).permute(0, 1, 3, 2).contiguous()
+
+
+def conv2d_bn_act_half(x0, weight, scale, shift, x1=None, up0=False, residual=None, stride=1, act=None, slope=0.1):
+    """conv2d_bn_act in the fp16 class (gfn_conv2d_bn_act_half_fwd, csrc/fpn_conv_half.hip): the same layer, the same arguments, with
+    x0, x1 and residual contiguous fp16 CUDA tensors and an fp16 result; scale and shift stay fp32.  weight is the layer's own
+    (Cout, Cin, K, K) weight, fp32 or fp16: it is rounded to fp16 and packed here at every call (conv2d_pack_half).  Cout must be a
+    multiple of 8.  fp16 x fp16 products summed in fp32 on the matrix core, the epilogue in fp32, one rounding at the store, overflow
+    to inf; with up0 the interpolated operand is rounded to fp16 once.  No autograd."""
+    if act not in CONV_ACTS:
+        raise ValueError(f"conv2d_bn_act_half: act must be one of {list(CONV_ACTS)}, got {act!r}")
+    tensors = {"x0": x0, "weight": weight, "scale": scale, "shift": shift, "x1": x1, "residual": residual}
+    dev = require_gpu(*tensors.values())
+    for name, t in tensors.items():
+        want = (torch.float32,) if name in ("scale", "shift") else (torch.float16, torch.float32) if name == "weight" else (torch.float16,)
+        if t is not None and (t.dtype not in want or not t.is_contiguous()):
+            raise TypeError(f"conv2d_bn_act_half: {name} must be a contiguous {' or '.join(str(d)[6:] for d in want)} tensor, got "
+                            f"{t.dtype}, contiguous={t.is_contiguous()}")
+    if x0.dim() != 4 or weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
+        raise ValueError(f"conv2d_bn_act_half: x0 (B,C0,H,W) and weight (Cout,Cin,K,K) expected, got {tuple(x0.shape)}, {tuple(weight.shape)}")
+    B, C0 = x0.shape[:2]
+    H, W = (2 * x0.shape[2], 2 * x0.shape[3]) if up0 else x0.shape[2:]
+    C1 = 0 if x1 is None else x1.shape[1]
+    Cout, Cin, K, _ = weight.shape
+    if x1 is not None and (x1.dim() != 4 or x1.shape[0] != B or tuple(x1.shape[2:]) != (H, W)):
+        raise ValueError(f"conv2d_bn_act_half: x1 must be ({B}, C1, {H}, {W}), got {tuple(x1.shape)}")
+    if Cin != C0 + C1 or tuple(scale.shape) != (Cout,) or tuple(shift.shape) != (Cout,):
+        raise ValueError(f"conv2d_bn_act_half: weight takes {Cin} channels but the inputs have {C0} + {C1}; scale and shift must be "
+                         f"({Cout},), got {tuple(scale.shape)}, {tuple(shift.shape)}")
+    if stride not in (1, 2):
+        raise ValueError(f"conv2d_bn_act_half: stride must be 1 or 2, got {stride!r}")
+    out = torch.empty((B, Cout, (H + stride - 1) // stride, (W + stride - 1) // stride), device=dev, dtype=torch.float16)
+    if residual is not None and residual.shape != out.shape:
+        raise ValueError(f"conv2d_bn_act_half: residual must have the output's shape {tuple(out.shape)}, got {tuple(residual.shape)}")
+    packed = conv2d_pack_half(weight)
+    _timed("conv2d_bn_act_half", lambda: _L().gfn_conv2d_bn_act_half_fwd(ptr(x0), C0, int(bool(up0)), ptr(x1), C1, ptr(packed), ptr(scale),
+                                                                         ptr(shift), ptr(residual), ptr(out), B, H, W, Cout, K, stride,
+                                                                         CONV_ACTS[act], float(slope), stream_ptr(dev)))
+    return out
+
+
 def _conv2d_train_args(what, x0, x1, weight, residual, vectors, stride, act, up0=False):
     """The refusals of conv2d_bn_act, for the training entry points; vectors: name -> (Cout,) tensor or None.  Returns
     (dev, B, C0, C1, H, W, Cout, K, Ho, Wo); with up0 x0 is the coarse map and H, W are twice its height and width."""

@@ -50,6 +50,13 @@ def _check_fpn_train_impl(fpn, fpn_train_impl):
         raise ValueError(f"fpn_train_impl={fpn_train_impl!r} needs fpn='hip': the checkout's FPN modules train through torch only")
 
 
+def _check_fpn_precision(fpn, fpn_precision):
+    if fpn_precision not in ("fp32", "fp16"):
+        raise ValueError(f"fpn_precision must be 'fp32' or 'fp16', got {fpn_precision!r}")
+    if fpn_precision != "fp32" and fpn != "hip":
+        raise ValueError(f"fpn_precision={fpn_precision!r} needs fpn='hip': the checkout's FPN modules run in fp32 only")
+
+
 def _check_decoder_train_impl(decoder, decoder_train_impl):
     if decoder_train_impl not in ("torch", "hip"):
         raise ValueError(f"decoder_train_impl must be 'torch' or 'hip', got {decoder_train_impl!r}")
@@ -134,16 +141,23 @@ class ReferenceBackbone(nn.Module):
     fpn_train_impl: "torch" (default), "hip" or "hip_fused" ("hip" with the decoder's 2x upsample inside the innerN op), the
     train_conv_impl of the three native FPN modules: what they run under train() (see gfnet_amd/model/fpn.py).  The checkout's modules have no such switch: anything but "torch" with fpn="checkout" raises ValueError.
 
+    fpn_precision: "fp32" (default) or "fp16", the conv_precision of the three native FPN modules (see gfnet_amd/model/fpn.py): with
+    "fp16" their eval() HIP path keeps fp16 maps and runs on the matrix core, and in eval() on the GPU ALL FIVE LEVELS ARE RETURNED IN
+    fp16 as stored (the stride-16 map is cast to fp16 too), not widened: GFNet.match / match_batch read fp16 pyramids directly.
+    train() and CPU tensors return fp32 levels as before.  Needs fpn="hip", else ValueError.
+
     decoder_train_impl: "torch" (default) or "hip", the train_block_impl of the native cross-view decoder: "hip" trains its blocks
     through the backward kernels of csrc/decoder_block.hip under fp16 or bf16 autocast: amp_dtype=torch.bfloat16 selects the bf16 class of
     the attention and of the blocks, with nothing else to set (see gfnet_amd/model/crossview_decoder.py).  Anything
     but "torch" with decoder="checkout" raises ValueError."""
 
     def __init__(self, conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout",
-                 dino="checkout", fpn_train_impl="torch", decoder_train_impl="torch"):
+                 dino="checkout", fpn_train_impl="torch", decoder_train_impl="torch", fpn_precision="fp32"):
         super().__init__()
         _check_choices(decoder, fpn, dino)
         _check_fpn_train_impl(fpn, fpn_train_impl)
+        _check_fpn_precision(fpn, fpn_precision)
+        self.fpn_precision = fpn_precision
         _check_decoder_train_impl(decoder, decoder_train_impl)
         self.fpn = fpn
         if fpn == "hip":
@@ -167,7 +181,7 @@ class ReferenceBackbone(nn.Module):
             from model.crossview_decoder_light import CrossVITDecoder_noself
 
             self.dino_decoder = CrossVITDecoder_noself(conf=conf, upsample=False)
-        native = {"train_conv_impl": fpn_train_impl} if fpn == "hip" else {}
+        native = {"train_conv_impl": fpn_train_impl, "conv_precision": fpn_precision} if fpn == "hip" else {}
         self.encoder = FPNEncoder(feat_chs=chs[::-1], **native)
         self.decoder = FPNDecoder_concat(feat_chs=chs[::-1], **native)
         if fpn == "hip":
@@ -197,24 +211,27 @@ class ReferenceBackbone(nn.Module):
         # (the native merge layer takes both maps and adds conv31 itself: one launch, no concatenation)
         c3 = self.merge_layer(c3, side) if self.fpn == "hip" else c3 + self.merge_layer(torch.cat((c3, side), dim=1))
         levels = [vit_feat] + list(self.decoder(c0, c1, c2, c3))
+        # the fp16 class hands its maps on as stored (fp16 where its HIP path ran: eval() on the GPU), every level in that one dtype
+        keep = levels[-1].dtype if self.fpn_precision == "fp16" and levels[-1].dtype == torch.float16 else torch.float32
         pyr_a, pyr_b = {}, {}
         for name, t in zip(("16", "8", "4", "2", "1"), levels):
             if upsample and name == "16":
                 continue
-            a, b = t.float().chunk(2)
+            a, b = t.to(keep).chunk(2)
             pyr_a[name], pyr_b[name] = a.contiguous(), b.contiguous()
         return pyr_a, pyr_b
 
 
 def reference_backbone(conf, amp=True, amp_dtype=torch.float16, vit=None, dino_weights=None, decoder="checkout", fpn="checkout",
-                       dino="checkout", fpn_train_impl="torch", decoder_train_impl="torch"):
+                       dino="checkout", fpn_train_impl="torch", decoder_train_impl="torch", fpn_precision="fp32"):
     """Build the backbone from the checkout on sys.path; raises ImportError with the reason when a module this choice needs from it
-    is missing.  decoder, fpn, dino, fpn_train_impl, decoder_train_impl: see ReferenceBackbone."""
+    is missing.  decoder, fpn, dino, fpn_train_impl, decoder_train_impl, fpn_precision: see ReferenceBackbone."""
     _check_choices(decoder, fpn, dino)
     _check_fpn_train_impl(fpn, fpn_train_impl)
+    _check_fpn_precision(fpn, fpn_precision)
     _check_decoder_train_impl(decoder, decoder_train_impl)
     if not checkout_available(decoder, fpn):
         raise ImportError(f"no KN-Zhang/GFNet checkout on sys.path: {' / '.join(f'`{m}`' for m in _needed(decoder, fpn))} cannot be found "
                           "(put the checkout behind compat/ on PYTHONPATH, or run the script through compat/run.py)")
     return ReferenceBackbone(conf, amp=amp, amp_dtype=amp_dtype, vit=vit, dino_weights=dino_weights, decoder=decoder, fpn=fpn,
-                             dino=dino, fpn_train_impl=fpn_train_impl, decoder_train_impl=decoder_train_impl)
+                             dino=dino, fpn_train_impl=fpn_train_impl, decoder_train_impl=decoder_train_impl, fpn_precision=fpn_precision)

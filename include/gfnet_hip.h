@@ -836,6 +836,28 @@ int gfn_conv2d_bn_act_fwd(const float *x0, int C0, int up0, const float *x1, int
                           const float *shift, const float *residual, float *out, int B, int H, int W, int Cout, int K, int stride,
                           int act, float slope, gfn_stream_t stream);
 
+/* The same layer in an fp16 CLASS, inference only; csrc/fpn_conv_half.hip: fp16 maps in memory as stored, the convolution an
+ * implicit GEMM on the matrix core (v_mfma_f32_16x16x32_f16 below 32 output channels, v_mfma_f32_32x32x16_f16 from there).
+ * x0, x1, residual, out: fp16, NCHW, contiguous, shapes and meaning (up0, x1, residual, K, stride, act, slope) as above; scale,
+ * shift (Cout) fp32.  residual may alias x0 or x1, out aliases nothing.
+ * weight: the (Cout, Cin, K, K) weight rounded ONCE to fp16 to nearest even and PACKED by the caller (ops.conv2d_pack_half) as
+ *   packed[co][cg][u][c] = weight[co][8 cg + c][u / K][u % K]     fp16, (CoutP, CG, UP, 8), 16-byte aligned
+ * in k-index order k = (cg UP + u) 8 + c: CG = ceil(Cin / 8) groups of eight input channels, u = ky K + kx the tap, UP = K K rounded
+ * up to a multiple of 4 (4, 12, 28, 52), CoutP = Cout rounded up to a multiple of 16 where Cout < 32 and of 32 otherwise.  Whatever
+ * lies past Cin, past K K or past Cout is ZERO.  Eight consecutive k -- one tap's eight channels -- are a lane's fragment of a
+ * matrix instruction, one aligned 16-byte read.
+ * Limits: those of gfn_conv2d_bn_act_fwd (per-image maps below 2^31 bytes, counted in fp16), and Cout a MULTIPLE OF 8: this class
+ * has no general kernel.  Anything else returns GFN_ERR_INVALID_ARG before a launch; B = 0 returns GFN_OK.  Batch offsets are
+ * 64-bit.  No atomics and a fixed order of sums: identical calls give identical bits.
+ * The class's arithmetic: products fp16 x fp16, exact in fp32; sums fp32 on the matrix core.  With up0 the coarse fp16 values are
+ * interpolated in fp32 in ATen's order of operations (as the fp32 entry does) and the result is rounded once to fp16 as the
+ * operand.  Scale, shift, activation and the residual add are fp32; ONE rounding to nearest even at the store; a value past 65504
+ * is stored as +-inf (nothing is clamped), as in the refiners' "amp" class.
+ * Not here: bf16 (nothing downstream reads bf16 maps as stored), training, Cout that is no multiple of 8. */
+int gfn_conv2d_bn_act_half_fwd(const void *x0, int C0, int up0, const void *x1, int C1, const void *weight, const float *scale,
+                               const float *shift, const void *residual, void *out, int B, int H, int W, int Cout, int K, int stride,
+                               int act, float slope, gfn_stream_t stream);
+
 /* The same layer in TRAINING mode (model.train(): the reference trains the whole FPN, trainer/train.py:108, through torch autograd);
  * csrc/fpn_conv_train.hip.  fp32, NCHW, contiguous, x = cat(x0, x1) with x0 (B, C0, H, W) and x1 (B, C1, H, W) or NULL with C1 = 0 (no
  * up0 in these three: x0 is read as it is; the gfn_conv2d_up_bn_act_train_* entry points below take the coarse map):

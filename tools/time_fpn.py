@@ -3,12 +3,16 @@
 library convolutions plus separate BatchNorm, activation, interpolate, cat and add launches that a checkout's FPN runs -- on the same
 parameters and inputs.
 
-    python tools/time_fpn.py [--images 64] [--sizes 448 560] [--rounds 7] [--reps 5] [--out fpn_timing.json]
+    python tools/time_fpn.py [--images 64] [--sizes 448 560] [--rounds 7] [--reps 5] [--precision fp32|fp16] [--out fpn_timing.json]
 
 Per size: every layer on its real input (the maps of one torch-path forward), then the whole pyramid (encoder, merge layer, decoder).
 The two paths ALTERNATE round by round; a round is `reps` back-to-back calls between two device events; reported per path are the
 median round and the spread (min .. max) over the rounds, in ms per call.  Every shape is warmed up on both paths first (the library
 picks its algorithms then).  The largest difference between the two paths' outputs at the timed size is printed beside the times.
+--precision fp16 adds two legs to the same alternation: "half", the HIP path in its fp16 class (conv_precision "fp16": fp16 maps, the
+matrix core, csrc/fpn_conv_half.hip) on fp16 inputs, and "torch_amp", the torch path under torch.autocast(dtype=float16) on the same
+fp16 inputs.  The fp32 HIP leg is the comparator of the fp16 class: the table gives fp32 HIP / half and torch_amp / half per layer and
+for the whole pyramid, and for the whole pyramid the gap between the two medians beside the larger min .. max spread of the two legs.
 Needs a GPU; nothing here falls back."""
 import argparse
 import json
@@ -39,26 +43,38 @@ def build(device):
     return mods
 
 
+PATHS = {"fp32": ("hip", "torch"), "fp16": ("half", "hip", "torch", "torch_amp")}
+
+
+def on_path(path, hip_call, torch_call):
+    """One call on a leg: hip_call(half) for "hip" / "half", torch_call() for "torch", and under fp16 autocast for "torch_amp"."""
+    if path in ("hip", "half"):
+        return hip_call(path == "half")
+    with torch.autocast("cuda", dtype=torch.float16, enabled=path == "torch_amp"):
+        return torch_call()
+
+
 def layer_calls(mods):
-    """[(name, inputs(ctx) -> tuple, call(hip, *inputs) -> map, key under which the map goes into ctx)] in forward order."""
+    """[(name, inputs(ctx) -> tuple, call(path, *inputs) -> map, key under which the map goes into ctx)] in forward order."""
     enc, dec, merge = mods["encoder"], mods["decoder"], mods["merge_layer"]
     calls, prev = [], "image"
     for name in ENCODER:
-        calls.append((name, (prev,), (lambda layer: lambda hip, x: layer.run(x, hip))(getattr(enc, name)), name))
+        calls.append((name, (prev,), (lambda layer: lambda path, x: on_path(path, lambda half: layer.run(x, True, half=half),
+                                                                            lambda: layer.run(x, False)))(getattr(enc, name)), name))
         prev = name
 
-    def run_merge(hip, c3, side):
-        merge.conv_impl = "hip" if hip else "torch"
-        return merge(c3, side)
+    def run_merge(path, c3, side):
+        merge.conv_impl = "hip" if path in ("hip", "half") else "torch"
+        merge.conv_precision = "fp16" if path == "half" else "fp32"
+        return on_path(path, lambda half: merge(c3, side), lambda: merge(c3, side))
 
     def head(seq):
-        return lambda hip, x: fpn._hip_layer(*fpn._head(seq), x) if hip else seq(x)
+        return lambda path, x: on_path(path, lambda half: fpn._hip_layer(*fpn._head(seq), x, half=half), lambda: seq(x))
 
     def inner(seq):
-        def run(hip, intra, skip):
-            if hip:
-                return fpn._hip_layer(*fpn._head(seq), intra, x1=skip, up0=True, residual=skip)
-            return skip + seq(torch.cat((fpn._up2(intra), skip), dim=1))
+        def run(path, intra, skip):
+            return on_path(path, lambda half: fpn._hip_layer(*fpn._head(seq), intra, x1=skip, up0=True, residual=skip, half=half),
+                           lambda: skip + seq(torch.cat((fpn._up2(intra), skip), dim=1)))
         return run
 
     calls.append(("merge_layer", ("conv31", "side"), run_merge, "merged"))
@@ -72,25 +88,29 @@ def layer_calls(mods):
     return calls
 
 
-def pyramid(mods, hip, image, side):
+def pyramid(mods, path, image, side):
     for m in mods.values():
-        m.conv_impl = "hip" if hip else "torch"
-    c0, c1, c2, c3 = mods["encoder"](image)
-    return mods["decoder"](c0, c1, c2, mods["merge_layer"](c3, side))
+        m.conv_impl = "hip" if path in ("hip", "half") else "torch"
+        m.conv_precision = "fp16" if path == "half" else "fp32"
+
+    def run():
+        c0, c1, c2, c3 = mods["encoder"](image)
+        return mods["decoder"](c0, c1, c2, mods["merge_layer"](c3, side))
+    return on_path(path, lambda half: run(), run)
 
 
-def time_pair(fn, rounds, reps):
-    """fn(hip) timed on both paths, alternating: {"hip": [ms per call, one per round], "torch": [...]}."""
-    out = {"hip": [], "torch": []}
-    for hip in (True, False, True, False):  # warm-up: code objects, algorithm choice, allocator
-        fn(hip)
+def time_pair(fn, rounds, reps, paths=PATHS["fp32"]):
+    """fn(path) timed on every leg, alternating round by round: {leg: [ms per call, one per round]}."""
+    out = {path: [] for path in paths}
+    for path in paths + paths:  # warm-up: code objects, algorithm choice, allocator
+        fn(path)
     torch.cuda.synchronize()
     for _ in range(rounds):
-        for path in ("hip", "torch"):
+        for path in paths:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(reps):
-                fn(path == "hip")
+                fn(path)
             e1.record()
             e1.synchronize()
             out[path].append(e0.elapsed_time(e1) / reps)
@@ -107,6 +127,7 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[448, 560])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--precision", choices=sorted(PATHS), default="fp32", help="fp16: add the fp16 class and torch's fp16 autocast as legs")
     ap.add_argument("--out", default=None, help="write the numbers as JSON here")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -114,23 +135,30 @@ def main():
     dev = torch.device("cuda")
     mods = build(dev)
     calls = layer_calls(mods)
-    result = {"device": torch.cuda.get_device_name(0), "images": args.images, "rounds": args.rounds, "reps": args.reps, "sizes": {}}
+    paths, fp16 = PATHS[args.precision], args.precision == "fp16"
+    result = {"device": torch.cuda.get_device_name(0), "images": args.images, "rounds": args.rounds, "reps": args.reps,
+              "precision": args.precision, "sizes": {}}
     with torch.no_grad():
         for size in args.sizes:
             g = torch.Generator(device=dev).manual_seed(size)
             ctx = {"image": torch.rand((args.images, 3, size, size), device=dev, generator=g) * 2 - 1,
                    "side": torch.randn((args.images, FEAT_CHS[-1], size // 8, size // 8), device=dev, generator=g) * 0.5}
+            ctx16 = {k: v.half() for k, v in ctx.items()}  # the fp16 legs' inputs: the maps of one forward of the fp16 class
             rows, worst = {}, 0.0
             for name, keys, call, key in calls:
                 inputs = tuple(ctx[k] for k in keys)
-                ctx[key] = call(False, *inputs)
-                diff = float((call(True, *inputs) - ctx[key]).abs().max())
+                ctx[key] = call("torch", *inputs)
+                diff = float((call("hip", *inputs) - ctx[key]).abs().max())
                 worst = max(worst, diff)
-                t = time_pair(lambda hip: call(hip, *inputs), args.rounds, args.reps)
-                rows[name] = {"hip": summary(t["hip"]), "torch": summary(t["torch"]), "max_abs_diff": diff,
-                              "shape": list(ctx[key].shape)}
-            t = time_pair(lambda hip: pyramid(mods, hip, ctx["image"], ctx["side"]), args.rounds, args.reps)
-            total = {"hip": summary(t["hip"]), "torch": summary(t["torch"])}
+                if fp16:
+                    inputs16 = tuple(ctx16[k] for k in keys)
+                    ctx16[key] = call("half", *inputs16)
+                t = time_pair(lambda path: call(path, *(inputs16 if path in ("half", "torch_amp") else inputs)), args.rounds, args.reps, paths)
+                rows[name] = dict({path: summary(t[path]) for path in paths}, max_abs_diff=diff, shape=list(ctx[key].shape))
+                if fp16:
+                    rows[name]["half_max_abs_diff"] = float((ctx16[key].float() - ctx[key]).abs().max())
+            t = time_pair(lambda path: pyramid(mods, path, ctx["image"], ctx["side"]), args.rounds, args.reps, paths)
+            total = {path: summary(t[path]) for path in paths}
             result["sizes"][str(size)] = {"layers": rows, "total": total, "max_abs_diff": worst}
             print(f"\n{args.images} images of {size} x {size} on {result['device']}: ms per call, median (min .. max) of {args.rounds} rounds of {args.reps}")
             print("| layer | output | HIP | torch | torch / HIP |\n|---|---|---|---|---|")
@@ -139,7 +167,19 @@ def main():
                 print(f"| {name} | {'x'.join(str(v) for v in r['shape'][1:])} | {h['median_ms']:.3f} ({h['min_ms']:.3f} .. {h['max_ms']:.3f}) | "
                       f"{c['median_ms']:.3f} ({c['min_ms']:.3f} .. {c['max_ms']:.3f}) | {c['median_ms'] / h['median_ms']:.2f} |")
             print(f"largest difference between the two paths over all layers: {worst:.3e}")
-            del ctx
+            if fp16:
+                print("\n| layer | half (fp16 class) | fp32 HIP | torch fp16 autocast | fp32 HIP / half | autocast / half |\n|---|---|---|---|---|---|")
+                for name, r in list(rows.items()) + [("whole pyramid", total)]:
+                    cells = [f"{r[p]['median_ms']:.3f} ({r[p]['min_ms']:.3f} .. {r[p]['max_ms']:.3f})" for p in ("half", "hip", "torch_amp")]
+                    print(f"| {name} | {' | '.join(cells)} | {r['hip']['median_ms'] / r['half']['median_ms']:.2f} | "
+                          f"{r['torch_amp']['median_ms'] / r['half']['median_ms']:.2f} |")
+                gap = total["hip"]["median_ms"] - total["half"]["median_ms"]
+                spread = max(total[p]["max_ms"] - total[p]["min_ms"] for p in ("hip", "half"))
+                result["sizes"][str(size)]["gate"] = {"gap_ms": gap, "spread_ms": spread, "met": gap > spread}
+                print(f"whole pyramid: fp32 HIP median - half median = {gap:.3f} ms, larger min .. max spread of the two legs {spread:.3f} ms: "
+                      f"the fp16 class is {'faster beyond the spread' if gap > spread else 'NOT faster beyond the spread'}")
+                print(f"largest |half - torch fp32| over all layers: {max(r['half_max_abs_diff'] for r in rows.values()):.3e}")
+            del ctx, ctx16
             torch.cuda.empty_cache()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
