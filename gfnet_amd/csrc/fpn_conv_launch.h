@@ -3,6 +3,7 @@
 // (conv_tile_kernel for Cout a multiple of 8, conv_general_kernel otherwise).  The kernels themselves are instantiated once, in
 // fpn_conv.hip; the training path runs them with scale = 1 and shift = 0 (fmaf(acc, 1, 0) is acc, bit for bit) for the raw
 // convolution output u and, on the stride-1 layers, for the input gradient (the same convolution of gu with repacked weights).
+// fpn_conv_tf32_launch is the same seam in the TF32 class (fpn_conv_tf32.hip), which the gfn_conv2d_bn_act_train_tf32_* entry points take.
 #pragma once
 #include <cmath>
 
@@ -56,5 +57,15 @@ __device__ __forceinline__ float up2_blend(const Up2Taps &t, float v00, float v0
 
 // the kernel for (K, stride, a.Cout) on stream s; the caller has checked the sizes (gfn_conv2d_bn_act_fwd's limits)
 int fpn_conv_launch(const ConvArgs &a, int B, int K, int stride, hipStream_t s);
+
+// The same convolution in the TF32 class (fpn_conv_tf32.hip): split-bf16 operands on the matrix core, fp32 maps, fp32 sums and epilogue.
+// a.weight is the plain fp32 (a.Cout, a.C0 + a.C1, K, K) weight; it is split and packed into `pack` (fpn_conv_tf32_pack_bytes bytes of
+// 16-byte aligned device memory) by one small launch in front of the convolution.  a.Cout must be a multiple of 8.
+int64_t fpn_conv_tf32_pack_bytes(int Cout, int Cin, int K);
+int fpn_conv_tf32_launch(const ConvArgs &a, int B, int K, int stride, void *pack, hipStream_t s);
+// The stride-1 weight gradient in that class: `parts` partial (Cout, C0 + C1, K, K) gradients into `part`, cut up as fpn_conv_train.hip's
+// WgradShape says (8 x 32 pixel tiles, `cig` input channels per workgroup, cig K K <= 256), for ft_wsum_kernel to add up
+int fpn_wgrad_tf32_launch(const float *x0, const float *x1, const float *gu, float *part, int C0, int C1, int H, int W, int Cout, int K, int IH,
+                          int IW, int PITCH, int cig, int nci, int parts, int tiles_x, int tiles_y, int64_t ntiles, hipStream_t s);
 
 }  // namespace gfn

@@ -26,6 +26,10 @@
 //                           footprint of the tile goes into LDS first and the halo tile of an x0 channel is interpolated from it
 //                           with up2_at's operations (fpn_conv_launch.h), so that it holds what the forward's staging held.
 // Every sum has a fixed order and there are no floating-point atomics: identical calls give identical bits.
+// The TF32 class (gfn_conv2d_bn_act_train_tf32_*): the same launches with u and the stride-1 input gradient by fpn_conv_tf32.hip's
+// kernels wherever the launch's output channels are a multiple of 8 (conv() below), and the weight gradient under stride 1 without up0
+// by that file's wgrad_tf32_kernel (the same partials, the same ft_wsum_kernel); ft_gather_s2_kernel, ft_wgrad_kernel under stride 2 and
+// up0, and the BatchNorm passes are reused as they are, so those gradients stay exact fp32.
 #include <algorithm>
 
 #include "conv_train_common.h"
@@ -442,18 +446,24 @@ struct Plan {
     WgradShape wg;
     int64_t off_ident, fwd_floats;                                        // forward: part, ident
     int64_t off_dgdb, off_gu, off_wt, off_wpart, off_gx0f, bwd_floats;    // backward: part, ident, dgdb, gu, wt, wpart; up0: the gradient of x0'
+    int64_t off_pack_fwd, off_pack_bwd;                                   // the TF32 class: the split and packed weight, last in both
 
-    Plan(int C0, int C1, int B, int H, int W, int Cout, int K, int S, int up0)
+    Plan(int C0, int C1, int B, int H, int W, int Cout, int K, int S, int up0, int tf32)
         : Cin(C0 + C1), Ho((H + S - 1) / S), Wo((W + S - 1) / S), HW(Ho * Wo), red_chunks((HW + kRed - 1) / kRed), nparts(B * red_chunks),
           ew_chunks((HW + kEw - 1) / kEw), nident(std::max(Cout, std::max(C0, C1))), wg(B, C0 + C1, Cout, Ho, Wo, K, S, up0) {
         off_ident = align4((int64_t)Cout * nparts * 2);
         fwd_floats = off_ident + align4(2 * (int64_t)nident);
-        off_dgdb = fwd_floats;
+        off_dgdb = fwd_floats;  // (before the TF32 class's packed weight is added to it below)
         off_gu = off_dgdb + align4(2 * (int64_t)Cout);
         off_wt = off_gu + align4((int64_t)B * Cout * HW);
         off_wpart = off_wt + align4(wg.wn);
         off_gx0f = off_wpart + align4((int64_t)wg.parts * wg.wn);
         bwd_floats = off_gx0f + (up0 ? align4((int64_t)B * C0 * H * W) : 0);
+        // one packed weight at a time: the forward's, then the input gradient's for x0 and for x1 (the roles of Cout and Cin swapped)
+        const int64_t pack = !tf32 ? 0 : align4(std::max(gfn::fpn_conv_tf32_pack_bytes(Cout, Cin, K),
+                                                         gfn::fpn_conv_tf32_pack_bytes(std::max(C0, C1), Cout, K)) / (int64_t)sizeof(float));
+        off_pack_fwd = fwd_floats, off_pack_bwd = bwd_floats;
+        fwd_floats += pack, bwd_floats += pack;
     }
 };
 
@@ -489,17 +499,23 @@ int check_sizes(const char *what, int C0, int C1, int B, int H, int W, int Cout,
     return GFN_OK;
 }
 
-int64_t train_ws_bytes(int C0, int C1, int B, int H, int W, int Cout, int K, int stride, int backward, int up0) {
+// The convolution of either class: with tf32 on the matrix core (fpn_conv_tf32.hip) where that class has a kernel, Cout a multiple of 8;
+// every other Cout -- an input gradient's is C0 or C1 of the layer -- on the fp32 kernels, whose exact products lie within the class
+int conv(const ConvArgs &a, int B, int K, int stride, int tf32, void *pack, hipStream_t s) {
+    return tf32 && a.Cout % 8 == 0 ? gfn::fpn_conv_tf32_launch(a, B, K, stride, pack, s) : gfn::fpn_conv_launch(a, B, K, stride, s);
+}
+
+int64_t train_ws_bytes(int C0, int C1, int B, int H, int W, int Cout, int K, int stride, int backward, int up0, int tf32 = 0) {
     if (C0 < 1 || C1 < 0 || B < 1 || H < 1 || W < 1 || Cout < 1 || (K != 1 && K != 3 && K != 5 && K != 7) || (stride != 1 && stride != 2)) return 0;
     if (!up0_fits(up0, H, W, stride)) return 0;
-    const Plan p(C0, C1, B, H, W, Cout, K, stride, up0);
+    const Plan p(C0, C1, B, H, W, Cout, K, stride, up0, tf32);
     return (backward ? p.bwd_floats : p.fwd_floats) * (int64_t)sizeof(float);
 }
 
 int train_fwd(const char *what, const float *x0, int C0, int up0, const float *x1, int C1, const float *weight, const float *conv_bias,
               const float *bn_w, const float *bn_b, float *running_mean, float *running_var, const float *residual, float *u, float *mean,
               float *invstd, float *out, int B, int H, int W, int Cout, int K, int stride, int act, float slope, double momentum, double eps,
-              void *ws, int64_t ws_bytes, gfn_stream_t stream) {
+              void *ws, int64_t ws_bytes, gfn_stream_t stream, int tf32 = 0) {
     if (int rc = check_sizes(what, C0, C1, B, H, W, Cout, K, stride, act, up0)) return rc;
     if (!(momentum >= 0.0 && momentum <= 1.0) || !(eps >= 0.0))
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: momentum must lie in [0, 1] and eps be >= 0", what);
@@ -508,7 +524,7 @@ int train_fwd(const char *what, const float *x0, int C0, int up0, const float *x
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: null pointer", what);
     if (u == out || u == x0 || u == x1 || out == x0 || out == x1)
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: u and out must be maps of their own", what);
-    const Plan p(C0, C1, B, H, W, Cout, K, stride, up0);
+    const Plan p(C0, C1, B, H, W, Cout, K, stride, up0, tf32);
     if (int rc = check_workspace(what, ws, ws_bytes, p.fwd_floats)) return rc;
     hipStream_t s = (hipStream_t)stream;
     float *part = static_cast<float *>(ws), *ident = part + p.off_ident;
@@ -516,7 +532,7 @@ int train_fwd(const char *what, const float *x0, int C0, int up0, const float *x
     hipLaunchKernelGGL(ft_identity_kernel, dim3(1), dim3(64), 0, s, ident, p.nident);
     if (int rc = gfn::check_launch("ft_identity_kernel")) return rc;
     const ConvArgs a{x0, x1, weight, ident, ident + p.nident, nullptr, u, C0, C1, up0, H, W, Cout, p.Ho, p.Wo, 0, 0.f};
-    if (int rc = gfn::fpn_conv_launch(a, B, K, stride, s)) return rc;
+    if (int rc = conv(a, B, K, stride, tf32, part + p.off_pack_fwd, s)) return rc;
     hipLaunchKernelGGL(ft_moments_kernel, dim3((unsigned)(Cout * p.nparts)), dim3(256), 0, s, (const float *)u, part, Cout, p.HW, p.red_chunks,
                        p.nparts);
     if (int rc = gfn::check_launch("ft_moments_kernel")) return rc;
@@ -537,7 +553,7 @@ int train_fwd(const char *what, const float *x0, int C0, int up0, const float *x
 int train_bwd(const char *what, const float *gy, const float *x0, int C0, int up0, const float *x1, int C1, const float *weight,
               const float *bn_w, const float *bn_b, const float *u, const float *mean, const float *invstd, float *gx0, float *gx1,
               float *d_weight, float *d_bn_w, float *d_bn_b, int B, int H, int W, int Cout, int K, int stride, int act, float slope, int need,
-              void *ws, int64_t ws_bytes, gfn_stream_t stream) {
+              void *ws, int64_t ws_bytes, gfn_stream_t stream, int tf32 = 0) {
     if (int rc = check_sizes(what, C0, C1, B, H, W, Cout, K, stride, act, up0)) return rc;
     const int all = GFN_CBT_NEED_X | GFN_CBT_NEED_W | GFN_CBT_NEED_BN;
     if (need < 0 || (need & ~all)) return gfn::fail(GFN_ERR_INVALID_ARG, "%s: unknown need mask %d", what, need);
@@ -547,7 +563,7 @@ int train_bwd(const char *what, const float *gy, const float *x0, int C0, int up
     if (((need & GFN_CBT_NEED_X) && (!gx0 || (C1 > 0 && !gx1))) || ((need & GFN_CBT_NEED_W) && !d_weight) ||
         ((need & GFN_CBT_NEED_BN) && (!d_bn_w || !d_bn_b)))
         return gfn::fail(GFN_ERR_INVALID_ARG, "%s: the need mask asks for a gradient whose pointer is null", what);
-    const Plan p(C0, C1, B, H, W, Cout, K, stride, up0);
+    const Plan p(C0, C1, B, H, W, Cout, K, stride, up0, tf32);
     if (int rc = check_workspace(what, ws, ws_bytes, p.bwd_floats)) return rc;
     hipStream_t s = (hipStream_t)stream;
     float *w = static_cast<float *>(ws);
@@ -574,7 +590,7 @@ int train_bwd(const char *what, const float *gy, const float *x0, int C0, int up
             if (int rc = gfn::check_launch("ft_repack_kernel")) return rc;
             float *gx0f = up0 ? w + p.off_gx0f : gx0;  // the gradient of what the convolution read: x0, or with up0 its doubled image
             const ConvArgs a0{gu, nullptr, wt, ident, ident + p.nident, nullptr, gx0f, Cout, 0, 0, H, W, C0, H, W, 0, 0.f};
-            if (int rc = gfn::fpn_conv_launch(a0, B, K, 1, s)) return rc;
+            if (int rc = conv(a0, B, K, 1, tf32, w + p.off_pack_bwd, s)) return rc;
             if (up0) {
                 const int64_t total = (int64_t)B * C0 * (H / 2) * (W / 2);
                 hipLaunchKernelGGL(ft_up2_adjoint_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float *)gx0f, gx0, total,
@@ -583,7 +599,7 @@ int train_bwd(const char *what, const float *gy, const float *x0, int C0, int up
             }
             if (C1 > 0) {
                 const ConvArgs a1{gu, nullptr, wt + (int64_t)C0 * Cout * K * K, ident, ident + p.nident, nullptr, gx1, Cout, 0, 0, H, W, C1, H, W, 0, 0.f};
-                if (int rc = gfn::fpn_conv_launch(a1, B, K, 1, s)) return rc;
+                if (int rc = conv(a1, B, K, 1, tf32, w + p.off_pack_bwd, s)) return rc;
             }
         } else {
             const int chunks = (((H + 1) / 2) * ((W + 1) / 2) + 255) / 256;
@@ -596,6 +612,13 @@ int train_bwd(const char *what, const float *gy, const float *x0, int C0, int up
         const WgradShape &g = p.wg;
         const dim3 grid((unsigned)g.parts, (unsigned)g.nci, (unsigned)g.nco);
         const size_t lds = (size_t)g.lds_floats() * sizeof(float);
+        if (tf32 && stride == 1 && !up0) {  // the class's own weight gradient; stride 2 and up0 stay on ft_wgrad_kernel
+            if (int rc = gfn::fpn_wgrad_tf32_launch(x0, x1, gu, wpart, C0, C1, H, W, Cout, K, g.IH, g.IW, g.PITCH, g.cig, g.nci, g.parts, g.tiles_x,
+                                                    g.tiles_y, g.ntiles, s))
+                return rc;
+            hipLaunchKernelGGL(ft_wsum_kernel, dim3((unsigned)((g.wn + 255) / 256)), dim3(256), 0, s, (const float *)wpart, g.parts, g.wn, d_weight);
+            return gfn::check_launch("ft_wsum_kernel");
+        }
         auto kernel = ft_wgrad_kernel<false, 0>;
         if (up0) kernel = K == 1 ? ft_wgrad_kernel<true, 1> : K == 3 ? ft_wgrad_kernel<true, 3> : K == 5 ? ft_wgrad_kernel<true, 5> : ft_wgrad_kernel<true, 7>;
         hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, x0, x1, (const float *)gu, wpart, C0, C1, H, W, Cout, p.Ho, p.Wo, K, stride, g.IH,
@@ -654,3 +677,28 @@ GFN_EXPORT int gfn_conv2d_up_bn_act_train_bwd(const float *gy, const float *x0, 
                      d_weight, d_bn_w, d_bn_b, B, H, W, Cout, K, stride, act, slope, need, ws, ws_bytes, stream);
 }
 
+
+// The TF32 class of the four pairs above in one set (include/gfnet_hip.h): the same launches with the forward convolution and the
+// stride-1 input gradient on fpn_conv_tf32.hip's kernels
+GFN_EXPORT int64_t gfn_conv2d_bn_act_train_tf32_ws_bytes(int C0, int up0, int C1, int B, int H, int W, int Cout, int K, int stride,
+                                                         int backward) {
+    return train_ws_bytes(C0, C1, B, H, W, Cout, K, stride, backward, up0 ? 1 : 0, 1);
+}
+
+GFN_EXPORT int gfn_conv2d_bn_act_train_tf32_fwd(const float *x0, int C0, int up0, const float *x1, int C1, const float *weight,
+                                                const float *conv_bias, const float *bn_w, const float *bn_b, float *running_mean,
+                                                float *running_var, const float *residual, float *u, float *mean, float *invstd, float *out,
+                                                int B, int H, int W, int Cout, int K, int stride, int act, float slope, double momentum,
+                                                double eps, void *ws, int64_t ws_bytes, gfn_stream_t stream) {
+    return train_fwd("gfn_conv2d_bn_act_train_tf32_fwd", x0, C0, up0 ? 1 : 0, x1, C1, weight, conv_bias, bn_w, bn_b, running_mean, running_var,
+                     residual, u, mean, invstd, out, B, H, W, Cout, K, stride, act, slope, momentum, eps, ws, ws_bytes, stream, 1);
+}
+
+GFN_EXPORT int gfn_conv2d_bn_act_train_tf32_bwd(const float *gy, const float *x0, int C0, int up0, const float *x1, int C1, const float *weight,
+                                                const float *bn_w, const float *bn_b, const float *u, const float *mean, const float *invstd,
+                                                float *gx0, float *gx1, float *d_weight, float *d_bn_w, float *d_bn_b, int B, int H, int W,
+                                                int Cout, int K, int stride, int act, float slope, int need, void *ws, int64_t ws_bytes,
+                                                gfn_stream_t stream) {
+    return train_bwd("gfn_conv2d_bn_act_train_tf32_bwd", gy, x0, C0, up0 ? 1 : 0, x1, C1, weight, bn_w, bn_b, u, mean, invstd, gx0, gx1,
+                     d_weight, d_bn_w, d_bn_b, B, H, W, Cout, K, stride, act, slope, need, ws, ws_bytes, stream, 1);
+}

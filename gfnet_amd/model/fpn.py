@@ -32,7 +32,7 @@ Three paths over the same parameters:
     F.conv2d, BatchNorm, the activation, F.interpolate and torch.cat, as the reference writes them; differentiable, and the
     BatchNorm buffers move as in the reference.
 
-The top-level module's conv_impl, train_conv_impl and conv_precision govern its children (run(x, hip, train_hip, half)).
+The top-level module's conv_impl, train_conv_impl and conv_precision govern its children (run(x, hip, train_hip, half, tf32)).
 
 conv_precision "fp32" (the default, all of the above) or "fp16": an opt-in fp16 CLASS of the first path, and of that path only.
 Exactly where the fp32 HIP path runs -- eval(), CUDA, conv_impl "hip" -- every layer is then ONE ops.conv2d_bn_act_half launch
@@ -42,6 +42,26 @@ value), and EVERY RETURNED MAP IS fp16 -- the dtype of the result differs from t
 no multiple of 8) raises NotImplementedError naming the layer.  train(), CPU tensors and conv_impl "torch" run what they run under
 "fp32", in fp32, whatever conv_precision says.  The reference runs its FPN in fp32 outside autocast: "fp16" is this package's
 option, not the reference's arithmetic.
+
+conv_precision takes the values of ALL_CONV_PRECISIONS ("fp32", "fp16", "tf32"); CONV_PRECISIONS is the pair of them that governs
+eval() alone and keeps its older value.
+
+conv_precision "tf32": the reference's own class, opt-in, for BOTH HIP paths.  The reference runs its FPN in fp32 tensors with
+cuDNN's TF32 convolutions (train.py:151 sets torch.backends.cudnn.allow_tf32, torch's default for convolutions): fp32 maps, the
+operands of each product rounded, fp32 sums.  gfx950 has no TF32 matrix instruction, so the class is split-bf16 on the bf16 one, as
+include/gfnet_hip.h states it once:
+
+    the split of an fp32 value v: hi = bf16(v) to nearest even, lo = bf16(v - hi), lo = 0 where hi is not finite (an inf stays an inf);
+    a product a b is a_hi b_hi + a_hi b_lo + a_lo b_hi, each exact in fp32 and summed in fp32 on the matrix core; a_lo b_lo is dropped;
+    with up0 the interpolated value is computed in fp32 as today and then split; scale, shift, activation, residual and every map fp32.
+
+The error against exact arithmetic is at most 3 * 2^-16 * sum |a| |b| per output before fp32 accumulation, against TF32's 2^-10.
+Exactly where _use_hip is true every layer is ONE ops.conv2d_bn_act_tf32 launch (csrc/fpn_conv_tf32.hip), fp32 in and out; under
+train_conv_impl "hip" and "hip_fused" every layer passes precision="tf32" to ops.conv2d_bn_act_train, which runs the forward
+convolution, the stride-1 input gradient and the stride-1 weight gradient (without up0) in the class and leaves the stride-2 input
+gradient and the stride-2 and up0 weight gradients on the fp32 kernels.  A layer whose Cout is not a multiple of 8 (GFNet builds none) runs the fp32 kernels silently in both modes.  Nothing
+downstream changes: the maps, autograd's saved tensors and the BatchNorm passes are those of "fp32".  CPU tensors and the torch
+paths run what they run under "fp32".
 """
 import torch
 import torch.nn as nn
@@ -51,7 +71,12 @@ from .. import ops
 
 CONV_IMPLS = ("hip", "torch")
 TRAIN_CONV_IMPLS = ("hip", "hip_fused", "torch")  # "hip_fused": "hip" with the decoder's 2x upsample inside the innerN op
-CONV_PRECISIONS = ("fp32", "fp16")  # "fp16": fp16 maps and the matrix core on the eval() HIP path (module docstring)
+# The values conv_precision takes are ALL_CONV_PRECISIONS: that is the tuple to validate against and to offer as choices.
+# CONV_PRECISIONS is the older, shorter tuple kept under its name and value for callers that hold it: the classes that govern eval()
+# ALONE ("fp16": fp16 maps and the matrix core on the eval() HIP path).  "tf32" (fp32 maps, split-bf16 operands on the matrix core)
+# governs the eval() AND the train() HIP paths (module docstring)
+CONV_PRECISIONS = ("fp32", "fp16")
+ALL_CONV_PRECISIONS = CONV_PRECISIONS + ("tf32",)
 LEAKY_SLOPE = 0.1  # FPN.py:127
 
 
@@ -68,8 +93,8 @@ def _check_train_impl(train_conv_impl):
 
 
 def _check_precision(conv_precision):
-    if conv_precision not in CONV_PRECISIONS:
-        raise ValueError(f"conv_precision must be one of {CONV_PRECISIONS}, got {conv_precision!r}")
+    if conv_precision not in ALL_CONV_PRECISIONS:
+        raise ValueError(f"conv_precision must be one of {ALL_CONV_PRECISIONS}, got {conv_precision!r}")
     return conv_precision
 
 
@@ -78,6 +103,11 @@ def _use_half(module, x):
     _check_impl(module.conv_impl)
     return (_check_precision(module.conv_precision) == "fp16" and module.conv_impl == "hip" and not module.training and x.is_cuda
             and x.dtype in (torch.float32, torch.float16))
+
+
+def _use_tf32(module):
+    """The TF32 class: wherever a HIP path runs, eval() or train(), that path's convolutions in that class."""
+    return _check_precision(module.conv_precision) == "tf32"
 
 
 def _use_hip(module, x):
@@ -115,7 +145,7 @@ def _check_conv(conv, switch):
                                   f"and no groups; got {conv}: construct with {switch}='torch'")
 
 
-def _hip_train_layer(conv, bn, act, x0, x1=None, residual=None, up0=False):
+def _hip_train_layer(conv, bn, act, x0, x1=None, residual=None, up0=False, tf32=False):
     """One layer on the batch's own statistics through ops.conv2d_bn_act_train; where the layer upsamples x0 is the doubled map, or
     with up0 the coarse one."""
     _check_conv(conv, "train_conv_impl")
@@ -125,10 +155,10 @@ def _hip_train_layer(conv, bn, act, x0, x1=None, residual=None, up0=False):
     x0, x1, residual = (None if t is None else t.contiguous() for t in (x0, x1, residual))
     return ops.conv2d_bn_act_train(x0, conv.weight.contiguous(), conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                    bn.num_batches_tracked, bn.momentum, bn.eps, x1=x1, residual=residual, stride=conv.stride[0], act=act,
-                                   slope=LEAKY_SLOPE, up0=up0)
+                                   slope=LEAKY_SLOPE, up0=up0, precision="tf32" if tf32 else "fp32")
 
 
-def _hip_layer(conv, bn, act, x0, x1=None, up0=False, residual=None, half=False):
+def _hip_layer(conv, bn, act, x0, x1=None, up0=False, residual=None, half=False, tf32=False):
     _check_conv(conv, "conv_impl")
     scale, shift = _fold(conv, bn)
     x0, x1, residual = (None if t is None else t.contiguous() for t in (x0, x1, residual))
@@ -138,6 +168,9 @@ def _hip_layer(conv, bn, act, x0, x1=None, up0=False, residual=None, half=False)
                                       "construct with conv_precision='fp32'")
         return ops.conv2d_bn_act_half(x0, conv.weight.detach().contiguous(), scale.float(), shift.float(), x1=x1, up0=up0,
                                       residual=residual, stride=conv.stride[0], act=act, slope=LEAKY_SLOPE)
+    if tf32 and conv.out_channels % 8 == 0:  # (any other layer runs the fp32 op: exact products lie within the class)
+        return ops.conv2d_bn_act_tf32(x0, conv.weight.detach().contiguous(), scale, shift, x1=x1, up0=up0, residual=residual,
+                                      stride=conv.stride[0], act=act, slope=LEAKY_SLOPE)
     return ops.conv2d_bn_act(x0, conv.weight.detach().contiguous(), scale, shift, x1=x1, up0=up0, residual=residual, stride=conv.stride[0],
                              act=act, slope=LEAKY_SLOPE)
 
@@ -170,11 +203,11 @@ class Conv2d(nn.Module):
         self.bn = nn.BatchNorm2d(out_channels, momentum=bn_momentum) if bn else None
         self.relu = relu
 
-    def run(self, x, hip, train_hip=False, half=False):
+    def run(self, x, hip, train_hip=False, half=False, tf32=False):
         if hip:
-            return _hip_layer(self.conv, self.bn, "leaky_relu" if self.relu else None, x.half() if half else x, half=half)
+            return _hip_layer(self.conv, self.bn, "leaky_relu" if self.relu else None, x.half() if half else x, half=half, tf32=tf32)
         if train_hip:
-            return _hip_train_layer(self.conv, self.bn, "leaky_relu" if self.relu else None, x)
+            return _hip_train_layer(self.conv, self.bn, "leaky_relu" if self.relu else None, x, tf32=tf32)
         y = self.conv(x)
         if self.bn is not None:
             y = self.bn(y)
@@ -182,7 +215,7 @@ class Conv2d(nn.Module):
 
     def forward(self, x):
         half = _use_half(self, x)
-        return self.run(x, half or _use_hip(self, x), _use_train_hip(self, x), half)
+        return self.run(x, half or _use_hip(self, x), _use_train_hip(self, x), half, _use_tf32(self))
 
 
 class FPNEncoder(nn.Module):
@@ -217,11 +250,11 @@ class FPNEncoder(nn.Module):
         if x.dim() != 4 or x.shape[2] % 8 or x.shape[3] % 8:
             raise ValueError(f"FPNEncoder: height and width must be multiples of 8, got an input of shape {tuple(x.shape)}")
         half = _use_half(self, x)  # (the image is cast to fp16 by the first layer's run, every later map already is)
-        hip, th = half or _use_hip(self, x), _use_train_hip(self, x)
-        conv01 = self.conv01.run(self.conv00.run(x, hip, th, half), hip, th, half)
-        conv11 = self.conv11.run(self.conv10.run(self.downsample1.run(conv01, hip, th, half), hip, th, half), hip, th, half)
-        conv21 = self.conv21.run(self.conv20.run(self.downsample2.run(conv11, hip, th, half), hip, th, half), hip, th, half)
-        conv31 = self.conv31.run(self.conv30.run(self.downsample3.run(conv21, hip, th, half), hip, th, half), hip, th, half)
+        mode = (half or _use_hip(self, x), _use_train_hip(self, x), half, _use_tf32(self))
+        conv01 = self.conv01.run(self.conv00.run(x, *mode), *mode)
+        conv11 = self.conv11.run(self.conv10.run(self.downsample1.run(conv01, *mode), *mode), *mode)
+        conv21 = self.conv21.run(self.conv20.run(self.downsample2.run(conv11, *mode), *mode), *mode)
+        conv31 = self.conv31.run(self.conv30.run(self.downsample3.run(conv21, *mode), *mode), *mode)
         return [conv01, conv11, conv21, conv31]
 
 
@@ -246,9 +279,9 @@ class merge_layer(nn.Sequential):
             conv31 = conv31.half()
             return _hip_layer(*_head(self), conv31, x1=side.half(), residual=conv31, half=True)
         if _use_hip(self, conv31) and side.is_cuda and side.dtype == torch.float32:
-            return _hip_layer(*_head(self), conv31, x1=side, residual=conv31)
+            return _hip_layer(*_head(self), conv31, x1=side, residual=conv31, tf32=_use_tf32(self))
         if _use_train_hip(self, conv31) and side.is_cuda and side.dtype == torch.float32:
-            return _hip_train_layer(*_head(self), conv31, x1=side, residual=conv31)
+            return _hip_train_layer(*_head(self), conv31, x1=side, residual=conv31, tf32=_use_tf32(self))
         return conv31 + nn.Sequential.forward(self, torch.cat((conv31, side), dim=1))
 
 
@@ -288,18 +321,20 @@ class FPNDecoder_concat(nn.Module):
             maps = (conv31, conv21, conv11, conv01)
         hip = half or (_use_hip(self, conv31) and all(m.is_cuda and m.dtype == torch.float32 for m in maps))
         th = _use_train_hip(self, conv31) and all(m.is_cuda and m.dtype == torch.float32 for m in maps)
+        tf32 = _use_tf32(self)
         intra = conv31
         outs = []
         for inner, out, skip in ((None, self.out0, None), (self.inner1, self.out1, conv21), (self.inner2, self.out2, conv11),
                                  (self.inner3, self.out3, conv01)):
             if inner is not None:  # FPN.py:59: skip + inner(cat(interpolate(intra), skip))
                 if hip:
-                    intra = _hip_layer(*_head(inner), intra, x1=skip, up0=True, residual=skip, half=half)
+                    intra = _hip_layer(*_head(inner), intra, x1=skip, up0=True, residual=skip, half=half, tf32=tf32)
                 elif th and self.train_conv_impl == "hip_fused":  # the upsample inside the op, in both directions
-                    intra = _hip_train_layer(*_head(inner), intra, x1=skip, residual=skip, up0=True)
+                    intra = _hip_train_layer(*_head(inner), intra, x1=skip, residual=skip, up0=True, tf32=tf32)
                 elif th:  # the doubled map from torch, which differentiates the upsample; still no concatenation
-                    intra = _hip_train_layer(*_head(inner), _up2(intra), x1=skip, residual=skip)
+                    intra = _hip_train_layer(*_head(inner), _up2(intra), x1=skip, residual=skip, tf32=tf32)
                 else:
                     intra = skip + inner(torch.cat((_up2(intra), skip), dim=1))
-            outs.append(_hip_layer(*_head(out), intra, half=half) if hip else _hip_train_layer(*_head(out), intra) if th else out(intra))
+            outs.append(_hip_layer(*_head(out), intra, half=half, tf32=tf32) if hip
+                        else _hip_train_layer(*_head(out), intra, tf32=tf32) if th else out(intra))
         return outs

@@ -607,6 +607,62 @@ def conv2d_bn_act_half(x0, weight, scale, shift, x1=None, up0=False, residual=No
     return out
 
 
+def conv2d_bn_act_tf32(x0, weight, scale, shift, x1=None, up0=False, residual=None, stride=1, act=None, slope=0.1):
+    """conv2d_bn_act in the reference's TF32 class (gfn_conv2d_bn_act_tf32_fwd, csrc/fpn_conv_tf32.hip; the class is stated in
+    include/gfnet_hip.h): the same layer, the same arguments and checks, contiguous fp32 CUDA tensors in and an fp32 result.  The
+    operands of every product are split into two bf16 halves (16 significant bits against TF32's 11) and multiplied on the matrix
+    core, the sums and the epilogue are fp32.  weight is the layer's own fp32 (Cout, Cin, K, K) weight: it is split and packed on the
+    device inside the call.  Cout must be a multiple of 8.  No autograd."""
+    if act not in CONV_ACTS:
+        raise ValueError(f"conv2d_bn_act_tf32: act must be one of {list(CONV_ACTS)}, got {act!r}")
+    tensors = {"x0": x0, "weight": weight, "scale": scale, "shift": shift, "x1": x1, "residual": residual}
+    dev = require_gpu(*tensors.values())
+    for name, t in tensors.items():
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError(f"conv2d_bn_act_tf32: {name} must be a contiguous float32 tensor, got {t.dtype}, contiguous={t.is_contiguous()}")
+    if x0.dim() != 4 or weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
+        raise ValueError(f"conv2d_bn_act_tf32: x0 (B,C0,H,W) and weight (Cout,Cin,K,K) expected, got {tuple(x0.shape)}, {tuple(weight.shape)}")
+    B, C0 = x0.shape[:2]
+    H, W = (2 * x0.shape[2], 2 * x0.shape[3]) if up0 else x0.shape[2:]
+    C1 = 0 if x1 is None else x1.shape[1]
+    Cout, Cin, K, _ = weight.shape
+    if x1 is not None and (x1.dim() != 4 or x1.shape[0] != B or tuple(x1.shape[2:]) != (H, W)):
+        raise ValueError(f"conv2d_bn_act_tf32: x1 must be ({B}, C1, {H}, {W}), got {tuple(x1.shape)}")
+    if Cin != C0 + C1 or tuple(scale.shape) != (Cout,) or tuple(shift.shape) != (Cout,):
+        raise ValueError(f"conv2d_bn_act_tf32: weight takes {Cin} channels but the inputs have {C0} + {C1}; scale and shift must be "
+                         f"({Cout},), got {tuple(scale.shape)}, {tuple(shift.shape)}")
+    if stride not in (1, 2):
+        raise ValueError(f"conv2d_bn_act_tf32: stride must be 1 or 2, got {stride!r}")
+    out = torch.empty((B, Cout, (H + stride - 1) // stride, (W + stride - 1) // stride), device=dev, dtype=torch.float32)
+    if residual is not None and residual.shape != out.shape:
+        raise ValueError(f"conv2d_bn_act_tf32: residual must have the output's shape {tuple(out.shape)}, got {tuple(residual.shape)}")
+    nws = int(_L().gfn_conv2d_bn_act_tf32_ws_bytes(C0, C1, Cout, K))
+    ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
+    _timed("conv2d_bn_act_tf32", lambda: _L().gfn_conv2d_bn_act_tf32_fwd(ptr(x0), C0, int(bool(up0)), ptr(x1), C1, ptr(weight), ptr(scale),
+                                                                         ptr(shift), ptr(residual), ptr(out), B, H, W, Cout, K, stride,
+                                                                         CONV_ACTS[act], float(slope), ptr(ws), nws, stream_ptr(dev)))
+    return out
+
+
+CONV_TRAIN_PRECISIONS = ("fp32", "tf32")  # "tf32": the split-bf16 class of include/gfnet_hip.h on the matrix core, fp32 maps
+
+
+def _check_train_precision(what, precision):
+    if precision not in CONV_TRAIN_PRECISIONS:
+        raise ValueError(f"{what}: precision must be one of {CONV_TRAIN_PRECISIONS}, got {precision!r}")
+
+
+def _conv2d_train_entries(direction, up0, C0, precision):
+    """(ws_bytes, entry, the arguments that stand for C0) of a training direction in a precision class."""
+    L = _L()
+    if precision == "tf32":  # one set of entries, up0 always among the arguments
+        return L.gfn_conv2d_bn_act_train_tf32_ws_bytes, getattr(L, f"gfn_conv2d_bn_act_train_tf32_{direction}"), (C0, int(bool(up0)))
+    # the entry points with the upsample inside only when asked: every other call keeps its launches
+    if up0:
+        return L.gfn_conv2d_up_bn_act_train_ws_bytes, getattr(L, f"gfn_conv2d_up_bn_act_train_{direction}"), (C0, 1)
+    return L.gfn_conv2d_bn_act_train_ws_bytes, getattr(L, f"gfn_conv2d_bn_act_train_{direction}"), (C0,)
+
+
 def _conv2d_train_args(what, x0, x1, weight, residual, vectors, stride, act, up0=False):
     """The refusals of conv2d_bn_act, for the training entry points; vectors: name -> (Cout,) tensor or None.  Returns
     (dev, B, C0, C1, H, W, Cout, K, Ho, Wo); with up0 x0 is the coarse map and H, W are twice its height and width."""
@@ -641,11 +697,12 @@ def _conv2d_train_args(what, x0, x1, weight, residual, vectors, stride, act, up0
 
 
 def conv2d_bn_act_train_fwd(x0, weight, conv_bias, bn_weight, bn_bias, running_mean, running_var, momentum, eps, x1=None, residual=None,
-                            stride=1, act=None, slope=0.1, up0=False):
+                            stride=1, act=None, slope=0.1, up0=False, precision="fp32"):
     """The forward launches of conv2d_bn_act_train (gfn_conv2d_bn_act_train_fwd; with up0 gfn_conv2d_up_bn_act_train_fwd, x0 the
-    coarse map): returns (out, u, mean, invstd) -- u the raw convolution output without the conv bias -- and updates running_mean /
-    running_var in place.  Contiguous float32 CUDA tensors."""
+    coarse map; with precision="tf32" gfn_conv2d_bn_act_train_tf32_fwd): returns (out, u, mean, invstd) -- u the raw convolution
+    output without the conv bias -- and updates running_mean / running_var in place.  Contiguous float32 CUDA tensors."""
     what = "conv2d_bn_act_train"
+    _check_train_precision(what, precision)
     if bn_weight is None or bn_bias is None or running_mean is None or running_var is None:
         raise ValueError(f"{what}: BatchNorm's weight, bias and running statistics are needed (affine, track_running_stats)")
     dev, B, C0, C1, H, W, Cout, K, Ho, Wo = _conv2d_train_args(
@@ -653,9 +710,7 @@ def conv2d_bn_act_train_fwd(x0, weight, conv_bias, bn_weight, bn_bias, running_m
                                          "running_var": running_var}, stride, act, up0)
     out, u = (torch.empty((B, Cout, Ho, Wo), device=dev, dtype=torch.float32) for _ in range(2))
     mean, invstd = torch.empty(Cout, device=dev, dtype=torch.float32), torch.empty(Cout, device=dev, dtype=torch.float32)
-    # the entry points with the upsample inside only when asked: every other call keeps its launches
-    size, entry, c0 = ((_L().gfn_conv2d_up_bn_act_train_ws_bytes, _L().gfn_conv2d_up_bn_act_train_fwd, (C0, 1)) if up0 else
-                       (_L().gfn_conv2d_bn_act_train_ws_bytes, _L().gfn_conv2d_bn_act_train_fwd, (C0,)))
+    size, entry, c0 = _conv2d_train_entries("fwd", up0, C0, precision)
     nws = int(size(*c0, C1, B, H, W, Cout, K, stride, 0))
     ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
     _timed("conv2d_bn_act_train_fwd", lambda: entry(
@@ -666,13 +721,15 @@ def conv2d_bn_act_train_fwd(x0, weight, conv_bias, bn_weight, bn_bias, running_m
 
 
 def conv2d_bn_act_train_bwd(gy, x0, weight, bn_weight, bn_bias, u, mean, invstd, x1=None, stride=1, act=None, slope=0.1,
-                            need=(True, True, True), buffers=None, up0=False):
+                            need=(True, True, True), buffers=None, up0=False, precision="fp32"):
     """Gradients of conv2d_bn_act_train's out given gy = dL/dout and what the forward saved (gfn_conv2d_bn_act_train_bwd; with up0
-    gfn_conv2d_up_bn_act_train_bwd, x0 the coarse map and gx0 of its shape): returns (gx0, gx1, d_weight, d_bn_weight, d_bn_bias),
+    gfn_conv2d_up_bn_act_train_bwd, x0 the coarse map and gx0 of its shape; with precision="tf32"
+    gfn_conv2d_bn_act_train_tf32_bwd, the stride-1 input gradient on the matrix core): returns (gx0, gx1, d_weight, d_bn_weight, d_bn_bias),
     None where `need` = (inputs, weight, BatchNorm) says so or x1 is None.  buffers: a
     dict under those five names of tensors to write into instead of fresh ones; one that `need` does not ask for is handed to the
     library all the same and comes back untouched.  Every result is reproducible bit for bit."""
     what = "conv2d_bn_act_train_bwd"
+    _check_train_precision(what, precision)
     dev, B, C0, C1, H, W, Cout, K, Ho, Wo = _conv2d_train_args(
         what, x0, x1, weight, None, {"bn_weight": bn_weight, "bn_bias": bn_bias, "mean": mean, "invstd": invstd}, stride, act, up0)
     for name, t in (("gy", gy), ("u", u)):
@@ -691,8 +748,7 @@ def conv2d_bn_act_train_bwd(gy, x0, weight, bn_weight, bn_bias, u, mean, invstd,
         elif t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape or not t.is_cuda:
             raise ValueError(f"{what}: buffer {name} must be a contiguous float32 CUDA tensor of shape {shape}")
     if mask:
-        size, entry, c0 = ((_L().gfn_conv2d_up_bn_act_train_ws_bytes, _L().gfn_conv2d_up_bn_act_train_bwd, (C0, 1)) if up0 else
-                           (_L().gfn_conv2d_bn_act_train_ws_bytes, _L().gfn_conv2d_bn_act_train_bwd, (C0,)))
+        size, entry, c0 = _conv2d_train_entries("bwd", up0, C0, precision)
         nws = int(size(*c0, C1, B, H, W, Cout, K, stride, 1))
         ws = torch.empty(max(nws, 16), device=dev, dtype=torch.uint8)
         _timed("conv2d_bn_act_train_bwd", lambda: entry(
@@ -709,30 +765,32 @@ class _Conv2dBnActTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, x1, weight, conv_bias, bn_weight, bn_bias, residual, running_mean, running_var, momentum, eps, stride, act, slope,
-                up0):
+                up0, precision):
         out, u, mean, invstd = conv2d_bn_act_train_fwd(x0, weight, conv_bias, bn_weight, bn_bias, running_mean, running_var, momentum, eps,
-                                                       x1=x1, residual=residual, stride=stride, act=act, slope=slope, up0=up0)
+                                                       x1=x1, residual=residual, stride=stride, act=act, slope=slope, up0=up0,
+                                                       precision=precision)
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(x0, x1, weight, bn_weight, bn_bias, u, mean, invstd)
-            ctx.meta = (stride, act, slope, None if conv_bias is None else conv_bias.shape, up0)
+            ctx.meta = (stride, act, slope, None if conv_bias is None else conv_bias.shape, up0, precision)
         return out
 
     @staticmethod
     def backward(ctx, gy):
         x0, x1, weight, bn_weight, bn_bias, u, mean, invstd = ctx.saved_tensors
-        stride, act, slope, bias_shape, up0 = ctx.meta
+        stride, act, slope, bias_shape, up0, precision = ctx.meta
         n = ctx.needs_input_grad
         gy = gy.contiguous()
         gx0, gx1, d_w, d_g, d_b = conv2d_bn_act_train_bwd(gy, x0, weight, bn_weight, bn_bias, u, mean, invstd, x1=x1, stride=stride, act=act,
-                                                          slope=slope, need=(n[0] or n[1], n[2], n[4] or n[5]), up0=up0)
+                                                          slope=slope, need=(n[0] or n[1], n[2], n[4] or n[5]), up0=up0,
+                                                          precision=precision)
         # the conv bias cancels in u - mean: its gradient is exactly zero
         d_cb = torch.zeros(bias_shape, device=gy.device, dtype=torch.float32) if n[3] and bias_shape is not None else None
         return (gx0 if n[0] else None, gx1 if n[1] else None, d_w, d_cb, d_g if n[4] else None, d_b if n[5] else None,
-                gy if n[6] else None) + (None,) * 8
+                gy if n[6] else None) + (None,) * 9
 
 
 def conv2d_bn_act_train(x0, weight, conv_bias, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum, eps, x1=None,
-                        residual=None, stride=1, act=None, slope=0.1, up0=False):
+                        residual=None, stride=1, act=None, slope=0.1, up0=False, precision="fp32"):
     """One FPN layer under model.train() with a backward, all in csrc/fpn_conv_train.hip (reference model/FPN.py:95-128, :43-66,
     model/network.py:66, 182, which torch autograd differentiates there):
 
@@ -749,11 +807,16 @@ def conv2d_bn_act_train(x0, weight, conv_bias, bn_weight, bn_bias, running_mean,
     under no_grad: forward and buffers only, nothing saved).  Gradients flow to x0, x1, residual (gy itself), weight, bn_weight and
     bn_bias; the conv bias's gradient is returned as EXACT zeros: in front of batch statistics it cancels in u - mean, so the true
     gradient is zero (torch's autograd returns rounding noise around 1e-7 there).  Only u is kept between the directions; identical
-    calls give identical bits."""
+    calls give identical bits.
+    precision "fp32" (the default) or "tf32": the reference's TF32 class as include/gfnet_hip.h states it -- the forward convolution
+    the stride-1 input gradient and the stride-1 weight gradient (without up0) with split-bf16 operands on the matrix core
+    (csrc/fpn_conv_tf32.hip), every map still fp32; the stride-2 input gradient, the stride-2 and up0 weight gradients and a
+    convolution whose output channels are no multiple of 8 stay on the fp32 kernels.  Any other value raises ValueError."""
+    _check_train_precision("conv2d_bn_act_train", precision)
     if momentum is None:
         raise ValueError("conv2d_bn_act_train: momentum must be a float (cumulative averaging, momentum=None, is not supported)")
     out = _Conv2dBnActTrainFn.apply(x0, x1, weight, conv_bias, bn_weight, bn_bias, residual, running_mean, running_var, float(momentum),
-                                    float(eps), stride, act, float(slope), bool(up0))
+                                    float(eps), stride, act, float(slope), bool(up0), precision)
     # the kernels wrote the buffers through raw pointers: tell autograd's version counters
     torch.autograd.graph.increment_version(running_mean)
     torch.autograd.graph.increment_version(running_var)

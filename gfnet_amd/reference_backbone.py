@@ -51,8 +51,8 @@ def _check_fpn_train_impl(fpn, fpn_train_impl):
 
 
 def _check_fpn_precision(fpn, fpn_precision):
-    if fpn_precision not in ("fp32", "fp16"):
-        raise ValueError(f"fpn_precision must be 'fp32' or 'fp16', got {fpn_precision!r}")
+    if fpn_precision not in ("fp32", "fp16", "tf32"):
+        raise ValueError(f"fpn_precision must be 'fp32', 'fp16' or 'tf32', got {fpn_precision!r}")
     if fpn_precision != "fp32" and fpn != "hip":
         raise ValueError(f"fpn_precision={fpn_precision!r} needs fpn='hip': the checkout's FPN modules run in fp32 only")
 
@@ -144,7 +144,9 @@ class ReferenceBackbone(nn.Module):
     fpn_precision: "fp32" (default) or "fp16", the conv_precision of the three native FPN modules (see gfnet_amd/model/fpn.py): with
     "fp16" their eval() HIP path keeps fp16 maps and runs on the matrix core, and in eval() on the GPU ALL FIVE LEVELS ARE RETURNED IN
     fp16 as stored (the stride-16 map is cast to fp16 too), not widened: GFNet.match / match_batch read fp16 pyramids directly.
-    train() and CPU tensors return fp32 levels as before.  Needs fpn="hip", else ValueError.
+    train() and CPU tensors return fp32 levels as before.  "tf32" is the reference's own TF32 class of the FPN's convolutions, for the
+    eval() and the train() HIP paths (fpn_train_impl "hip" / "hip_fused"): split-bf16 operands on the matrix core, fp32 maps, the five
+    levels returned in fp32 as under "fp32".  Either needs fpn="hip", else ValueError.
 
     decoder_train_impl: "torch" (default) or "hip", the train_block_impl of the native cross-view decoder: "hip" trains its blocks
     through the backward kernels of csrc/decoder_block.hip under fp16 or bf16 autocast: amp_dtype=torch.bfloat16 selects the bf16 class of

@@ -920,6 +920,44 @@ int gfn_conv2d_up_bn_act_train_bwd(const float *gy, const float *x0, int C0, int
                                    float *gx1, float *d_weight, float *d_bn_w, float *d_bn_b, int B, int H, int W, int Cout, int K, int stride,
                                    int act, float slope, int need, void *ws, int64_t ws_bytes, gfn_stream_t stream);
 
+/* The FPN layer in the reference's TF32 CLASS, inference and training; csrc/fpn_conv_tf32.hip.  The reference runs its FPN
+ * (model/FPN.py) outside autocast in fp32 tensors with cuDNN's TF32 convolutions: train.py:151 sets torch.backends.cudnn.allow_tf32,
+ * which is also torch's default for convolutions.  It keeps fp32 maps, rounds the operands of each product and sums in fp32.  gfx950
+ * has no TF32 matrix instruction; this class is SPLIT-bf16 on the bf16 one, said once here:
+ *   the split of an fp32 value v:  hi = bf16(v) to nearest even (v_cvt_pk_bf16_f32), lo = bf16(v - hi), and lo = 0 where hi is not
+ *     finite, so that an inf stays an inf as on the fp32 path and does not become inf - inf;
+ *   a product a b of the convolution is a_hi b_hi + a_hi b_lo + a_lo b_hi: each of the three is exact in fp32, they are summed into
+ *     an fp32 accumulator by v_mfma_f32_16x16x32_bf16 (Cout < 32) or v_mfma_f32_32x32x16_bf16 (Cout >= 32); a_lo b_lo is dropped;
+ *   with up0 the interpolated value is computed in fp32 exactly as on the fp32 path and then split;
+ *   scale, shift, activation and residual are fp32 and every map is fp32, in and out.  A fixed order of sums and no atomics:
+ *     identical calls give identical bits.
+ * Against exact arithmetic the class errs by at most 3 * 2^-16 * sum |a| |b| per output before fp32 accumulation (2^-8 per
+ * rounding; measured 1.8 * 2^-16) -- the figure beside TF32's 2^-10.
+ * gfn_conv2d_bn_act_tf32_fwd: gfn_conv2d_bn_act_fwd's arguments, meaning, limits and refusals; weight is the
+ *   plain fp32 (Cout, C0 + C1, K, K) weight, split and packed on the device by one small launch into ws:
+ *   gfn_conv2d_bn_act_tf32_ws_bytes(C0, C1, Cout, K) bytes, 16-byte aligned (0 for sizes the entry refuses).  Cout must be a MULTIPLE OF
+ *   8, as in the fp16 class; anything else returns GFN_ERR_INVALID_ARG before a launch.
+ * gfn_conv2d_bn_act_train_tf32_{ws_bytes,fwd,bwd}: gfn_conv2d_up_bn_act_train_*'s arguments (up0 and the need mask included), meaning,
+ *   limits, refusals and saved tensors (u, mean, invstd, all fp32) for both existing pairs.  In the class: the forward convolution u,
+ *   the stride-1 input gradient (the same convolution of gu with the transposed and flipped weight), and the weight gradient under
+ *   stride 1 without up0 -- a GEMM over the pixels on v_mfma_f32_16x16x32_bf16 with gu and the shifted x both split, per-workgroup
+ *   partials added in order in double as on the fp32 path.  On today's fp32 kernels, whose exact products lie inside the class's
+ *   bound: the stride-2 input gradient (ft_gather_s2_kernel), the weight gradient under stride 2 and under up0 (ft_wgrad_kernel), and
+ *   any convolution launch whose output-channel count -- for an input gradient C0 or C1 of the layer -- is not a multiple of 8.  The BatchNorm passes are the fp32 entries' own.  ws grows by the largest packed weight of the launches. */
+int64_t gfn_conv2d_bn_act_tf32_ws_bytes(int C0, int C1, int Cout, int K);
+int gfn_conv2d_bn_act_tf32_fwd(const float *x0, int C0, int up0, const float *x1, int C1, const float *weight, const float *scale,
+                               const float *shift, const float *residual, float *out, int B, int H, int W, int Cout, int K, int stride,
+                               int act, float slope, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+int64_t gfn_conv2d_bn_act_train_tf32_ws_bytes(int C0, int up0, int C1, int B, int H, int W, int Cout, int K, int stride, int backward);
+int gfn_conv2d_bn_act_train_tf32_fwd(const float *x0, int C0, int up0, const float *x1, int C1, const float *weight, const float *conv_bias,
+                                     const float *bn_w, const float *bn_b, float *running_mean, float *running_var, const float *residual,
+                                     float *u, float *mean, float *invstd, float *out, int B, int H, int W, int Cout, int K, int stride,
+                                     int act, float slope, double momentum, double eps, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+int gfn_conv2d_bn_act_train_tf32_bwd(const float *gy, const float *x0, int C0, int up0, const float *x1, int C1, const float *weight,
+                                     const float *bn_w, const float *bn_b, const float *u, const float *mean, const float *invstd, float *gx0,
+                                     float *gx1, float *d_weight, float *d_bn_w, float *d_bn_b, int B, int H, int W, int Cout, int K,
+                                     int stride, int act, float slope, int need, void *ws, int64_t ws_bytes, gfn_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Self-attention forward of the DINOv2 ViT at head dim 64 -- model/transformer/layers/attention.py:77-101 (Attention.forward:
  * the F.scaled_dot_product_attention call at :96, which MemEffAttention falls back to without xformers, :106-110);

@@ -3,7 +3,7 @@
 library convolutions plus separate BatchNorm, activation, interpolate, cat and add launches that a checkout's FPN runs -- on the same
 parameters and inputs.
 
-    python tools/time_fpn.py [--images 64] [--sizes 448 560] [--rounds 7] [--reps 5] [--precision fp32|fp16] [--out fpn_timing.json]
+    python tools/time_fpn.py [--images 64] [--sizes 448 560] [--rounds 7] [--reps 5] [--precision fp32|fp16|tf32] [--out fpn_timing.json]
 
 Per size: every layer on its real input (the maps of one torch-path forward), then the whole pyramid (encoder, merge layer, decoder).
 The two paths ALTERNATE round by round; a round is `reps` back-to-back calls between two device events; reported per path are the
@@ -13,6 +13,9 @@ picks its algorithms then).  The largest difference between the two paths' outpu
 matrix core, csrc/fpn_conv_half.hip) on fp16 inputs, and "torch_amp", the torch path under torch.autocast(dtype=float16) on the same
 fp16 inputs.  The fp32 HIP leg is the comparator of the fp16 class: the table gives fp32 HIP / half and torch_amp / half per layer and
 for the whole pyramid, and for the whole pyramid the gap between the two medians beside the larger min .. max spread of the two legs.
+--precision tf32 adds one leg to the alternation: "tf32", the HIP path in the reference's TF32 class (conv_precision "tf32": fp32 maps,
+split-bf16 operands on the matrix core, csrc/fpn_conv_tf32.hip) on the same fp32 inputs; the table gives fp32 HIP / tf32 and torch /
+tf32 per layer and for the whole pyramid.
 Needs a GPU; nothing here falls back."""
 import argparse
 import json
@@ -43,13 +46,16 @@ def build(device):
     return mods
 
 
-PATHS = {"fp32": ("hip", "torch"), "fp16": ("half", "hip", "torch", "torch_amp")}
+PATHS = {"fp32": ("hip", "torch"), "fp16": ("half", "hip", "torch", "torch_amp"), "tf32": ("tf32", "hip", "torch")}
+HIP_LEGS = ("hip", "half", "tf32")
+PRECISION_OF = {"half": "fp16", "tf32": "tf32"}  # conv_precision of a leg; every other leg is "fp32"
 
 
 def on_path(path, hip_call, torch_call):
-    """One call on a leg: hip_call(half) for "hip" / "half", torch_call() for "torch", and under fp16 autocast for "torch_amp"."""
-    if path in ("hip", "half"):
-        return hip_call(path == "half")
+    """One call on a leg: hip_call(half, tf32) for "hip" / "half" / "tf32", torch_call() for "torch", and under fp16 autocast for
+    "torch_amp"."""
+    if path in HIP_LEGS:
+        return hip_call(path == "half", path == "tf32")
     with torch.autocast("cuda", dtype=torch.float16, enabled=path == "torch_amp"):
         return torch_call()
 
@@ -59,21 +65,21 @@ def layer_calls(mods):
     enc, dec, merge = mods["encoder"], mods["decoder"], mods["merge_layer"]
     calls, prev = [], "image"
     for name in ENCODER:
-        calls.append((name, (prev,), (lambda layer: lambda path, x: on_path(path, lambda half: layer.run(x, True, half=half),
+        calls.append((name, (prev,), (lambda layer: lambda path, x: on_path(path, lambda half, tf32: layer.run(x, True, half=half, tf32=tf32),
                                                                             lambda: layer.run(x, False)))(getattr(enc, name)), name))
         prev = name
 
     def run_merge(path, c3, side):
-        merge.conv_impl = "hip" if path in ("hip", "half") else "torch"
-        merge.conv_precision = "fp16" if path == "half" else "fp32"
-        return on_path(path, lambda half: merge(c3, side), lambda: merge(c3, side))
+        merge.conv_impl = "hip" if path in HIP_LEGS else "torch"
+        merge.conv_precision = PRECISION_OF.get(path, "fp32")
+        return on_path(path, lambda half, tf32: merge(c3, side), lambda: merge(c3, side))
 
     def head(seq):
-        return lambda path, x: on_path(path, lambda half: fpn._hip_layer(*fpn._head(seq), x, half=half), lambda: seq(x))
+        return lambda path, x: on_path(path, lambda half, tf32: fpn._hip_layer(*fpn._head(seq), x, half=half, tf32=tf32), lambda: seq(x))
 
     def inner(seq):
         def run(path, intra, skip):
-            return on_path(path, lambda half: fpn._hip_layer(*fpn._head(seq), intra, x1=skip, up0=True, residual=skip, half=half),
+            return on_path(path, lambda half, tf32: fpn._hip_layer(*fpn._head(seq), intra, x1=skip, up0=True, residual=skip, half=half, tf32=tf32),
                            lambda: skip + seq(torch.cat((fpn._up2(intra), skip), dim=1)))
         return run
 
@@ -90,13 +96,13 @@ def layer_calls(mods):
 
 def pyramid(mods, path, image, side):
     for m in mods.values():
-        m.conv_impl = "hip" if path in ("hip", "half") else "torch"
-        m.conv_precision = "fp16" if path == "half" else "fp32"
+        m.conv_impl = "hip" if path in HIP_LEGS else "torch"
+        m.conv_precision = PRECISION_OF.get(path, "fp32")
 
     def run():
         c0, c1, c2, c3 = mods["encoder"](image)
         return mods["decoder"](c0, c1, c2, mods["merge_layer"](c3, side))
-    return on_path(path, lambda half: run(), run)
+    return on_path(path, lambda half, tf32: run(), run)
 
 
 def time_pair(fn, rounds, reps, paths=PATHS["fp32"]):
@@ -127,7 +133,7 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[448, 560])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--precision", choices=sorted(PATHS), default="fp32", help="fp16: add the fp16 class and torch's fp16 autocast as legs")
+    ap.add_argument("--precision", choices=sorted(PATHS), default="fp32", help="fp16: add the fp16 class and torch's fp16 autocast as legs; tf32: add the TF32 class as a leg")
     ap.add_argument("--out", default=None, help="write the numbers as JSON here")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -157,6 +163,8 @@ def main():
                 rows[name] = dict({path: summary(t[path]) for path in paths}, max_abs_diff=diff, shape=list(ctx[key].shape))
                 if fp16:
                     rows[name]["half_max_abs_diff"] = float((ctx16[key].float() - ctx[key]).abs().max())
+                if "tf32" in paths:
+                    rows[name]["tf32_max_abs_diff"] = float((call("tf32", *inputs) - ctx[key]).abs().max())
             t = time_pair(lambda path: pyramid(mods, path, ctx["image"], ctx["side"]), args.rounds, args.reps, paths)
             total = {path: summary(t[path]) for path in paths}
             result["sizes"][str(size)] = {"layers": rows, "total": total, "max_abs_diff": worst}
@@ -179,6 +187,13 @@ def main():
                 print(f"whole pyramid: fp32 HIP median - half median = {gap:.3f} ms, larger min .. max spread of the two legs {spread:.3f} ms: "
                       f"the fp16 class is {'faster beyond the spread' if gap > spread else 'NOT faster beyond the spread'}")
                 print(f"largest |half - torch fp32| over all layers: {max(r['half_max_abs_diff'] for r in rows.values()):.3e}")
+            if "tf32" in paths:
+                print("\n| layer | tf32 class | fp32 HIP | torch | fp32 HIP / tf32 | torch / tf32 |\n|---|---|---|---|---|---|")
+                for name, r in list(rows.items()) + [("whole pyramid", total)]:
+                    cells = [f"{r[p]['median_ms']:.3f} ({r[p]['min_ms']:.3f} .. {r[p]['max_ms']:.3f})" for p in ("tf32", "hip", "torch")]
+                    print(f"| {name} | {' | '.join(cells)} | {r['hip']['median_ms'] / r['tf32']['median_ms']:.2f} | "
+                          f"{r['torch']['median_ms'] / r['tf32']['median_ms']:.2f} |")
+                print(f"largest |tf32 - torch fp32| over all layers: {max(r['tf32_max_abs_diff'] for r in rows.values()):.3e}")
             del ctx, ctx16
             torch.cuda.empty_cache()
     if args.out:
